@@ -10,10 +10,15 @@ no data-path collective; the only collective is the one-time RCCL broadcast of r
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W      # one rank per GPU over RCCL
 
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs of the last timed step as
+DIR/<name>.npy if `--dump-outputs DIR` is given (logits and probs, float32; logits alone with `--front group`; rank r > 0 adds `_rank<r>`; the inputs are seeded, so two
+builds can be compared output for output), and the JSON line.  Every side measurement and check described below -- roofline, in-kernel
+clocks, latency, host buffers, CPU baseline, broadcast probe, config 4, group front, per-rank numbers -- runs only with `--full`.
+
 Timing: after the warm-up steps (and at least `--warm-seconds` of them, so that clocks and caches are in their loaded state) the
-script times `--windows` (default 5) windows of EXACTLY `--steps` steps each, every window bracketed by a barrier +
+script times `--windows` (default 1; 5 with `--full`) windows of EXACTLY `--steps` steps each, every window bracketed by a barrier +
 synchronize on both sides and taken as the MAX over ranks; `value` / `ms_per_step` are the MEDIAN window (`value_min`,
-`value_max`, `window_values` carry the spread), and `effective_clock_ghz` is the shader clock the power-limited part sustained during
+`value_max`, `window_values` carry the spread), and `effective_clock_ghz` (`--full`) is the shader clock the power-limited part sustained during
 the timed windows: s_memtime against the 100 MHz s_memrealtime, summed by workgroup 0 over EVERY launch of each of the five heavy kernel
 kinds (`kernel_clocks_ghz`: QKV / attn-out / FFN-in / FFN-out GEMMs, attention), weighted by each kind's share of the step -- boxes
 differ by several per cent in exactly that clock (`images_per_sec_per_ghz` is the figure to compare across boxes).
@@ -124,7 +129,8 @@ class Watchdog:
 def group_front(api, path, devices, dt, B, S, num_classes, steps, windows, warmup=2):
     """Throughput through the C-ABI's multi-device front end with HOST buffers on both sides (page-locked f32 images in, logits out):
     one process, `len(devices)` devices, the global batch of len(devices) * B images split contiguously, two batches in flight from this
-    one host thread (dinov2_hip_group_submit / _wait).  Returns the median window and the group's own facts."""
+    one host thread (dinov2_hip_group_submit / _wait).  Returns the median window and the group's own facts, and the outputs of the
+    last timed step."""
     G = len(devices)
     grp = api.Group(path, devices=list(devices), dtype=dt, classify=True, broadcast=G > 1, streams_per_device=2)
     try:
@@ -147,7 +153,7 @@ def group_front(api, path, devices, dt, B, S, num_classes, steps, windows, warmu
                     grp.wait(q.pop(0))
                 q.append(grp.submit(pin, **kw))
             while q:
-                grp.wait(q.pop(0))
+                out = grp.wait(q.pop(0))
             win.append(time.perf_counter() - t0)
         med = float(np.median(win))
         return {"value": round(G * B * steps / med, 2), "unit": "images/sec", "ms_per_step": round(med / steps * 1e3, 3), "steps": steps, "windows": windows,
@@ -155,9 +161,16 @@ def group_front(api, path, devices, dt, B, S, num_classes, steps, windows, warmu
                 "in_flight": 2, "host_buffers": "page-locked f32 [B, 3, S, S] in, f32 logits out",
                 "group_broadcast_ms": round(grp.broadcast_ms, 2) if G > 1 and grp.broadcast_ms >= 0 else None, "topology": grp.topology,
                 "definition": "wall time around whole predict calls with the input upload and the result download inside (the reference's "
-                              "inference.cpp:64-68), two batches in flight from one host thread"}
+                              "inference.cpp:64-68), two batches in flight from one host thread"}, out
     finally:
         grp.close()
+
+
+def dump_outputs(dirname, arrays, suffix=""):
+    """--dump-outputs: each array as DIR/<name><suffix>.npy, float32."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def main():
@@ -171,21 +184,27 @@ def main():
     ap.add_argument("--registers", type=int, default=4)
     ap.add_argument("--dtype", default="f16", choices=["f16", "bf16"])
     ap.add_argument("--wtype", default="f16", help="GGUF storage type of the 2-D weights (f16, q8_0, q4_0, ...)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true")
-    ap.add_argument("--no-config4", action="store_true", help="N > 1 only: skip the ViT-g bf16 global-batch-64 leg")
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps each; value = the median window")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every side measurement and check (roofline, clocks, latency, host buffers, "
+                         "CPU baseline, broadcast probe, config 4, group front); a plain run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the batch-1 latency and two-session legs")
+    ap.add_argument("--no-config4", action="store_true", help="--full, N > 1 only: skip the ViT-g bf16 global-batch-64 leg")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of --steps steps each; value = the median window (default 1; 5 with --full)")
     ap.add_argument("--warm-seconds", type=float, default=1.0, help="minimum wall time of the warm-up before the first window")
     ap.add_argument("--backend", default=os.environ.get("DINOV2_BENCH_BACKEND", "nccl"), choices=["nccl", "gloo"],
                     help="gloo = dry run of the N > 1 path with all ranks on the visible GPU(s) (labelled as such)")
     ap.add_argument("--front", default="session", choices=["session", "group"],
                     help="group = time dinov2_hip_group_submit/_wait (one process, --gpus devices, page-locked host buffers in and out) as the headline")
     ap.add_argument("--devices", default="", help="--front group: comma-separated device ordinals (default 0 .. gpus-1; a 1-GPU box can rehearse with 0,0,0,0)")
-    ap.add_argument("--no-host-buffers", action="store_true", help="N = 1: skip the host-buffer leg (value_host_buffers)")
+    ap.add_argument("--no-host-buffers", action="store_true", help="--full, N = 1: skip the host-buffer leg (value_host_buffers)")
     ap.add_argument("--dist-timeout", type=float, default=180.0, help="seconds a collective set-up stage may take before the watchdog exits")
-    ap.add_argument("--no-exact", action="store_true", help="skip the exact-arithmetic / ggml-style-mode distances in cpu_baseline")
+    ap.add_argument("--no-exact", action="store_true", help="--full: skip the exact-arithmetic / ggml-style-mode distances in cpu_baseline")
     args = ap.parse_args()
-    args.windows = max(1, args.windows)
+    args.windows = max(1, args.windows if args.windows is not None else (5 if args.full else 1))
 
     # the pool's host driver only supports dmabuf IPC: without this RCCL's cross-process buffer sharing fails (hipIpcGetMemHandle);
     # already exported on the GPU boxes, set here as well so that a bare `torchrun bench.py` does not depend on the shell
@@ -217,7 +236,9 @@ def main():
             os.replace(tmp, path)
         dtg = api.F16 if args.dtype == "f16" else api.BF16
         with wd.stage("group front (create + weight broadcast + timed windows)", max(600.0, args.dist_timeout)):
-            g = group_front(api, path, devices, dtg, args.batch, args.size, 1000, args.steps, args.windows, warmup=max(2, args.warmup))
+            g, last = group_front(api, path, devices, dtg, args.batch, args.size, 1000, args.steps, args.windows, warmup=max(2, args.warmup))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"logits": last["logits"]})
         gflop_img = pkg.synth.flops_per_image(cfg, args.size, args.size, args.registers, 1000) / 1e9
         out = {"metric": ("images/sec (518x518), ViT-L/14 fp16" if (args.model, args.size, args.dtype) == ("large", 518, "f16") else
                           f"images/sec ({args.size}x{args.size}), ViT-{args.model[0].upper()}/14 {'fp16' if args.dtype == 'f16' else args.dtype}"),
@@ -234,7 +255,7 @@ def main():
         print(json.dumps(out), flush=True)
         return
 
-    dist = None
+    dist = tail_pg = None
     dryrun = args.backend == "gloo"
     if dryrun:  # rehearsal: every rank on the GPU(s) this box has
         local = local % max(1, torch.cuda.device_count())
@@ -306,7 +327,7 @@ def main():
 
     # every rank runs ONE shared probe image on its (broadcast) arena; rank 0 checks that all ranks agree with it bit for bit
     bcast_ok = None
-    if dist is not None:
+    if dist is not None and args.full:
         pg = torch.Generator(device=f"cuda:{local}").manual_seed(1234)
         probe = torch.randn((1, 3, args.size, args.size), generator=pg, device=f"cuda:{local}", dtype=torch.float32)
         plog = torch.empty((1, num_classes), device=f"cuda:{local}", dtype=torch.float32)
@@ -362,7 +383,7 @@ def main():
         except Exception:
             return None
 
-    clk0 = read_clock_sums()
+    clk0 = read_clock_sums() if args.full else None
     window_s, own_s = [], []
     with wd.stage("timed windows", 600.0 + args.dist_timeout):
         for _ in range(args.windows):
@@ -380,12 +401,14 @@ def main():
         if dist is not None:
             dist.barrier()
     elapsed = float(np.median(window_s))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logits": logits.cpu().numpy(), "probs": probs.cpu().numpy()}, "" if rank == 0 else f"_rank{rank}")
     # the clock this rank's device sustained inside each heavy kernel kind over ALL launches of the timed windows (workgroup 0's s_memtime
     # against the 100 MHz s_memrealtime, running sums on the device, read before and after): FFN-in alone (`dom_clock`, the roofline's
     # kernel) and all five kinds (`slot_clock`)
     dom_clock = dom_dev_ms = None
     slot_clock = {}
-    clk1 = read_clock_sums()
+    clk1 = read_clock_sums() if args.full else None
     if clk0 and clk1:
         for i, nm in enumerate(("gemm_qkv", "gemm_attn_out", "gemm_ffn_in", "gemm_ffn_out", "attention")):
             dc, dk, dn = clk1[3 * i] - clk0[3 * i], clk1[3 * i + 1] - clk0[3 * i + 1], clk1[3 * i + 2] - clk0[3 * i + 2]
@@ -396,7 +419,7 @@ def main():
                     dom_dev_ms = dk / dn * 1e-5  # what workgroup 0 (persistent: first tile to last) spent inside a launch on average, device clock
     # every rank's own numbers (a straggling GPU or a slow link is invisible in a max over ranks): gathered on all, printed by rank 0
     per_rank = None
-    if dist is not None:
+    if dist is not None and args.full:
         own_med = float(np.median(own_s))
         mine = torch.tensor([[float(rank), float(local), B * args.steps / own_med, own_med / args.steps * 1e3, float(dom_clock or 0.0),
                               float(bcast_ms or 0.0), B * args.steps / max(own_s), B * args.steps / min(own_s)]], dtype=torch.float64,
@@ -411,7 +434,7 @@ def main():
 
     # ---- BASELINE configs[3] (N > 1 only): ViT-g/14 SwiGLU bf16, global batch 64 = N x 64/N, weights by RCCL broadcast ----
     config4 = None
-    if dist is not None and not args.no_config4 and 64 % world == 0:
+    if dist is not None and args.full and not args.no_config4 and 64 % world == 0:
         try:
             del sess
             model.close()
@@ -482,6 +505,32 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
     gflop_img = pkg.synth.flops_per_image(cfg, S, S, args.registers, num_classes) / 1e9
+    out = {
+        # BASELINE.json's metric on its default configuration; other --model / --size / --dtype runs are labelled as what they are
+        "metric": ("images/sec (518x518), ViT-L/14 fp16" if (args.model, args.size, args.dtype) == ("large", 518, "f16") else
+                   f"images/sec ({args.size}x{args.size}), ViT-{args.model[0].upper()}/14 {'fp16' if args.dtype == 'f16' else args.dtype}"),
+        "value": round(value, 2), "unit": "images/sec", "commit": commit_id(),
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        "windows": args.windows, "value_min": round(world * B * args.steps / max(window_s), 2),
+        "value_max": round(world * B * args.steps / min(window_s), 2),
+        "window_values": [round(world * B * args.steps / w, 2) for w in window_s],
+        "timing": f"median of {args.windows} windows of {args.steps} steps (barrier + synchronize around each, max over ranks), after "
+                  f">= {args.warm_seconds:g} s of warm-up",
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": f"dinov2-{args.model} (ViT-{args.model[0].upper()}/14, {args.registers} registers) "
+                               f"{args.wtype} GGUF, {S}x{S}, batch={B} per GPU, classify head, random-init weights",
+                   "global_batch": world * B, "tokens_per_image": T, "parallelism": f"dp{world}",
+                   "gflop_per_image": round(gflop_img, 1)},
+        "ln_fold": os.environ.get("DINOV2_HIP_LN_FOLD", "0") not in ("0", ""),  # (the headline runs the library's default: off)
+        "load_s": round(load_s, 2), "weight_broadcast_ms": None if bcast_ms is None else round(bcast_ms, 2),
+    }
+    if dryrun:
+        out["backend"] = "gloo-dryrun"
+        out["backend_note"] = ("rehearsal of the N > 1 code path: all ranks time-share the visible GPU(s) and the collectives go through "
+                               "gloo -- NOT a scaling measurement")
+    if not args.full:
+        emit(out, dist, tail_pg)
+        return
 
     # ---- roofline of the dominant kernel: HIP events around every launch, on the stream the kernels run on ----
     sess.profile(True)
@@ -629,7 +678,7 @@ def main():
     if world == 1 and not dryrun and not args.no_host_buffers:
         try:
             with wd.stage("host-buffer leg (dinov2_hip_group_*)", 600.0):
-                host_leg = group_front(api, path, [local], dt, B, S, num_classes, steps=max(4, min(args.steps, 10)), windows=3)
+                host_leg = group_front(api, path, [local], dt, B, S, num_classes, steps=max(4, min(args.steps, 10)), windows=3)[0]
             host_leg["ratio_to_value"] = round(host_leg["value"] / value, 4)
         except Exception as e:  # a side measurement must not take the headline down
             host_leg = {"error": repr(e)}
@@ -732,42 +781,26 @@ def main():
                "distance_to_exact": exact}
         del got
 
-    out = {
-        # BASELINE.json's metric on its default configuration; other --model / --size / --dtype runs are labelled as what they are
-        "metric": ("images/sec (518x518), ViT-L/14 fp16" if (args.model, args.size, args.dtype) == ("large", 518, "f16") else
-                   f"images/sec ({args.size}x{args.size}), ViT-{args.model[0].upper()}/14 {'fp16' if args.dtype == 'f16' else args.dtype}"),
-        "value": round(value, 2), "unit": "images/sec", "commit": commit_id(),
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-        "windows": args.windows, "value_min": round(world * B * args.steps / max(window_s), 2),
-        "value_max": round(world * B * args.steps / min(window_s), 2),
-        "window_values": [round(world * B * args.steps / w, 2) for w in window_s],
-        "timing": f"median of {args.windows} windows of {args.steps} steps (barrier + synchronize around each, max over ranks), after "
-                  f">= {args.warm_seconds:g} s of warm-up",
+    out.update({
         "effective_clock_ghz": eff_clock, "nominal_clock_ghz": 2.4,
         "effective_clock_note": "time-weighted over the five heavy kernel kinds (kernel_clocks_ghz; they cover %s of the step's kernel time); "
                                 "rank 0's device, averaged over every launch of the timed windows" % clk_cover,
         "kernel_clocks_ghz": {k: round(v, 4) for k, v in slot_clock.items()} or None,
         "images_per_sec_per_ghz": None if not eff_clock else round(value / world / eff_clock, 1),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": f"dinov2-{args.model} (ViT-{args.model[0].upper()}/14, {args.registers} registers) "
-                               f"{args.wtype} GGUF, {S}x{S}, batch={B} per GPU, classify head, random-init weights",
-                   "global_batch": world * B, "tokens_per_image": T, "parallelism": f"dp{world}",
-                   "gflop_per_image": round(gflop_img, 1)},
         "p50_latency_ms_batch1": p50, "p99_latency_ms_batch1": p99,
         "latency_mode": "batch-invariant kernels (batch-1 bits == the image's bits inside any batch)",
         "p50_latency_ms_batch1_224x224": p50_224, "p99_latency_ms_batch1_224x224": p99_224,
         "p50_latency_ms_batch1_ln_fold": p50_fold, "p50_latency_ms_batch1_224x224_ln_fold": p50_224_fold,
-        "ln_fold": os.environ.get("DINOV2_HIP_LN_FOLD", "0") not in ("0", ""),  # (the headline runs the library's default: off)
         "two_sessions_images_per_sec": two_stream, "group_front": group_leg,
         "roofline": roofline, "cpu_baseline": cpu, "kernels": kernels,
-        "load_s": round(load_s, 2), "weight_broadcast_ms": None if bcast_ms is None else round(bcast_ms, 2),
         "broadcast_verified": bcast_ok, "config4": config4, "per_rank": per_rank,
         "value_host_buffers": host_leg,
-    }
-    if dryrun:
-        out["backend"] = "gloo-dryrun"
-        out["backend_note"] = ("rehearsal of the N > 1 code path: all ranks time-share the visible GPU(s) and the collectives go through "
-                               "gloo -- NOT a scaling measurement")
+    })
+    emit(out, dist, tail_pg)
+
+
+def emit(out, dist, tail_pg):
+    """Rank 0's one JSON line, then the final rendezvous with the other ranks."""
     try:  # anything a native library still holds in C stdio goes out BEFORE the JSON line, which stays the last one
         import ctypes
         ctypes.CDLL(None).fflush(None)

@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -24,10 +25,10 @@ def _free_port():
     return p
 
 
-def _run(n, extra):
+def _run(n, extra, full=True):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1",
-           "--windows", "2", "--warm-seconds", "0", "--backend", "gloo", "--no-cpu-baseline", "--no-latency"] + extra
+           "--windows", "2", "--warm-seconds", "0", "--backend", "gloo"] + (["--full", "--no-cpu-baseline", "--no-latency"] if full else []) + extra
     env = dict(os.environ, OMP_NUM_THREADS="4", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -61,6 +62,17 @@ def test_bench_multi_rank_dry_run(n, batch):
     assert 0.3 < gf["ratio_to_value"] < 1.3
 
 
+def test_bench_multi_rank_plain_run_dumps_every_rank(tmp_path):
+    """The N > 1 path without --full: the headline over both ranks, none of the side legs, and each rank's last timed step on disk."""
+    j = _run(2, ["--batch", "4", "--dump-outputs", str(tmp_path)], full=False)
+    assert j["n_gpus"] == 2 and j["backend"] == "gloo-dryrun" and j["config"]["global_batch"] == 8 and j["windows"] == 2
+    assert j["value"] > 0 and j["weight_broadcast_ms"] > 0
+    assert not {"broadcast_verified", "config4", "per_rank", "group_front", "roofline"} & set(j)
+    for r in ("", "_rank1"):
+        logits = np.load(tmp_path / f"logits{r}.npy")
+        assert logits.shape == (4, 1000) and np.isfinite(logits).all() and np.load(tmp_path / f"probs{r}.npy").shape == (4, 1000)
+
+
 def test_bench_group_front_eight_entries():
     """`--front group`: the C-ABI's own multi-device front end (one process, dinov2_hip_group_submit / _wait, page-locked host buffers) as
     the headline, rehearsed as an 8-entry group on the one visible device with a global batch of 8 x 4."""
@@ -86,9 +98,9 @@ def test_bench_watchdog_names_the_stage():
 
 
 def test_bench_single_rank_line_has_spread_and_clock():
-    """N = 1, the driver's own invocation shape (small steps here): the line carries the window spread and the in-kernel clock."""
+    """N = 1 with --full (small steps here): the line carries the window spread and the in-kernel clock."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--windows", "3", "--warm-seconds", "0.2",
-                        "--no-cpu-baseline", "--no-latency"], cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--no-latency"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert j["n_gpus"] == 1 and "backend" not in j and j["windows"] == 3 and len(j["window_values"]) == 3
@@ -99,3 +111,27 @@ def test_bench_single_rank_line_has_spread_and_clock():
     assert j["images_per_sec_per_ghz"] > 0 and j["per_rank"] is None
     hb = j["value_host_buffers"]  # host buffers in and out through dinov2_hip_group_submit / _wait, never the headline
     assert hb and hb["value"] > 0 and 0.5 < hb["ratio_to_value"] < 1.1 and hb["in_flight"] == 2
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps in one window and prints the headline without the side legs; --dump-outputs
+    writes the last timed step's logits and probs, and a second run with the same arguments writes the same arrays bit for bit."""
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
+                            "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and j["windows"] == 1 and len(j["window_values"]) == 1 and j["higher_is_better"] is True
+        assert j["unit"] == "images/sec" and j["dtype"] == "f16" and j["metric"].startswith("images/sec")
+        assert abs(j["ms_per_step"] * j["value"] / 1e3 - 4) < 0.05  # value = 4 images per ms_per_step
+        assert not {"roofline", "kernels", "cpu_baseline", "value_host_buffers", "p50_latency_ms_batch1", "effective_clock_ghz"} & set(j)
+        logits, probs = np.load(d / "logits.npy"), np.load(d / "probs.npy")
+        assert logits.shape == probs.shape == (4, 1000) and logits.dtype == probs.dtype == np.float32
+        e = np.exp(logits.astype(np.float64) - logits.max(1, keepdims=True))
+        assert np.isfinite(logits).all() and np.allclose(probs, e / e.sum(1, keepdims=True), atol=1e-5)  # one step's pair
+        runs.append((logits, probs))
+    assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1])

@@ -1,10 +1,10 @@
 #!/bin/bash
 # A/B of the LN fold on one box, interleaved: bench.py with DINOV2_HIP_LN_FOLD=0 / 1 (batch 32 throughput + batch-1 latency), N rounds.
-cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/ab_ln
+cd "$(dirname "$0")/.."; O=${OUT:-out}/ab_ln; mkdir -p $O
 for r in 1 2 3; do
   for f in 0 1; do
-    DINOV2_HIP_LN_FOLD=$f timeout 600 python bench.py --no-cpu-baseline --no-host-buffers "$@" > gpurun_out/ab_ln/b_${f}_$r.json 2> gpurun_out/ab_ln/b_${f}_$r.err
-    python - gpurun_out/ab_ln/b_${f}_$r.json $f <<'PY'
+    DINOV2_HIP_LN_FOLD=$f timeout 600 python bench.py --full --no-cpu-baseline --no-host-buffers "$@" > $O/b_${f}_$r.json 2> $O/b_${f}_$r.err
+    python - $O/b_${f}_$r.json $f <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 k = d.get("kernels", {})

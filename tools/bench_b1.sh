@@ -1,7 +1,7 @@
-cd $GRAFT_REPO_ROOT
-timeout 600 python bench.py --no-cpu-baseline --no-latency --batch 1 --steps 50 --warmup 20 > gpurun_out/b1.json 2> gpurun_out/b1.err; python - <<'PY'
-import json
-d = json.load(open("gpurun_out/b1.json"))
+cd "$(dirname "$0")/.."; O=${OUT:-out}; mkdir -p $O
+timeout 600 python bench.py --full --no-cpu-baseline --no-latency --batch 1 --steps 50 --warmup 20 > $O/b1.json 2> $O/b1.err; python - $O/b1.json <<'PY'
+import json, sys
+d = json.load(open(sys.argv[1]))
 print(d["value"], "img/s", d["ms_per_step"], "ms/step")
 tot = 0
 for k, v in d["kernels"].items():

@@ -12,7 +12,7 @@ for rep in 1 2 3; do
 done
 for v in "product:" "nt4gen4:$V/libdinov2_hip_vnt4.so:4" "g2ntx:$V/libdinov2_hip_vg2ntx.so" "product:" "nt4gen4:$V/libdinov2_hip_vnt4.so:4" "g2ntx:$V/libdinov2_hip_vg2ntx.so"; do
   IFS=: read name lib gen <<< "$v"
-  DINOV2_HIP_LIB=$lib DINOV2_HIP_GEMM_GEN=${gen:-0} python bench.py --steps 20 --windows 3 --no-cpu-baseline --no-latency --no-host-buffers 2>/dev/null | N=$name python -c "
+  DINOV2_HIP_LIB=$lib DINOV2_HIP_GEMM_GEN=${gen:-0} python bench.py --full --steps 20 --windows 3 --no-cpu-baseline --no-latency --no-host-buffers 2>/dev/null | N=$name python -c "
 import json,os,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=j['kernels']; print('bench', os.environ['N'], j['value'], j['effective_clock_ghz'], {n: k[n]['avg_ms'] for n in ('gemm_qkv','gemm_attn_out','gemm_ffn_in','gemm_ffn_out','layernorm')})"
 done
 } 2>&1 | tee gpurun_out/r05_nt/nt_loads2.txt
