@@ -68,6 +68,9 @@ class GroupOpts(C.Structure):
 
 _lib = None
 
+# dinov2_hip_op_attention_ex: a guard row around the device output changed (include/dinov2_hip_ops.h)
+OP_GUARD_CHANGED = -2
+
 
 def set_tuning(key, value):
     """Testing aid (include/dinov2_hip_ops.h): flip one of the library's tuning switches inside this process; 0 = its own choice."""
@@ -170,6 +173,7 @@ def lib():
     L.dinov2_hip_op_im2col.argtypes = [i32, fp, fp, i32, i32, i32, i32, i32, i32]
     L.dinov2_hip_op_ln_fold_vectors.argtypes = [i32, fp, fp, fp, fp, fp, fp, i32, i32]
     L.dinov2_hip_op_attention.argtypes = [i32, fp, fp, i32, i32, i32, i32]
+    L.dinov2_hip_op_attention_ex.argtypes = [i32, fp, fp, i32, i32, i32, i32, i32]
     L.dinov2_hip_op_layernorm.argtypes = [i32, fp, fp, fp, fp, i32, i32, C.c_float]
     L.dinov2_hip_op_convert_weight.argtypes = [i32, vp, C.c_uint64, u32, fp, i32, i32, i32, i32]
     L.dinov2_hip_op_pca_ritz.argtypes = [vp, vp, vp, i32, vp, vp]

@@ -212,15 +212,43 @@ extern "C" int dinov2_hip_op_ln_fold_vectors(int32_t dtype, const float* W, cons
 
 extern "C" int dinov2_hip_op_attention(int32_t dtype, const float* qkv, float* out, int32_t B, int32_t T, int32_t H,
                                        int32_t nh) {
+    return dinov2_hip_op_attention_ex(dtype, qkv, out, B, T, H, nh, 0);
+}
+
+extern "C" int dinov2_hip_op_attention_ex(int32_t dtype, const float* qkv, float* out, int32_t B, int32_t T, int32_t H,
+                                          int32_t nh, int32_t log2_scores) {
     const DType dt = dtype == 1 ? DT_BF16 : DT_F16;
+    if (B <= 0 || T <= 0 || H <= 0) return -1;
+    // the output sits between two guard bands of DINOV2_HIP_OP_GUARD_ROWS rows; the whole buffer starts as 0xffff, a NaN in f16
+    // and in bf16, so a row the kernel never wrote comes back as NaN and a write outside [0, B*T) rows changes a guard byte
+    constexpr size_t G = DINOV2_HIP_OP_GUARD_ROWS;
     DevBuf dQ, dO;
-    const size_t nq = (size_t)B * T * 3 * H, no = (size_t)B * T * H;
+    const size_t nq = (size_t)B * T * 3 * H, no = (size_t)B * T * H, ng = G * (size_t)H;
+    const size_t nall = no + 2 * ng;
     OP_TRY(upload_as(dt, qkv, nq, dQ));
-    OP_TRY(dO.alloc(no * 2));
-    OP_TRY(hipMemset(dO.p, 0, no * 2));
-    OP_TRY(launch_attention(dt, dQ.p, dO.p, B, T, H, nh, false, nullptr));
+    OP_TRY(dO.alloc(nall * 2));
+    OP_TRY(hipMemset(dO.p, 0xff, nall * 2));
+    OP_TRY(launch_attention(dt, dQ.p, (uint16_t*)dO.p + ng, B, T, H, nh, log2_scores != 0, nullptr));
     OP_TRY(hipDeviceSynchronize());
-    OP_TRY(download_as(dt, dO.p, no, out));
+    std::vector<uint16_t> raw(nall);
+    OP_TRY(hipMemcpy(raw.data(), dO.p, nall * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < nall; ++i) {
+        const uint16_t h = raw[i];
+        if (i < ng || i >= ng + no) {
+            if (h != 0xffffu) return DINOV2_HIP_OP_GUARD_CHANGED;
+            continue;
+        }
+        float f;
+        if (dt == DT_F16) {
+            _Float16 x;
+            std::memcpy(&x, &h, 2);
+            f = (float)x;
+        } else {
+            const uint32_t u = (uint32_t)h << 16;
+            std::memcpy(&f, &u, 4);
+        }
+        out[i - ng] = f;
+    }
     return 0;
 }
 

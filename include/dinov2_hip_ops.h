@@ -4,7 +4,8 @@
  * NOT part of the drop-in boundary (that is include/dinov2_hip.h).  These run one hand-written kernel on host f32
  * data (converted to the compute dtype on the way in, back to f32 on the way out) so the parity tests can check each
  * kernel against the oracle in isolation -- the per-op granularity the reference gets from ggml's own op tests and
- * that /root/reference itself never had (it holds no tests at all).  All return 0 on success, -1 on a HIP error.
+ * that /root/reference itself never had (it holds no tests at all).  All return 0 on success, -1 on a HIP error
+ * (dinov2_hip_op_attention_ex: also DINOV2_HIP_OP_GUARD_CHANGED).
  */
 #ifndef DINOV2_HIP_OPS_H
 #define DINOV2_HIP_OPS_H
@@ -41,6 +42,15 @@ int dinov2_hip_op_ln_fold_vectors(int32_t dtype, const float *W, const float *bi
 
 /* fused attention over token-major qkv [B*T, 3H] (q already scaled) -> [B*T, H]; replaces dinov2.cpp:479-543 */
 int dinov2_hip_op_attention(int32_t dtype, const float *qkv, float *out, int32_t B, int32_t T, int32_t H, int32_t nh);
+/* the same with the forward's choice of score domain: log2_scores = 1 runs the instances the forward launches (q pre-scaled by
+ * log2(e)/8 in the QKV epilogue, softmax on exp2, csrc/model.cpp), 0 the natural-exp ones (dinov2_hip_op_attention forwards with 0).
+ * The kernel and its workgroup size follow the "attn_v" / "attn_nwv" switches exactly as in the forward.  The device output is
+ * framed by DINOV2_HIP_OP_GUARD_ROWS rows on either side and the whole buffer starts as 0xffff (NaN in f16 and bf16): a row the
+ * kernel did not write comes back as NaN, and a changed guard byte returns DINOV2_HIP_OP_GUARD_CHANGED instead of 0. */
+#define DINOV2_HIP_OP_GUARD_ROWS 128
+#define DINOV2_HIP_OP_GUARD_CHANGED (-2)
+int dinov2_hip_op_attention_ex(int32_t dtype, const float *qkv, float *out, int32_t B, int32_t T, int32_t H, int32_t nh,
+                               int32_t log2_scores);
 
 /* ggml_norm * w + b (dinov2.cpp:694-700); dtype -1 = f32 output (final layernorm), 0/1 = f16/bf16 output */
 int dinov2_hip_op_layernorm(int32_t dtype, const float *x, const float *w, const float *b, float *out, int32_t rows,
