@@ -176,6 +176,8 @@ def lib():
     L.dinov2_hip_op_attention_ex.argtypes = [i32, fp, fp, i32, i32, i32, i32, i32]
     L.dinov2_hip_op_layernorm.argtypes = [i32, fp, fp, fp, fp, i32, i32, C.c_float]
     L.dinov2_hip_op_convert_weight.argtypes = [i32, vp, C.c_uint64, u32, fp, i32, i32, i32, i32]
+    L.dinov2_hip_op_permute_bias.argtypes = [fp, fp, i32, i32]
+    L.dinov2_hip_op_head.argtypes = [i32, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, C.c_float]
     L.dinov2_hip_op_pca_ritz.argtypes = [vp, vp, vp, i32, vp, vp]
     L.dinov2_hip_op_clock_probe.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.dinov2_hip_op_clock_slots.argtypes = [C.POINTER(C.c_uint64)]

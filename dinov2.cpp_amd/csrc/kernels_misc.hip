@@ -37,11 +37,16 @@ static __device__ __forceinline__ double wave_sum_f64(double v) {
 // LayerNorm: ggml_norm + mul + add  (/root/reference/dinov2.cpp:694-700, 722-728, 756-760)
 // one wave per token row, row kept in registers (H <= 1536 -> <= 6 float4 per lane), statistics in double like
 // ggml (mean, then centred sum of squares), 1/sqrtf(var + eps) in f32.
+// Rounding points, those of ggml's three graph nodes (norm, mul, add each store an f32 tensor): f32(v * scale), then
+// f32(. * w), then f32(. + b), then the store's rounding to OutT.  `fp contract(off)` keeps hipcc from fusing the affine
+// into an FMA; tests/test_gpu_misc_kernels.py (bit-exact against tests/misc_cases.py: ln_emulate) and
+// tests/test_kernel_build_checks.py (same instruction stream as a -ffp-contract=off build) hold it there.
 // ---------------------------------------------------------------------------------------------------------
 template <typename OutT, int MAXV>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         const float* __restrict__ bta, OutT* __restrict__ y, int rows,
                                                         int H, float eps) {
+#pragma clang fp contract(off)  // ggml's rounding points (header above)
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -296,8 +301,12 @@ hipError_t launch_im2col(DType dt, const float* img, void* col, int B, int Hh, i
 // csrc/preprocess.cpp: u8 BGR [B,h,w,3] -> /255 -> bicubic (cv::INTER_CUBIC: A = -0.75, half-pixel centres, clamped
 // taps, horizontal pass first) to rh x rw -> crop (y0, x0, oh, ow) -> (c - mean[2-c]) / std[2-c] -> f32 BGR [B,oh,ow,3].
 // One thread per output pixel; the 16 source pixels of a thread are 4 runs of <= 4 adjacent BGR triples (L2 resident).
+// Rounding points: every operation of the host's (x86-64 baseline: no FMA), taps included -- the kernel's pragma does not
+// reach an inlined helper, so cubic_taps_dev carries its own.  Held bit-equal to dinov2_hip_preprocess by
+// tests/test_gpu_misc_kernels.py and to a -ffp-contract=off build by tests/test_kernel_build_checks.py.
 // ---------------------------------------------------------------------------------------------------------
 static __device__ __forceinline__ void cubic_taps_dev(float t, float w[4]) {
+#pragma clang fp contract(off)  // as csrc/preprocess.cpp: cubic_taps
     const float A = -0.75f;
     w[0] = ((A * (t + 1.f) - 5.f * A) * (t + 1.f) + 8.f * A) * (t + 1.f) - 4.f * A;
     w[1] = ((A + 2.f) * t - (A + 3.f)) * t * t + 1.f;

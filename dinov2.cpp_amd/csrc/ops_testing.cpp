@@ -260,6 +260,7 @@ extern "C" int dinov2_hip_op_layernorm(int32_t dtype, const float* x, const floa
     OP_TRY(dW.alloc((size_t)H * 4));
     OP_TRY(dB.alloc((size_t)H * 4));
     OP_TRY(dO.alloc(n * 4));
+    OP_TRY(hipMemset(dO.p, 0xff, n * 4));  // NaN in f32, f16 and bf16: an element the kernel never wrote comes back as NaN
     OP_TRY(hipMemcpy(dX.p, x, n * 4, hipMemcpyHostToDevice));
     OP_TRY(hipMemcpy(dW.p, w, (size_t)H * 4, hipMemcpyHostToDevice));
     OP_TRY(hipMemcpy(dB.p, b, (size_t)H * 4, hipMemcpyHostToDevice));
@@ -284,9 +285,53 @@ extern "C" int dinov2_hip_op_convert_weight(int32_t dtype, const void* src, uint
     OP_TRY(dS.alloc(src_bytes));
     OP_TRY(hipMemcpy(dS.p, src, src_bytes, hipMemcpyHostToDevice));
     OP_TRY(dO.alloc((size_t)N * Kpad * 2));
+    OP_TRY(hipMemset(dO.p, 0xff, (size_t)N * Kpad * 2));  // NaN: an element the kernel never wrote comes back as NaN
     OP_TRY(launch_convert_weight(dt, dS.p, ggml_type, dO.p, N, K, Kpad, interleaveF, nullptr));
     OP_TRY(hipDeviceSynchronize());
     OP_TRY(download_as(dt, dO.p, (size_t)N * Kpad, out));
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_permute_bias(const float* src, float* dst, int32_t N, int32_t interleaveF) {
+    if (!src || !dst || N <= 0 || interleaveF < 0 || (interleaveF > 0 && N != 2 * interleaveF)) return -1;
+    DevBuf dS, dD;
+    OP_TRY(dS.alloc((size_t)N * 4));
+    OP_TRY(dD.alloc((size_t)N * 4));
+    OP_TRY(hipMemcpy(dS.p, src, (size_t)N * 4, hipMemcpyHostToDevice));
+    OP_TRY(hipMemset(dD.p, 0xff, (size_t)N * 4));
+    OP_TRY(launch_permute_bias((const float*)dS.p, (float*)dD.p, N, interleaveF, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    OP_TRY(hipMemcpy(dst, dD.p, (size_t)N * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// launch_head as csrc/model.cpp runs it after the final LayerNorm, on host f32 data: W [C, 2H] rounded to the compute type as
+// upload_as rounds it (nearest even), every output buffer NaN-filled first.
+extern "C" int dinov2_hip_op_head(int32_t dtype, const float* fin, const float* W, const float* bias, float* feat, float* logits,
+                                  float* probs, int32_t B, int32_t T, int32_t H, int32_t C, int32_t first, float inv_div) {
+    // head_logits_kernel reads W and feat in 8-element pieces: 2H % 8 == 0
+    if (!fin || !W || !bias || !feat || !logits || !probs || B <= 0 || T <= 0 || H <= 0 || H % 4 != 0 || C <= 0 || first < 0 || first > T)
+        return -1;
+    const DType dt = dtype == 1 ? DT_BF16 : DT_F16;
+    DevBuf dF, dW, dB, dFeat, dL, dP;
+    const size_t nf = (size_t)B * T * H, nfeat = (size_t)B * 2 * H, nl = (size_t)B * C;
+    OP_TRY(dF.alloc(nf * 4));
+    OP_TRY(hipMemcpy(dF.p, fin, nf * 4, hipMemcpyHostToDevice));
+    OP_TRY(upload_as(dt, W, (size_t)C * 2 * H, dW));
+    OP_TRY(dB.alloc((size_t)C * 4));
+    OP_TRY(hipMemcpy(dB.p, bias, (size_t)C * 4, hipMemcpyHostToDevice));
+    OP_TRY(dFeat.alloc(nfeat * 4));
+    OP_TRY(dL.alloc(nl * 4));
+    OP_TRY(dP.alloc(nl * 4));
+    OP_TRY(hipMemset(dFeat.p, 0xff, nfeat * 4));
+    OP_TRY(hipMemset(dL.p, 0xff, nl * 4));
+    OP_TRY(hipMemset(dP.p, 0xff, nl * 4));
+    OP_TRY(launch_head(dt, (const float*)dF.p, dW.p, (const float*)dB.p, (float*)dFeat.p, (float*)dL.p, (float*)dP.p, B, T, H, C, first,
+                       inv_div, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    OP_TRY(hipMemcpy(feat, dFeat.p, nfeat * 4, hipMemcpyDeviceToHost));
+    OP_TRY(hipMemcpy(logits, dL.p, nl * 4, hipMemcpyDeviceToHost));
+    OP_TRY(hipMemcpy(probs, dP.p, nl * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -495,6 +540,7 @@ extern "C" int dinov2_hip_op_preprocess_u8(int32_t mode, const uint8_t* bgr, int
     const size_t nsrc = (size_t)B * h * w * 3, ndst = (size_t)B * oh * ow * 3;
     OP_TRY(dS.alloc(nsrc));
     OP_TRY(dD.alloc(ndst * sizeof(float)));
+    OP_TRY(hipMemset(dD.p, 0xff, ndst * sizeof(float)));  // NaN: a pixel the kernel never wrote comes back as NaN
     OP_TRY(hipMemcpy(dS.p, bgr, nsrc, hipMemcpyHostToDevice));
     const int rh = mode == 1 ? 256 : oh, rw = mode == 1 ? 256 : ow;
     OP_TRY(launch_preprocess_u8((const uint8_t*)dS.p, (float*)dD.p, B, h, w, rh, rw, (rh - oh) / 2, (rw - ow) / 2, oh, ow, nullptr));

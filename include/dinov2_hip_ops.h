@@ -56,9 +56,19 @@ int dinov2_hip_op_attention_ex(int32_t dtype, const float *qkv, float *out, int3
 int dinov2_hip_op_layernorm(int32_t dtype, const float *x, const float *w, const float *b, float *out, int32_t rows,
                             int32_t H, float eps);
 
-/* load-time tensor conversion / dequantisation (F32,F16,BF16,Q4_0,Q4_1,Q5_0,Q5_1,Q8_0 -> compute dtype) */
+/* load-time tensor conversion / dequantisation (F32,F16,BF16,Q4_0,Q4_1,Q5_0,Q5_1,Q8_0 -> compute dtype).  interleaveF > 0: N = 2F rows
+ * of a SwiGLU weights_in [x1 (F rows); x2 (F rows)] come out as alternating 32-row blocks x1 | x2 (csrc/model.cpp).  The output
+ * starts as NaN (as do those of the layernorm, preprocess_u8, permute_bias and head entry points). */
 int dinov2_hip_op_convert_weight(int32_t dtype, const void *src, uint64_t src_bytes, uint32_t ggml_type, float *out,
                                  int32_t N, int32_t K, int32_t Kpad, int32_t interleaveF);
+/* the matching bias permutation (permute_bias_kernel): dst[n] = src[source row of weight row n]; interleaveF = 0 copies */
+int dinov2_hip_op_permute_bias(const float *src, float *dst, int32_t N, int32_t interleaveF);
+
+/* the classifier head (launch_head, as csrc/model.cpp runs it after the final LayerNorm; dinov2.cpp:792-821): fin [B, T, H] f32,
+ * W [C, 2H] (rounded to the compute dtype on the way in), bias [C] -> feat [B, 2H] = [T(cls) ; T(f32(f32(sum_{t >= first} fin) * inv_div))]
+ * as f32, logits [B, C], probs [B, C].  H % 4 == 0. */
+int dinov2_hip_op_head(int32_t dtype, const float *fin, const float *W, const float *bias, float *feat, float *logits, float *probs,
+                       int32_t B, int32_t T, int32_t H, int32_t C, int32_t first, float inv_div);
 
 /* what ds_read_b64_tr_b16 hands each lane for addr = lane*8 over an LDS image of its own indices: out[64][4] */
 int dinov2_hip_op_probe_tr16(int16_t *out256);

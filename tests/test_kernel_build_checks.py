@@ -130,3 +130,52 @@ def test_gemm4_no_instruction_touches_a_fragment_before_its_wait(gemm4_asm):
                     used |= _regs(t.split(" ")[0])
                 assert not (used & pending), (name, s, sorted(used & pending))
     assert checked > 1000
+
+
+# ------------------------------------------------------------------------------------------------------------- kernels_misc.hip
+MISC_FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-result", "-Wno-unused-lambda-capture"]  # the Makefile's
+
+
+def misc_instruction_streams(asm_text):
+    """kernel name -> its instructions (comments and directives dropped, branch labels numbered per function)."""
+    out = {}
+    for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end", asm_text, re.S | re.M):
+        ins = []
+        for line in m.group(2).splitlines():
+            s = line.split(";")[0].strip()
+            if s and not s.startswith(".") and not s.endswith(":"):
+                ins.append(re.sub(r"\.LBB\d+_(\d+)", r"L\1", s))
+        out[m.group(1)] = ins
+    return out
+
+
+def compile_misc_both_ways(src, outdir):
+    """Cross-compile `src` with the Makefile's flags and again with -ffp-contract=off (in parallel): (default, contract-off) asm."""
+    outs = [os.path.join(outdir, "misc_default.s"), os.path.join(outdir, "misc_nocontract.s")]
+    procs = [subprocess.Popen([HIPCC, *MISC_FLAGS, *extra, "-x", "hip", "-S", "--cuda-device-only", src, "-o", o],
+                              stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
+             for o, extra in zip(outs, ([], ["-ffp-contract=off"]))]
+    for p in procs:
+        _, err = p.communicate(timeout=600)
+        assert p.returncode == 0, err.decode(errors="replace")[-2000:]
+    return tuple(open(o).read() for o in outs)
+
+
+def fused_kernels(asm_default, asm_nocontract, pattern=r"preprocess_u8_kernel|layernorm_kernel"):
+    """Kernels matching `pattern` whose instruction stream changes when contraction is switched off, and how many matched."""
+    a, b = misc_instruction_streams(asm_default), misc_instruction_streams(asm_nocontract)
+    names = [n for n in a if re.search(pattern, n)]
+    return [n for n in names if a[n] != b.get(n)], len(names)
+
+
+def test_misc_kernels_keep_their_rounding_points(tmp_path):
+    """preprocess_u8_kernel (bit-equal to the host preprocess, which has no FMA) and every layernorm_kernel instance (ggml's three
+    rounding points) must compile to the same instruction stream with and without -ffp-contract=off: hipcc fused nothing the source
+    writes as separate operations -- including in helpers they inline (cubic_taps_dev was one).  On the tree before the two
+    `fp contract(off)` pragmas this failed for all ten kernels."""
+    if not shutil.which(HIPCC):
+        pytest.skip("hipcc not available")
+    src = os.path.join(ROOT, "dinov2.cpp_amd", "csrc", "kernels_misc.hip")
+    fused, n = fused_kernels(*compile_misc_both_ways(src, str(tmp_path)))
+    assert n == 10, n  # preprocess_u8_kernel + layernorm_kernel<f32 | f16 | bf16, MAXV 2 | 4 | 8>
+    assert not fused, "contracted into FMAs: %s" % fused
