@@ -134,18 +134,6 @@ static __device__ __forceinline__ float max32(const f32x16 (&s)[2]) {
 #ifndef DINO_PREC
 #define DINO_PREC 0  // tuning builds: which operand roundings attention_kernel removes (gemm.hip, "DINO_PREC"); 0 in the product
 #endif
-#ifndef DINO_ATT_LOADER
-#define DINO_ATT_LOADER 0  // attention_kernel, tuning builds (profiles/r05_attention_loader.md): a LOADER wave issues every global_load_lds of the K / V
-                           // ring, the compute waves none.  1: 4 compute + 1 loader, registers capped for four such workgroups per CU (96);
-                           // 3: the same at 128 registers (three workgroups per CU); 2: 3 compute + 1 loader at 128 registers (96-query blocks)
-#endif
-#ifndef DINO_ATT_ABL
-#define DINO_ATT_ABL 0  // attention2_kernel, timing-only ablations (WRONG results): 1 no exp, 2 no staging, 4 no barrier, 8 no V
-                        // reads, 16 no K reads.  The same study of attention_kernel: tools/probes/attention_abl.hip
-#endif
-#ifndef DINO_ATT3_WAVES
-#define DINO_ATT3_WAVES 2  // waves per workgroup of the 64-queries-per-wave kernel (2: 128-query blocks, 4: 256-query blocks)
-#endif
 
 // LOG2: scores arrive multiplied by log2(e) (folded into the q scale by the QKV epilogue), so p = exp2(s - m) needs no
 // multiply.  launch_bounds(256, 2): allow up to 256 VGPRs -- with the default budget hipcc parked 128 values in AGPRs
@@ -156,11 +144,7 @@ static __device__ __forceinline__ float max32(const f32x16 (&s)[2]) {
 // half the LDS bytes per MFMA for twice the registers (two waves per SIMD).  Per query the arithmetic is the same instruction
 // sequence in the same order, so QB does not change a single bit of the result.
 template <typename T, bool LOG2, int NWV, int QB = 1>
-#if DINO_ATT_LOADER
-__global__ __launch_bounds__((NWV + 1) * 64, DINO_ATT_LOADER == 1 ? 5 : DINO_ATT_LOADER == 2 ? 4 : 3) void attention_kernel(
-#else
 __global__ __launch_bounds__(NWV * 64, QB == 2 ? 2 : (NWV == 8 ? 4 : 2)) void attention_kernel(
-#endif
     const T* __restrict__ qkv, T* __restrict__ out, int Ttok, int H) {
     using E = Elem<T>;
     using vec8 = typename E::vec8;
@@ -219,22 +203,14 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 2 : (NWV == 8 ? 4 : 2)) void at
     // 32-bit byte offsets from the (image, head) K base, advanced by one tile per step and clamped to the last key (tail rows
     // re-read it and are masked below): 2 VALU per instruction instead of a 64-bit multiply-add chain.
     const int srow = lane >> 3;
-#if DINO_ATT_LOADER
-    constexpr int SI = 8;         // the loader wave (wid == NWV) moves all eight 8-row pieces of K and of V
-    constexpr int SW = 1;         // piece j covers rows 8 j .. 8 j + 7
-    const int swid = 0;
-#else
     constexpr int SI = 8 / NWV;
-    constexpr int SW = NWV;
-    const int swid = wid;
-#endif
     const char* kbase = base + ((size_t)h * 64 + H) * 2;
     const unsigned rowb = (unsigned)H3 * 2u;
     const char* vbase = kbase + (size_t)H * 2;
     unsigned stoff[SI], stmax[SI];
 #pragma unroll
     for (int j = 0; j < SI; ++j) {
-        const int r = (j * SW + swid) * 8 + srow;
+        const int r = (j * NWV + wid) * 8 + srow;
         const unsigned lc = ((lane & 7) ^ ((r >> 1) & 7)) * 16;
         stoff[j] = (unsigned)r * rowb + lc;
         stmax[j] = (unsigned)(Ttok - 1) * rowb + lc;
@@ -242,11 +218,6 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 2 : (NWV == 8 ? 4 : 2)) void at
     // The V tile has its own chunk swizzle (see vaddr below): chunk ^ (((row >> 1) & 1) << 2) instead of K's
     // chunk ^ ((row >> 1) & 7).  Both depend on the lane only (row >> 1 = 4 * (j * NWV + wid) + (lane >> 4)), and the chunk
     // index is bits 6:4 of the source offset, so V's source offset is K's with those bits XORed by a per-lane constant.
-#if DINO_ATT_LOADER
-    unsigned vswzj[SI];  // (row >> 1 = 4 j + (lane >> 4): the piece's parity replaces the wave's)
-#pragma unroll
-    for (int j = 0; j < SI; ++j) vswzj[j] = (unsigned)((((j & 1) << 2) | ((lane >> 4) & 3)) ^ (((lane >> 4) & 1) << 2)) << 4;
-#endif
     const unsigned vswz = (unsigned)((((wid & 1) << 2) | ((lane >> 4) & 3)) ^ (((lane >> 4) & 1) << 2)) << 4;
     auto stage = [&](int buf, int jt) {  // tiles are staged in order: jt only documents which one this call fetches
         char* sK = smem + buf * 2 * TILEB;
@@ -255,10 +226,6 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 2 : (NWV == 8 ? 4 : 2)) void at
         for (int j = 0; j < SI; ++j) {
             const unsigned off = stoff[j] < stmax[j] ? stoff[j] : stmax[j];
             stoff[j] += KT * rowb;
-#if DINO_ATT_LOADER
-            glds16(kbase + off, sK + j * 8 * ROWB);
-            glds16(vbase + (off ^ vswzj[j]), sV + j * 8 * ROWB);
-#else
             glds16(kbase + off, sK + (j * NWV + wid) * 8 * ROWB);  // uniform base + 32-bit lane offset: scalar-base loads
             glds16(vbase + (off ^ vswz), sV + (j * NWV + wid) * 8 * ROWB);
 #if DINO_PREC & 8
@@ -266,7 +233,6 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 2 : (NWV == 8 ? 4 : 2)) void at
 #endif
 #if DINO_PREC & 16
             glds16(vbase + (size_t)3 * H * 2 + (off ^ vswz), sV + 4 * TILEB + (j * NWV + wid) * 8 * ROWB);
-#endif
 #endif
         }
     };
@@ -321,9 +287,7 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 2 : (NWV == 8 ? 4 : 2)) void at
         DINO_TS(0)
         __syncthreads();
         DINO_TS(1)
-#if !DINO_ATT_LOADER
         if (!MASKED) stage((jt + 1) & 1, jt + 1);
-#endif
         if (idle_wave) return;  // a wave whose 32 queries all lie past the last token only helps with staging and barriers
         const char* sK = smem + (jt & 1) * 2 * TILEB;
         const char* sV = sK + TILEB;
@@ -457,18 +421,7 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 2 : (NWV == 8 ? 4 : 2)) void at
         __builtin_amdgcn_s_setprio(0);
         DINO_TS(5)
     };
-#if DINO_ATT_LOADER
-    if (wid == NWV) {  // the loader wave: one tile ahead of the compute waves, the same barriers, nothing else
-        stage(0, 0);
-        for (int jt = 0; jt < ntiles; ++jt) {
-            __syncthreads();
-            if (jt + 1 < ntiles) stage((jt + 1) & 1, jt + 1);
-        }
-        return;
-    }
-#else
     stage(0, 0);
-#endif
     for (int jt = 0; jt + 1 < ntiles; ++jt) tile(jt, std::false_type{});
     tile(ntiles - 1, std::true_type{});
     DINO_TS_FLUSH
@@ -504,10 +457,6 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 2 : (NWV == 8 ? 4 : 2)) void at
 // further ahead than V.  The instruction order is written out in groups (one MFMA + its share of VALU + the LDS reads for
 // later groups) and pinned with sched_barrier, so that hipcc neither clusters the MFMAs nor sinks the reads to their uses.
 #define DINO_SB() __builtin_amdgcn_sched_barrier(0)
-#ifndef DINO_ATT_LSUM
-#define DINO_ATT_LSUM 0  // 1: softmax denominators on the matrix core (l += ones x P^T, one extra MFMA per 16 keys).  Sums the
-                        // f16-rounded probabilities, so it is NOT bit-identical to attention_kernel: off by default
-#endif
 // QB = 32-query blocks per wave, NWV = waves per workgroup.  <1, 4>: the batch-1 kernel (2 waves per SIMD).  <2, 2>: 64 queries per
 // wave, ONE wave per SIMD with the whole 512-entry register file (two 128-query workgroups per CU): every K / V^T fragment read
 // from LDS feeds two MFMAs (half the LDS bytes per MFMA) and the MFMA / softmax overlap happens inside the wave's own instruction
@@ -519,14 +468,12 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(c
     using vec8 = typename E::vec8;
     using vec4 = typename E::vec4;
     constexpr int KT = 64, ROWB = 128, TILEB = KT * ROWB;
-    constexpr bool LSUM = DINO_ATT_LSUM != 0;
     constexpr int QW = 32 * QB, WGQ = NWV * QW;  // queries per wave / per workgroup
     constexpr int SI = (8 + NWV - 1) / NWV;      // 8-row staging pieces per wave, for K and for V (three waves: 3, 3, 2)
     // K/V ring depth.  Two slots (the batch-1 kernel): a tile is staged one step before its use, and the other waves of the SIMD
     // cover what is left of its latency.  Three slots (one wave per SIMD: nobody covers anything): a tile is staged TWO steps ahead
     // and the step begins with a counted wait that leaves the newest tile's loads in flight.
     constexpr int RD = QB == 2 ? 3 : 2;
-    static_assert(!LSUM || QB == 1, "the matrix-core row sums exist for the single-block kernel only");
     __shared__ __attribute__((aligned(16))) char smem[RD * 2 * TILEB];  // [slot][K|V]
 
     const int tid = threadIdx.x;
@@ -611,18 +558,13 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(c
         }
         return vf;
     };
-    auto ex2 = [](float x) { return (DINO_ATT_ABL & 1) ? x * 0.5f : LOG2 ? __builtin_amdgcn_exp2f(x) : __expf(x); };
+    auto ex2 = [](float x) { return LOG2 ? __builtin_amdgcn_exp2f(x) : __expf(x); };
 
-    f32x16 o[QB][2], negm[QB], lacc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) lacc[r] = 0.f;
+    f32x16 o[QB][2], negm[QB];
 #pragma unroll
     for (int u = 0; u < QB; ++u)
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[u][0][r] = o[u][1][r] = negm[u][r] = 0.f;
-    vec8 ones;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ones[j] = E::from_f32(1.0f);
     float m_run[QB], l_run[QB];
 #pragma unroll
     for (int u = 0; u < QB; ++u) m_run[u] = l_run[u] = 0.f;
@@ -649,7 +591,6 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(c
             for (int r = 0; r < 16; ++r) {
                 o[u][0][r] *= alpha;
                 o[u][1][r] *= alpha;
-                if (LSUM) lacc[r] *= alpha;
                 negm[u][r] = -m_run[u];
                 s[0][r] -= d;
                 s[1][r] -= d;
@@ -673,23 +614,21 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(c
 #pragma unroll
     for (int i = 0; i < 4; ++i) vad[i >> 1][i & 1] = lds0 + vaddr[i >> 1][i & 1];
 #define DINO_KRD(DST, ADDR, OFF)                                                                             \
-    if (!(DINO_ATT_ABL & 16)) {                                                                              \
+    {                                                                                                        \
         if constexpr (QB == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(DST) : "v"(ADDR), "n"(OFF)); \
         else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF));                \
     }
 #define DINO_VRD(DST, ADDR, OFF) \
-    if (!(DINO_ATT_ABL & 8)) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF))
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF))
     auto iter = [&](int jt, f32x16(&cur)[QB][2], f32x16(&nxt)[QB][2], auto mask_tag, auto par_tag) {
         constexpr bool MASKNEXT = decltype(mask_tag)::value;
         constexpr int PAR = decltype(par_tag)::value;
         constexpr int KOFF = RD == 2 ? ((PAR + 1) & 1) * 2 * TILEB : 0;  // K_{jt+1}
         constexpr int VOFF = RD == 2 ? PAR * 2 * TILEB + TILEB : 0;      // V_jt
         DINO_TS(0)
-        if (!(DINO_ATT_ABL & 4)) {
-            if constexpr (RD == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * SI) : "memory");  // all but the previous step's loads (K_{jt+2}, V_{jt+1})
-            __syncthreads();  // K_{jt+1}, V_jt landed; the slots of K_jt, V_{jt-1} are free
-        }
+        if constexpr (RD == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * SI) : "memory");  // all but the previous step's loads (K_{jt+2}, V_{jt+1})
+        __syncthreads();  // K_{jt+1}, V_jt landed; the slots of K_jt, V_{jt-1} are free
         DINO_TS(1)
         // ring slots of this step: K_{jt+1} / V_jt are read, K_{jt+RD} / V_{jt+RD-1} are staged.  Two slots: compile-time parity,
         // LDS offsets are immediates.  Three slots: run-time offsets added to the eight fragment address registers.
@@ -715,13 +654,6 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(c
         }
         vec8 kf[8], pf[QB][4];
         s16x4 vl[8], vh[8];
-        if (DINO_ATT_ABL & 24) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                kf[i] = qf[0][i & 3];
-                vl[i] = vh[i] = __builtin_bit_cast(s16x4, (double)jt);
-            }
-        }
         DINO_KRD(kf[0], kA[0], KOFF);
         DINO_KRD(kf[1], kA[1], KOFF);
         DINO_KRD(kf[2], kA[2], KOFF);
@@ -753,7 +685,7 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(c
                     const int idx = (G) * 4 + j;                                                             \
                     const float pv = ex2(cur[u][idx >> 4][idx & 15]);                                        \
                     cur[u][idx >> 4][idx & 15] = pv;                                                         \
-                    if (!LSUM) ps[u][j] += pv;                                                               \
+                    ps[u][j] += pv;                                                                          \
                 }                                                                                            \
                 if (((G) & 1) && (G) < 4) {                                                                  \
                     _Pragma("unroll") for (int j = 0; j < 8; ++j)                                            \
@@ -772,20 +704,18 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(c
                     DINO_SB();                                                                               \
                 }                                                                                            \
             }                                                                                                \
-            if (LSUM && ((G) & 1)) lacc = E::mfma32(ones, pf[0][(G) >> 1], lacc);                            \
-            if (!(DINO_ATT_ABL & 2)) {  /* K_{jt+RD} and V_{jt+RD-1}: the loads go out under the MFMAs */     \
-                if (SI == 2) {                                                                               \
-                    if ((G) == 0) stage_k1(kst, 0);                                                          \
-                    if ((G) == 1) stage_k1(kst, 1);                                                          \
-                    if ((G) == 2) stage_v1(vst, 0);                                                          \
-                    if ((G) == 3) stage_v1(vst, 1);                                                          \
-                } else if (SI == 3) {                                                                        \
-                    if ((G) < 3) stage_k1(kst, (G));                                                         \
-                    else if ((G) < 6) stage_v1(vst, (G) - 3);                                                \
-                } else {                                                                                     \
-                    if ((G) < 4) stage_k1(kst, (G) & (SI - 1));                                              \
-                    else stage_v1(vst, ((G) - 4) & (SI - 1));                                                \
-                }                                                                                            \
+            /* K_{jt+RD} and V_{jt+RD-1}: the loads go out under the MFMAs */                                \
+            if (SI == 2) {                                                                                   \
+                if ((G) == 0) stage_k1(kst, 0);                                                              \
+                if ((G) == 1) stage_k1(kst, 1);                                                              \
+                if ((G) == 2) stage_v1(vst, 0);                                                              \
+                if ((G) == 3) stage_v1(vst, 1);                                                              \
+            } else if (SI == 3) {                                                                            \
+                if ((G) < 3) stage_k1(kst, (G));                                                             \
+                else if ((G) < 6) stage_v1(vst, (G) - 3);                                                    \
+            } else {                                                                                         \
+                if ((G) < 4) stage_k1(kst, (G) & (SI - 1));                                                  \
+                else stage_v1(vst, ((G) - 4) & (SI - 1));                                                    \
             }                                                                                                \
             if ((G) < 4) DINO_KRD(kf[((G) + 4) & 7], kA[(G) & 3], KOFF + 4096);                              \
             DINO_VRD(vl[G], vA[0][(G) & 1], VOFF + ((G) >> 1) * 16 * ROWB);                                  \
@@ -794,10 +724,8 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(c
         }
         DINO_GROUP(0) DINO_GROUP(1) DINO_GROUP(2) DINO_GROUP(3) DINO_GROUP(4) DINO_GROUP(5) DINO_GROUP(6) DINO_GROUP(7)
 #undef DINO_GROUP
-        if (!LSUM) {
 #pragma unroll
-            for (int u = 0; u < QB; ++u) l_run[u] += (ps[u][0] + ps[u][1]) + (ps[u][2] + ps[u][3]);
-        }
+        for (int u = 0; u < QB; ++u) l_run[u] += (ps[u][0] + ps[u][1]) + (ps[u][2] + ps[u][3]);
         DINO_TS(2)
         if constexpr (MASKNEXT) {
 #pragma unroll
@@ -848,7 +776,6 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(c
                     ps[u][j & 3] += pv;
                     pf[u][j] = E::from_f32(pv);
                 }
-            if (LSUM) lacc = E::mfma32(ones, pf[0], lacc);
 #pragma unroll
             for (int db = 0; db < 2; ++db) {
                 const vec8 vf = read_vt(sV, t, db);
@@ -856,10 +783,8 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(c
                 for (int u = 0; u < QB; ++u) o[u][db] = E::mfma32(vf, pf[u], o[u][db]);
             }
         }
-        if (!LSUM) {
 #pragma unroll
-            for (int u = 0; u < QB; ++u) l_run[u] += (ps[u][0] + ps[u][1]) + (ps[u][2] + ps[u][3]);
-        }
+        for (int u = 0; u < QB; ++u) l_run[u] += (ps[u][0] + ps[u][1]) + (ps[u][2] + ps[u][3]);
     };
 
     // prologue: K_0, V_0, K_1 (and, with three slots, V_1, K_2) in flight; scores of tile 0 (needs K_0 only)
@@ -921,8 +846,7 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(c
     DINO_CLK_END(g_clk_att, CLK_ATTENTION)
 #pragma unroll
     for (int u = 0; u < QB; ++u) {
-        // with LSUM every element of lacc is the full row sum (both lane halves included)
-        const float l_tot = LSUM ? lacc[0] : l_run[u] + __shfl_xor(l_run[u], 32);
+        const float l_tot = l_run[u] + __shfl_xor(l_run[u], 32);
         const float inv = 1.0f / l_tot;
         const int qrow = qrow0 + 32 * u;
         if (qrow < Ttok) {
@@ -1012,7 +936,7 @@ static hipError_t launch_attention_impl(DType dt, const void* qkv, void* out, in
         return hipGetLastError();
     }
     if (ver == 3) {  // 64 queries per wave, NWQ waves per workgroup
-        constexpr int NWQ = DINO_ATT3_WAVES;
+        constexpr int NWQ = 2;
         const dim3 grid3(((T + NWQ * 64 - 1) / (NWQ * 64)) * nh * B), block3(NWQ * 64);
 #define DINO_ATT3(TT, LG) hipLaunchKernelGGL((attention_kernel<TT, LG, NWQ, 2>), grid3, block3, 0, st, (const TT*)qkv, (TT*)out, T, H)
         if (dt == DT_F16) { if (log2_scores) DINO_ATT3(_Float16, true); else DINO_ATT3(_Float16, false); }
@@ -1020,16 +944,9 @@ static hipError_t launch_attention_impl(DType dt, const void* qkv, void* out, in
 #undef DINO_ATT3
         return hipGetLastError();
     }
-#if DINO_ATT_LOADER
-    constexpr int cw = DINO_ATT_LOADER == 2 ? 3 : 4;  // compute waves; one loader wave on top
-    const dim3 grid(((T + cw * 32 - 1) / (cw * 32)) * nh * B), block((cw + 1) * 64);
-#define DINO_ATT(TT, LG, NW) \
-    hipLaunchKernelGGL((attention_kernel<TT, LG, cw>), grid, block, 0, st, (const TT*)qkv, (TT*)out, T, H)
-#else
     const dim3 grid(((T + nwv * 32 - 1) / (nwv * 32)) * nh * B), block(nwv * 64);
 #define DINO_ATT(TT, LG, NW) \
     hipLaunchKernelGGL((attention_kernel<TT, LG, NW>), grid, block, 0, st, (const TT*)qkv, (TT*)out, T, H)
-#endif
 #define DINO_ATT_N(TT, LG) { DINO_ATT(TT, LG, 4); }
     if (dt == DT_F16) { if (log2_scores) DINO_ATT_N(_Float16, true) else DINO_ATT_N(_Float16, false) }
     else { if (log2_scores) DINO_ATT_N(__bf16, true) else DINO_ATT_N(__bf16, false) }

@@ -94,10 +94,7 @@ static __device__ __forceinline__ void gemm2_body(const GemmArgs& p, char* smem)
     // logical tile id -> (m0, n0): groups of GM row panels are swept column by column, so the 32 tiles an XCD runs side
     // by side form an 8 x 4 patch (8 activation panels + 4 weight panels live in its L2) instead of 2 x 16
     // (2 + 16 panels): ~1.5x less refill traffic per K step.  Pure speed choice.
-#ifndef DINO_GEMM_GM
-#define DINO_GEMM_GM 8  // (tuning builds: -DDINO_GEMM_GM=4|16|32; traffic and time of each in profiles/r03_gemm_notes.md section 4)
-#endif
-    constexpr int GM = DINO_GEMM_GM;
+    constexpr int GM = 8;
     auto tile_mn = [&](int lid, int& m0, int& n0) {
         const int g = lid / (GM * ntn), r = lid - g * (GM * ntn);
         const int gm = ntm - g * GM < GM ? ntm - g * GM : GM;
@@ -139,13 +136,6 @@ static __device__ __forceinline__ void gemm2_body(const GemmArgs& p, char* smem)
         const bool half8 = h == 1 && RX1 == 32;
         if (h == 1 && ONE) return;
         char* dst = smem + buf * BUF + (ONE && h >= 2 ? h - 1 : h) * 16384 + (half8 ? wid : 2 * wid) * 1024;
-#ifdef DINO_GEMM2_NTX  // tuning builds: non-temporal LDS-DMA for the X pieces of the residual epilogue (profiles/r05_gemm4_nt_loads.txt)
-        if (EPI == EPI_RESID && h < 2) {
-            __builtin_amdgcn_global_load_lds((const DINO_GLOBAL_AS void*)(base + src[h][0]), (DINO_LDS_AS void*)dst, 16, 0, 2);
-            if (!half8) __builtin_amdgcn_global_load_lds((const DINO_GLOBAL_AS void*)(base + src[h][1]), (DINO_LDS_AS void*)(dst + 1024), 16, 0, 2);
-            return;
-        }
-#endif
         glds16(base + src[h][0], dst);
         if (!half8) glds16(base + src[h][1], dst + 1024);
     };
@@ -369,14 +359,9 @@ static __device__ __forceinline__ void gemm2_body(const GemmArgs& p, char* smem)
             // fall inside a 256-column tile
             const float qs = (EPI == EPI_QKV && n0 + ww * 64 < p.qcols) ? p.qscale : 1.0f;
             constexpr int BN_ = EPI == EPI_SWIGLU ? 1 : 2;
-            // SUBP sub-passes per token half.  1: 64 rows through the wave's whole 8 KiB slice.  2 (the epilogues with real VALU work
-            // per element): 32 rows through alternating 4 KiB halves of the slice, so that the stores of one sub-pass and the
-            // arithmetic of the next are independent and the two waves of a SIMD -- which share its VALU -- fall out of step.
-#ifdef DINO_EPI_SPLIT
-            constexpr int SUBP = EPI == EPI_SWIGLU ? 1 : 2;
-#else
+            // SUBP = 1 sub-pass per token half: 64 rows through the wave's whole 8 KiB slice.  (The sub-pass form stays: written as a
+            // plain loop over the token halves, the same code compiles to a different instruction order.)
             constexpr int SUBP = 1;
-#endif
             constexpr int IPS = 4 / SUBP;  // 16-row blocks per sub-pass
 #pragma unroll
             for (int sp = 0; sp < 2 * SUBP; ++sp) {
@@ -400,8 +385,11 @@ static __device__ __forceinline__ void gemm2_body(const GemmArgs& p, char* smem)
                         for (int i = ih * IPS; i < (ih + 1) * IPS; ++i) {
                             if (q == 1 && i >= NI1) continue;  // 192-row tiles: the second pass has 32 rows
                             vec4 o;
-#ifndef DINO_GELU_SCALAR
                             if constexpr (EPI == EPI_GELU) {
+                                // ggml semantics: y = table[f16(x)], table[h] = f16(gelu_tanh(f32(h))).
+                                // 0.5 x (1 + tanh u) == x / (1 + exp(-2u)); the reference's x <= -10 -> 0 and
+                                // x >= 10 -> x branches fall out of the formula after the f16 roundings (exp -> inf
+                                // gives -0, exp -> 0 gives x), so no compares are needed.
                                 // Two columns per instruction: the bias add, x^2, the cubic, 1 + 2^t and the final product
                                 // run as v_pk_*_f32 (IEEE results identical to the scalar ops of gemm.hip, so both kernels
                                 // still agree bit for bit); v_exp / v_rcp / the f16 conversions stay per element.
@@ -423,7 +411,6 @@ static __device__ __forceinline__ void gemm2_body(const GemmArgs& p, char* smem)
                                     o[2 * e2 + 1] = E::from_f32((float)(_Float16)gl[1]);
                                 }
                             } else
-#endif
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
                                 float v = acc[q][b][i][j][e] + bb[e];
@@ -436,22 +423,12 @@ static __device__ __forceinline__ void gemm2_body(const GemmArgs& p, char* smem)
                                     float vq = v * qs;
                                     asm("" : "+v"(vq));
                                     o[e] = E::from_f32(vq);
-                                } else if constexpr (EPI == EPI_SWIGLU) {
-                                    // W rows interleaved in 32-blocks: column half 0 holds x1[32 units], half 1 holds x2 of the same units
+                                } else {
+                                    // EPI_SWIGLU: W rows interleaved in 32-blocks: column half 0 holds x1[32 units], half 1 holds x2 of the same units
                                     const float h2 = acc[q][1][i][j][e] + b2[e];
                                     float sg = v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)) * h2;  // silu(x1) * x2
                                     asm("" : "+v"(sg));
                                     o[e] = E::from_f32(sg);
-                                } else {
-                                    // EPI_GELU, ggml semantics: y = table[f16(x)], table[h] = f16(gelu_tanh(f32(h))).
-                                    // 0.5 x (1 + tanh u) == x / (1 + exp(-2u)); the reference's x <= -10 -> 0 and
-                                    // x >= 10 -> x branches fall out of the formula after the f16 roundings (exp -> inf
-                                    // gives -0, exp -> 0 gives x), so no compares are needed.
-                                    const float xr = (float)(_Float16)v;
-                                    const float t = xr * __builtin_fmaf(xr * xr, -0.1029432397f, -2.302208199f);  // -2 log2(e) u
-                                    float gl = xr * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t));
-                                    asm("" : "+v"(gl));
-                                    o[e] = E::from_f32((float)(_Float16)gl);
                                 }
                             }
                             const int row = (i - ih * IPS) * 16 + er;  // row within the sub-pass
