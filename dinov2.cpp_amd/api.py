@@ -98,6 +98,21 @@ def gemm_plan(dtype, epilogue, M, N, K):
     return buf.value.decode()
 
 
+PLAN_PART_FIELDS = ("step", "part", "row0", "rows", "col0", "cols", "M", "N", "K", "ldo", "qcols", "nt_out", "clk_slot", "ln_gs",
+                    "whole_nt_out", "whole_clk_slot", "whole_ln_gs",
+                    "off_A", "off_W", "off_bias", "off_aux", "off_out", "off_xg", "off_stats", "off_ln_gamma", "off_ln_s", "off_ln_c")
+
+
+def gemm_plan_parts(dtype, epilogue, M, N, K):
+    """The same plan as data (dinov2_hip_op_gemm_plan_parts): one dict per argument block a kernel of the plan is launched with."""
+    nf = len(PLAN_PART_FIELDS)
+    buf = (C.c_int64 * (8 * nf))()
+    n = lib().dinov2_hip_op_gemm_plan_parts(int(dtype), int(epilogue), int(M), int(N), int(K), buf, 8)
+    if n < 0:
+        raise ValueError(f"launch_gemm refuses dtype={dtype} epilogue={epilogue} M={M} N={N} K={K}")
+    return [dict(zip(PLAN_PART_FIELDS, buf[i * nf:(i + 1) * nf])) for i in range(n)]
+
+
 def lib():
     """Load libdinov2_hip.so; raise loudly if it is not built (no CPU fallback exists)."""
     global _lib
@@ -190,6 +205,7 @@ def lib():
     L.dinov2_hip_op_set_tuning.argtypes = [cp, i32]
     L.dinov2_hip_op_get_tuning.argtypes = [cp]
     L.dinov2_hip_op_gemm_plan.argtypes = [i32, i32, i32, i32, i32, C.c_char_p, i32]
+    L.dinov2_hip_op_gemm_plan_parts.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64), i32]
     _lib = L
     return L
 

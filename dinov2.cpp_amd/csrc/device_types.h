@@ -71,7 +71,7 @@ enum ClockSlot : int { CLK_QKV = 0, CLK_ATTN_OUT = 1, CLK_FFN_IN = 2, CLK_FFN_OU
         atomicAdd(&(ARR)[(SLOT) * 4 + 3], 1ull);                                                 \
     }
 // which slot a GEMM launch belongs to (EPI: kernels.h Epilogue incl. the LN-fold variants; the residual epilogue serves attn-out, K = N, and
-// FFN-out, K > N).  Evaluated ONCE per logical launch by launch_gemm on the caller's N and K (GemmArgs::clk_slot): the parts of a split
+// FFN-out, K > N).  Evaluated ONCE per logical launch by gemm_plan (gemm.hip) on the caller's N and K (GemmArgs::clk_slot): the parts of a split
 // launch see a smaller N (ViT-S attn-out, N = 384 -> 256 + 128, was counted as FFN-out).
 #define DINO_CLK_GEMM_SLOT(EPI, N, K)                                                                                             \
     (((EPI) == 1 || (EPI) == 7) ? CLK_QKV : ((EPI) == 2 || (EPI) == 6) ? ((K) > (N) ? CLK_FFN_OUT : CLK_ATTN_OUT)                   \

@@ -16,12 +16,14 @@
 //     again on the ds_read address: 16-byte chunk c of row r lives at chunk c ^ ((r >> 1) & 7), which makes every
 //     16-lane ds_read_b128 group hit 16 distinct bank slots.
 //   * 1-D grid with an XCD-aware remap so tiles that share an A row-panel run on the same XCD (shared L2).
+//
+// Host side, below the kernel: gemm_plan decides which kernels of this file, gemm2.hip and gemm4.hip run a problem and which rows and columns
+// each of them covers, as data (GemmPlan, kernels.h); launch_gemm launches that plan's steps, gemm_plan_describe prints them.  The rules of
+// kernel choice, with their measurements, are written next to plan_rows and small_cfg.
 #include <atomic>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
-#include <string>
 
 #include "device_types.h"
 #include "kernels.h"
@@ -505,35 +507,32 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs p) {
     DINO_SP_FLUSH
 }
 
+// The epilogues of the small-tile kernel, written ONCE: launch_cfg and set_attr_cfg both take their kernel from this selector, so a kernel
+// that can be launched always has its LDS limit raised.
+#define DINO_SMALL_EPIS(X) \
+    X(EPI_PATCH) X(EPI_QKV) X(EPI_RESID) X(EPI_GELU) X(EPI_SWIGLU) X(EPI_PLAIN_F32) X(EPI_RESID_LN) X(EPI_QKV_LN) X(EPI_GELU_LN) X(EPI_SWIGLU_LN)
+template <typename T, int BM, int BN, int WM, int WN, int NST, int KSUB>
+static GemmKernelFn small_kernel(int epi) {
+    switch (epi) {
+#define DINO_X(E)                                                                                                                       \
+    case E: /* (SwiGLU's column pairing needs 64-wide wave tiles) */                                                                    \
+        if constexpr (BN / WN == 64 || (E != EPI_SWIGLU && E != EPI_SWIGLU_LN)) return gemm_kernel<T, BM, BN, WM, WN, NST, E, KSUB>; \
+        else return nullptr;
+        DINO_SMALL_EPIS(DINO_X)
+#undef DINO_X
+        default: return nullptr;
+    }
+}
+
 template <typename T, int BM, int BN, int WM, int WN, int NST, int KSUB = 1>
 static hipError_t launch_cfg(Epilogue epi, const GemmArgs& a, hipStream_t st) {
+    const GemmKernelFn k = small_kernel<T, BM, BN, WM, WN, NST, KSUB>(epi);
+    if (!k) return hipErrorInvalidValue;
     const int ntn = (a.N + BN - 1) / BN, ntm = (a.M + BM - 1) / BM;
     const dim3 grid(ntn * ntm), block(WM * WN * 64);
     const size_t lds = NST * KSUB * (size_t)(BM + BN) * 128 + (epi == EPI_RESID_LN ? (size_t)BM * (BN / 16) * 8 : 0) +
                        (epi_ln_consumer(epi) ? (size_t)BM * a.ln_gs * 8 : 0);
-#define DINO_LAUNCH(E)                                                                             \
-    case E:                                                                                        \
-        hipLaunchKernelGGL((gemm_kernel<T, BM, BN, WM, WN, NST, E, KSUB>), grid, block, lds, st, a); \
-        break;
-    switch (epi) {
-        DINO_LAUNCH(EPI_PATCH)
-        DINO_LAUNCH(EPI_QKV)
-        DINO_LAUNCH(EPI_RESID)
-        DINO_LAUNCH(EPI_GELU)
-        DINO_LAUNCH(EPI_PLAIN_F32)
-        DINO_LAUNCH(EPI_RESID_LN)
-        DINO_LAUNCH(EPI_QKV_LN)
-        DINO_LAUNCH(EPI_GELU_LN)
-        case EPI_SWIGLU:  // (its column pairing needs 64-wide wave tiles)
-            if constexpr (BN / WN == 64) hipLaunchKernelGGL((gemm_kernel<T, BM, BN, WM, WN, NST, EPI_SWIGLU, KSUB>), grid, block, lds, st, a);
-            else return hipErrorInvalidValue;
-            break;
-        case EPI_SWIGLU_LN:
-            if constexpr (BN / WN == 64) hipLaunchKernelGGL((gemm_kernel<T, BM, BN, WM, WN, NST, EPI_SWIGLU_LN, KSUB>), grid, block, lds, st, a);
-            else return hipErrorInvalidValue;
-            break;
-    }
-#undef DINO_LAUNCH
+    hipLaunchKernelGGL(k, grid, block, lds, st, a);
 #ifdef DINO_GEMM_SPROF
     {
         unsigned long long h[8], z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -568,60 +567,57 @@ static hipError_t launch_cfg(Epilogue epi, const GemmArgs& a, hipStream_t st) {
 
 template <typename T, int BM, int BN, int WM, int WN, int NST, int KSUB = 1>
 static hipError_t set_attr_cfg() {
-    const int lds = NST * KSUB * (BM + BN) * 128 + BM * LN_MAX_GROUPS * 8;  // (+ the LN-fold variants' row statistics, <= 24 KiB)
+    const size_t lds = NST * KSUB * (BM + BN) * 128 + BM * LN_MAX_GROUPS * 8;  // (+ the LN-fold variants' row statistics, <= 24 KiB)
     hipError_t e = hipSuccess;
-#define DINO_ATTR(E)                                                                                          \
-    if (e == hipSuccess)                                                                                      \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<T, BM, BN, WM, WN, NST, E, KSUB>),  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    DINO_ATTR(EPI_PATCH)
-    DINO_ATTR(EPI_QKV)
-    DINO_ATTR(EPI_RESID)
-    DINO_ATTR(EPI_GELU)
-    DINO_ATTR(EPI_PLAIN_F32)
-    DINO_ATTR(EPI_RESID_LN)
-    DINO_ATTR(EPI_QKV_LN)
-    DINO_ATTR(EPI_GELU_LN)
-    if constexpr (BN / WN == 64) DINO_ATTR(EPI_SWIGLU)
-    if constexpr (BN / WN == 64) DINO_ATTR(EPI_SWIGLU_LN)
-#undef DINO_ATTR
+    for (int epi = 0; epi < EPI_COUNT && e == hipSuccess; ++epi) e = gemm_raise_lds((const void*)small_kernel<T, BM, BN, WM, WN, NST, KSUB>(epi), lds);
     return e;
 }
 
-#ifdef DINO_GEMM_SWEEP
-template <int BM, int BN, int WM, int WN, int NST, int KSUB>
-static void hipFuncSetAttribute_all() { (void)set_attr_cfg<_Float16, BM, BN, WM, WN, NST, KSUB>(); }
-#endif
+// The small-tile configurations the library uses, written ONCE: gemm_init prepares exactly these, launch_small launches exactly these, and the
+// planner (small_cfg) names its choice by the enumerator generated here -- a configuration that is chosen but not prepared does not compile.
+//    BM   BN  WM WN NST KSUB
+#define DINO_SMALL_CFGS(X)  \
+    X(128, 128, 2, 2, 2, 1) \
+    X(64, 128, 2, 2, 2, 1)  \
+    X(64, 128, 2, 2, 3, 1)  \
+    X(64, 128, 4, 2, 3, 1)  \
+    X(64, 128, 4, 2, 3, 2)  \
+    X(64, 128, 2, 4, 3, 2)  \
+    X(64, 64, 2, 4, 3, 2)   \
+    X(32, 64, 1, 4, 3, 2)
+#define DINO_SMALL_ID(BM, BN, WM, WN, NST, KSUB) SMALL_##BM##x##BN##_w##WM##x##WN##_st##NST##_ks##KSUB
+namespace {
+enum SmallCfg : int {
+#define DINO_X(...) DINO_SMALL_ID(__VA_ARGS__),
+    DINO_SMALL_CFGS(DINO_X)
+#undef DINO_X
+};
+}  // namespace
 
-hipError_t launch_gemm2(DType dt, Epilogue epi, const GemmArgs& a, hipStream_t st);      // gemm2.hip, 256-row tiles
-hipError_t launch_gemm2_192(DType dt, Epilogue epi, const GemmArgs& a, hipStream_t st);  // gemm2.hip, 192-row tiles
-hipError_t launch_gemm2_128(DType dt, Epilogue epi, const GemmArgs& a, hipStream_t st);  // gemm2.hip, 128-row tiles, one per workgroup
+static hipError_t launch_small(DType dt, int cfg, Epilogue epi, const GemmArgs& a, hipStream_t st) {
+    switch (cfg) {
+#define DINO_X(...) case DINO_SMALL_ID(__VA_ARGS__): return dt == DT_F16 ? launch_cfg<_Float16, __VA_ARGS__>(epi, a, st) : launch_cfg<__bf16, __VA_ARGS__>(epi, a, st);
+        DINO_SMALL_CFGS(DINO_X)
+#undef DINO_X
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// gemm2.hip: 64 xrep-row tiles (256 / 192 rows persistent, 128 rows one per workgroup), and 256- then 192-row tiles in one launch
+hipError_t launch_gemm2(DType dt, Epilogue epi, const GemmArgs& a, int xrep, hipStream_t st);
 hipError_t launch_gemm2_mixed(DType dt, Epilogue epi, const GemmArgs& a, const GemmArgs& b, hipStream_t st);
 hipError_t gemm2_init();
 // gemm4.hip: the same tiles on four waves with a hand-ordered K loop (256-row tiles; whole rounds of 256-row + a round of 192-row tiles)
-bool gemm4_ok(Epilogue epi, const GemmArgs& a);
-hipError_t launch_gemm4(DType dt, Epilogue epi, const GemmArgs& a, hipStream_t st);
+bool gemm4_ok(Epilogue epi, int N, int K);
+hipError_t launch_gemm4(DType dt, Epilogue epi, const GemmArgs& a, int ni, hipStream_t st);  // 32 ni-row tiles: ni = 8 persistent, 2 / 3 / 4 one per workgroup
 hipError_t launch_gemm4_mixed(DType dt, Epilogue epi, const GemmArgs& a, const GemmArgs& b, hipStream_t st);
-hipError_t launch_gemm4_short(DType dt, Epilogue epi, const GemmArgs& a, int ni, hipStream_t st);  // 32 ni-row tiles, one per workgroup
 hipError_t gemm4_init();
 
 hipError_t gemm_init() {
-    hipError_t e = set_attr_cfg<_Float16, 128, 128, 2, 2, 2>();
-    if (e == hipSuccess) e = set_attr_cfg<__bf16, 128, 128, 2, 2, 2>();
-    if (e == hipSuccess) e = set_attr_cfg<_Float16, 64, 128, 2, 2, 2>();
-    if (e == hipSuccess) e = set_attr_cfg<__bf16, 64, 128, 2, 2, 2>();
-    if (e == hipSuccess) e = set_attr_cfg<_Float16, 64, 128, 2, 2, 3>();
-    if (e == hipSuccess) e = set_attr_cfg<__bf16, 64, 128, 2, 2, 3>();
-    if (e == hipSuccess) e = set_attr_cfg<_Float16, 64, 128, 4, 2, 3>();
-    if (e == hipSuccess) e = set_attr_cfg<__bf16, 64, 128, 4, 2, 3>();
-    if (e == hipSuccess) e = set_attr_cfg<_Float16, 64, 128, 4, 2, 3, 2>();
-    if (e == hipSuccess) e = set_attr_cfg<__bf16, 64, 128, 4, 2, 3, 2>();
-    if (e == hipSuccess) e = set_attr_cfg<_Float16, 64, 128, 2, 4, 3, 2>();
-    if (e == hipSuccess) e = set_attr_cfg<__bf16, 64, 128, 2, 4, 3, 2>();
-    if (e == hipSuccess) e = set_attr_cfg<_Float16, 64, 64, 2, 4, 3, 2>();
-    if (e == hipSuccess) e = set_attr_cfg<__bf16, 64, 64, 2, 4, 3, 2>();
-    if (e == hipSuccess) e = set_attr_cfg<_Float16, 32, 64, 1, 4, 3, 2>();
-    if (e == hipSuccess) e = set_attr_cfg<__bf16, 32, 64, 1, 4, 3, 2>();
+    hipError_t e = hipSuccess;
+#define DINO_X(...) if (e == hipSuccess) e = set_attr_cfg<_Float16, __VA_ARGS__>(); if (e == hipSuccess) e = set_attr_cfg<__bf16, __VA_ARGS__>();
+    DINO_SMALL_CFGS(DINO_X)
+#undef DINO_X
     if (e == hipSuccess) e = gemm2_init();
     if (e == hipSuccess) e = gemm4_init();
     return e;
@@ -650,32 +646,136 @@ void tune_set(TuneKey k, int v) {
     g_tune[k].store(v < 0 ? g_tune_env[k] : v, std::memory_order_relaxed);
 }
 
-// ---- plan recording (gemm_plan_describe): with a sink installed the leaves of launch_gemm note their kernel instead of launching it ------
+// ======== the planner: validate -> stamp the per-output policies once -> optional column split -> plan_rows per column range.  Host code
+// only; it fills a GemmPlan (kernels.h) and launches nothing.  launch_gemm and gemm_plan_describe below are its two readers. ==============
 namespace {
-thread_local std::string* t_plan_sink = nullptr;
-}
-static bool plan_note(const char* fmt, ...) {
-    if (!t_plan_sink) return false;
-    char buf[128];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (!t_plan_sink->empty()) *t_plan_sink += ';';
-    *t_plan_sink += buf;
-    return true;
-}
-template <typename T, int BM, int BN, int WM, int WN, int NST, int KSUB = 1>
-static hipError_t leaf_cfg(Epilogue epi, const GemmArgs& a, hipStream_t st) {
-    if (BN / WN != 64 && epi_base(epi) == EPI_SWIGLU) return hipErrorInvalidValue;  // (refused plans leave no text behind: ADVICE r5)
-    if (plan_note("small<%dx%d,w%dx%d,st%d,ks%d>", BM, BN, WM, WN, NST, KSUB)) return hipSuccess;
-    return launch_cfg<T, BM, BN, WM, WN, NST, KSUB>(epi, a, st);
-}
-#define DINO_LEAF(CALL, ...) (plan_note(__VA_ARGS__) ? hipSuccess : (CALL))
 
-// Kernel choice: the 256x256 kernel (gemm2.hip) needs N % 256 == 0 (tiles must not straddle q|k|v or a SwiGLU pair,
-// and it has no N edge guards) and enough tiles to fill the 256 CUs; everything else takes the 128x128 kernel here.
-// ---- which kernel(s) for a shape --------------------------------------------------------------------------------------
+// Validation, and the policies that are decided ONCE per logical output, before any split: every step's arguments are slices of `a`, so one
+// output never leaves under two store policies, two clock-probe slots or two statistics layouts.
+hipError_t stamp_args(Epilogue epi, const GemmArgs& in, bool check_pointers, GemmArgs* out) {
+    GemmArgs& a = *out;
+    a = in;
+    if (a.K % 64 != 0 || a.M <= 0 || a.N <= 0) return hipErrorInvalidValue;
+    a.small_only = a.sub = 0;  // (not inputs: kernels.h)
+    // 2-byte outputs much larger than the chip's L2s (8 x 4 MiB = 32 MiB) leave with non-temporal stores: they would only evict the operand
+    // panels, and their consumer (another kernel) reads them through the memory side; small ones (batch 1) are found in L2 by the next
+    // kernel.  The threshold, 48 MiB = 1.5 x the L2s, sits between the two regimes that were MEASURED (ViT-L batch 1: outputs <= 11 MB,
+    // ordinary stores win by 3 % of p50; batch 32: outputs >= 90 MB, non-temporal stores win by 0.7 % of the forward -- profiles/r04_gemm4w.md
+    // section 5b); nothing in between was.
+    const Epilogue eb = epi_base(epi);  // the LN-fold variants are dispatched like the epilogue they specialise
+    a.nt_out = 0;
+    if (eb == EPI_QKV || eb == EPI_GELU || eb == EPI_SWIGLU)
+        a.nt_out = (size_t)a.M * (size_t)(eb == EPI_SWIGLU ? a.N / 2 : a.N) * 2 > ((size_t)48 << 20) ? 1 : 0;
+    a.clk_slot = DINO_CLK_GEMM_SLOT((int)epi, a.N, a.K);
+    if (eb != epi) {
+        // LN fold: statistics are kept per 64 columns of the LayerNorm's rows, at most LN_MAX_GROUPS of them; the producer writes full
+        // 64-column groups with vector stores from every kernel it may be split over
+        const int hcols = epi == EPI_RESID_LN ? a.N : a.K;
+        if (hcols % 128 != 0 || hcols / LN_GROUP > LN_MAX_GROUPS || (epi == EPI_RESID_LN && a.ldo != a.N)) return hipErrorInvalidValue;
+        if (a.ln_gs == 0) a.ln_gs = ln_stat_slots(hcols);
+        if (a.ln_gs != ln_stat_slots(hcols)) return hipErrorInvalidValue;
+        if (check_pointers) {  // (plan queries carry no pointers)
+            if (!a.stats) return hipErrorInvalidValue;
+            if (epi == EPI_RESID_LN && (!a.ln_gamma || !a.xg || (((size_t)a.ln_gamma | (size_t)a.aux | (size_t)a.bias) & 15))) return hipErrorInvalidValue;
+            if (epi != EPI_RESID_LN && (!a.ln_s || !a.ln_c || (((size_t)a.ln_s | (size_t)a.ln_c) & 15))) return hipErrorInvalidValue;
+        }
+    }
+    // staging cursors are 32-bit byte offsets from A and W (dinov2_hip_predict splits batches long before this)
+    const size_t lda = a.lda ? a.lda : a.K, ldw = a.ldw ? a.ldw : a.K;
+    // rows are fetched with 16-byte global -> LDS DMA pieces and 16-byte vector loads: strides must keep rows 16-byte aligned
+    if (a.lda < 0 || a.ldw < 0 || lda % 8 != 0 || ldw % 8 != 0 || lda < (size_t)a.K || ldw < (size_t)a.K) return hipErrorInvalidValue;
+    if ((size_t)a.M * lda * 2 >= ((size_t)1 << 32) || (size_t)a.N * ldw * 2 >= ((size_t)1 << 32)) return hipErrorInvalidValue;
+    return hipSuccess;
+}
+
+// p + bytes, on integers; a null pointer (plan queries, optional operands) stays null
+template <class P>
+P advance(P p, size_t bytes) {
+    return p ? (P)((uintptr_t)p + bytes) : p;
+}
+
+// The arguments of the sub-problem rows [row0, row0 + rows) x columns [col0, col0 + cols) of `a`: ALL the pointer arithmetic of a split
+// launch, for every epilogue.  The parts keep the whole problem's row strides (lda, ldw, ldo, ln_gs).  The planner never cuts the patch-embed
+// epilogue (it maps row -> (image, patch) and indexes `aux` with N) and cuts the SwiGLU epilogues by rows only (interleaved column pairs).
+GemmArgs slice(Epilogue epi, const GemmArgs& a, int row0, int rows, int col0, int cols) {
+    const Epilogue eb = epi_base(epi);
+    const size_t lda = a.lda ? a.lda : a.K, ldw = a.ldw ? a.ldw : a.K;
+    const size_t osz = (eb == EPI_RESID || eb == EPI_PLAIN_F32) ? 4 : 2;
+    const size_t cell = (size_t)row0 * a.ldo + col0;  // first element of the part in out / xg
+    GemmArgs s = a;
+    s.M = rows;
+    s.N = cols;
+    s.A = advance(a.A, (size_t)row0 * lda * 2);
+    s.W = advance(a.W, (size_t)col0 * ldw * 2);
+    s.bias = advance(a.bias, (size_t)col0 * 4);
+    s.aux = advance(a.aux, (size_t)col0 * 4);  // (EPI_RESID: LayerScale [N]; unused by the other epilogues that are cut by columns)
+    s.out = advance(a.out, cell * osz);
+    s.qcols = a.qcols <= col0 ? 0 : a.qcols - col0 < cols ? a.qcols - col0 : cols;
+    if (epi == EPI_RESID_LN) {
+        s.ln_gamma = advance(a.ln_gamma, (size_t)col0 * 4);
+        s.xg = advance(a.xg, cell * 2);
+        s.stats = advance(a.stats, ((size_t)row0 * a.ln_gs + col0 / LN_GROUP) * 8);
+    } else if (eb != epi) {  // consumers: the statistics are those of A's rows
+        s.ln_s = advance(a.ln_s, (size_t)col0 * 4);
+        s.ln_c = advance(a.ln_c, (size_t)col0 * 4);
+        s.stats = advance(a.stats, (size_t)row0 * a.ln_gs * 8);
+    }
+    return s;
+}
+
+struct PlanCtx {
+    Epilogue epi, eb;   // eb = epi_base(epi)
+    int forced, gen;    // TUNE_GEMM_TILE, TUNE_GEMM_GEN, read once per plan
+};
+
+// one more step: `family` over rows [row0, row0 + rows) x columns [col0, col0 + cols); the two-height kernels take rows0 rows as 256-row tiles
+hipError_t add_step(const PlanCtx& c, GemmPlan* p, GemmFamily family, int tile, int row0, int rows, int col0, int cols, int rows0 = -1, int cfg = 0) {
+    if (p->nsteps == GEMM_PLAN_MAX_STEPS) return hipErrorInvalidValue;
+    const bool two = family == GEMM2_MIXED || family == GEMM4_MIXED;
+    GemmStep& s = p->steps[p->nsteps++];
+    s = GemmStep{family, tile, cfg, row0, rows, col0, cols, two ? rows0 : rows, {}};
+    s.args[0] = slice(c.epi, p->whole, row0, s.rows0, col0, cols);
+    if (two) s.args[1] = slice(c.epi, p->whole, row0 + rows0, rows - rows0, col0, cols);
+    return hipSuccess;
+}
+
+// small problems (batch 1: M = 1374): 128x128 tiles leave most CUs idle and one workgroup per CU cannot hide the
+// global -> LDS latency of its K loop.  64x128 tiles with 2 LDS stages (48 KiB: three workgroups per CU hide each other's
+// latency) when there are enough tiles, with 3 stages (72 KiB) when there are not (N = 1024 at batch 1: 176 tiles; the
+// K = 4096 GEMM 39.7 -> 33.8 us).  Measured at M = 1374: 128x128 / 64x128x2 / 64x128x3 = qkv 21.8 / 19.5 / 27.1 us,
+// ffn-in 31.2 / 24.9 / 34.0, ffn-out 49.0 / 39.7 / 33.8.
+SmallCfg small_cfg(Epilogue eb, int M, int N, int K) {
+    const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
+    const long t64 = (long)((M + 63) / 64) * ((N + 127) / 128);
+    const int cfg = t128 >= 512 ? 0 : t64 >= 384 ? 1 : 2;
+    // Fewer tiles than CUs (batch 1: the two N = hidden GEMMs at 518 x 518, every GEMM at 224 x 224): one workgroup per CU walks
+    // a serial K loop (wait -> barrier -> issue -> fragment reads -> MFMAs per stage) and nothing overlaps it, so what counts is how
+    // short one link is (profiles/r03_small_m_gemm.md):
+    //  * eight waves, two 64-wide K sub-tiles per LDS stage (half the links);
+    //  * wave tiles of 32 x 32 (2 x 4 waves) rather than 16 x 64 (4 x 2): the loop is bound by LDS reads -- a 16 x 64 wave tile reads
+    //    five 1 KiB fragments per four MFMAs, a 32 x 32 one four -- and the LDS moves 128 B/clk (FFN-out at M = 1 374: 28.0 -> 25.4 us);
+    //  * the SMALLEST tile that still gives at most one workgroup per CU: every CU that joins shortens everybody's chain (M = 261:
+    //    attn-out 9.8 -> 5.7 us, FFN-out 27.3 -> 14.5 on 32 x 64 tiles; QKV 8.9 -> 6.3 on 64 x 64); two workgroups per CU lose again.
+    // Nothing about the arithmetic changes -- each output's MFMA chain runs over K in the same order in every configuration.
+    if (cfg == 2 && t64 < 256 && (K / 64) % 2 == 0 && K >= 256 && eb != EPI_SWIGLU) {  // (SwiGLU has no instantiation on these 32- / 16-wide wave tiles)
+        const long t6464 = (long)((M + 63) / 64) * ((N + 63) / 64), t3264 = (long)((M + 31) / 32) * ((N + 63) / 64);
+        if (t3264 <= 256) return SMALL_32x64_w1x4_st3_ks2;
+        if (t6464 <= 256) return SMALL_64x64_w2x4_st3_ks2;
+        return SMALL_64x128_w2x4_st3_ks2;
+    }
+    if (cfg == 2 && t64 < 256 && (K / 64) % 2 == 0 && K >= 256) return SMALL_64x128_w4x2_st3_ks2;  // (SwiGLU pairs columns inside a 64-wide wave tile)
+    if (cfg == 2 && t64 < 256) return SMALL_64x128_w4x2_st3_ks1;
+    if (cfg == 1) return SMALL_64x128_w2x2_st2_ks1;
+    if (cfg == 2) return SMALL_64x128_w2x2_st3_ks1;
+    return SMALL_128x128_w2x2_st2_ks1;
+}
+hipError_t plan_small(const PlanCtx& c, GemmPlan* p, int row0, int rows, int col0, int cols) {
+    return add_step(c, p, GEMM_SMALL, 0, row0, rows, col0, cols, -1, small_cfg(c.eb, rows, cols, p->whole.K));
+}
+
+// Kernel choice for all M rows of the column range [col0, col0 + N): the 256x256 kernels (gemm2.hip, gemm4.hip) need N % 256 == 0 (tiles
+// must not straddle q|k|v or a SwiGLU pair, and they have no N edge guards) and enough tiles to fill the 256 CUs; everything else takes
+// the small-tile kernel here.
 // The persistent kernel (gemm2.hip; needs N % 256 == 0 and an even K / 64) works in rounds of 256 tiles, and a partial last
 // round costs a whole one (QKV at batch 32: 2 064 tiles of 256 rows = 8 rounds + 16 tiles -> 9; out-proj / FFN-out: 688 =
 // 2.69 -> 3; ViT-g at batch 8: 258 -> 2).  Every kernel here produces the same bits for a row
@@ -687,265 +787,216 @@ static hipError_t leaf_cfg(Epilogue epi, const GemmArgs& a, hipStream_t st) {
 //   C  whole rounds of 256-row tiles, rest 192-row tiles,   R + ceil(tail192 / 256) * 0.79      (gemm2_mixed_kernel)
 //      one launch
 //   D  whole rounds of 256-row tiles, rest small-tile       R + tail share of a round / 0.5 + 0.1 launch
-//      kernel (two launches; pays for a few left-over tiles)
+//      kernel (two steps; pays for a few left-over tiles)
 //   E  small-tile kernel only                               outputs / (256 tiles) / 0.5
 // Measured (M = 43 968): QKV 0.292 -> 0.285 ms (D), out-proj 0.129 -> 0.125 (C), FFN-out 0.393 -> 0.374 (C); ViT-g bf16 batch 8
 // 221 -> 244 images/s.  DINOV2_HIP_GEMM_TILE=128|256 forces E / A (testing aid: include/dinov2_hip.h, "Environment").
-hipError_t launch_gemm(DType dt, Epilogue epi, const GemmArgs& a_in, hipStream_t st) {
-    GemmArgs a = a_in;
-    if (a.K % 64 != 0 || a.M <= 0 || a.N <= 0) return hipErrorInvalidValue;
-    // 2-byte outputs much larger than the chip's L2s (8 x 4 MiB = 32 MiB) leave with non-temporal stores: they would only evict the operand
-    // panels, and their consumer (another kernel) reads them through the memory side; small ones (batch 1) are found in L2 by the next
-    // kernel.  The threshold, 48 MiB = 1.5 x the L2s, sits between the two regimes that were MEASURED (ViT-L batch 1: outputs <= 11 MB,
-    // ordinary stores win by 3 % of p50; batch 32: outputs >= 90 MB, non-temporal stores win by 0.7 % of the forward -- profiles/r04_gemm4w.md
-    // section 5b); nothing in between was.  Decided ONCE per logical output, at the top-level call: the parts of a split launch (`sub`)
-    // inherit it, so one output never leaves under two store policies.
-    const Epilogue eb = epi_base(epi);  // the LN-fold variants are dispatched like the epilogue they specialise
+hipError_t plan_rows(const PlanCtx& c, GemmPlan* p, int col0, int N) {
+    const Epilogue epi = c.epi, eb = c.eb;
+    const int M = p->whole.M, K = p->whole.K, forced = c.forced, gen = c.gen;
     const bool ln = eb != epi;
-    if (!a.sub) {
-        a.nt_out = 0;
-        if (eb == EPI_QKV || eb == EPI_GELU || eb == EPI_SWIGLU)
-            a.nt_out = (size_t)a.M * (size_t)(eb == EPI_SWIGLU ? a.N / 2 : a.N) * 2 > ((size_t)48 << 20) ? 1 : 0;
-        a.clk_slot = DINO_CLK_GEMM_SLOT((int)epi, a.N, a.K);
-        if (ln) {
-            // LN fold: statistics are kept per 64 columns of the LayerNorm's rows, at most LN_MAX_GROUPS of them; the producer writes full
-            // 64-column groups with vector stores from every kernel it may be split over
-            const int hcols = epi == EPI_RESID_LN ? a.N : a.K;
-            if (hcols % 128 != 0 || hcols / LN_GROUP > LN_MAX_GROUPS || (epi == EPI_RESID_LN && a.ldo != a.N)) return hipErrorInvalidValue;
-            if (a.ln_gs == 0) a.ln_gs = ln_stat_slots(hcols);
-            if (a.ln_gs != ln_stat_slots(hcols)) return hipErrorInvalidValue;
-            if (!t_plan_sink) {  // (plan queries carry no pointers)
-                if (!a.stats) return hipErrorInvalidValue;
-                if (epi == EPI_RESID_LN && (!a.ln_gamma || !a.xg || (((size_t)a.ln_gamma | (size_t)a.aux | (size_t)a.bias) & 15))) return hipErrorInvalidValue;
-                if (epi != EPI_RESID_LN && (!a.ln_s || !a.ln_c || (((size_t)a.ln_s | (size_t)a.ln_c) & 15))) return hipErrorInvalidValue;
-            }
-        }
+    const bool is_patch = epi == EPI_PATCH;  // (the patch-embed epilogue maps row -> (image, patch): no row splits for it)
+    const bool g4_ok = gemm4_ok(epi, N, K);
+    auto whole = [&](GemmFamily family, int tile) { return add_step(c, p, family, tile, 0, M, col0, N, 0); };
+    // (the LN-fold epilogues exist in gemm4.hip and in the small-tile kernel, not in gemm2.hip)
+    if (forced == 128 || N % 256 != 0 || (K / 64) % 2 != 0 || (ln && (gen == 2 || !g4_ok))) return plan_small(c, p, 0, M, col0, N);
+    const int ntn = N / 256;
+    const long t256 = (long)ntn * ((M + 255) / 256), t192 = (long)ntn * ((M + 191) / 192);
+    auto rnd = [](long t) { return (double)((t + 255) / 256); };
+    const double unit = 256.0 * 65536.0;  // outputs of one round of 256-row tiles
+    const double costE = (double)M * N / unit / 0.5;
+    char plan = 'A';
+    double best = rnd(t256);
+    if (forced == 256) {
+        best = -1.0;
+    } else {
+        if (t256 < 192 && costE < best) { plan = 'E'; best = costE; }  // far from filling the chip with big tiles
+        if (t192 >= 192 && rnd(t192) * 0.79 < best - 0.02) { plan = 'B'; best = rnd(t192) * 0.79; }
     }
-    // staging cursors are 32-bit byte offsets from A and W (dinov2_hip_predict splits batches long before this)
-    const size_t lda_ = a.lda ? a.lda : a.K, ldw_ = a.ldw ? a.ldw : a.K;
-    // rows are fetched with 16-byte global -> LDS DMA pieces and 16-byte vector loads: strides must keep rows 16-byte aligned
-    if (a.lda < 0 || a.ldw < 0 || lda_ % 8 != 0 || ldw_ % 8 != 0 || lda_ < (size_t)a.K || ldw_ < (size_t)a.K) return hipErrorInvalidValue;
-    if ((size_t)a.M * lda_ * 2 >= ((size_t)1 << 32) || (size_t)a.N * ldw_ * 2 >= ((size_t)1 << 32)) return hipErrorInvalidValue;
-    const int forced = tune_get(TUNE_GEMM_TILE);
-    const int gen = tune_get(TUNE_GEMM_GEN);
-#ifdef DINO_GEMM_SWEEP  // tuning builds only: DINOV2_HIP_GEMM_CFG=<n> forces one small-tile configuration (f16)
-    {
-        const char* e = getenv("DINOV2_HIP_GEMM_CFG");
-        const int c = e ? atoi(e) : -1;
-        if (c >= 0 && t_plan_sink) return hipErrorInvalidValue;  // (plan queries must not launch: ADVICE r5)
-        if (c >= 0 && dt == DT_F16) {
-            switch (c) {
-#define DINO_SW(n, ...) case n: { static bool once = (hipFuncSetAttribute_all<__VA_ARGS__>(), true); (void)once; return launch_cfg<_Float16, __VA_ARGS__>(epi, a, st); }
-                DINO_SW(0, 64, 128, 2, 2, 2, 1)
-                DINO_SW(1, 64, 128, 2, 2, 3, 1)
-                DINO_SW(2, 64, 128, 4, 2, 3, 2)
-                DINO_SW(3, 64, 128, 4, 2, 6, 1)
-                DINO_SW(4, 64, 128, 4, 2, 3, 1)
-                DINO_SW(5, 64, 128, 4, 2, 4, 1)
-                DINO_SW(6, 128, 128, 4, 2, 2, 1)
-                DINO_SW(7, 128, 128, 4, 2, 3, 1)
-                DINO_SW(8, 128, 128, 4, 2, 4, 1)
-                DINO_SW(9, 192, 128, 4, 2, 3, 1)
-                DINO_SW(10, 192, 128, 4, 2, 4, 1)
-                DINO_SW(11, 64, 128, 2, 2, 6, 1)
-                DINO_SW(12, 128, 128, 2, 2, 2, 1)
-                DINO_SW(13, 64, 128, 2, 2, 4, 1)
-                DINO_SW(14, 128, 128, 4, 2, 5, 1)
-                DINO_SW(15, 64, 128, 2, 4, 3, 2)
-                DINO_SW(16, 64, 128, 2, 4, 3, 1)
-                DINO_SW(17, 128, 128, 2, 4, 2, 1)
-                DINO_SW(18, 128, 128, 2, 2, 3, 1)
-                DINO_SW(19, 128, 128, 2, 4, 3, 1)
-                DINO_SW(20, 64, 64, 2, 2, 3, 2)
-                DINO_SW(21, 64, 64, 2, 4, 3, 2)
-                DINO_SW(22, 32, 128, 1, 4, 3, 2)
-                DINO_SW(23, 32, 64, 1, 4, 3, 2)
-                DINO_SW(24, 32, 64, 2, 2, 3, 2)
-                DINO_SW(25, 64, 64, 2, 2, 4, 2)
-                DINO_SW(26, 64, 64, 2, 2, 3, 1)
-#undef DINO_SW
-                default: return hipErrorInvalidValue;
-            }
-        }
+    const long R = t256 / 256;
+    const int M1 = (int)(R * 256 / ntn) * 256;  // the rows of the whole rounds' row panels: plans C and D cut here
+    if (!is_patch && forced != 256 && R >= 1 && M1 > 0 && M1 < M) {
+        const long tail192 = (long)ntn * ((M - M1 + 191) / 192);
+        const double costC = (double)R + rnd(tail192) * 0.79;
+        const double costD = (double)R + (double)(M - M1) * N / unit / 0.5 + 0.1;
+        if (costC < best - 0.02) { plan = 'C'; best = costC; }
+        if (costD < best - 0.02) { plan = 'D'; best = costD; }
     }
+#ifdef DINO_GEMM_SWEEP
+    if (forced == 192) plan = 'B';
+    if (forced == 129 && !is_patch) return whole(GEMM2, 128);
 #endif
+    // F4 (round 4): 128-row tiles' idea (F, below) on gemm4.hip with the tile HEIGHT chosen for the launch: the shortest of 128 / 96 / 64 rows
+    // that still gives at most one tile per CU (QKV at ViT-L batch 1: 180 tiles of 96 rows instead of 132 of 128; FFN-in 240 instead of 176),
+    // for the 2-byte epilogues (profiles/r04_gemm4w.md section 6).  DINOV2_HIP_GEMM_GEN=2 keeps plan F.
+    const bool two_byte = eb == EPI_QKV || eb == EPI_GELU || eb == EPI_SWIGLU;
+    if ((two_byte || epi == EPI_RESID_LN) && !forced && gen != 2 && g4_ok && (gen == 4 || ln || K >= 1024)) {
+        int ni = 0;
+        for (int h = 2; h <= 4 && !ni; ++h)
+            if ((long)ntn * ((M + 32 * h - 1) / (32 * h)) <= 256) ni = h;
+        const long tiles = ni ? (long)ntn * ((M + 32 * ni - 1) / (32 * ni)) : 0;
+        // (EPI_RESID_LN: only where the plain residual epilogue would leave the small-tile kernel too, at >= 112 tiles of 128 rows.
+        //  Its epilogue is twice as long as the plain one and one wave per SIMD issues it; measured on ViT-L with the fold on:
+        //  batch 2 (88 such tiles) small-tile kernel - 1.5 % of the forward against the unfolded path, 172 tiles of 64 rows - 8 %,
+        //  116 of 96 rows - 13 %; batch 3 (132) small-tile - 16 %, 172 tiles of 96 rows - 3.5 %; batch 4 (172) small-tile - 15 %,
+        //  232 tiles of 96 rows - 2.5 %, 172 of 128 rows - 5.6 % -- profiles/r06_ln_fold.md)
+        if (epi == EPI_RESID_LN && (long)ntn * ((M + 127) / 128) < 112) ni = 0;
+        if (ni && tiles >= 112) return whole(GEMM4_SHORT, 32 * ni);
+    }
+    // F: 128-row tiles of the persistent kernel's schedule, one per workgroup, when they give 112 ... 256 workgroups: too few rows to
+    // fill the chip with 256- or 192-row tiles, enough columns that 128 x 256 tiles do (ViT-L batch 1 at 518 x 518: QKV 132 tiles
+    // 18.0 -> 15.0 us, FFN-in 176 tiles 21.1 -> 17.6; ViT-g QKV 42 -> 24; batch 4 FFN-out 64 -> 51).  Below ~112 tiles the
+    // small-tile kernel's many workgroups win, above 256 a second round starts (profiles/r03_small_m_gemm.md section 9).
+    const long t128r = (long)ntn * ((M + 127) / 128);
+    if (!is_patch && !ln && !forced && t128r >= 112 && t128r <= 256) return whole(GEMM2, 128);
+    if (is_patch) plan = (plan == 'E' || t192 < 192) ? 'E' : 'B';  // only the 192-row instantiation exists for this epilogue
+    // which generation runs the 256-row / mixed plans: gemm4.hip (four waves, hand-ordered K loop) where it applies, unless
+    // DINOV2_HIP_GEMM_GEN=2 asks for gemm2.hip (testing aid: the bit-equality tests compare the two)
+    // default: gemm4.hip wherever it applies (in the model: FFN-out - 4 %, QKV and FFN-in within 0.5 %, attn-out + 2 %; forward + 0.8 %
+    // over gemm2.hip everywhere, same box, interleaved runs -- profiles/r04_gemm4w.md)
+    // ... for K >= 1 024: with fewer K-tiles per output tile the four-wave kernel's longer epilogue (one wave per SIMD issues it alone)
+    // outweighs its K loop -- ViT-B / ViT-S (K = 768 / 384) measured 1.4 % / 3 % faster on gemm2.hip, ViT-L / ViT-g on gemm4.hip.
+    // DINOV2_HIP_GEMM_GEN=4 forces gemm4.hip wherever it can run (tests).
+    // ... and not the residual epilogue at K < 2 048 (attn-out: its read-modify-write burst is 36 % of a tile and eight waves keep more
+    // of it in flight: 0.131 against 0.133 ms in the model, four interleaved runs).
+    const bool g4 = ln || (gen != 2 && g4_ok && (gen == 4 || (K >= 1024 && !(epi == EPI_RESID && K < 2048))));
+    switch (plan) {
+        case 'A': return whole(g4 ? GEMM4 : GEMM2, 256);
+        case 'B':  // (the LN-fold epilogues: gemm4.hip's two-height launch with an empty 256-row part)
+            return ln ? whole(GEMM4_MIXED, 256) : whole(GEMM2, 192);
+        case 'C': return add_step(c, p, g4 ? GEMM4_MIXED : GEMM2_MIXED, 256, 0, M, col0, N, M1);
+        case 'D': {  // (the tail of a split goes straight to the small-tile kernel)
+            const hipError_t e = add_step(c, p, g4 ? GEMM4 : GEMM2, 256, 0, M1, col0, N);
+            return e == hipSuccess ? plan_small(c, p, M1, M - M1, col0, N) : e;
+        }
+        default: return plan_small(c, p, 0, M, col0, N);  // 'E'
+    }
+}
+
+}  // namespace
+
+hipError_t gemm_plan(DType, Epilogue epi, const GemmArgs& a_in, bool check_pointers, GemmPlan* p) {
+    p->nsteps = 0;
+    hipError_t e = stamp_args(epi, a_in, check_pointers, &p->whole);
+    if (e != hipSuccess) return e;
+    const GemmArgs& a = p->whole;
+    const PlanCtx c{epi, epi_base(epi), tune_get(TUNE_GEMM_TILE), tune_get(TUNE_GEMM_GEN)};
     // N not a multiple of 256 (ViT-S: 384, 1 152): the persistent kernel takes the leading multiple of 256 columns, the small-tile
     // kernel the remaining ones (two launches; every kernel gives a row the same bits, so the cut is invisible in the results).
     // Only where the persistent part fills the chip; not for the patch / SwiGLU epilogues (row -> token scatter indexed with N,
     // interleaved column pairs).
-    {
-        const int nrem = a.N % 256, n1 = a.N - nrem;
-        const bool epi_ok = eb == EPI_QKV || eb == EPI_RESID || eb == EPI_GELU || eb == EPI_PLAIN_F32;
-        if (!a.small_only && forced != 128 && nrem != 0 && n1 >= 256 && epi_ok && (a.K / 64) % 2 == 0 &&
-            (long)(n1 / 256) * ((a.M + 191) / 192) >= 192) {
-            const size_t osz = (eb == EPI_RESID || eb == EPI_PLAIN_F32) ? 4 : 2;
-            GemmArgs a1 = a, a2 = a;
-            a1.sub = a2.sub = 1;
-            if (epi == EPI_RESID_LN) {  // (row strides of xg and stats come from ldo, which the parts keep)
-                a2.ln_gamma = a.ln_gamma + n1;
-                a2.xg = (char*)a.xg + (size_t)n1 * 2;
-                a2.stats = a.stats + (size_t)(n1 / LN_GROUP) * 2;
-            } else if (ln) {
-                a2.ln_s = a.ln_s + n1;
-                a2.ln_c = a.ln_c + n1;
-            }
-            a1.N = n1;
-            a1.qcols = a.qcols < n1 ? a.qcols : n1;
-            a2.N = nrem;
-            a2.W = (const char*)a.W + (size_t)n1 * ldw_ * 2;
-            a2.bias = a.bias ? a.bias + n1 : nullptr;
-            a2.aux = a.aux ? a.aux + n1 : nullptr;  // (EPI_RESID: LayerScale [N]; unused by the other three)
-            a2.out = (char*)a.out + (size_t)n1 * osz;
-            a2.qcols = a.qcols > n1 ? a.qcols - n1 : 0;
-            a2.small_only = 1;
-            const hipError_t e = launch_gemm(dt, epi, a1, st);
-            if (e != hipSuccess) return e;
-            return launch_gemm(dt, epi, a2, st);
-        }
+    const int nrem = a.N % 256, n1 = a.N - nrem;
+    const bool epi_ok = c.eb == EPI_QKV || c.eb == EPI_RESID || c.eb == EPI_GELU || c.eb == EPI_PLAIN_F32;
+    if (c.forced != 128 && nrem != 0 && n1 >= 256 && epi_ok && (a.K / 64) % 2 == 0 && (long)(n1 / 256) * ((a.M + 191) / 192) >= 192) {
+        e = plan_rows(c, p, 0, n1);
+        if (e == hipSuccess) e = plan_small(c, p, 0, a.M, n1, nrem);
+    } else {
+        e = plan_rows(c, p, 0, a.N);
     }
-    constexpr bool split_ok = true;
-    // (the patch-embed epilogue maps row -> (image, patch): no row splits for it)
-    const bool is_patch = epi == EPI_PATCH;
-    // (the LN-fold epilogues exist in gemm4.hip and in the small-tile kernel, not in gemm2.hip)
-    const bool big_ok = !a.small_only && forced != 128 && a.N % 256 == 0 && (a.K / 64) % 2 == 0 && (!ln || (gen != 2 && gemm4_ok(epi, a)));
-    if (big_ok) {
-        const int ntn = a.N / 256;
-        const long t256 = (long)ntn * ((a.M + 255) / 256), t192 = (long)ntn * ((a.M + 191) / 192);
-        auto rnd = [](long t) { return (double)((t + 255) / 256); };
-        const double unit = 256.0 * 65536.0;  // outputs of one round of 256-row tiles
-        const double costE = (double)a.M * a.N / unit / 0.5;
-        char plan = 'A';
-        double best = rnd(t256);
-        if (forced == 256) {
-            best = -1.0;
-        } else {
-            if (t256 < 192 && costE < best) { plan = 'E'; best = costE; }  // far from filling the chip with big tiles
-            if (split_ok && t192 >= 192 && rnd(t192) * 0.79 < best - 0.02) { plan = 'B'; best = rnd(t192) * 0.79; }
-        }
-        const long R = t256 / 256;
-        const int panels1 = (int)(R * 256 / ntn);
-        const int M1 = panels1 * 256;
-        GemmArgs a1 = a, a2 = a;
-        if (split_ok && !is_patch && forced != 256 && R >= 1 && M1 > 0 && M1 < a.M) {
-            const size_t osz = (eb == EPI_RESID || eb == EPI_PLAIN_F32) ? 4 : 2;
-            a1.M = M1;
-            a2.M = a.M - M1;
-            a2.A = (const char*)a.A + (size_t)M1 * lda_ * 2;
-            a2.out = (char*)a.out + (size_t)M1 * a.ldo * osz;
-            if (epi == EPI_RESID_LN) {
-                a2.xg = (char*)a.xg + (size_t)M1 * a.ldo * 2;
-                a2.stats = a.stats + (size_t)M1 * a.ln_gs * 2;
-            } else if (ln) {
-                a2.stats = a.stats + (size_t)M1 * a.ln_gs * 2;
+    if (e != hipSuccess) p->nsteps = 0;  // (a refused shape leaves no steps, and so no text: ADVICE r5)
+    return e;
+}
+
+static int step_name(const GemmStep& s, char* buf, size_t cap) {  // snprintf's return value
+    switch (s.family) {
+        case GEMM_SMALL:
+            switch (s.cfg) {
+#define DINO_X(BM, BN, WM, WN, NST, KSUB) case DINO_SMALL_ID(BM, BN, WM, WN, NST, KSUB): return snprintf(buf, cap, "small<" #BM "x" #BN ",w" #WM "x" #WN ",st" #NST ",ks" #KSUB ">");
+                DINO_SMALL_CFGS(DINO_X)
+#undef DINO_X
             }
-            a1.sub = a2.sub = 1;
-            const long tail192 = (long)ntn * ((a2.M + 191) / 192);
-            const double costC = (double)R + rnd(tail192) * 0.79;
-            const double costD = (double)R + (double)a2.M * a.N / unit / 0.5 + 0.1;
-            if (costC < best - 0.02) { plan = 'C'; best = costC; }
-            if (costD < best - 0.02) { plan = 'D'; best = costD; }
-        }
-#ifdef DINO_GEMM_SWEEP
-        if (forced == 192) plan = 'B';
-        if (forced == 129 && !is_patch) return DINO_LEAF(launch_gemm2_128(dt, epi, a, st), "gemm2<128>");
+            break;
+        case GEMM2: return snprintf(buf, cap, "gemm2<%d>", s.tile);
+        case GEMM2_MIXED: return snprintf(buf, cap, "gemm2_mixed<256+192>");
+        case GEMM4: return snprintf(buf, cap, "gemm4<%d>", s.tile);
+        case GEMM4_MIXED: return snprintf(buf, cap, "gemm4_mixed<%d+192>", s.rows0 ? 256 : 0);
+        case GEMM4_SHORT: return snprintf(buf, cap, "gemm4_short<%d>", s.tile);
+    }
+    return snprintf(buf, cap, "?");
+}
+
+static hipError_t launch_step(DType dt, Epilogue epi, const GemmStep& s, hipStream_t st) {
+    switch (s.family) {
+        case GEMM_SMALL: return launch_small(dt, s.cfg, epi, s.args[0], st);
+        case GEMM2: return launch_gemm2(dt, epi, s.args[0], s.tile / 64, st);
+        case GEMM2_MIXED: return launch_gemm2_mixed(dt, epi, s.args[0], s.args[1], st);
+        case GEMM4:
+        case GEMM4_SHORT: return launch_gemm4(dt, epi, s.args[0], s.tile / 32, st);
+        case GEMM4_MIXED: return launch_gemm4_mixed(dt, epi, s.args[0], s.args[1], st);
+    }
+    return hipErrorInvalidValue;
+}
+
+#ifdef DINO_GEMM_SWEEP  // tuning builds only: DINOV2_HIP_GEMM_CFG=<n> forces one small-tile configuration (f16)
+static int sweep_cfg() {
+    const char* e = getenv("DINOV2_HIP_GEMM_CFG");
+    return e ? atoi(e) : -1;
+}
+// true = the launch was taken over (*err is its result); the arguments are validated and stamped as for any launch
+static bool launch_gemm_sweep(DType dt, Epilogue epi, const GemmArgs& a_in, hipStream_t st, hipError_t* err) {
+    const int c = sweep_cfg();
+    if (c < 0 || dt != DT_F16) return false;
+    GemmArgs a;
+    if ((*err = stamp_args(epi, a_in, true, &a)) != hipSuccess) return true;
+    switch (c) {
+#define DINO_SW(n, ...) case n: { static bool once = ((void)set_attr_cfg<_Float16, __VA_ARGS__>(), true); (void)once; *err = launch_cfg<_Float16, __VA_ARGS__>(epi, a, st); return true; }
+        DINO_SW(0, 64, 128, 2, 2, 2, 1)
+        DINO_SW(1, 64, 128, 2, 2, 3, 1)
+        DINO_SW(2, 64, 128, 4, 2, 3, 2)
+        DINO_SW(3, 64, 128, 4, 2, 6, 1)
+        DINO_SW(4, 64, 128, 4, 2, 3, 1)
+        DINO_SW(5, 64, 128, 4, 2, 4, 1)
+        DINO_SW(6, 128, 128, 4, 2, 2, 1)
+        DINO_SW(7, 128, 128, 4, 2, 3, 1)
+        DINO_SW(8, 128, 128, 4, 2, 4, 1)
+        DINO_SW(9, 192, 128, 4, 2, 3, 1)
+        DINO_SW(10, 192, 128, 4, 2, 4, 1)
+        DINO_SW(11, 64, 128, 2, 2, 6, 1)
+        DINO_SW(12, 128, 128, 2, 2, 2, 1)
+        DINO_SW(13, 64, 128, 2, 2, 4, 1)
+        DINO_SW(14, 128, 128, 4, 2, 5, 1)
+        DINO_SW(15, 64, 128, 2, 4, 3, 2)
+        DINO_SW(16, 64, 128, 2, 4, 3, 1)
+        DINO_SW(17, 128, 128, 2, 4, 2, 1)
+        DINO_SW(18, 128, 128, 2, 2, 3, 1)
+        DINO_SW(19, 128, 128, 2, 4, 3, 1)
+        DINO_SW(20, 64, 64, 2, 2, 3, 2)
+        DINO_SW(21, 64, 64, 2, 4, 3, 2)
+        DINO_SW(22, 32, 128, 1, 4, 3, 2)
+        DINO_SW(23, 32, 64, 1, 4, 3, 2)
+        DINO_SW(24, 32, 64, 2, 2, 3, 2)
+        DINO_SW(25, 64, 64, 2, 2, 4, 2)
+        DINO_SW(26, 64, 64, 2, 2, 3, 1)
+#undef DINO_SW
+        default: *err = hipErrorInvalidValue; return true;
+    }
+}
 #endif
-        // F: 128-row tiles of the persistent kernel's schedule, one per workgroup, when they give 112 ... 256 workgroups: too few rows to
-        // fill the chip with 256- or 192-row tiles, enough columns that 128 x 256 tiles do (ViT-L batch 1 at 518 x 518: QKV 132 tiles
-        // 18.0 -> 15.0 us, FFN-in 176 tiles 21.1 -> 17.6; ViT-g QKV 42 -> 24; batch 4 FFN-out 64 -> 51).  Below ~112 tiles the
-        // small-tile kernel's many workgroups win, above 256 a second round starts (profiles/r03_small_m_gemm.md section 9).
-        // F4 (round 4): the same idea on gemm4.hip with the tile HEIGHT chosen for the launch: the shortest of 128 / 96 / 64 rows that still
-        // gives at most one tile per CU (QKV at ViT-L batch 1: 180 tiles of 96 rows instead of 132 of 128; FFN-in 240 instead of 176),
-        // for the 2-byte epilogues (profiles/r04_gemm4w.md section 6).  DINOV2_HIP_GEMM_GEN=2 keeps plan F.
-        {
-            const bool two_byte = eb == EPI_QKV || eb == EPI_GELU || eb == EPI_SWIGLU;
-            if ((two_byte || epi == EPI_RESID_LN) && !forced && gen != 2 && gemm4_ok(epi, a) && (gen == 4 || ln || a.K >= 1024)) {
-                int ni = 0;
-                for (int c = 2; c <= 4 && !ni; ++c)
-                    if ((long)ntn * ((a.M + 32 * c - 1) / (32 * c)) <= 256) ni = c;
-                const long tiles = ni ? (long)ntn * ((a.M + 32 * ni - 1) / (32 * ni)) : 0;
-                // (EPI_RESID_LN: only where the plain residual epilogue would leave the small-tile kernel too, at >= 112 tiles of 128 rows.
-                //  Its epilogue is twice as long as the plain one and one wave per SIMD issues it; measured on ViT-L with the fold on:
-                //  batch 2 (88 such tiles) small-tile kernel - 1.5 % of the forward against the unfolded path, 172 tiles of 64 rows - 8 %,
-                //  116 of 96 rows - 13 %; batch 3 (132) small-tile - 16 %, 172 tiles of 96 rows - 3.5 %; batch 4 (172) small-tile - 15 %,
-                //  232 tiles of 96 rows - 2.5 %, 172 of 128 rows - 5.6 % -- profiles/r06_ln_fold.md)
-                if (epi == EPI_RESID_LN && (long)ntn * ((a.M + 127) / 128) < 112) ni = 0;
-                if (ni && tiles >= 112) return DINO_LEAF(launch_gemm4_short(dt, epi, a, ni, st), "gemm4_short<%d>", 32 * ni);
-            }
-        }
-        {
-            const long t128r = (long)ntn * ((a.M + 127) / 128);
-            if (!is_patch && !ln && !forced && t128r >= 112 && t128r <= 256) return DINO_LEAF(launch_gemm2_128(dt, epi, a, st), "gemm2<128>");
-        }
-        if (is_patch) plan = (plan == 'E' || t192 < 192) ? 'E' : 'B';  // only the 192-row instantiation exists for this epilogue
-        // which generation runs the 256-row / mixed plans: gemm4.hip (four waves, hand-ordered K loop) where it applies, unless
-        // DINOV2_HIP_GEMM_GEN=2 asks for gemm2.hip (testing aid: the bit-equality tests compare the two)
-        // default: gemm4.hip wherever it applies (in the model: FFN-out - 4 %, QKV and FFN-in within 0.5 %, attn-out + 2 %; forward + 0.8 %
-        // over gemm2.hip everywhere, same box, interleaved runs -- profiles/r04_gemm4w.md)
-        // ... for K >= 1 024: with fewer K-tiles per output tile the four-wave kernel's longer epilogue (one wave per SIMD issues it alone)
-        // outweighs its K loop -- ViT-B / ViT-S (K = 768 / 384) measured 1.4 % / 3 % faster on gemm2.hip, ViT-L / ViT-g on gemm4.hip.
-        // DINOV2_HIP_GEMM_GEN=4 forces gemm4.hip wherever it can run (tests).
-        // ... and not the residual epilogue at K < 2 048 (attn-out: its read-modify-write burst is 36 % of a tile and eight waves keep more
-        // of it in flight: 0.131 against 0.133 ms in the model, four interleaved runs).
-        const bool g4 = ln || (gen != 2 && gemm4_ok(epi, a) && (gen == 4 || (a.K >= 1024 && !(epi == EPI_RESID && a.K < 2048))));
-        switch (plan) {
-            case 'A': return g4 ? DINO_LEAF(launch_gemm4(dt, epi, a, st), "gemm4<256>") : DINO_LEAF(launch_gemm2(dt, epi, a, st), "gemm2<256>");
-            case 'B': {
-                if (!ln) return DINO_LEAF(launch_gemm2_192(dt, epi, a, st), "gemm2<192>");
-                GemmArgs a0 = a;  // (the LN-fold epilogues: gemm4.hip's two-height launch with an empty 256-row part)
-                a0.M = 0;
-                return DINO_LEAF(launch_gemm4_mixed(dt, epi, a0, a, st), "gemm4_mixed<0+192>");
-            }
-            case 'C':
-                return g4 ? DINO_LEAF(launch_gemm4_mixed(dt, epi, a1, a2, st), "gemm4_mixed<256+192>")
-                          : DINO_LEAF(launch_gemm2_mixed(dt, epi, a1, a2, st), "gemm2_mixed<256+192>");
-            case 'D': {
-                const hipError_t e = g4 ? DINO_LEAF(launch_gemm4(dt, epi, a1, st), "gemm4<256>") : DINO_LEAF(launch_gemm2(dt, epi, a1, st), "gemm2<256>");
-                if (e != hipSuccess) return e;
-                a2.small_only = 1;  // the tail of a split goes straight to the small-tile kernel below
-                return launch_gemm(dt, epi, a2, st);
-            }
-            default: break;  // 'E'
-        }
-    }
-    // small problems (batch 1: M = 1374): 128x128 tiles leave most CUs idle and one workgroup per CU cannot hide the
-    // global -> LDS latency of its K loop.  64x128 tiles with 2 LDS stages (48 KiB: three workgroups per CU hide each other's
-    // latency) when there are enough tiles, with 3 stages (72 KiB) when there are not (N = 1024 at batch 1: 176 tiles; the
-    // K = 4096 GEMM 39.7 -> 33.8 us).  Measured at M = 1374: 128x128 / 64x128x2 / 64x128x3 = qkv 21.8 / 19.5 / 27.1 us,
-    // ffn-in 31.2 / 24.9 / 34.0, ffn-out 49.0 / 39.7 / 33.8.
-    const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-    const long t64 = (long)((a.M + 63) / 64) * ((a.N + 127) / 128);
-    const int cfg = t128 >= 512 ? 0 : t64 >= 384 ? 1 : 2;
-    // Fewer tiles than CUs (batch 1: the two N = hidden GEMMs at 518 x 518, every GEMM at 224 x 224): one workgroup per CU walks
-    // a serial K loop (wait -> barrier -> issue -> fragment reads -> MFMAs per stage) and nothing overlaps it, so what counts is how
-    // short one link is (profiles/r03_small_m_gemm.md):
-    //  * eight waves, two 64-wide K sub-tiles per LDS stage (half the links);
-    //  * wave tiles of 32 x 32 (2 x 4 waves) rather than 16 x 64 (4 x 2): the loop is bound by LDS reads -- a 16 x 64 wave tile reads
-    //    five 1 KiB fragments per four MFMAs, a 32 x 32 one four -- and the LDS moves 128 B/clk (FFN-out at M = 1 374: 28.0 -> 25.4 us);
-    //  * the SMALLEST tile that still gives at most one workgroup per CU: every CU that joins shortens everybody's chain (M = 261:
-    //    attn-out 9.8 -> 5.7 us, FFN-out 27.3 -> 14.5 on 32 x 64 tiles; QKV 8.9 -> 6.3 on 64 x 64); two workgroups per CU lose again.
-    // Nothing about the arithmetic changes -- each output's MFMA chain runs over K in the same order in every configuration.
-    if (cfg == 2 && t64 < 256 && (a.K / 64) % 2 == 0 && a.K >= 256 && eb != EPI_SWIGLU) {
-        const long t6464 = (long)((a.M + 63) / 64) * ((a.N + 63) / 64), t3264 = (long)((a.M + 31) / 32) * ((a.N + 63) / 64);
-        if (t3264 <= 256) return dt == DT_F16 ? leaf_cfg<_Float16, 32, 64, 1, 4, 3, 2>(epi, a, st) : leaf_cfg<__bf16, 32, 64, 1, 4, 3, 2>(epi, a, st);
-        if (t6464 <= 256) return dt == DT_F16 ? leaf_cfg<_Float16, 64, 64, 2, 4, 3, 2>(epi, a, st) : leaf_cfg<__bf16, 64, 64, 2, 4, 3, 2>(epi, a, st);
-        return dt == DT_F16 ? leaf_cfg<_Float16, 64, 128, 2, 4, 3, 2>(epi, a, st) : leaf_cfg<__bf16, 64, 128, 2, 4, 3, 2>(epi, a, st);
-    }
-    if (cfg == 2 && t64 < 256 && (a.K / 64) % 2 == 0 && a.K >= 256)  // (SwiGLU pairs columns inside a 64-wide wave tile)
-        return dt == DT_F16 ? leaf_cfg<_Float16, 64, 128, 4, 2, 3, 2>(epi, a, st) : leaf_cfg<__bf16, 64, 128, 4, 2, 3, 2>(epi, a, st);
-    if (cfg == 2 && t64 < 256)
-        return dt == DT_F16 ? leaf_cfg<_Float16, 64, 128, 4, 2, 3>(epi, a, st) : leaf_cfg<__bf16, 64, 128, 4, 2, 3>(epi, a, st);
-    if (cfg == 1) return dt == DT_F16 ? leaf_cfg<_Float16, 64, 128, 2, 2, 2>(epi, a, st) : leaf_cfg<__bf16, 64, 128, 2, 2, 2>(epi, a, st);
-    if (cfg == 2) return dt == DT_F16 ? leaf_cfg<_Float16, 64, 128, 2, 2, 3>(epi, a, st) : leaf_cfg<__bf16, 64, 128, 2, 2, 3>(epi, a, st);
-    return dt == DT_F16 ? leaf_cfg<_Float16, 128, 128, 2, 2, 2>(epi, a, st) : leaf_cfg<__bf16, 128, 128, 2, 2, 2>(epi, a, st);
+
+hipError_t launch_gemm(DType dt, Epilogue epi, const GemmArgs& a, hipStream_t st) {
+#ifdef DINO_GEMM_SWEEP
+    hipError_t swept;
+    if (launch_gemm_sweep(dt, epi, a, st, &swept)) return swept;
+#endif
+    GemmPlan plan;  // (on the stack, as the argument copies always were: a launch allocates nothing)
+    hipError_t e = gemm_plan(dt, epi, a, true, &plan);
+    for (int i = 0; i < plan.nsteps && e == hipSuccess; ++i) e = launch_step(dt, epi, plan.steps[i], st);
+    return e;
 }
 
 hipError_t gemm_plan_describe(DType dt, Epilogue epi, const GemmArgs& a, char* out, size_t cap) {
     if (!out || cap == 0) return hipErrorInvalidValue;
-    std::string s;
-    t_plan_sink = &s;
-    const hipError_t e = launch_gemm(dt, epi, a, nullptr);
-    t_plan_sink = nullptr;
-    snprintf(out, cap, "%s", s.c_str());
+    out[0] = 0;
+    GemmPlan plan;
+    const hipError_t e = gemm_plan(dt, epi, a, false, &plan);
+#ifdef DINO_GEMM_SWEEP
+    if (sweep_cfg() >= 0) return hipErrorInvalidValue;  // (a forced configuration is outside the planner: ADVICE r5)
+#endif
+    size_t n = 0;
+    for (int i = 0; i < plan.nsteps && n + 1 < cap; ++i) {  // (snprintf keeps a text that does not fit terminated inside cap)
+        if (i) out[n++] = ';';
+        n += (size_t)step_name(plan.steps[i], out + n, cap - n);
+    }
     return e;
 }
 

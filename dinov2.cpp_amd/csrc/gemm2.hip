@@ -571,115 +571,77 @@ static void gemm_prof_dump(const char* what, int nblocks) {
 }
 #endif
 
+// The epilogues this file instantiates, written ONCE: the launchers and gemm2_init both take their kernels from the two selectors below, so
+// a kernel that can be launched always has its LDS limit raised.  (The LN-fold epilogues live in gemm4.hip and the small-tile kernel.)
+#define DINO2_EPIS(X) X(EPI_QKV) X(EPI_RESID) X(EPI_GELU) X(EPI_SWIGLU) X(EPI_PLAIN_F32)
 template <typename T, int XREP>
-static hipError_t launch2_t(Epilogue epi, const GemmArgs& a, hipStream_t st) {
-    const int tiles = (a.N / 256) * ((a.M + 64 * XREP - 1) / (64 * XREP));
-    const dim3 grid(XREP == 2 ? tiles : tiles < 256 ? tiles : 256), block(512);  // (128-row tiles: one tile per workgroup)
-    const size_t lds = XREP == 2 ? 3 * 49152 : 2 * 512 * 128;
-#define DINO_L2(E)                                                         \
-    case E:                                                                \
-        hipLaunchKernelGGL((gemm2_kernel<T, E, XREP>), grid, block, lds, st, a); \
-        break;
+static GemmKernelFn kernel2(int epi) {
     switch (epi) {
         case EPI_PATCH:  // the 256-row instantiation spills (the pos-embed prefetch on top of 128 accumulators); 192-row does not
-            if (XREP != 3) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((gemm2_kernel<T, EPI_PATCH, 3>), grid, block, lds, st, a);
-            break;
-        DINO_L2(EPI_QKV)
-        DINO_L2(EPI_RESID)
-        DINO_L2(EPI_GELU)
-        DINO_L2(EPI_SWIGLU)
-        DINO_L2(EPI_PLAIN_F32)
-        default: return hipErrorInvalidValue;  // (the LN-fold epilogues live in gemm4.hip and the small-tile kernel)
+            return XREP == 3 ? gemm2_kernel<T, EPI_PATCH, 3> : nullptr;
+#define DINO_X(E) case E: return gemm2_kernel<T, E, XREP>;
+            DINO2_EPIS(DINO_X)
+#undef DINO_X
+        default: return nullptr;
     }
-#undef DINO_L2
+}
+template <typename T>
+static GemmKernelFn2 kernel2_mixed(int epi) {
+    switch (epi) {
+#define DINO_X(E) case E: return gemm2_mixed_kernel<T, E>;
+        DINO2_EPIS(DINO_X)
+#undef DINO_X
+        default: return nullptr;
+    }
+}
+constexpr size_t lds2(int xrep) { return xrep == 2 ? 3 * 49152 : 2 * 512 * 128; }
+
+template <typename T, int XREP>
+static hipError_t launch2_t(Epilogue epi, const GemmArgs& a, hipStream_t st) {
+    const GemmKernelFn k = kernel2<T, XREP>(epi);
+    if (!k) return hipErrorInvalidValue;
+    const int tiles = (a.N / 256) * ((a.M + 64 * XREP - 1) / (64 * XREP));
+    const dim3 grid(XREP == 2 ? tiles : tiles < 256 ? tiles : 256), block(512);  // (128-row tiles: one tile per workgroup)
+    hipLaunchKernelGGL(k, grid, block, lds2(XREP), st, a);
 #ifdef DINO_GEMM_PROF
     gemm_prof_dump(epi == EPI_QKV ? "plain-launch QKV" : "plain-launch", (int)grid.x);
 #endif
     return hipGetLastError();
 }
 
-// requires N % 256 == 0 and (K / 64) even
-hipError_t launch_gemm2(DType dt, Epilogue epi, const GemmArgs& a, hipStream_t st) {
-    return dt == DT_F16 ? launch2_t<_Float16, 4>(epi, a, st) : launch2_t<__bf16, 4>(epi, a, st);
+// 64 xrep-row tiles: 256 and 192 rows persistent (see gemm2_kernel), 128 rows one per workgroup (see gemm2_body); requires N % 256 == 0 and
+// (K / 64) even
+hipError_t launch_gemm2(DType dt, Epilogue epi, const GemmArgs& a, int xrep, hipStream_t st) {
+    if (dt == DT_F16) return xrep == 4 ? launch2_t<_Float16, 4>(epi, a, st) : xrep == 3 ? launch2_t<_Float16, 3>(epi, a, st) : launch2_t<_Float16, 2>(epi, a, st);
+    return xrep == 4 ? launch2_t<__bf16, 4>(epi, a, st) : xrep == 3 ? launch2_t<__bf16, 3>(epi, a, st) : launch2_t<__bf16, 2>(epi, a, st);
 }
 
-
-template <typename T>
-static hipError_t launch2_mixed_t(Epilogue epi, const GemmArgs& a, const GemmArgs& b, hipStream_t st) {
-    const dim3 grid(256), block(512);
-    const size_t lds = 2 * 512 * 128;
-#define DINO_LM(E)                                                                  \
-    case E:                                                                         \
-        hipLaunchKernelGGL((gemm2_mixed_kernel<T, E>), grid, block, lds, st, a, b); \
-        break;
-    switch (epi) {
-        DINO_LM(EPI_QKV)
-        DINO_LM(EPI_RESID)
-        DINO_LM(EPI_GELU)
-        DINO_LM(EPI_SWIGLU)
-        DINO_LM(EPI_PLAIN_F32)
-        default: return hipErrorInvalidValue;
-    }
-#undef DINO_LM
+// 256-row tiles for `a` (must be >= 256 tiles), then 192-row tiles for `b`, in one launch (see gemm2_mixed_kernel)
+hipError_t launch_gemm2_mixed(DType dt, Epilogue epi, const GemmArgs& a, const GemmArgs& b, hipStream_t st) {
+    const GemmKernelFn2 k = dt == DT_F16 ? kernel2_mixed<_Float16>(epi) : kernel2_mixed<__bf16>(epi);
+    if (!k) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k, dim3(256), dim3(512), lds2(4), st, a, b);
 #ifdef DINO_GEMM_PROF
     gemm_prof_dump(epi == EPI_GELU ? "mixed GELU" : epi == EPI_RESID ? "mixed RESID" : epi == EPI_QKV ? "mixed QKV" : "mixed", 256);
 #endif
     return hipGetLastError();
 }
 
-// 256-row tiles for `a` (must be >= 256 tiles), then 192-row tiles for `b`, in one launch (see gemm2_mixed_kernel)
-hipError_t launch_gemm2_mixed(DType dt, Epilogue epi, const GemmArgs& a, const GemmArgs& b, hipStream_t st) {
-    return dt == DT_F16 ? launch2_mixed_t<_Float16>(epi, a, b, st) : launch2_mixed_t<__bf16>(epi, a, b, st);
-}
-
-// same kernel with 192-row tiles (see gemm2_kernel)
-hipError_t launch_gemm2_192(DType dt, Epilogue epi, const GemmArgs& a, hipStream_t st) {
-    return dt == DT_F16 ? launch2_t<_Float16, 3>(epi, a, st) : launch2_t<__bf16, 3>(epi, a, st);
-}
-// 128-row tiles, one per workgroup (see gemm2_body)
-hipError_t launch_gemm2_128(DType dt, Epilogue epi, const GemmArgs& a, hipStream_t st) {
-    return dt == DT_F16 ? launch2_t<_Float16, 2>(epi, a, st) : launch2_t<__bf16, 2>(epi, a, st);
-}
-
-template <typename T, int XREP>
+template <typename T>
 static hipError_t attr2_t() {
     hipError_t e = hipSuccess;
-    const int lds = XREP == 2 ? 3 * 49152 : 2 * 512 * 128;
-#define DINO_A2(E)                                                                  \
-    if (e == hipSuccess)                                                            \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_kernel<T, E, XREP>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess && XREP == 3)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_kernel<T, EPI_PATCH, 3>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    DINO_A2(EPI_QKV)
-    DINO_A2(EPI_RESID)
-    DINO_A2(EPI_GELU)
-    DINO_A2(EPI_SWIGLU)
-    DINO_A2(EPI_PLAIN_F32)
-#undef DINO_A2
-#define DINO_A3(E)                                                                        \
-    if (e == hipSuccess && XREP == 4)                                                     \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2_mixed_kernel<T, E>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    DINO_A3(EPI_QKV)
-    DINO_A3(EPI_RESID)
-    DINO_A3(EPI_GELU)
-    DINO_A3(EPI_SWIGLU)
-    DINO_A3(EPI_PLAIN_F32)
-#undef DINO_A3
+    for (int epi = 0; epi < EPI_COUNT && e == hipSuccess; ++epi) {
+        e = gemm_raise_lds((const void*)kernel2<T, 4>(epi), lds2(4));
+        if (e == hipSuccess) e = gemm_raise_lds((const void*)kernel2<T, 3>(epi), lds2(3));
+        if (e == hipSuccess) e = gemm_raise_lds((const void*)kernel2<T, 2>(epi), lds2(2));
+        if (e == hipSuccess) e = gemm_raise_lds((const void*)kernel2_mixed<T>(epi), lds2(4));
+    }
     return e;
 }
 
 hipError_t gemm2_init() {
-    hipError_t e = attr2_t<_Float16, 4>();
-    if (e == hipSuccess) e = attr2_t<__bf16, 4>();
-    if (e == hipSuccess) e = attr2_t<_Float16, 3>();
-    if (e == hipSuccess) e = attr2_t<__bf16, 3>();
-    if (e == hipSuccess) e = attr2_t<_Float16, 2>();
-    if (e == hipSuccess) e = attr2_t<__bf16, 2>();
-    return e;
+    const hipError_t e = attr2_t<_Float16>();
+    return e == hipSuccess ? attr2_t<__bf16>() : e;
 }
 
 }  // namespace dinov2

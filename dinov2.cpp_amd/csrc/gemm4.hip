@@ -801,142 +801,81 @@ static void gemm4_prof_dump(const char* what, int epi, int nblocks) {
 }
 #endif
 
+// The epilogues this file instantiates, written ONCE: the launchers and gemm4_init both take their kernels from the two selectors below, so
+// a kernel that can be launched always has its LDS limit raised.
+#define DINO4_EPIS(X) X(EPI_QKV) X(EPI_RESID) X(EPI_GELU) X(EPI_SWIGLU) X(EPI_PLAIN_F32) X(EPI_RESID_LN) X(EPI_QKV_LN) X(EPI_GELU_LN) X(EPI_SWIGLU_LN)
+// Short tiles (NI = 2 / 3 / 4: 64 / 96 / 128 rows), one per workgroup: for launches whose 256-row tiles would leave most CUs idle (batch 1: M = 1 374 ->
+// QKV 15 panels of 96 rows x 12 column tiles = 180 workgroups instead of 132 of 128 rows; FFN-in 240 instead of 176).  The 2-byte
+// epilogues (the plain f32 ones go to the small-tile kernel or to gemm2.hip's 128-row tiles at these sizes) and EPI_RESID_LN, which has no
+// gemm2.hip form (batch 4: without it the LN fold fell back to the small-tile kernel where the default path runs 128-row tiles: - 15 %).
+// Same K order, same bits.
+constexpr bool gemm4_short_epi(int e) { return e != EPI_RESID && e != EPI_PLAIN_F32; }
 template <typename T, int NI>
-static hipError_t launch4_t(Epilogue epi, const GemmArgs& a, hipStream_t st) {
-    const int tiles = (a.N / 256) * ((a.M + 32 * NI - 1) / (32 * NI));
-    const dim3 grid(tiles < 256 ? tiles : 256), block(256);
-#define DINO_L4(E)                                                                \
-    case E:                                                                       \
-        hipLaunchKernelGGL((gemm4_kernel<T, E, NI>), grid, block, G4_LDS, st, a); \
-        break;
+static GemmKernelFn kernel4(int epi) {
     switch (epi) {
-        DINO_L4(EPI_QKV)
-        DINO_L4(EPI_RESID)
-        DINO_L4(EPI_GELU)
-        DINO_L4(EPI_SWIGLU)
-        DINO_L4(EPI_PLAIN_F32)
-        DINO_L4(EPI_RESID_LN)
-        DINO_L4(EPI_QKV_LN)
-        DINO_L4(EPI_GELU_LN)
-        DINO_L4(EPI_SWIGLU_LN)
-        default: return hipErrorInvalidValue;
+#define DINO_X(E)                                                                        \
+    case E:                                                                              \
+        if constexpr (NI == 8 || gemm4_short_epi(E)) return gemm4_kernel<T, E, NI>; \
+        else return nullptr;
+        DINO4_EPIS(DINO_X)
+#undef DINO_X
+        default: return nullptr;
     }
-#undef DINO_L4
+}
+template <typename T>
+static GemmKernelFn2 kernel4_mixed(int epi) {
+    switch (epi) {
+#define DINO_X(E) case E: return gemm4_mixed_kernel<T, E>;
+        DINO4_EPIS(DINO_X)
+#undef DINO_X
+        default: return nullptr;
+    }
+}
+
+// all three require N % 256 == 0, K / 64 even and >= 4, and an epilogue other than EPI_PATCH (gemm4_ok)
+bool gemm4_ok(Epilogue epi, int N, int K) { return epi != EPI_PATCH && N % 256 == 0 && K % 128 == 0 && K >= 256; }
+template <typename T>
+static GemmKernelFn kernel4_ni(int ni, int epi) {
+    return ni == 8 ? kernel4<T, 8>(epi) : ni == 2 ? kernel4<T, 2>(epi) : ni == 3 ? kernel4<T, 3>(epi) : ni == 4 ? kernel4<T, 4>(epi) : nullptr;
+}
+// rows per tile = 32 ni: ni = 8 the persistent kernel (at most 256 workgroups walk the tiles), ni in {2, 3, 4} one tile per workgroup
+hipError_t launch_gemm4(DType dt, Epilogue epi, const GemmArgs& a, int ni, hipStream_t st) {
+    const GemmKernelFn k = dt == DT_F16 ? kernel4_ni<_Float16>(ni, epi) : kernel4_ni<__bf16>(ni, epi);
+    if (!k) return hipErrorInvalidValue;
+    const int tiles = (a.N / 256) * ((a.M + 32 * ni - 1) / (32 * ni));
+    if (ni != 8 && tiles > 256) return hipErrorInvalidValue;  // (one tile per workgroup, one workgroup per CU)
+    hipLaunchKernelGGL(k, dim3(tiles < 256 ? tiles : 256), dim3(256), G4_LDS, st, a);
 #ifdef DINO_GEMM4_PROF
-    gemm4_prof_dump("plain launch", (int)epi, (int)grid.x);
+    if (ni == 8) gemm4_prof_dump("plain launch", (int)epi, tiles < 256 ? tiles : 256);
 #endif
     return hipGetLastError();
 }
-
-template <typename T>
-static hipError_t launch4_mixed_t(Epilogue epi, const GemmArgs& a, const GemmArgs& b, hipStream_t st) {
-    const dim3 grid(256), block(256);
-#define DINO_LM4(E)                                                                    \
-    case E:                                                                            \
-        hipLaunchKernelGGL((gemm4_mixed_kernel<T, E>), grid, block, G4_LDS, st, a, b); \
-        break;
-    switch (epi) {
-        DINO_LM4(EPI_QKV)
-        DINO_LM4(EPI_RESID)
-        DINO_LM4(EPI_GELU)
-        DINO_LM4(EPI_SWIGLU)
-        DINO_LM4(EPI_PLAIN_F32)
-        DINO_LM4(EPI_RESID_LN)
-        DINO_LM4(EPI_QKV_LN)
-        DINO_LM4(EPI_GELU_LN)
-        DINO_LM4(EPI_SWIGLU_LN)
-        default: return hipErrorInvalidValue;
-    }
-#undef DINO_LM4
+// 256-row tiles for `a` (whole rounds), then 192-row tiles for `b`, in one launch
+hipError_t launch_gemm4_mixed(DType dt, Epilogue epi, const GemmArgs& a, const GemmArgs& b, hipStream_t st) {
+    const GemmKernelFn2 k = dt == DT_F16 ? kernel4_mixed<_Float16>(epi) : kernel4_mixed<__bf16>(epi);
+    if (!k) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k, dim3(256), dim3(256), G4_LDS, st, a, b);
 #ifdef DINO_GEMM4_PROF
     gemm4_prof_dump("mixed launch", (int)epi, 256);
 #endif
     return hipGetLastError();
 }
-
-// both require N % 256 == 0, K / 64 even and >= 4, and an epilogue other than EPI_PATCH (gemm4_ok)
-bool gemm4_ok(Epilogue epi, const GemmArgs& a) {
-    return epi != EPI_PATCH && a.N % 256 == 0 && a.K % 128 == 0 && a.K >= 256;
-}
-hipError_t launch_gemm4(DType dt, Epilogue epi, const GemmArgs& a, hipStream_t st) {
-    return dt == DT_F16 ? launch4_t<_Float16, 8>(epi, a, st) : launch4_t<__bf16, 8>(epi, a, st);
-}
-// 256-row tiles for `a` (whole rounds), then 192-row tiles for `b`, in one launch
-hipError_t launch_gemm4_mixed(DType dt, Epilogue epi, const GemmArgs& a, const GemmArgs& b, hipStream_t st) {
-    return dt == DT_F16 ? launch4_mixed_t<_Float16>(epi, a, b, st) : launch4_mixed_t<__bf16>(epi, a, b, st);
-}
-
-// Short tiles (64 / 96 / 128 rows), one per workgroup: for launches whose 256-row tiles would leave most CUs idle (batch 1: M = 1 374 ->
-// QKV 15 panels of 96 rows x 12 column tiles = 180 workgroups instead of 132 of 128 rows; FFN-in 240 instead of 176).  The 2-byte
-// epilogues (the plain f32 ones go to the small-tile kernel or to gemm2.hip's 128-row tiles at these sizes) and EPI_RESID_LN, which has no
-// gemm2.hip form (batch 4: without it the LN fold fell back to the small-tile kernel where the default path runs 128-row tiles: - 15 %).
-// Same K order, same bits.
-template <typename T, int NI>
-static hipError_t launch4_short_t(Epilogue epi, const GemmArgs& a, hipStream_t st) {
-    const int tiles = (a.N / 256) * ((a.M + 32 * NI - 1) / (32 * NI));
-    if (tiles > 256) return hipErrorInvalidValue;  // (one tile per workgroup, one workgroup per CU)
-    const dim3 grid(tiles), block(256);
-    switch (epi) {
-        case EPI_QKV: hipLaunchKernelGGL((gemm4_kernel<T, EPI_QKV, NI>), grid, block, G4_LDS, st, a); break;
-        case EPI_GELU: hipLaunchKernelGGL((gemm4_kernel<T, EPI_GELU, NI>), grid, block, G4_LDS, st, a); break;
-        case EPI_SWIGLU: hipLaunchKernelGGL((gemm4_kernel<T, EPI_SWIGLU, NI>), grid, block, G4_LDS, st, a); break;
-        case EPI_QKV_LN: hipLaunchKernelGGL((gemm4_kernel<T, EPI_QKV_LN, NI>), grid, block, G4_LDS, st, a); break;
-        case EPI_GELU_LN: hipLaunchKernelGGL((gemm4_kernel<T, EPI_GELU_LN, NI>), grid, block, G4_LDS, st, a); break;
-        case EPI_SWIGLU_LN: hipLaunchKernelGGL((gemm4_kernel<T, EPI_SWIGLU_LN, NI>), grid, block, G4_LDS, st, a); break;
-        case EPI_RESID_LN: hipLaunchKernelGGL((gemm4_kernel<T, EPI_RESID_LN, NI>), grid, block, G4_LDS, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-// rows per tile = 32 ni, ni in {2, 3, 4}
-hipError_t launch_gemm4_short(DType dt, Epilogue epi, const GemmArgs& a, int ni, hipStream_t st) {
-    if (dt == DT_F16) return ni == 2 ? launch4_short_t<_Float16, 2>(epi, a, st) : ni == 3 ? launch4_short_t<_Float16, 3>(epi, a, st) : launch4_short_t<_Float16, 4>(epi, a, st);
-    return ni == 2 ? launch4_short_t<__bf16, 2>(epi, a, st) : ni == 3 ? launch4_short_t<__bf16, 3>(epi, a, st) : launch4_short_t<__bf16, 4>(epi, a, st);
-}
-
-template <typename T, int NI>
-static hipError_t attr4_short_t() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4_kernel<T, EPI_QKV, NI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G4_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4_kernel<T, EPI_GELU, NI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G4_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4_kernel<T, EPI_SWIGLU, NI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G4_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4_kernel<T, EPI_QKV_LN, NI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G4_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4_kernel<T, EPI_GELU_LN, NI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G4_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4_kernel<T, EPI_SWIGLU_LN, NI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G4_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4_kernel<T, EPI_RESID_LN, NI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G4_LDS);
-    return e;
-}
-
 template <typename T>
 static hipError_t attr4_t() {
     hipError_t e = hipSuccess;
-#define DINO_A4(E)                                                                                                                        \
-    if (e == hipSuccess)                                                                                                                  \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4_kernel<T, E, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G4_LDS); \
-    if (e == hipSuccess)                                                                                                                  \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4_mixed_kernel<T, E>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G4_LDS);
-    DINO_A4(EPI_QKV)
-    DINO_A4(EPI_RESID)
-    DINO_A4(EPI_GELU)
-    DINO_A4(EPI_SWIGLU)
-    DINO_A4(EPI_PLAIN_F32)
-    DINO_A4(EPI_RESID_LN)
-    DINO_A4(EPI_QKV_LN)
-    DINO_A4(EPI_GELU_LN)
-    DINO_A4(EPI_SWIGLU_LN)
-#undef DINO_A4
+    for (int epi = 0; epi < EPI_COUNT && e == hipSuccess; ++epi) {
+        e = gemm_raise_lds((const void*)kernel4<T, 8>(epi), G4_LDS);
+        if (e == hipSuccess) e = gemm_raise_lds((const void*)kernel4_mixed<T>(epi), G4_LDS);
+        if (e == hipSuccess) e = gemm_raise_lds((const void*)kernel4<T, 2>(epi), G4_LDS);
+        if (e == hipSuccess) e = gemm_raise_lds((const void*)kernel4<T, 3>(epi), G4_LDS);
+        if (e == hipSuccess) e = gemm_raise_lds((const void*)kernel4<T, 4>(epi), G4_LDS);
+    }
     return e;
 }
 
 hipError_t gemm4_init() {
-    hipError_t e = attr4_t<_Float16>();
-    if (e == hipSuccess) e = attr4_t<__bf16>();
-    if (e == hipSuccess) e = attr4_short_t<_Float16, 2>();
-    if (e == hipSuccess) e = attr4_short_t<_Float16, 3>();
-    if (e == hipSuccess) e = attr4_short_t<_Float16, 4>();
-    if (e == hipSuccess) e = attr4_short_t<__bf16, 2>();
-    if (e == hipSuccess) e = attr4_short_t<__bf16, 3>();
-    if (e == hipSuccess) e = attr4_short_t<__bf16, 4>();
-    return e;
+    const hipError_t e = attr4_t<_Float16>();
+    return e == hipSuccess ? attr4_t<__bf16>() : e;
 }
 
 }  // namespace dinov2

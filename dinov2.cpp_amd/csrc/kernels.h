@@ -33,6 +33,7 @@ inline Epilogue epi_base(Epilogue e) {
     return e == EPI_RESID_LN ? EPI_RESID : e == EPI_QKV_LN ? EPI_QKV : e == EPI_GELU_LN ? EPI_GELU : e == EPI_SWIGLU_LN ? EPI_SWIGLU : e;
 }
 inline bool epi_ln_consumer(Epilogue e) { return e == EPI_QKV_LN || e == EPI_GELU_LN || e == EPI_SWIGLU_LN; }
+constexpr int EPI_COUNT = 10;
 constexpr int LN_GROUP = 64;      // columns per partial-sum group of EPI_RESID_LN's row statistics
 constexpr int LN_MAX_GROUPS = 24; // hidden sizes up to 1 536 (ViT-g); larger models keep the LayerNorm launches
 inline int ln_stat_slots(int hidden) { return hidden / LN_GROUP <= 12 ? 12 : 24; }  // slots per row of the statistics buffer (device_types.h, ln_row_load)
@@ -49,10 +50,12 @@ struct GemmArgs {
     int P, T, R;        // EPI_PATCH token mapping
     int qcols;          // EPI_QKV: columns [0, qcols) are multiplied by qscale
     float qscale;
-    int small_only;     // launch_gemm internal: this is the tail of a split launch, use the small-tile kernel
-    int nt_out;         // launch_gemm internal: 2-byte outputs leave with non-temporal stores (set when the output is larger than the L2s)
-    int sub;            // launch_gemm internal: one part of a split launch (inherits nt_out from the whole)
-    int clk_slot;       // launch_gemm internal: the clock-probe slot of the LOGICAL launch (device_types.h), decided before any split
+    // The next four are written by the planner (gemm_plan), never read from the caller.  They stay members because this struct is the kernels'
+    // parameter block and its layout is fixed.
+    int small_only;     // unused (no kernel reads it); once steered launch_gemm's recursion.  Always 0 in a plan
+    int nt_out;         // 2-byte outputs leave with non-temporal stores (set when the output is larger than the L2s); one value per logical output
+    int sub;            // unused (no kernel reads it); once marked the parts of a split launch.  Always 0 in a plan
+    int clk_slot;       // the clock-probe slot of the LOGICAL launch (device_types.h), decided before any split
     // ---- LN fold (EPI_RESID_LN and the *_LN consumers).  Row statistics: stats[(m * ln_gs + g) * 2 + {0, 1}] = sum / sum of squares
     // of x[m, 64 g .. 64 g + 63] (f32, a fixed pairwise tree over the 64 columns: every kernel produces the same bits); ln_gs = slots per
     // row = ln_stat_slots(hidden): 12 or 24, the slots past hidden / 64 zero (set once, never written)
@@ -65,11 +68,48 @@ struct GemmArgs {
     float ln_eps;           // consumers: LayerNorm epsilon
 };
 
+using GemmKernelFn = void (*)(GemmArgs);             // a kernel of gemm.hip / gemm2.hip / gemm4.hip
+using GemmKernelFn2 = void (*)(GemmArgs, GemmArgs);  // a two-height kernel (gemm2_mixed_kernel, gemm4_mixed_kernel)
+// raises a kernel's dynamic-LDS limit (the *_init functions); a null kernel = an epilogue its family does not instantiate
+inline hipError_t gemm_raise_lds(const void* kernel, size_t bytes) {
+    return kernel ? hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
+}
+
+// ---- the plan of one GEMM: which kernels run it and which part of the output each of them covers.  Plain data, filled by gemm_plan without
+// touching the device; launch_gemm launches its steps in order, gemm_plan_describe prints them, tests/test_gemm_plans.py checks on the CPU
+// that the parts tile the output exactly once.
+enum GemmFamily : int {
+    GEMM_SMALL = 0,    // gemm.hip, the small-tile kernel; `cfg` names the configuration
+    GEMM2 = 1,         // gemm2.hip, `tile`-row tiles (256 | 192 persistent, 128 one per workgroup)
+    GEMM2_MIXED = 2,   // gemm2.hip, 256-row tiles for args[0], then 192-row tiles for args[1], one launch
+    GEMM4 = 3,         // gemm4.hip, 256-row tiles
+    GEMM4_MIXED = 4,   // gemm4.hip, as GEMM2_MIXED (args[0] may be empty: 192-row tiles only)
+    GEMM4_SHORT = 5    // gemm4.hip, `tile`-row tiles (64 | 96 | 128), one per workgroup
+};
+struct GemmStep {
+    GemmFamily family;
+    int tile;                    // tile height in rows (0 for GEMM_SMALL)
+    int cfg;                     // GEMM_SMALL: index into gemm.hip's list of small-tile configurations
+    int row0, rows, col0, cols;  // the rectangle of the output this step covers
+    int rows0;                   // rows [row0, row0 + rows0) are args[0]; the rest, for the two-height kernels only, args[1]
+    GemmArgs args[2];            // what the kernel is launched with: slices of GemmPlan::whole over those ranges
+};
+constexpr int GEMM_PLAN_MAX_STEPS = 4;  // the deepest plan has three: "gemm2<256>;small<..>;small<..>" (column split, then a row split of the first part)
+struct GemmPlan {
+    GemmArgs whole;  // the caller's arguments, validated, with nt_out / clk_slot / ln_gs decided once for all steps
+    int nsteps;      // 0 for a refused shape
+    GemmStep steps[GEMM_PLAN_MAX_STEPS];
+};
+// Launches nothing and calls no device API.  hipErrorInvalidValue for shapes launch_gemm refuses; check_pointers = false for plan queries,
+// which carry no pointers (none is dereferenced either way; a null pointer stays null in every slice).
+hipError_t gemm_plan(DType dt, Epilogue epi, const GemmArgs& a, bool check_pointers, GemmPlan* out);
+
+// gemm_plan (with pointer checks), then its steps in order, stopping at the first error
 hipError_t launch_gemm(DType dt, Epilogue epi, const GemmArgs& a, hipStream_t stream);
 // must be called once per device before the first launch_gemm (raises the dynamic-LDS limit)
 hipError_t gemm_init();
-// Which kernel(s) launch_gemm would run for this problem, without launching anything: a ';'-separated list of kernel plans, e.g.
-// "gemm4_mixed<256+192>" or "gemm4<256>;small<64x128,w2x2,st3,ks1>" (pointers in `a` are not dereferenced).  Returns hipErrorInvalidValue
+// Which kernel(s) launch_gemm would run for this problem: gemm_plan without pointer checks, the step names joined by ';', e.g.
+// "gemm4_mixed<256+192>" or "gemm4<256>;small<64x128,w2x2,st3,ks1>".  Returns hipErrorInvalidValue and an empty text
 // for shapes launch_gemm refuses.  The CPU-side coverage test enumerates the model shapes with it (tests/test_gemm_plans.py).
 hipError_t gemm_plan_describe(DType dt, Epilogue epi, const GemmArgs& a, char* out, size_t cap);
 

@@ -469,13 +469,44 @@ extern "C" int dinov2_hip_op_get_tuning(const char* key) {
     return -1;
 }
 // no device needed: nothing is launched and no pointer is dereferenced
-extern "C" int dinov2_hip_op_gemm_plan(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, char* out, int32_t cap) {
-    if (!out || cap <= 0 || epilogue < 0 || epilogue > EPI_SWIGLU_LN) return DINOV2_HIP_ERR_INVALID;
+static GemmArgs plan_query_args(int32_t epilogue, int32_t M, int32_t N, int32_t K) {
     GemmArgs a{};
     a.M = M; a.N = N; a.K = K; a.ldo = epi_base((Epilogue)epilogue) == EPI_SWIGLU ? N / 2 : N;
     a.P = 1; a.T = 2;
     a.qcols = N / 3;
+    return a;
+}
+extern "C" int dinov2_hip_op_gemm_plan(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, char* out, int32_t cap) {
+    if (!out || cap <= 0 || epilogue < 0 || epilogue > EPI_SWIGLU_LN) return DINOV2_HIP_ERR_INVALID;
+    const GemmArgs a = plan_query_args(epilogue, M, N, K);
     return gemm_plan_describe(dtype == 1 ? DT_BF16 : DT_F16, (Epilogue)epilogue, a, out, (size_t)cap) == hipSuccess ? DINOV2_HIP_OK : DINOV2_HIP_ERR_INVALID;
+}
+// The same plan as data.  Every pointer of the query is a distinct made-up address (never dereferenced), so that what a part's arguments add
+// to the caller's pointers can be read back from the arguments the kernels would get.
+extern "C" int dinov2_hip_op_gemm_plan_parts(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, int64_t* out, int32_t cap_records) {
+    if (!out || cap_records <= 0 || epilogue < 0 || epilogue > EPI_SWIGLU_LN) return -1;
+    auto base = [](int k) { return (uintptr_t)(k + 1) << 40; };
+    GemmArgs a = plan_query_args(epilogue, M, N, K);
+    a.A = (const void*)base(0); a.W = (const void*)base(1); a.bias = (const float*)base(2); a.aux = (const float*)base(3); a.out = (void*)base(4);
+    a.xg = (void*)base(5); a.stats = (float*)base(6); a.ln_gamma = (const float*)base(7); a.ln_s = (const float*)base(8); a.ln_c = (const float*)base(9);
+    GemmPlan plan;
+    if (gemm_plan(dtype == 1 ? DT_BF16 : DT_F16, (Epilogue)epilogue, a, false, &plan) != hipSuccess) return -1;
+    int n = 0;
+    for (int i = 0; i < plan.nsteps; ++i) {
+        const GemmStep& s = plan.steps[i];
+        for (int part = 0; part < (s.family == GEMM2_MIXED || s.family == GEMM4_MIXED ? 2 : 1); ++part, ++n) {
+            if (n == cap_records) return -1;
+            const GemmArgs& g = s.args[part];
+            const uintptr_t ptr[10] = {(uintptr_t)g.A, (uintptr_t)g.W, (uintptr_t)g.bias, (uintptr_t)g.aux, (uintptr_t)g.out,
+                                       (uintptr_t)g.xg, (uintptr_t)g.stats, (uintptr_t)g.ln_gamma, (uintptr_t)g.ln_s, (uintptr_t)g.ln_c};
+            int64_t* r = out + (size_t)n * DINOV2_HIP_PLAN_PART_FIELDS;
+            const int64_t head[17] = {i, part, part ? s.row0 + s.rows0 : s.row0, part ? s.rows - s.rows0 : s.rows0, s.col0, s.cols, g.M, g.N, g.K, g.ldo, g.qcols,
+                                      g.nt_out, g.clk_slot, g.ln_gs, plan.whole.nt_out, plan.whole.clk_slot, plan.whole.ln_gs};
+            for (int k = 0; k < 17; ++k) r[k] = head[k];
+            for (int k = 0; k < 10; ++k) r[17 + k] = (int64_t)(ptr[k] - base(k));
+        }
+    }
+    return n;
 }
 
 namespace dinov2 { void pca_ritz(const double* yprev, const double* ynext, const double* g_parts, int nparts, int H, double* evals, double* comp); }

@@ -101,9 +101,17 @@ int dinov2_hip_op_clock_slots(uint64_t *out18);
 int dinov2_hip_op_set_tuning(const char *key, int32_t value);
 int dinov2_hip_op_get_tuning(const char *key); /* -1: unknown key */
 
-/* Which kernel plan launch_gemm picks for a shape, as text: ';'-separated leaves such as "gemm4_mixed<256+192>", "gemm2<128>",
+/* Which kernel plan the GEMM planner (csrc/gemm.hip gemm_plan; launch_gemm launches it) picks for a shape, as text: ';'-separated leaves such as "gemm4_mixed<256+192>", "gemm2<128>",
  * "gemm4<256>;small<64x128,w2x2,st3,ks1>".  Needs no device (nothing is launched).  0 on success. */
 int dinov2_hip_op_gemm_plan(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, char *out, int32_t cap);
+/* The same plan as data: one record of DINOV2_HIP_PLAN_PART_FIELDS int64 per argument block a kernel of the plan is launched with (a step of
+ * a two-height kernel has two, the first possibly empty), in launch order:
+ *   0 step (index into the text's leaves)  1 part within the step  2 row0  3 rows  4 col0  5 cols: the rectangle of the output it covers
+ *   6 M  7 N  8 K  9 ldo  10 qcols  11 nt_out  12 clk_slot  13 ln_gs: the block's own fields   14 .. 16 nt_out, clk_slot, ln_gs of the whole problem
+ *   17 .. 26 byte offsets of the block's A, W, bias, aux, out, xg, stats, ln_gamma, ln_s, ln_c from the caller's pointers
+ * Returns the number of records, or -1 for a refused shape or too small a buffer.  Needs no device. */
+#define DINOV2_HIP_PLAN_PART_FIELDS 27
+int dinov2_hip_op_gemm_plan_parts(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, int64_t *out, int32_t cap_records);
 
 /* host-only: the Rayleigh-Ritz step behind dinov2_hip_pca3.  yprev [H][8] (any full-rank block), gram [8][8] = yprev^T yprev,
  * ynext [H][8] = cov * (yprev R^-1) with gram = R^T R  ->  evals [3] largest Ritz values of cov on span(yprev), comp [3][H] their
