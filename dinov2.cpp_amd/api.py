@@ -61,6 +61,16 @@ class Output(C.Structure):
                 ("topk_ids", C.c_void_p), ("topk_probs", C.c_void_p), ("topk", C.c_int32), ("on_device", C.c_int32)]
 
 
+class Layers(C.Structure):
+    """dinov2_hip_layers (include/dinov2_hip.h)."""
+    _fields_ = [("layers", C.POINTER(C.c_int32)), ("n_layers", C.c_int32), ("norm", C.c_int32), ("layout", C.c_int32),
+                ("patch_tokens", C.c_void_p), ("cls", C.c_void_p), ("registers", C.c_void_p), ("on_device", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+LAYERS_TOKENS, LAYERS_CHW = 0, 1
+
+
 class GroupOpts(C.Structure):
     _fields_ = [("load", LoadOpts), ("n_devices", C.c_int32), ("devices", C.POINTER(C.c_int32)), ("broadcast", C.c_int32),
                 ("streams_per_device", C.c_int32), ("reserved", C.c_int32 * 7)]
@@ -113,6 +123,32 @@ def gemm_plan_parts(dtype, epilogue, M, N, K):
     return [dict(zip(PLAN_PART_FIELDS, buf[i * nf:(i + 1) * nf])) for i in range(n)]
 
 
+def op_layer_tap(x, w, b, eps, R, h0, w0, *, norm, chw, want=("patch", "cls", "reg")):
+    """layer_tap_kernel alone (dinov2_hip_op_layer_tap): x [B, T, H] f32 -> dict of the destinations in `want`.  Raises on a HIP error or a
+    changed guard band."""
+    x = np.ascontiguousarray(x, np.float32)
+    B, T, H = x.shape
+    P = h0 * w0
+    fp = C.POINTER(C.c_float)
+    out = {}
+    if "patch" in want:
+        out["patch"] = np.zeros((B, H, h0, w0) if chw else (B, P, H), np.float32)
+    if "cls" in want:
+        out["cls"] = np.zeros((B, H), np.float32)
+    if "reg" in want:
+        out["reg"] = np.zeros((B, R, H), np.float32)
+    ptr = lambda a: a.ctypes.data_as(fp) if a is not None else None  # noqa: E731
+    w = None if w is None else np.ascontiguousarray(w, np.float32)
+    b = None if b is None else np.ascontiguousarray(b, np.float32)
+    rc = lib().dinov2_hip_op_layer_tap(ptr(x), ptr(w), ptr(b), float(eps), B, T, R, H, h0, w0, int(norm), int(chw), ptr(out.get("patch")),
+                                       ptr(out.get("cls")), ptr(out.get("reg")))
+    if rc == OP_GUARD_CHANGED:
+        raise AssertionError("layer_tap wrote outside its output (guard band changed)")
+    if rc != 0:
+        raise RuntimeError(f"dinov2_hip_op_layer_tap failed ({rc})")
+    return out
+
+
 def lib():
     """Load libdinov2_hip.so; raise loudly if it is not built (no CPU fallback exists)."""
     global _lib
@@ -151,6 +187,7 @@ def lib():
     L.dinov2_hip_session_stream.argtypes = [vp]
     L.dinov2_hip_session_stream.restype = vp
     L.dinov2_hip_predict.argtypes = [vp, C.POINTER(Input), C.POINTER(Output), u32, cp, sz]
+    L.dinov2_hip_predict_layers.argtypes = [vp, C.POINTER(Input), C.POINTER(Output), C.POINTER(Layers), u32, cp, sz]
     L.dinov2_hip_default_group_opts.argtypes = [C.POINTER(GroupOpts)]
     L.dinov2_hip_default_group_opts.restype = None
     L.dinov2_hip_group_create.argtypes = [cp, C.POINTER(GroupOpts), C.POINTER(vp), cp, sz]
@@ -190,6 +227,7 @@ def lib():
     L.dinov2_hip_op_attention.argtypes = [i32, fp, fp, i32, i32, i32, i32]
     L.dinov2_hip_op_attention_ex.argtypes = [i32, fp, fp, i32, i32, i32, i32, i32]
     L.dinov2_hip_op_layernorm.argtypes = [i32, fp, fp, fp, fp, i32, i32, C.c_float]
+    L.dinov2_hip_op_layer_tap.argtypes = [fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp]
     L.dinov2_hip_op_convert_weight.argtypes = [i32, vp, C.c_uint64, u32, fp, i32, i32, i32, i32]
     L.dinov2_hip_op_permute_bias.argtypes = [fp, fp, i32, i32]
     L.dinov2_hip_op_head.argtypes = [i32, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, C.c_float]
@@ -347,6 +385,74 @@ def pinned_empty(shape, dtype=np.float32) -> np.ndarray:
     return arr
 
 
+class DeviceArray:
+    """A float32 array in device memory for the *_device calls, for hosts that have no torch in the process: plain hipMalloc / hipMemcpy
+    through the HIP runtime the library itself is linked against, on HIP device `device` (the model's: Model.device).  `ptr` is the raw
+    device pointer.  free() waits for the device first: a session's stream may still be writing into the buffer."""
+    _hip = None
+
+    @classmethod
+    def _rt(cls):
+        if cls._hip is None:
+            lib()  # the library has the runtime loaded: dlopen by SONAME hands back that copy
+            for name in ("libamdhip64.so.7", "libamdhip64.so", "/opt/rocm/lib/libamdhip64.so"):
+                try:
+                    cls._hip = C.CDLL(name)
+                    break
+                except OSError:
+                    continue
+            else:
+                raise HipLibraryMissing("libamdhip64 not found")
+            cls._hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+            cls._hip.hipFree.argtypes = [C.c_void_p]
+            cls._hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+            cls._hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+            cls._hip.hipSetDevice.argtypes = [C.c_int]
+        return cls._hip
+
+    def _select(self):
+        if self._rt().hipSetDevice(self.device) != 0:
+            raise RuntimeError(f"hipSetDevice({self.device}) failed")
+        return self._hip
+
+    def __init__(self, shape, fill_nan: bool = False, device: int = 0):
+        self.shape = tuple(int(v) for v in shape)
+        self.nbytes = 4 * int(np.prod(self.shape))
+        self.device = int(device)
+        p = C.c_void_p()
+        if self._select().hipMalloc(C.byref(p), max(self.nbytes, 16)) != 0:
+            raise MemoryError(f"hipMalloc({self.nbytes}) failed")
+        self.ptr = int(p.value)
+        if fill_nan and (self._rt().hipMemset(self.ptr, 0xff, self.nbytes) != 0 or self._rt().hipDeviceSynchronize() != 0):
+            raise RuntimeError("hipMemset failed")  # (synchronised: a session's stream is not ordered after the null stream)
+
+    @classmethod
+    def from_host(cls, a: np.ndarray, device: int = 0):
+        a = np.ascontiguousarray(a, np.float32)
+        d = cls(a.shape, device=device)
+        if d._select().hipMemcpy(d.ptr, a.ctypes.data, d.nbytes, 1) != 0:  # hipMemcpyHostToDevice (synchronous)
+            raise RuntimeError("hipMemcpy to the device failed")
+        return d
+
+    def to_host(self) -> np.ndarray:
+        out = np.empty(self.shape, np.float32)
+        if self._select().hipMemcpy(out.ctypes.data, self.ptr, self.nbytes, 2) != 0:  # hipMemcpyDeviceToHost
+            raise RuntimeError("hipMemcpy to the host failed")
+        return out
+
+    def free(self):
+        if getattr(self, "ptr", 0):
+            self._select().hipDeviceSynchronize()
+            self._hip.hipFree(self.ptr)
+            self.ptr = 0
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Group:
     """dinov2_hip_group: N devices behind one handle -- host threads + sessions per device inside the library (two lanes per
     device by default: one lane's PCIe copies run under the other's kernels), the global batch split contiguously, outputs
@@ -470,6 +576,71 @@ class Session:
         o = Output(cls_ptr or None, patch_ptr or None, logits_ptr or None, probs_ptr or None, None, None, 0, 1)
         err = _errbuf()
         rc = lib().dinov2_hip_predict(self._h, C.byref(i), C.byref(o), CLASSIFY if classify else 0, err, len(err))
+        if rc != 0:
+            raise DinoError(rc, err.value.decode(errors="replace"))
+
+    def _layer_list(self, layers):
+        """`layers` as the C-ABI wants it: ascending numbers of blocks applied; an int n = the last n layers, as upstream."""
+        L = int(self.model.hparams.num_hidden_layers)
+        if isinstance(layers, (int, np.integer)):
+            if not 1 <= int(layers) <= L:
+                raise ValueError(f"layers = {layers}: the last n layers, 1 <= n <= {L}")
+            return list(range(L - int(layers) + 1, L + 1))
+        return [int(v) for v in layers]
+
+    def predict_layers(self, images: np.ndarray, layers, *, norm: bool = True, reshape: bool = False, return_class_token: bool = False,
+                       return_registers: bool = False, classify: bool = False, layout: int = RGB_CHW, topk: int = 0,
+                       want=("cls", "patch_tokens", "logits", "probs")) -> dict:
+        """predict() plus the outputs of chosen layers from the same forward (dinov2_hip_predict_layers; upstream DINOv2's
+        get_intermediate_layers).  `layers`: ascending list of layer numbers = blocks applied (0 = embeddings, L = the last block; upstream
+        block index i is layer i + 1, HuggingFace hidden_states[k] is layer k), or an int n = the last n layers.  norm: through the model's
+        final LayerNorm; reshape: patch tokens as [B, H, h0, w0] instead of [B, P, H].  Returns predict's dict plus "layers": one dict per
+        requested layer with "layer", "patch_tokens" and, if asked for, "cls" [B, H] and "registers" [B, R, H]."""
+        img = np.ascontiguousarray(images, dtype=np.uint8 if layout == U8_BGR_HWC else np.float32)
+        if img.ndim == 3:
+            img = img[None]
+        B = img.shape[0]
+        hh, ww = (img.shape[2], img.shape[3]) if layout == RGB_CHW else (img.shape[1], img.shape[2])
+        hp = self.model.hparams
+        out, o = _alloc_outputs(hp, B, hh, ww, layout, classify, topk, want)
+        ids = self._layer_list(layers)
+        n, Hd, R, ps = len(ids), hp.hidden_size, hp.num_register_tokens, hp.patch_size
+        nh, nw = preprocess_size(1 if classify else 0, hh, ww, ps) if layout == U8_BGR_HWC else (hh, ww)
+        h0, w0 = nh // ps, nw // ps
+        arr = (C.c_int32 * max(n, 1))(*ids)
+        patch = np.empty((n, B, Hd, h0, w0) if reshape else (n, B, h0 * w0, Hd), np.float32)
+        cls = np.empty((n, B, Hd), np.float32) if return_class_token else None
+        reg = np.empty((n, B, R, Hd), np.float32) if return_registers else None
+        ly = Layers(arr, n, int(bool(norm)), LAYERS_CHW if reshape else LAYERS_TOKENS, patch.ctypes.data,
+                    cls.ctypes.data if cls is not None else None, reg.ctypes.data if reg is not None else None, 0)
+        i = Input(img.ctypes.data, B, hh, ww, layout, 0)
+        err = _errbuf()
+        rc = lib().dinov2_hip_predict_layers(self._h, C.byref(i), C.byref(o), C.byref(ly), CLASSIFY if classify else 0, err, len(err))
+        if rc != 0:
+            raise DinoError(rc, err.value.decode(errors="replace"))
+        out["layers"] = []
+        for k, layer in enumerate(ids):
+            d = {"layer": layer, "patch_tokens": patch[k]}
+            if cls is not None:
+                d["cls"] = cls[k]
+            if reg is not None:
+                d["registers"] = reg[k]
+            out["layers"].append(d)
+        return out
+
+    def predict_layers_device(self, img_ptr: int, B: int, hh: int, ww: int, layers, *, norm: bool = True, reshape: bool = False,
+                              classify: bool = False, layout: int = RGB_CHW, layer_patch_ptr: int = 0, layer_cls_ptr: int = 0,
+                              layer_reg_ptr: int = 0, logits_ptr: int = 0, probs_ptr: int = 0, cls_ptr: int = 0, patch_ptr: int = 0):
+        """Asynchronous predict_layers on device-resident input and outputs (raw device pointers): the tap kernel writes straight into
+        layer_patch_ptr [n, B, P, H] (reshape: [n, B, H, h0, w0]), layer_cls_ptr [n, B, H] and layer_reg_ptr [n, B, R, H]."""
+        ids = self._layer_list(layers)
+        arr = (C.c_int32 * max(len(ids), 1))(*ids)
+        ly = Layers(arr, len(ids), int(bool(norm)), LAYERS_CHW if reshape else LAYERS_TOKENS, layer_patch_ptr or None,
+                    layer_cls_ptr or None, layer_reg_ptr or None, 1)
+        i = Input(img_ptr, B, hh, ww, layout, 1)
+        o = Output(cls_ptr or None, patch_ptr or None, logits_ptr or None, probs_ptr or None, None, None, 0, 1)
+        err = _errbuf()
+        rc = lib().dinov2_hip_predict_layers(self._h, C.byref(i), C.byref(o), C.byref(ly), CLASSIFY if classify else 0, err, len(err))
         if rc != 0:
             raise DinoError(rc, err.value.decode(errors="replace"))
 

@@ -131,6 +131,11 @@ hipError_t launch_layernorm(DType dt, const float* x, const float* w, const floa
 // same, f32 output (final layernorm)
 hipError_t launch_layernorm_f32(const float* x, const float* w, const float* b, float* y, int rows, int H, float eps,
                                 hipStream_t stream);
+// Layer tap (dinov2_hip_predict_layers): tokens of the residual stream x [B*T, H] f32 to up to three destinations, any of them nullptr:
+// cls_out [B, H] (token 0), reg_out [B, R, H] (tokens 1 .. R), patch_out (tokens 1 + R .. T - 1) as [B, P, H] or, `chw`, [B, H, P].
+// `norm`: through LayerNorm (w, b, eps) with the bits of launch_layernorm_f32; otherwise the rows as they are.  H % 4 == 0, H <= 2 048, P >= 1.
+hipError_t launch_layer_tap(const float* x, const float* w, const float* b, float eps, int B, int T, int R, int H, bool norm, bool chw,
+                            float* patch_out, float* cls_out, float* reg_out, hipStream_t stream);
 // LN fold (EPI_RESID_LN): what the residual epilogue leaves behind, computed from a residual stream no GEMM has written (before layer 0):
 // xg [rows, H] T = T(x gamma), stats [rows][gs][2] = (sum, sum of squares) per 64 columns in the producers' summation order (gs = ln_stat_slots(H))
 hipError_t launch_ln_prepare(DType dt, const float* x, const float* gamma, void* xg, float* stats, int gs, int rows, int H, hipStream_t stream);

@@ -42,18 +42,13 @@ static __device__ __forceinline__ double wave_sum_f64(double v) {
 // into an FMA; tests/test_gpu_misc_kernels.py (bit-exact against tests/misc_cases.py: ln_emulate) and
 // tests/test_kernel_build_checks.py (same instruction stream as a -ffp-contract=off build) hold it there.
 // ---------------------------------------------------------------------------------------------------------
-template <typename OutT, int MAXV>
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                        const float* __restrict__ bta, OutT* __restrict__ y, int rows,
-                                                        int H, float eps) {
-#pragma clang fp contract(off)  // ggml's rounding points (header above)
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nv = H >> 2;
-    const float4* xr = (const float4*)(x + (size_t)row * H);
-    float4 v[MAXV], gw[MAXV], gb[MAXV];
-    double sum = 0.0;
+// The row routine, shared with layer_tap_kernel (below) so that a tapped row gets the bits of launch_layernorm_f32: ln_row_load brings the row
+// and the affine parameters into registers, ln_row_scale centres it in place and returns 1/sqrt(var + eps), LN_ROW_AFFINE is the
+// three-rounding affine of one float4.  Each carries its own `fp contract(off)`; all are inlined, and layernorm_kernel's instruction
+// stream is the one it had with the code written out in its body.
+template <int MAXV>
+static __device__ __forceinline__ void ln_row_load(const float4* __restrict__ xr, const float* __restrict__ w, const float* __restrict__ bta,
+                                                   int nv, int lane, float4 (&v)[MAXV], float4 (&gw)[MAXV], float4 (&gb)[MAXV]) {
 #pragma unroll
     for (int j = 0; j < MAXV; ++j) {  // all loads of the row first: x, and the affine parameters needed only at the end
         const int i = lane + 64 * j;
@@ -63,6 +58,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
             gb[j] = ((const float4*)bta)[i];
         }
     }
+}
+
+template <int MAXV>
+static __device__ __forceinline__ float ln_row_scale(float4 (&v)[MAXV], int nv, int H, float eps, int lane) {
+#pragma clang fp contract(off)  // ggml's rounding points (header above)
+    double sum = 0.0;
 #pragma unroll
     for (int j = 0; j < MAXV; ++j) {
         const int i = lane + 64 * j;
@@ -82,16 +83,39 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     }
     sq = wave_sum_f64(sq);
     const float var = (float)(sq / H);
-    const float scale = 1.0f / sqrtf(var + eps);
+    return 1.0f / sqrtf(var + eps);
+}
+
+// (a macro, not a function: through a function's arguments hipcc commutes the operands of the multiplies and adds -- the same bits, but not
+// the instruction stream layernorm_kernel had.)  Assigns the four floats the CALLER declares; introduces no name of its own.
+#define LN_ROW_AFFINE(r0, r1, r2, r3, c, scale, ww, bb)                                                             \
+    do {                                                                                                             \
+        r0 = (c).x * (scale) * (ww).x + (bb).x; r1 = (c).y * (scale) * (ww).y + (bb).y;                              \
+        r2 = (c).z * (scale) * (ww).z + (bb).z; r3 = (c).w * (scale) * (ww).w + (bb).w;                              \
+        /* f32 result first, f16 rounding second (ggml rounds at the NEXT mul_mat): block v_fma_mix*_f16 fusion */ \
+        asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));                                                   \
+    } while (0)
+
+template <typename OutT, int MAXV>
+__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                        const float* __restrict__ bta, OutT* __restrict__ y, int rows,
+                                                        int H, float eps) {
+#pragma clang fp contract(off)  // ggml's rounding points (header above)
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int nv = H >> 2;
+    const float4* xr = (const float4*)(x + (size_t)row * H);
+    float4 v[MAXV], gw[MAXV], gb[MAXV];
+    ln_row_load<MAXV>(xr, w, bta, nv, lane, v, gw, gb);
+    const float scale = ln_row_scale<MAXV>(v, nv, H, eps, lane);
 #pragma unroll
     for (int j = 0; j < MAXV; ++j) {
         const int i = lane + 64 * j;
         if (i < nv) {
             const float4 ww = gw[j], bb = gb[j];
-            float r0 = v[j].x * scale * ww.x + bb.x, r1 = v[j].y * scale * ww.y + bb.y;
-            float r2 = v[j].z * scale * ww.z + bb.z, r3 = v[j].w * scale * ww.w + bb.w;
-            // f32 result first, f16 rounding second (ggml rounds at the NEXT mul_mat): block v_fma_mix*_f16 fusion
-            asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));
+            float r0, r1, r2, r3;
+            LN_ROW_AFFINE(r0, r1, r2, r3, v[j], scale, ww, bb);
             if constexpr (sizeof(OutT) == 4) {
                 ((float4*)(y + (size_t)row * H))[i] = make_float4(r0, r1, r2, r3);
             } else {
@@ -125,6 +149,181 @@ hipError_t launch_layernorm(DType dt, const float* x, const float* w, const floa
 hipError_t launch_layernorm_f32(const float* x, const float* w, const float* b, float* y, int rows, int H, float eps,
                                 hipStream_t st) {
     return ln_dispatch<float>(x, w, b, y, rows, H, eps, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Layer tap (dinov2_hip_predict_layers): rows of the f32 residual stream x [B*T, H] as it stands after some layer go out to up to
+// three destinations -- cls [B, H] (token 0), registers [B, R, H] (tokens 1 .. R) and the patch tokens, as rows [B, P, H] or
+// transposed [B, H, P] (CHW) -- raw or through the model's final LayerNorm.  One launch per tapped layer; HBM-bound: every wanted row is
+// read once, every output element written once.  NORM uses layernorm_kernel's row routine above, so a row gets the bits of
+// launch_layernorm_f32.  Every output offset is 64-bit (n_layers * B * P * H passes 2^31 elements).  A NULL destination is not written,
+// and its rows are not read.
+//  * layer_tap_rows_kernel: one wave per row, the row in registers, 16-byte loads and stores -- layernorm_kernel with a computed
+//    destination row.  Serves the TOKENS layout (all T rows of every image), and CHW requests without patch tokens.
+//  * layer_tap_chw_kernel: 16 waves, one PATCH row each (16 consecutive patches of one image), then the transpose in chunks of 256
+//    channels through LDS: every wave writes its float4 per lane as a row of a [16][256 + 4] tile (ds_write_b128, contiguous), and after
+//    one barrier (two tiles alternate, so one barrier per chunk suffices) lane l of wave w takes channel 16 w + l / 4 and four of the
+//    16 patches, l % 4 choosing which: 4 x ds_read_b32 down a column, then ONE 16-byte store along the patch dimension; four
+//    neighbouring lanes cover the tile's 64-byte run of a channel.  The pitch of 260 floats puts row r of the tile at bank 4 r: the 16
+//    channels x 4 row groups a wave reads at once fall on 64 different banks, whatever the alignment shift below.
+//    P is odd at 518 x 518 (1 369), so a channel's run starts at any of the four alignments: each lane's four patches are the ALIGNED
+//    piece (tile patches sh + 4 (q - 1) .. + 3, sh = floats to the next 16-byte boundary), and lane q = 0 takes what is left at both ends
+//    (sh patches at the front, 4 - sh at the back) as scalar stores -- as does any lane whose piece crosses the end of the image.
+//    The blocks past the patch tiles take the CLS and register rows, 16 rows each, by the row path.
+// ---------------------------------------------------------------------------------------------------------
+struct TapDst {
+    float* patch;  // [B, P, H] or [B, H, P], or nullptr
+    float* cls;    // [B, H] or nullptr
+    float* reg;    // [B, R, H] or nullptr
+};
+
+// destination of token t of image b as a row of H floats (the TOKENS layout); nullptr: nobody asked for it
+static __device__ __forceinline__ float* tap_row_dst(const TapDst& d, long long b, int t, int R, int P, int H, bool patch_rows) {
+    if (t == 0) return d.cls ? d.cls + b * H : nullptr;
+    if (t <= R) return d.reg ? d.reg + (b * R + (t - 1)) * H : nullptr;
+    return (patch_rows && d.patch) ? d.patch + (b * P + (t - 1 - R)) * H : nullptr;
+}
+
+// one wave: row `xr` -> `dst` (H floats), normalised or as it is
+template <int MAXV, bool NORM>
+static __device__ __forceinline__ void tap_row_to_registers(const float4* __restrict__ xr, const float* __restrict__ w,
+                                                            const float* __restrict__ bta, int nv, int H, float eps, int lane,
+                                                            float4 (&v)[MAXV]) {
+#pragma clang fp contract(off)  // ggml's rounding points, as in layernorm_kernel
+    if constexpr (NORM) {
+        float4 gw[MAXV], gb[MAXV];
+        ln_row_load<MAXV>(xr, w, bta, nv, lane, v, gw, gb);
+        const float scale = ln_row_scale<MAXV>(v, nv, H, eps, lane);
+#pragma unroll
+        for (int j = 0; j < MAXV; ++j) {
+            if (lane + 64 * j < nv) {
+                const float4 ww = gw[j], bb = gb[j];
+                float r0, r1, r2, r3;
+                LN_ROW_AFFINE(r0, r1, r2, r3, v[j], scale, ww, bb);
+                v[j] = make_float4(r0, r1, r2, r3);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < MAXV; ++j) {  // (every element defined: a partly written array does not stay in registers)
+            v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (lane + 64 * j < nv) v[j] = xr[lane + 64 * j];
+        }
+    }
+}
+
+template <int MAXV, bool NORM>
+__global__ __launch_bounds__(256) void layer_tap_rows_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                             const float* __restrict__ bta, TapDst d, int B, int T, int R, int H,
+                                                             float eps, int patch_rows) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= (long long)B * T) return;
+    const long long b = row / T;
+    const int t = (int)(row - b * T);
+    float* dst = tap_row_dst(d, b, t, R, T - 1 - R, H, patch_rows != 0);
+    if (!dst) return;
+    const int nv = H >> 2;
+    float4 v[MAXV];
+    tap_row_to_registers<MAXV, NORM>((const float4*)(x + row * H), w, bta, nv, H, eps, lane, v);
+#pragma unroll
+    for (int j = 0; j < MAXV; ++j)
+        if (lane + 64 * j < nv) ((float4*)dst)[lane + 64 * j] = v[j];
+}
+
+constexpr int TAP_TP = 16;       // patches per tile = waves per workgroup
+constexpr int TAP_PITCH = 260;   // floats per tile row: 256 channels + 4 (row r starts at bank 4 r)
+
+template <int MAXV, bool NORM>
+__global__ __launch_bounds__(1024) void layer_tap_chw_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                             const float* __restrict__ bta, TapDst d, int B, int T, int R, int H,
+                                                             float eps, int tiles_per_image) {
+    __shared__ float tile[2][TAP_TP * TAP_PITCH];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int P = T - 1 - R, nv = H >> 2;
+    const long long patch_blocks = (long long)B * tiles_per_image;
+    if ((long long)blockIdx.x >= patch_blocks) {  // CLS and register rows, 16 per workgroup (no barrier on this path)
+        const long long rr = ((long long)blockIdx.x - patch_blocks) * TAP_TP + wv;
+        if (rr >= (long long)B * (1 + R)) return;
+        const long long b = rr / (1 + R);
+        const int t = (int)(rr - b * (1 + R));
+        float* dst = tap_row_dst(d, b, t, R, P, H, false);
+        if (!dst) return;
+        float4 v[MAXV];
+        tap_row_to_registers<MAXV, NORM>((const float4*)(x + (b * T + t) * H), w, bta, nv, H, eps, lane, v);
+#pragma unroll
+        for (int j = 0; j < MAXV; ++j)
+            if (lane + 64 * j < nv) ((float4*)dst)[lane + 64 * j] = v[j];
+        return;
+    }
+    const long long b = (long long)blockIdx.x / tiles_per_image;
+    const int p0 = (int)((long long)blockIdx.x - b * tiles_per_image) * TAP_TP;
+    const bool have_row = p0 + wv < P;  // (the image's last tile may be short; its idle waves still meet the barriers)
+    float4 v[MAXV];
+    if (have_row) tap_row_to_registers<MAXV, NORM>((const float4*)(x + (b * T + 1 + R + p0 + wv) * H), w, bta, nv, H, eps, lane, v);
+    const int q = lane & 3, cl = wv * 16 + (lane >> 2);  // which four patches, which channel of the chunk
+    const int nchunks = (H + 255) >> 8;
+#pragma unroll
+    for (int j = 0; j < MAXV; ++j) {
+        if (j >= nchunks) break;  // (uniform)
+        float* buf = tile[j & 1];
+        if (have_row && lane + 64 * j < nv) *(float4*)(buf + wv * TAP_PITCH + 4 * lane) = v[j];
+        __syncthreads();
+        const int c = 256 * j + cl;
+        if (c < H) {
+            float* run = d.patch + ((b * H + c) * P + p0);         // the channel's 16 patches of this tile
+            const int sh = (int)((16u - ((unsigned)(uintptr_t)run & 15u)) & 15u) >> 2;  // floats to the next 16-byte boundary
+            const int r0 = (sh + 4 * q - 4) & 15;
+            float f[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) f[k] = buf[((r0 + k) & 15) * TAP_PITCH + cl];
+            if (r0 <= TAP_TP - 4 && p0 + r0 + 3 < P) {
+                *(float4*)(run + r0) = make_float4(f[0], f[1], f[2], f[3]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int r = (r0 + k) & 15;
+                    if (p0 + r < P) run[r] = f[k];
+                }
+            }
+        }
+    }
+}
+
+template <int MAXV>
+static hipError_t tap_dispatch(const float* x, const float* w, const float* b, const TapDst& d, int B, int T, int R, int H, float eps,
+                               bool norm, bool chw, hipStream_t st) {
+    const int P = T - 1 - R;
+    if (chw && d.patch) {
+        const int tiles = (P + TAP_TP - 1) / TAP_TP;
+        const long long extra = (d.cls || d.reg) ? ((long long)B * (1 + R) + TAP_TP - 1) / TAP_TP : 0;
+        const long long blocks = (long long)B * tiles + extra;
+        if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+        const dim3 grid((unsigned)blocks), block(64 * TAP_TP);
+        if (norm) hipLaunchKernelGGL((layer_tap_chw_kernel<MAXV, true>), grid, block, 0, st, x, w, b, d, B, T, R, H, eps, tiles);
+        else hipLaunchKernelGGL((layer_tap_chw_kernel<MAXV, false>), grid, block, 0, st, x, w, b, d, B, T, R, H, eps, tiles);
+    } else {
+        const long long blocks = ((long long)B * T + 3) / 4;
+        if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+        const dim3 grid((unsigned)blocks), block(256);
+        const int patch_rows = d.patch != nullptr;
+        if (norm) hipLaunchKernelGGL((layer_tap_rows_kernel<MAXV, true>), grid, block, 0, st, x, w, b, d, B, T, R, H, eps, patch_rows);
+        else hipLaunchKernelGGL((layer_tap_rows_kernel<MAXV, false>), grid, block, 0, st, x, w, b, d, B, T, R, H, eps, patch_rows);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_layer_tap(const float* x, const float* w, const float* b, float eps, int B, int T, int R, int H, bool norm, bool chw,
+                            float* patch_out, float* cls_out, float* reg_out, hipStream_t st) {
+    if (H % 4 != 0 || H <= 0 || H > 64 * 4 * 8 || B <= 0 || R < 0 || T < 2 + R) return hipErrorInvalidValue;  // ln_dispatch's widths; P >= 1
+    if (reg_out && R == 0) return hipErrorInvalidValue;
+    if (norm && (!w || !b)) return hipErrorInvalidValue;
+    if (!patch_out && !cls_out && !reg_out) return hipSuccess;
+    const TapDst d{patch_out, cls_out, reg_out};
+    const int nv = (H / 4 + 63) / 64;
+    if (nv <= 2) return tap_dispatch<2>(x, w, b, d, B, T, R, H, eps, norm, chw, st);
+    if (nv <= 4) return tap_dispatch<4>(x, w, b, d, B, T, R, H, eps, norm, chw, st);
+    return tap_dispatch<8>(x, w, b, d, B, T, R, H, eps, norm, chw, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------

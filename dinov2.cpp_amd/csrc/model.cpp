@@ -26,11 +26,11 @@ namespace {
 
 enum Kind : int {
     K_IM2COL = 0, K_INIT, K_PATCH_GEMM, K_LAYERNORM, K_QKV_GEMM, K_ATTENTION, K_OPROJ_GEMM, K_FC1_GEMM, K_FC2_GEMM,
-    K_FINAL_LN, K_HEAD, K_COUNT
+    K_FINAL_LN, K_HEAD, K_LAYER_TAP, K_COUNT
 };
 const char* const kKindNames[K_COUNT] = {"im2col", "init_tokens", "gemm_patch_embed", "layernorm", "gemm_qkv",
                                          "attention", "gemm_attn_out", "gemm_ffn_in", "gemm_ffn_out", "final_layernorm",
-                                         "head"};
+                                         "head", "layer_tap"};
 
 void set_err(char* err, size_t n, const char* fmt, ...) {
     if (!err || n == 0) return;
@@ -651,8 +651,9 @@ int prepare_pos(dinov2_hip_session* s, int B, int h, int w, char* err, size_t er
 }
 
 // `img` is a DEVICE pointer.  Leaves final-LN tokens in s->fin, logits/probs in s->logits/s->probs.
+// `taps` (dinov2_hip_predict_layers): one layer_tap launch per requested layer, on x as it stands after that many layers; nullptr: none.
 int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int layout, bool classify, int nlayers,
-            bool finalize, char* err, size_t errlen) {
+            bool finalize, char* err, size_t errlen, const TapRun* taps = nullptr) {
     const dinov2_hip_model* m = s->model;
     const int H = (int)m->hp.hidden_size, F = (int)m->hp.ffn_hidden, R = (int)m->hp.num_register_tokens;
     const int nh = (int)m->hp.num_attention_heads, ps = (int)m->hp.patch_size;
@@ -681,6 +682,17 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
         HIP_TRY(launch_gemm(dt, EPI_PATCH, a, st));
     }
     const float eps = m->hp.eps;
+    int next_tap = 0;
+    auto tap = [&](int layer) -> hipError_t {  // x holds the output of `layer` layers: hand it out if it was asked for
+        if (!taps || next_tap >= taps->n || taps->layers[next_tap] != layer) return hipSuccess;
+        const size_t k = (size_t)next_tap++;
+        Scope sc(s, K_LAYER_TAP);
+        return launch_layer_tap(s->x, m->ln_w, m->ln_b, eps, B, d.T, R, H, taps->norm, taps->chw,
+                                taps->patch ? taps->patch + k * taps->patch_stride : nullptr,
+                                taps->cls ? taps->cls + k * taps->cls_stride : nullptr,
+                                taps->reg ? taps->reg + k * taps->reg_stride : nullptr, st);
+    };
+    HIP_TRY(tap(0));
     // LN fold (dinov2_hip_load_opts.ln_fold; kernels.h EPI_RESID_LN): no LayerNorm launches inside the layers.  `ln` holds T(gamma x) for the
     // NEXT LayerNorm and `stats` the row sums behind it, both written by whoever wrote x last: ln_prepare before layer 0, the residual
     // epilogues afterwards; the QKV / FFN-in epilogues apply mean, rstd and beta.
@@ -749,6 +761,7 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
             }
             HIP_TRY(launch_gemm(dt, feeds_ln1 ? EPI_RESID_LN : EPI_RESID, a, st));
         }
+        HIP_TRY(tap(il + 1));
     }
     if (!finalize) return DINOV2_HIP_OK;
     {
@@ -919,6 +932,7 @@ extern "C" void dinov2_hip_session_free(dinov2_hip_session* s) {
     if (s->ws) (void)hipFree(s->ws);
     if (s->raw) (void)hipFree(s->raw);
     if (s->pca_buf) (void)hipFree(s->pca_buf);
+    if (s->tap_buf) (void)hipFree(s->tap_buf);
     if (s->own_stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
@@ -975,8 +989,9 @@ size_t dinov2_max_pass_batch(const dinov2_hip_model* m, int h, int w) {
 // =============================================================================================================
 // predict
 // =============================================================================================================
-extern "C" int dinov2_hip_predict(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out,
-                                  uint32_t flags, char* err, size_t errlen) {
+// `taps`: the layer taps of dinov2_hip_predict_layers (device pointers), nullptr for a plain predict
+static int predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out, uint32_t flags, const TapRun* taps,
+                        char* err, size_t errlen) {
     int rc = check_input(s, in, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
     const dinov2_hip_model* m = s->model;
@@ -1028,7 +1043,15 @@ extern "C" int dinov2_hip_predict(dinov2_hip_session* s, const dinov2_hip_input*
                     if (out->topk_ids) co.topk_ids = out->topk_ids + b0 * (size_t)out->topk;
                     if (out->topk_probs) co.topk_probs = out->topk_probs + b0 * (size_t)out->topk;
                 }
-                rc = dinov2_hip_predict(s, &ci, out ? &co : nullptr, flags, err, errlen);
+                TapRun ct;
+                if (taps) {  // this pass's images at their offset inside every layer's block; the layer stride stays the whole batch's
+                    ct = *taps;
+                    const size_t Pn = (size_t)d1.P, Rn = m->hp.num_register_tokens;
+                    if (ct.patch) ct.patch += b0 * Pn * H;
+                    if (ct.cls) ct.cls += b0 * H;
+                    if (ct.reg) ct.reg += b0 * Rn * H;
+                }
+                rc = predict_impl(s, &ci, out ? &co : nullptr, flags, taps ? &ct : nullptr, err, errlen);
                 if (rc != DINOV2_HIP_OK) return rc;
             }
             s->last_b = 0;  // the workspace holds chunk 0 only: nothing for dinov2_hip_fetch
@@ -1064,7 +1087,9 @@ extern "C" int dinov2_hip_predict(dinov2_hip_session* s, const dinov2_hip_input*
     }
     rc = prepare_pos(s, B, h, w, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
-    rc = forward_maybe_graph(s, img, B, h, w, layout, classify, err, errlen);
+    // (a tapped forward runs eagerly, past the graph cache: its key knows nothing of the caller's tap pointers)
+    rc = taps ? forward(s, img, B, h, w, layout, classify, (int)m->hp.num_hidden_layers, true, err, errlen, taps)
+              : forward_maybe_graph(s, img, B, h, w, layout, classify, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
     {  // what dinov2_hip_pca3(tokens = NULL) works on: the patch rows of image 0 in `fin`
         const Dims dd = dims_of(m, B, h, w);
@@ -1077,6 +1102,118 @@ extern "C" int dinov2_hip_predict(dinov2_hip_session* s, const dinov2_hip_input*
     s->last_classify = classify;
     if (!out) return DINOV2_HIP_OK;
     return fetch_outputs(s, out, err, errlen);
+}
+
+extern "C" int dinov2_hip_predict(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out,
+                                  uint32_t flags, char* err, size_t errlen) {
+    return predict_impl(s, in, out, flags, nullptr, err, errlen);
+}
+
+// =============================================================================================================
+// predict + intermediate layers (no reference counterpart; upstream DINOv2: get_intermediate_layers, HuggingFace: output_hidden_states)
+// =============================================================================================================
+extern "C" int dinov2_hip_predict_layers(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out,
+                                         const dinov2_hip_layers* ly, uint32_t flags, char* err, size_t errlen) {
+    int rc = check_input(s, in, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    const dinov2_hip_model* m = s->model;
+    const int L = (int)m->hp.num_hidden_layers, R = (int)m->hp.num_register_tokens;
+    if (!ly || !ly->layers) {
+        set_err(err, errlen, "null layers / layer list");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (ly->n_layers < 1 || ly->n_layers > L + 1) {
+        set_err(err, errlen, "n_layers %d outside 1 .. %d", (int)ly->n_layers, L + 1);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    for (int i = 0; i < ly->n_layers; ++i) {
+        if (ly->layers[i] < 0 || ly->layers[i] > L) {
+            set_err(err, errlen, "layer %d outside 0 .. %d (number of blocks applied; 0 = embeddings)", (int)ly->layers[i], L);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+        if (i > 0 && ly->layers[i] <= ly->layers[i - 1]) {
+            set_err(err, errlen, "the layer list must be strictly ascending");
+            return DINOV2_HIP_ERR_INVALID;
+        }
+    }
+    if (ly->layout != DINOV2_HIP_LAYERS_TOKENS && ly->layout != DINOV2_HIP_LAYERS_CHW) {
+        set_err(err, errlen, "unknown layers layout %d", (int)ly->layout);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (ly->registers && R == 0) {
+        set_err(err, errlen, "register tokens requested from a model without registers");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (ly->on_device) {  // the kernel stores 16 bytes at a time through these pointers
+        const float* const ptrs[3] = {ly->patch_tokens, ly->cls, ly->registers};
+        for (const float* p : ptrs)
+            if (reinterpret_cast<uintptr_t>(p) & 15) {
+                set_err(err, errlen, "device pointers of dinov2_hip_layers must be 16-byte aligned");
+                return DINOV2_HIP_ERR_INVALID;
+            }
+    }
+    // dinov2_hip_predict's own argument checks, here as well: nothing below may run for a call that is refused
+    const bool classify = (flags & DINOV2_HIP_CLASSIFY) != 0;
+    if (classify && !m->hp.has_classifier) {
+        set_err(err, errlen, "classify requested but the model was loaded without a classifier head");
+        return DINOV2_HIP_ERR_NO_HEAD;
+    }
+    if (out && out->on_device && (out->topk_ids || out->topk_probs)) {
+        set_err(err, errlen, "top-k outputs are host-only");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    int h = in->height, w = in->width;
+    if (in->layout == DINOV2_HIP_U8_BGR_HWC) {
+        int32_t oh, ow;
+        dinov2_hip_preprocess_size(classify ? 1 : 0, in->height, in->width, (int32_t)m->hp.patch_size, &oh, &ow);
+        h = oh;
+        w = ow;
+    }
+    const size_t B = (size_t)in->batch, H = m->hp.hidden_size, P = (size_t)dims_of(m, 1, h, w).P, n = (size_t)ly->n_layers;
+    TapRun t;
+    t.layers = ly->layers;
+    t.n = ly->n_layers;
+    t.norm = ly->norm != 0;
+    t.chw = ly->layout == DINOV2_HIP_LAYERS_CHW;
+    t.patch_stride = B * P * H;
+    t.cls_stride = B * H;
+    t.reg_stride = B * (size_t)R * H;
+    if (ly->on_device) {  // the kernel writes straight into the caller's buffers
+        t.patch = ly->patch_tokens;
+        t.cls = ly->cls;
+        t.reg = ly->registers;
+        return predict_impl(s, in, out, flags, &t, err, errlen);
+    }
+    // host outputs: the kernel writes into the session's tap buffer (its own allocation, like pca_buf), which leaves by asynchronous copies
+    const size_t np = ly->patch_tokens ? n * t.patch_stride : 0, nc = ly->cls ? n * t.cls_stride : 0,
+                 nr = ly->registers ? n * t.reg_stride : 0;
+    const size_t need = sizeof(float) * (np + nc + nr);
+    HIP_TRY(hipSetDevice(m->device));
+    if (need > s->tap_bytes) {
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        if (s->tap_buf) HIP_TRY(hipFree(s->tap_buf));
+        s->tap_buf = nullptr;
+        s->tap_bytes = 0;
+        HIP_TRY(hipMalloc((void**)&s->tap_buf, need));
+        s->tap_bytes = need;
+    }
+    if (np) t.patch = s->tap_buf;  // (every block is a multiple of H floats, H % 4 == 0: all three stay 16-byte aligned)
+    if (nc) t.cls = s->tap_buf + np;
+    if (nr) t.reg = s->tap_buf + np + nc;
+    // One synchronise for the whole call: the forward alone first, then the taps' copies, then `out`'s copies (fetch_outputs, which waits
+    // when `out` is host memory).  A batch that is split into passes hands `out` to the passes instead, which wait once each.
+    const bool split = B > dinov2_max_pass_batch(m, h, w);
+    rc = predict_impl(s, in, split ? out : nullptr, flags, &t, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    if (np) HIP_TRY(hipMemcpyAsync(ly->patch_tokens, t.patch, sizeof(float) * np, hipMemcpyDeviceToHost, s->stream));
+    if (nc) HIP_TRY(hipMemcpyAsync(ly->cls, t.cls, sizeof(float) * nc, hipMemcpyDeviceToHost, s->stream));
+    if (nr) HIP_TRY(hipMemcpyAsync(ly->registers, t.reg, sizeof(float) * nr, hipMemcpyDeviceToHost, s->stream));
+    if (out && !split) {
+        rc = fetch_outputs(s, out, err, errlen);
+        if (rc != DINOV2_HIP_OK || !out->on_device) return rc;  // (host `out`: fetch_outputs has waited for the stream)
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return DINOV2_HIP_OK;
 }
 
 extern "C" int dinov2_hip_fetch(dinov2_hip_session* s, dinov2_hip_output* out, char* err, size_t errlen) {

@@ -19,6 +19,17 @@ struct LayerWeights {
     float *qkv_s = nullptr, *qkv_c = nullptr, *fc1_s = nullptr, *fc1_c = nullptr;
 };
 
+// The taps of ONE pass of dinov2_hip_predict_layers: device pointers to where image 0 of this pass goes in the first requested layer's
+// block, and the distance (in floats) from one requested layer's block to the next -- that of the caller's WHOLE batch, so the passes of a
+// split batch fill one set of buffers.
+struct TapRun {
+    const int32_t* layers = nullptr;  // [n] strictly ascending, each in [0, L]
+    int n = 0;
+    bool norm = false, chw = false;
+    float *patch = nullptr, *cls = nullptr, *reg = nullptr;
+    size_t patch_stride = 0, cls_stride = 0, reg_stride = 0;
+};
+
 }  // namespace dinov2
 
 // replaces `struct dino_model` (/root/reference/dinov2.h:49-55): hparams + one device buffer + name->tensor map
@@ -56,6 +67,8 @@ struct dinov2_hip_session {
     size_t raw_bytes = 0;
     char* pca_buf = nullptr;  // dinov2_hip_pca3's device scratch, grown on demand
     size_t pca_bytes = 0;
+    float* tap_buf = nullptr;  // dinov2_hip_predict_layers with host outputs: where the tap kernel writes before the copy-out; grown on demand
+    size_t tap_bytes = 0;
     int last_b = 0, last_h = 0, last_w = 0;  // shape of the last un-split forward (0: none): what dinov2_hip_fetch copies out
     bool last_classify = false;
     int last_first = 0, last_patches = 0;  // rows [last_first, last_first + last_patches) of image 0 in `fin`: its patch tokens

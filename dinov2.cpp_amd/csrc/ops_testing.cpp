@@ -278,6 +278,45 @@ extern "C" int dinov2_hip_op_layernorm(int32_t dtype, const float* x, const floa
     return 0;
 }
 
+extern "C" int dinov2_hip_op_layer_tap(const float* x, const float* w, const float* b, float eps, int32_t B, int32_t T, int32_t R, int32_t H,
+                                       int32_t h0, int32_t w0, int32_t norm, int32_t layout, float* patch_out, float* cls_out, float* reg_out) {
+    if (B <= 0 || H <= 0 || R < 0 || h0 <= 0 || w0 <= 0 || T != 1 + R + h0 * w0 || (layout != 0 && layout != 1)) return -1;
+    if (norm && (!w || !b)) return -1;
+    const size_t P = (size_t)h0 * w0, n = (size_t)B * T * H, ng = (size_t)DINOV2_HIP_OP_GUARD_ROWS * H;
+    // each output between two guard bands, the whole buffer 0xff bytes (NaN): an element the kernel never wrote comes back as NaN and a
+    // write outside the output changes a guard
+    const size_t counts[3] = {(size_t)B * P * H, (size_t)B * H, (size_t)B * R * H};
+    float* const host[3] = {patch_out, cls_out, reg_out};
+    DevBuf dX, dW, dB, dO[3];
+    OP_TRY(dX.alloc(n * 4));
+    OP_TRY(hipMemcpy(dX.p, x, n * 4, hipMemcpyHostToDevice));
+    if (norm) {
+        OP_TRY(dW.alloc((size_t)H * 4));
+        OP_TRY(dB.alloc((size_t)H * 4));
+        OP_TRY(hipMemcpy(dW.p, w, (size_t)H * 4, hipMemcpyHostToDevice));
+        OP_TRY(hipMemcpy(dB.p, b, (size_t)H * 4, hipMemcpyHostToDevice));
+    }
+    float* dev[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3; ++i) {
+        if (!host[i]) continue;
+        OP_TRY(dO[i].alloc((counts[i] + 2 * ng) * 4));
+        OP_TRY(hipMemset(dO[i].p, 0xff, (counts[i] + 2 * ng) * 4));
+        dev[i] = (float*)dO[i].p + ng;
+    }
+    OP_TRY(launch_layer_tap((const float*)dX.p, (const float*)dW.p, (const float*)dB.p, eps, B, T, R, H, norm != 0, layout == 1, dev[0], dev[1],
+                            dev[2], nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    for (int i = 0; i < 3; ++i) {
+        if (!host[i]) continue;
+        std::vector<uint32_t> raw(counts[i] + 2 * ng);
+        OP_TRY(hipMemcpy(raw.data(), dO[i].p, raw.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < ng; ++k)
+            if (raw[k] != 0xffffffffu || raw[ng + counts[i] + k] != 0xffffffffu) return DINOV2_HIP_OP_GUARD_CHANGED;
+        std::memcpy(host[i], raw.data() + ng, counts[i] * 4);
+    }
+    return 0;
+}
+
 extern "C" int dinov2_hip_op_convert_weight(int32_t dtype, const void* src, uint64_t src_bytes, uint32_t ggml_type,
                                             float* out, int32_t N, int32_t K, int32_t Kpad, int32_t interleaveF) {
     const DType dt = dtype == 1 ? DT_BF16 : DT_F16;

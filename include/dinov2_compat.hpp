@@ -223,6 +223,55 @@ inline std::unique_ptr<dino_output> dino_predict(const dino_model& model, const 
     return output;
 }
 
+// No reference counterpart: upstream DINOv2's get_intermediate_layers(x, n, reshape, return_class_token, norm) on the shim's types, through
+// dinov2_hip_predict_layers -- one forward, one extra kernel launch per layer.  `layers`: strictly ascending NUMBERS OF BLOCKS APPLIED
+// (0 = embeddings, num_hidden_layers = the last block; upstream's block index i is layer i + 1, HuggingFace hidden_states[k] is layer k).
+struct dino_layer_output {
+    int layer = 0;
+    Mat32f patch_tokens;        // P x H (row = y*w0 + x), or with reshape H x P: row c = channel c over the h0 x w0 grid
+    std::vector<float> cls;     // H, when asked for
+    int grid_h = 0, grid_w = 0; // h0, w0
+};
+inline std::vector<dino_layer_output> dino_get_intermediate_layers(const dino_model& model, const Mat32f& img, const std::vector<int>& layers,
+                                                                   bool norm = true, bool reshape = false, bool return_class_token = false,
+                                                                   dinov2_hip_session* allocr = nullptr) {
+    dinov2_hip_session* s = allocr ? allocr : model.default_session;
+    if (!s || !img.data || img.channels != 3 || !img.isContinuous()) {
+        fprintf(stderr, "%s: need a continuous 3-channel float image\n", __func__);
+        return {};
+    }
+    const int ps = (int)model.hparams.patch_size, H = (int)model.hparams.hidden_size;
+    const int h0 = img.rows / ps, w0 = img.cols / ps, P = h0 * w0;
+    const size_t n = layers.size();
+    std::vector<int32_t> ids(layers.begin(), layers.end());
+    std::vector<float> patch(n * (size_t)P * H), cls(return_class_token ? n * (size_t)H : 0);
+    dinov2_hip_input in{img.data, 1, img.rows, img.cols, DINOV2_HIP_BGR_HWC, 0};
+    dinov2_hip_layers ly{};
+    ly.layers = ids.data();
+    ly.n_layers = (int32_t)n;
+    ly.norm = norm ? 1 : 0;
+    ly.layout = reshape ? DINOV2_HIP_LAYERS_CHW : DINOV2_HIP_LAYERS_TOKENS;
+    ly.patch_tokens = patch.data();
+    ly.cls = return_class_token ? cls.data() : nullptr;
+    char err[512] = {0};
+    if (dinov2_hip_predict_layers(s, &in, nullptr, &ly, 0, err, sizeof err) != DINOV2_HIP_OK) {
+        fprintf(stderr, "%s: %s\n", __func__, err);
+        return {};
+    }
+    std::vector<dino_layer_output> out(n);
+    for (size_t k = 0; k < n; ++k) {
+        out[k].layer = layers[k];
+        out[k].grid_h = h0;
+        out[k].grid_w = w0;
+        Mat32f& m = out[k].patch_tokens;
+        m.rows = reshape ? H : P; m.cols = reshape ? P : H; m.channels = 1;
+        m.owner = std::make_shared<std::vector<float>>(patch.begin() + (long)(k * (size_t)P * H), patch.begin() + (long)((k + 1) * (size_t)P * H));
+        m.data = m.owner->data();
+        if (return_class_token) out[k].cls.assign(cls.begin() + (long)(k * (size_t)H), cls.begin() + (long)((k + 1) * (size_t)H));
+    }
+    return out;
+}
+
 // 8-bit BGR interleaved image view, as cv::imread returns it (CV_8UC3, continuous)
 struct Mat8u {
     int rows = 0, cols = 0;

@@ -140,6 +140,43 @@ void *dinov2_hip_session_stream(dinov2_hip_session *session);
 int dinov2_hip_predict(dinov2_hip_session *session, const dinov2_hip_input *in, dinov2_hip_output *out,
                        uint32_t flags, char *err, size_t errlen);
 
+/* -- predict + intermediate layers (no reference counterpart: the backbone use of DINOv2 -- DPT / linear decoders read four intermediate
+ *    blocks, the linear-probe recipe the CLS tokens of the last four; upstream DINOv2: get_intermediate_layers(x, n, reshape,
+ *    return_class_token, norm), HuggingFace: output_hidden_states).  ONE ordinary forward; each requested layer costs one more kernel launch
+ *    (layer_tap_kernel, csrc/kernels_misc.hip), which reads the f32 residual stream as it stands after that layer and writes the rows asked for.
+ *    Index convention -- `layers[i]` is the NUMBER OF BLOCKS APPLIED:
+ *        this library (and dinov2_hip_debug_hidden)   HuggingFace                 upstream DINOv2
+ *        0                                            hidden_states[0]            (embeddings; no block index)
+ *        k, 1 <= k <= L                               hidden_states[k]            get_intermediate_layers(n = [k - 1])
+ *    so the usual ViT-L taps, upstream blocks 4, 11, 17, 23, are layers 5, 12, 18, 24. */
+enum dinov2_hip_layers_layout { DINOV2_HIP_LAYERS_TOKENS = 0, DINOV2_HIP_LAYERS_CHW = 1 };
+
+typedef struct dinov2_hip_layers {
+    const int32_t *layers; /* [n_layers], strictly ascending, each in [0, L] (table above)                                              */
+    int32_t n_layers;      /* 1 .. L + 1                                                                                               */
+    int32_t norm;          /* 1: the model's FINAL LayerNorm (ln_w, ln_b, eps) applied to the tapped rows -- norm = True upstream -- with the
+                              bits dinov2_hip_predict's own final LayerNorm gives (layer L, norm 1 IS predict's cls / patch_tokens);
+                              0: the raw f32 residual stream                                                                           */
+    int32_t layout;        /* of patch_tokens only: TOKENS [n, B, P, H];  CHW [n, B, H, h0, w0] (reshape = True upstream): element
+                              (c, y, x) = channel c of patch y*w0 + x -- the same bits, permuted                                       */
+    float *patch_tokens;   /* patch rows only (CLS and registers stripped, with or without DINOV2_HIP_CLASSIFY); any of the three
+                              pointers may be NULL                                                                                     */
+    float *cls;            /* [n, B, H]                                                                                                */
+    float *registers;      /* [n, B, R, H] (DINOV2_HIP_ERR_INVALID if non-NULL on a model without registers)                            */
+    int32_t on_device;     /* 0: host pointers (the call returns after the copy-out; staged through a session-owned device buffer);
+                              1: device pointers, 16-byte aligned, written by the kernel itself, asynchronously on the session's stream */
+    int32_t reserved[4];
+} dinov2_hip_layers;
+
+/* `out` (may be NULL) and `flags` as for dinov2_hip_predict: one call returns logits and taps.  Argument errors (NULL `layers` or list,
+ * n_layers or a layer out of range, a list not strictly ascending, an unknown layout, registers from a register-free model, a device
+ * pointer that is not 16-byte aligned), like those of dinov2_hip_predict itself, return their status before anything is launched,
+ * allocated or copied.  Batches that dinov2_hip_predict splits into passes are split here too,
+ * every pass writing its images at their offset.  Afterwards dinov2_hip_fetch and dinov2_hip_pca3(tokens = NULL) behave as after a
+ * dinov2_hip_predict of the same shape.  Runs eagerly under DINOV2_HIP_GRAPHS=1 (the graph cache is not keyed by the caller's pointers). */
+int dinov2_hip_predict_layers(dinov2_hip_session *session, const dinov2_hip_input *in, dinov2_hip_output *out,
+                              const dinov2_hip_layers *layers, uint32_t flags, char *err, size_t errlen);
+
 /* Copy-out half of dinov2_hip_predict on its own: the outputs of the session's LAST predict (which may have been called with
  * out = NULL, i.e. forward only) into the caller's buffers.  Lets a host overlap the device -> host copy of batch k with the
  * forward of batch k + 1 on another session (this is what the group's lanes do).  Not available after a predict that had to
@@ -237,7 +274,7 @@ int dinov2_hip_session_profile(dinov2_hip_session *session, int32_t enable);
 int dinov2_hip_session_profile_read(dinov2_hip_session *session, int32_t max, const char **names, float *total_ms,
                                     int32_t *launches);
 /* Debug/parity: copy the f32 token stream [B, T, H] as it stands after `layer` layers (0 = embeddings) of the
- * LAST predict with the same shape re-run up to that point.  Host pointer. */
+ * LAST predict with the same shape re-run up to that point.  Host pointer.  (Product code wants dinov2_hip_predict_layers.) */
 int dinov2_hip_debug_hidden(dinov2_hip_session *session, const dinov2_hip_input *in, int32_t layer, float *out,
                             char *err, size_t errlen);
 

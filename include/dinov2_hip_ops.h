@@ -56,6 +56,14 @@ int dinov2_hip_op_attention_ex(int32_t dtype, const float *qkv, float *out, int3
 int dinov2_hip_op_layernorm(int32_t dtype, const float *x, const float *w, const float *b, float *out, int32_t rows,
                             int32_t H, float eps);
 
+/* layer_tap_kernel alone (the kernel behind dinov2_hip_predict_layers, csrc/kernels_misc.hip): x [B, T, H] f32, T = 1 + R + h0 * w0 ->
+ * cls_out [B, H] (token 0), reg_out [B, R, H] (tokens 1 .. R), patch_out [B, P, H] (layout 0) or [B, H, h0, w0] (layout 1); any of the three
+ * may be NULL.  norm = 1: LayerNorm (w, b, eps) with the bits of dinov2_hip_op_layernorm(dtype = -1); norm = 0: the rows as they are (w, b
+ * may be NULL).  Every device output is framed by guard bands of DINOV2_HIP_OP_GUARD_ROWS * H floats and starts as NaN; a changed guard
+ * returns DINOV2_HIP_OP_GUARD_CHANGED. */
+int dinov2_hip_op_layer_tap(const float *x, const float *w, const float *b, float eps, int32_t B, int32_t T, int32_t R, int32_t H, int32_t h0,
+                            int32_t w0, int32_t norm, int32_t layout, float *patch_out, float *cls_out, float *reg_out);
+
 /* load-time tensor conversion / dequantisation (F32,F16,BF16,Q4_0,Q4_1,Q5_0,Q5_1,Q8_0 -> compute dtype).  interleaveF > 0: N = 2F rows
  * of a SwiGLU weights_in [x1 (F rows); x2 (F rows)] come out as alternating 32-row blocks x1 | x2 (csrc/model.cpp).  The output
  * starts as NaN (as do those of the layernorm, preprocess_u8, permute_bias and head entry points). */
