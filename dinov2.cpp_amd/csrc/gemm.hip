@@ -26,6 +26,7 @@
 #include <mutex>
 
 #include "device_types.h"
+#include "gemm_epilogue.h"
 #include "kernels.h"
 
 namespace dinov2 {
@@ -59,7 +60,7 @@ __device__ unsigned long long g_sprof_t[2 * 1024];  // wall clock (100 MHz) at e
 
 template <typename T, int BM, int BN, int WM, int WN, int NST, int EPI, int KSUB = 1>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs p) {
-#pragma clang fp contract(off)  // position-independent results: see gemm2.hip
+#pragma clang fp contract(off)  // position-independent results: see gemm_epilogue.h
     using E = Elem<T>;
     using vec8 = typename E::vec8;
     constexpr int NW = WM * WN;
@@ -273,22 +274,20 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs p) {
                     if (row < M && c2 < N) {
                         float h1, h2;
                         if constexpr (LNC) {
-                            h1 = __builtin_fmaf(lnr[i], acc[i][jh][r], __builtin_fmaf(lnn[i], s1, b1));
-                            h2 = __builtin_fmaf(lnr[i], acc[i][jh + 2][r], __builtin_fmaf(lnn[i], s2, b2));
+                            h1 = epi_ln_raw(lnr[i], lnn[i], acc[i][jh][r], s1, b1);
+                            h2 = epi_ln_raw(lnr[i], lnn[i], acc[i][jh + 2][r], s2, b2);
                         } else {
-                            h1 = acc[i][jh][r] + b1;
-                            h2 = acc[i][jh + 2][r] + b2;
+                            h1 = epi_bias_raw(acc[i][jh][r], b1);
+                            h2 = epi_bias_raw(acc[i][jh + 2][r], b2);
                         }
-                        float sl = h1 * __builtin_amdgcn_rcpf(1.0f + __expf(-h1)) * h2;  // silu(x1) * x2, dinov2.cpp:605
-                        asm("" : "+v"(sl));
-                        out[(size_t)row * p.ldo + hu] = E::from_f32(sl);
+                        out[(size_t)row * p.ldo + hu] = E::from_f32(epi_swiglu(h1, h2));
                     }
                 }
             }
         return;
     } else if (vec_ok) {
-        // the common case: whole tile inside N, aligned rows; the operands were fetched before the K loop.  Arithmetic identical, expression
-        // by expression, to the guarded path below (and to gemm2.hip).
+        // the common case: whole tile inside N, aligned rows; the operands were fetched before the K loop.  The arithmetic of this path, of
+        // the guarded path below and of gemm2.hip / gemm4.hip is gemm_epilogue.h's.
         // One unconditional use of every prefetched register first: the compiler then waits for those loads HERE, once.  Left to the
         // row-guarded blocks below it puts an `s_waitcnt vmcnt(0)` into each of them, and on gfx9 vmcnt also counts stores: every
         // block would wait for the previous block's store to retire (measured: 8.8 us of a 20 us FFN-in launch at M = 1 374).
@@ -316,23 +315,19 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs p) {
                 float v[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    if constexpr (LNC) v[r] = __builtin_fmaf(lnr[i], acc[i][jn][r], __builtin_fmaf(lnn[i], lns4[jn][r], bias4[jn][r]));
-                    else v[r] = acc[i][jn][r] + bias4[jn][r];
-                    asm("" : "+v"(v[r]));
+                    if constexpr (LNC) v[r] = epi_ln(lnr[i], lnn[i], acc[i][jn][r], lns4[jn][r], bias4[jn][r]);
+                    else v[r] = epi_bias(acc[i][jn][r], bias4[jn][r]);
                 }
                 if constexpr (EB == EPI_RESID) {
                     float* x = (float*)p.out + (size_t)row * p.ldo + col0;
                     const f32x4 xi = xin4[i][jn], au = aux4[jn];
-                    const f32x4 xn = f32x4{v[0] * au[0] + xi[0], v[1] * au[1] + xi[1], v[2] * au[2] + xi[2], v[3] * au[3] + xi[3]};
+                    const f32x4 xn = f32x4{epi_residual(epi_layerscale(v[0], au[0]), xi[0]), epi_residual(epi_layerscale(v[1], au[1]), xi[1]),
+                                           epi_residual(epi_layerscale(v[2], au[2]), xi[2]), epi_residual(epi_layerscale(v[3], au[3]), xi[3])};
                     *(f32x4*)x = xn;
                     if constexpr (EPI == EPI_RESID_LN) {
                         typename E::vec4 og;
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            float g = xn[r] * gam4[EPI == EPI_RESID_LN ? jn : 0][r];
-                            asm("" : "+v"(g));  // f32 product first, then the rounding (as everywhere)
-                            og[r] = E::from_f32(g);
-                        }
+                        for (int r = 0; r < 4; ++r) og[r] = epi_xg<E>(xn[r], gam4[EPI == EPI_RESID_LN ? jn : 0][r]);
                         *(typename E::vec4*)((T*)p.xg + (size_t)row * p.ldo + col0) = og;
                         float s4, q4;
                         ln_leaf4(xn[0], xn[1], xn[2], xn[3], s4, q4);
@@ -350,46 +345,22 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs p) {
                     if constexpr (EB == EPI_QKV) {
                         const float qs = col0 < p.qcols ? p.qscale : 1.0f;  // (qcols % 4 == 0: one answer for the lane's four columns)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            float vq = v[r] * qs;
-                            asm("" : "+v"(vq));
-                            o[r] = E::from_f32(vq);
-                        }
+                        for (int r = 0; r < 4; ++r) o[r] = epi_qkv<E>(v[r], qs);
 #if DINO_PREC & 25
                         if (p.ldo >= 2 * N) {  // second word of q | k | v: columns [N, 2N) of the (6H-wide) row model.cpp allocates in these builds
                                                // (a launch with a dense output -- dinov2_hip_op_gemm -- has nowhere to put it: ADVICE r5)
                             typename E::vec4 lo;
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                float vq = v[r] * qs;
-                                asm("" : "+v"(vq));
-                                lo[r] = E::from_f32(vq - E::to_f32(o[r]));
-                            }
+                            for (int r = 0; r < 4; ++r) lo[r] = E::from_f32(epi_qkv_f32(v[r], qs) - E::to_f32(o[r]));
                             *(typename E::vec4*)((T*)p.out + (size_t)row * p.ldo + N + col0) = lo;
                         }
 #endif
                     } else {
-                        // two columns per instruction (v_pk_*_f32; v_exp / v_rcp / the conversions per element), exactly as gemm2.hip
-                        typedef float f32x2 __attribute__((ext_vector_type(2)));
-                        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
-                        for (int e2 = 0; e2 < 2; ++e2) {
-                            const f32x2 vv = {v[2 * e2], v[2 * e2 + 1]};
-                            const f32x2 xr = __builtin_convertvector(__builtin_convertvector(vv, f16x2), f32x2);
-                            const f32x2 c1 = {-0.1029432397f, -0.1029432397f}, c2 = {-2.302208199f, -2.302208199f};
-                            const f32x2 t = xr * __builtin_elementwise_fma(xr * xr, c1, c2);  // -2 log2(e) u
-                            const f32x2 den = f32x2{1.0f, 1.0f} + f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
-                            f32x2 gl = xr * f32x2{__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-#if DINO_PREC & 4
-#pragma unroll
-                            for (int e = 0; e < 2; ++e) {
-                                const double xd = (double)xr[e];
-                                gl[e] = xd <= -10.0 ? 0.0f : xd >= 10.0 ? xr[e] : (float)(0.5 * xd * (1.0 + tanh(0.79788456080286535587989211986876 * xd * (1.0 + 0.044715 * xd * xd))));
-                            }
-#endif
-                            asm("" : "+v"(gl));
-                            o[2 * e2] = E::from_f32((float)(_Float16)gl[0]);
-                            o[2 * e2 + 1] = E::from_f32((float)(_Float16)gl[1]);
+                        for (int e2 = 0; e2 < 2; ++e2) {  // two columns per instruction
+                            const f32x2 g = epi_gelu(f32x2{v[2 * e2], v[2 * e2 + 1]});
+                            o[2 * e2] = E::from_f32(g[0]);
+                            o[2 * e2 + 1] = E::from_f32(g[1]);
                         }
                     }
                     *(typename E::vec4*)((T*)p.out + (size_t)row * p.ldo + col0) = o;
@@ -419,9 +390,8 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs p) {
                 float v[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    if constexpr (LNC) v[r] = __builtin_fmaf(lnr[i], acc[i][jn][r], __builtin_fmaf(lnn[i], lnsv[r], bias[r]));
-                    else v[r] = acc[i][jn][r] + bias[r];
-                    asm("" : "+v"(v[r]));  // f32 value first, then any f16 rounding (no v_fma_mix fusion: gemm2.hip)
+                    if constexpr (LNC) v[r] = epi_ln(lnr[i], lnn[i], acc[i][jn][r], lnsv[r], bias[r]);
+                    else v[r] = epi_bias(acc[i][jn][r], bias[r]);
                 }
                 if constexpr (EPI == EPI_PATCH) {
                     const int b = row / p.P, pp = row - b * p.P;
@@ -434,11 +404,11 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs p) {
                     float* x = (float*)p.out + (size_t)row * p.ldo;
                     if (full) {
                         const float4 xin = *(const float4*)(x + col0);
-                        *(float4*)(x + col0) = make_float4(v[0] * auxv[0] + xin.x, v[1] * auxv[1] + xin.y, v[2] * auxv[2] + xin.z, v[3] * auxv[3] + xin.w);
+                        *(float4*)(x + col0) = epi_residual(make_float4(epi_layerscale(v[0], auxv[0]), epi_layerscale(v[1], auxv[1]), epi_layerscale(v[2], auxv[2]), epi_layerscale(v[3], auxv[3])), xin);
                     } else {
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            if (col0 + r < N) x[col0 + r] = v[r] * auxv[r] + x[col0 + r];
+                            if (col0 + r < N) x[col0 + r] = epi_residual(epi_layerscale(v[r], auxv[r]), x[col0 + r]);
                     }
                 } else if constexpr (EPI == EPI_PLAIN_F32) {
                     float* x = (float*)p.out + (size_t)row * p.ldo;
@@ -453,27 +423,13 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_kernel(GemmArgs p) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if constexpr (EB == EPI_QKV) {
-                            float vq = v[r] * auxv[r];
-                            asm("" : "+v"(vq));
+                            const float vq = epi_qkv_f32(v[r], auxv[r]);
                             o[r] = E::from_f32(vq);
 #if DINO_PREC & 25
                             if (col0 + r < N && p.ldo >= 2 * N) ((T*)p.out)[(size_t)row * p.ldo + N + col0 + r] = E::from_f32(vq - E::to_f32(o[r]));
 #endif
                         } else {
-                            // ggml_gelu = f16 lookup table: table[f16(x)] = f16(gelu(f32(f16(x)))).  EXACTLY the expression of
-                            // gemm2.hip (same constants, same operation order; the x <= -10 / x >= 10 branches fall out of it):
-                            // a token must get the same bits from either kernel, whatever batch it arrives in.
-                            const float xr = (float)(_Float16)v[r];
-                            const float t = xr * __builtin_fmaf(xr * xr, -0.1029432397f, -2.302208199f);  // -2 log2(e) u
-                            float g = xr * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(t));
-#if DINO_PREC & 4
-                            {
-                                const double xd = (double)xr;
-                                g = xd <= -10.0 ? 0.0f : xd >= 10.0 ? xr : (float)(0.5 * xd * (1.0 + tanh(0.79788456080286535587989211986876 * xd * (1.0 + 0.044715 * xd * xd))));
-                            }
-#endif
-                            asm("" : "+v"(g));
-                            o[r] = E::from_f32((float)(_Float16)g);
+                            o[r] = E::from_f32(epi_gelu(v[r]));  // (one column at a time: the same bits as the packed form)
                         }
                     }
                     T* y = (T*)p.out + (size_t)row * p.ldo;

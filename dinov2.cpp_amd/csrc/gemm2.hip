@@ -20,6 +20,7 @@
 #include <cstdio>
 
 #include "device_types.h"
+#include "gemm_epilogue.h"
 #include "kernels.h"
 
 // The timing-only experiment switches this kernel carried while it was tuned (no staging / no MFMA / no fragment reads / deeper
@@ -27,14 +28,6 @@
 // profiles/r02_gemm_kloop.md.  The product kernel has one schedule.
 
 namespace dinov2 {
-
-// 16-byte store of the 2-byte epilogues: non-temporal for outputs larger than the L2s (GemmArgs::nt_out; see gemm4.hip, DINO4_ST16 --
-// ViT-B / ViT-S at batch 32, which run on this kernel: + 1.7 % / + 2.6 % images/s)
-#define DINO2_ST16(PTR, V)                               \
-    {                                                    \
-        if (nt_out) __builtin_nontemporal_store((V), (PTR)); \
-        else *(PTR) = (V);                               \
-    }
 
 // -DDINO_GEMM_PROF (tuning builds): s_memtime sums per workgroup -- [0] tile prologue (both barriers + the counted wait), [1] K loop,
 // [2] epilogue, [3] tiles -- of wave 0 and of wave 4 (+ 4), printed by the launcher after each launch.
@@ -59,9 +52,8 @@ __device__ unsigned long long g_gemm_prof[256 * 8];
 // K-tile is still two K-tile times in flight although a K-tile takes half as long.
 template <typename T, int EPI, int XREP>
 static __device__ __forceinline__ void gemm2_body(const GemmArgs& p, char* smem) {
-    // No implicit mul+add -> fma contraction anywhere in this kernel: the unrolled epilogue instances would otherwise be
-    // contracted differently, making an output element's last f32 bit (and, after the f16 rounding, occasionally its
-    // value) depend on WHERE its row sits in the tile.  B images must equal B independent forwards bit for bit.
+    // No implicit mul+add -> fma contraction anywhere in this kernel (gemm_epilogue.h says why): B images must equal B independent
+    // forwards bit for bit.
 #pragma clang fp contract(off)
     using E = Elem<T>;
     using vec8 = typename E::vec8;
@@ -385,51 +377,21 @@ static __device__ __forceinline__ void gemm2_body(const GemmArgs& p, char* smem)
                         for (int i = ih * IPS; i < (ih + 1) * IPS; ++i) {
                             if (q == 1 && i >= NI1) continue;  // 192-row tiles: the second pass has 32 rows
                             vec4 o;
+                            // the arithmetic is gemm_epilogue.h's, shared with gemm.hip and gemm4.hip
                             if constexpr (EPI == EPI_GELU) {
-                                // ggml semantics: y = table[f16(x)], table[h] = f16(gelu_tanh(f32(h))).
-                                // 0.5 x (1 + tanh u) == x / (1 + exp(-2u)); the reference's x <= -10 -> 0 and
-                                // x >= 10 -> x branches fall out of the formula after the f16 roundings (exp -> inf
-                                // gives -0, exp -> 0 gives x), so no compares are needed.
-                                // Two columns per instruction: the bias add, x^2, the cubic, 1 + 2^t and the final product
-                                // run as v_pk_*_f32 (IEEE results identical to the scalar ops of gemm.hip, so both kernels
-                                // still agree bit for bit); v_exp / v_rcp / the f16 conversions stay per element.
-                                typedef float f32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
-                                for (int e2 = 0; e2 < 2; ++e2) {
-                                    f32x2 v = {acc[q][b][i][j][2 * e2], acc[q][b][i][j][2 * e2 + 1]};
-                                    v += f32x2{bb[2 * e2], bb[2 * e2 + 1]};
-                                    asm("" : "+v"(v));  // f32 sums first (no v_fma_mix fusion), then the f16 rounding
-                                    // (vector converts: one v_cvt_pk_f16_f32 + v_cvt_f32_f16 / its SDWA form instead of four scalar converts)
-                                    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-                                    const f32x2 xr = __builtin_convertvector(__builtin_convertvector(v, f16x2), f32x2);
-                                    const f32x2 c1 = {-0.1029432397f, -0.1029432397f}, c2 = {-2.302208199f, -2.302208199f};
-                                    const f32x2 t = xr * __builtin_elementwise_fma(xr * xr, c1, c2);  // -2 log2(e) u
-                                    const f32x2 den = f32x2{1.0f, 1.0f} + f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
-                                    f32x2 gl = xr * f32x2{__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-                                    asm("" : "+v"(gl));
-                                    o[2 * e2] = E::from_f32((float)(_Float16)gl[0]);
-                                    o[2 * e2 + 1] = E::from_f32((float)(_Float16)gl[1]);
+                                for (int e2 = 0; e2 < 2; ++e2) {  // two columns per instruction
+                                    const f32x2 g = epi_gelu(epi_bias(f32x2{acc[q][b][i][j][2 * e2], acc[q][b][i][j][2 * e2 + 1]}, f32x2{bb[2 * e2], bb[2 * e2 + 1]}));
+                                    o[2 * e2] = E::from_f32(g[0]);
+                                    o[2 * e2 + 1] = E::from_f32(g[1]);
                                 }
                             } else
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
-                                float v = acc[q][b][i][j][e] + bb[e];
-                                // keep the f32 sum a real register value: hipcc otherwise fuses "add, then round to f16"
-                                // into v_fma_mixlo_f16 for SOME unrolled instances (single rounding instead of the
-                                // reference's f32-then-f16 double rounding), which made results depend on the row's
-                                // position in the tile
-                                asm("" : "+v"(v));
-                                if constexpr (EPI == EPI_QKV) {
-                                    float vq = v * qs;
-                                    asm("" : "+v"(vq));
-                                    o[e] = E::from_f32(vq);
-                                } else {
-                                    // EPI_SWIGLU: W rows interleaved in 32-blocks: column half 0 holds x1[32 units], half 1 holds x2 of the same units
-                                    const float h2 = acc[q][1][i][j][e] + b2[e];
-                                    float sg = v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)) * h2;  // silu(x1) * x2
-                                    asm("" : "+v"(sg));
-                                    o[e] = E::from_f32(sg);
-                                }
+                                const float v = epi_bias(acc[q][b][i][j][e], bb[e]);
+                                if constexpr (EPI == EPI_QKV) o[e] = epi_qkv<E>(v, qs);
+                                // EPI_SWIGLU: W rows interleaved in 32-blocks: column half 0 holds x1[32 units], half 1 holds x2 of the same units
+                                else o[e] = E::from_f32(epi_swiglu(v, epi_bias_raw(acc[q][1][i][j][e], b2[e])));
                             }
                             const int row = (i - ih * IPS) * 16 + er;  // row within the sub-pass
                             const int slot = (4 * b + 2 * j + (eq >> 1)) ^ (row & 7);  // 8 columns (16 B) per slot
@@ -445,7 +407,7 @@ static __device__ __forceinline__ void gemm2_body(const GemmArgs& p, char* smem)
                         const u32x4 v = *(const u32x4*)(eh + row * 128 + ((slot ^ (row & 7)) << 4));
                         const int m = mbase + q * 64 + row;
                         if (m < M && (XREP == 4 || q * 64 + row < 32 * XREP))
-                            DINO2_ST16((u32x4*)((T*)p.out + (size_t)m * p.ldo + hid0 + slot * 8), v);
+                            DINO_EPI_ST16((u32x4*)((T*)p.out + (size_t)m * p.ldo + hid0 + slot * 8), v, nt_out);
                     }
                 } else {
 #pragma unroll
@@ -455,7 +417,7 @@ static __device__ __forceinline__ void gemm2_body(const GemmArgs& p, char* smem)
                         const int tr = q * 64 + ih * (64 / SUBP) + row;  // token row within the wave's 128
                         const int m = mbase + tr;
                         if (m < M && (XREP == 4 || tr < 32 * XREP))
-                            DINO2_ST16((u32x4*)((T*)p.out + (size_t)m * p.ldo + n0 + ww * 64 + slot * 8), v);
+                            DINO_EPI_ST16((u32x4*)((T*)p.out + (size_t)m * p.ldo + n0 + ww * 64 + slot * 8), v, nt_out);
                     }
                 }
                 // (two halves: the next sub-pass writes the OTHER half, and a wave's LDS operations execute in order, so only the
@@ -494,9 +456,7 @@ static __device__ __forceinline__ void gemm2_body(const GemmArgs& p, char* smem)
                         if (q == 1 && i >= NI1) continue;
                         const int row = i * 16 + er;
                         const int slot = (4 * j + eq) ^ (row & 7);  // 4 columns (16 B) per slot
-                        *(float4*)(ep + row * 128 + slot * 16) =
-                            make_float4((acc[q][b][i][j][0] + b4.x) * ls.x, (acc[q][b][i][j][1] + b4.y) * ls.y,
-                                        (acc[q][b][i][j][2] + b4.z) * ls.z, (acc[q][b][i][j][3] + b4.w) * ls.w);
+                        *(float4*)(ep + row * 128 + slot * 16) = epi_layerscale(acc[q][b][i][j], b4, ls);
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -504,8 +464,7 @@ static __device__ __forceinline__ void gemm2_body(const GemmArgs& p, char* smem)
                 for (int it = 0; it < 8; ++it) {
                     const int row = it * 8 + (el >> 3), slot = el & 7;
                     float4 v = *(const float4*)(ep + row * 128 + ((slot ^ (row & 7)) << 4));
-                    if constexpr (EPI == EPI_RESID || EPI == EPI_PATCH)
-                        v = make_float4(v.x + add[it].x, v.y + add[it].y, v.z + add[it].z, v.w + add[it].w);
+                    if constexpr (EPI == EPI_RESID || EPI == EPI_PATCH) v = epi_residual(v, add[it]);
                     const int m = mbase + q * 64 + row;
                     if (m < M && (XREP == 4 || q * 64 + row < 32 * XREP)) {
                         size_t o;

@@ -36,6 +36,7 @@
 #include <utility>
 
 #include "device_types.h"
+#include "gemm_epilogue.h"
 #include "kernels.h"
 
 namespace dinov2 {
@@ -72,17 +73,6 @@ hipError_t gemm4_clock_probe_read(unsigned long long* out) {
 
 constexpr int G4_PA = 39, G4_PB = 103;  // barrier A / B behind these MFMA indices
 
-// 16-byte store of the 2-byte epilogues.  NON-TEMPORAL when the launcher says so (GemmArgs::nt_out: outputs larger than the chip's 32 MiB of
-// L2), so that a tile's 128 KiB of output does not push the operand panels out of the XCD's 4 MiB L2 (32 CUs x 128 KiB = all of it); the
-// consumer is another kernel and reads it through the memory side anyway.  Same box, interleaved: QKV 0.2496 -> 0.2378 ms in the
-// micro-benchmark, forward 927 - 930 -> 933 - 935 images/s (the FFN-out GEMM that reads the FFN hidden buffer gains most: 0.331 -> 0.325 ms).
-// Small outputs (batch 1) stay ordinary stores: their consumer finds them in L2 (p50 2.50 against 2.58 ms with non-temporal stores).
-#define DINO4_ST16(PTR, V)                               \
-    {                                                    \
-        if (nt_out) __builtin_nontemporal_store((V), (PTR)); \
-        else *(PTR) = (V);                               \
-    }
-
 // -DDINO_GEMM4_PROF (tuning builds): s_memtime sums per workgroup of wave 0 -- [0] K loops, [1] epilogues, [2] tiles, [3] the 100 MHz ticks of
 // both -- printed by the launcher after each launch.
 #ifdef DINO_GEMM4_PROF
@@ -102,7 +92,7 @@ __device__ unsigned long long g_gemm4_prof[256 * 4];
 
 template <typename T, int EPI, int NI>
 static __device__ __forceinline__ void gemm4_body(const GemmArgs& p, char* smem) {
-    // (no implicit mul+add -> fma contraction: an element's bits must not depend on where its row sits in a tile -- see gemm2.hip)
+    // (no implicit mul+add -> fma contraction: an element's bits must not depend on where its row sits in a tile -- see gemm_epilogue.h)
 #pragma clang fp contract(off)
     using E = Elem<T>;
     using vec4 = typename E::vec4;
@@ -487,50 +477,32 @@ static __device__ __forceinline__ void gemm4_body(const GemmArgs& p, char* smem)
                                 if (q * 4 + i >= NI) continue;  // shorter tiles: fewer 16-token blocks
                                 const int ir = i;  // (index of this block's row coefficients)
                                 vec4 o;
+                                // the arithmetic is gemm_epilogue.h's, shared with gemm.hip and gemm2.hip
                                 if constexpr (EB == EPI_GELU) {
-                                    // ggml semantics: y = table[f16(x)], table[h] = f16(gelu_tanh(f32(h))); two columns per instruction
-                                    // (v_pk_*_f32: IEEE results identical to the scalar ops of gemm.hip, so the kernels agree bit for bit)
-                                    typedef float f32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
-                                    for (int e2 = 0; e2 < 2; ++e2) {
-                                        f32x2 v = {DINO4_ACC(q, b, i, j)[2 * e2], DINO4_ACC(q, b, i, j)[2 * e2 + 1]};
-                                        if constexpr (LNC) {  // r (acc - mean s[n]) + c[n] as two fused multiply-adds per column (v_pk_fma_f32)
-                                            const f32x2 d = __builtin_elementwise_fma(f32x2{lnn[LNC ? ir : 0], lnn[LNC ? ir : 0]}, f32x2{sb[2 * e2], sb[2 * e2 + 1]},
-                                                                                      f32x2{bb[2 * e2], bb[2 * e2 + 1]});
-                                            v = __builtin_elementwise_fma(f32x2{lnr[LNC ? ir : 0], lnr[LNC ? ir : 0]}, v, d);
-                                        } else {
-                                            v += f32x2{bb[2 * e2], bb[2 * e2 + 1]};
-                                        }
-                                        asm("" : "+v"(v));  // f32 sums first (no v_fma_mix fusion), then the f16 rounding
-                                        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-                                        const f32x2 xr = __builtin_convertvector(__builtin_convertvector(v, f16x2), f32x2);
-                                        const f32x2 c1 = {-0.1029432397f, -0.1029432397f}, c2 = {-2.302208199f, -2.302208199f};
-                                        const f32x2 t = xr * __builtin_elementwise_fma(xr * xr, c1, c2);  // -2 log2(e) u
-                                        const f32x2 den = f32x2{1.0f, 1.0f} + f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
-                                        f32x2 gl = xr * f32x2{__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-                                        asm("" : "+v"(gl));
-                                        o[2 * e2] = E::from_f32((float)(_Float16)gl[0]);
-                                        o[2 * e2 + 1] = E::from_f32((float)(_Float16)gl[1]);
+                                    for (int e2 = 0; e2 < 2; ++e2) {  // two columns per instruction
+                                        const f32x2 a2 = {DINO4_ACC(q, b, i, j)[2 * e2], DINO4_ACC(q, b, i, j)[2 * e2 + 1]};
+                                        f32x2 v;
+                                        if constexpr (LNC) v = epi_ln(lnr[LNC ? ir : 0], lnn[LNC ? ir : 0], a2, f32x2{sb[2 * e2], sb[2 * e2 + 1]}, f32x2{bb[2 * e2], bb[2 * e2 + 1]});
+                                        else v = epi_bias(a2, f32x2{bb[2 * e2], bb[2 * e2 + 1]});
+                                        const f32x2 g = epi_gelu(v);
+                                        o[2 * e2] = E::from_f32(g[0]);
+                                        o[2 * e2 + 1] = E::from_f32(g[1]);
                                     }
                                 } else {
 #pragma unroll
                                     for (int e = 0; e < 4; ++e) {
                                         float v;
-                                        if constexpr (LNC) v =__builtin_fmaf(lnr[LNC ? ir : 0], DINO4_ACC(q, b, i, j)[e], __builtin_fmaf(lnn[LNC ? ir : 0], sb[e], bb[e]));
-                                        else v = DINO4_ACC(q, b, i, j)[e] + bb[e];
-                                        asm("" : "+v"(v));  // a real f32 sum: no "add, then round" fusion into v_fma_mixlo_f16
+                                        if constexpr (LNC) v = epi_ln(lnr[LNC ? ir : 0], lnn[LNC ? ir : 0], DINO4_ACC(q, b, i, j)[e], sb[e], bb[e]);
+                                        else v = epi_bias(DINO4_ACC(q, b, i, j)[e], bb[e]);
                                         if constexpr (EB == EPI_QKV) {
-                                            float vq = v * qs;
-                                            asm("" : "+v"(vq));
-                                            o[e] = E::from_f32(vq);
+                                            o[e] = epi_qkv<E>(v, qs);
                                         } else {
                                             // EPI_SWIGLU: W rows interleaved in 32-blocks: column half 0 holds x1[32 units], half 1 x2 of the same units
                                             float h2;
-                                            if constexpr (LNC) h2 = __builtin_fmaf(lnr[LNC ? ir : 0], DINO4_ACC(q, 1, i, j)[e], __builtin_fmaf(lnn[LNC ? ir : 0], s2[e], b2[e]));
-                                            else h2 = DINO4_ACC(q, 1, i, j)[e] + b2[e];
-                                            float sg = v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)) * h2;  // silu(x1) * x2
-                                            asm("" : "+v"(sg));
-                                            o[e] = E::from_f32(sg);
+                                            if constexpr (LNC) h2 = epi_ln_raw(lnr[LNC ? ir : 0], lnn[LNC ? ir : 0], DINO4_ACC(q, 1, i, j)[e], s2[e], b2[e]);
+                                            else h2 = epi_bias_raw(DINO4_ACC(q, 1, i, j)[e], b2[e]);
+                                            o[e] = E::from_f32(epi_swiglu(v, h2));
                                         }
                                     }
                                 }
@@ -548,7 +520,7 @@ static __device__ __forceinline__ void gemm4_body(const GemmArgs& p, char* smem)
                             const u32x4 v = *(const u32x4*)(ep + row * 128 + ((slot ^ (row & 7)) << 4));
                             const int m = mbase + q * 64 + row;
                             if (m < M && (NI == 8 || q * 64 + row < 16 * NI))
-                                DINO4_ST16((u32x4*)((T*)p.out + (size_t)m * p.ldo + hid0 + slot * 8), v);
+                                DINO_EPI_ST16((u32x4*)((T*)p.out + (size_t)m * p.ldo + hid0 + slot * 8), v, nt_out);
                         }
                     } else {
 #pragma unroll
@@ -558,7 +530,7 @@ static __device__ __forceinline__ void gemm4_body(const GemmArgs& p, char* smem)
                             const int trw = q * 64 + row;  // token row within the wave's 16 NI
                             const int m = mbase + trw;
                             if (m < M && (NI == 8 || trw < 16 * NI))
-                                DINO4_ST16((u32x4*)((T*)p.out + (size_t)m * p.ldo + nw0 + slot * 8), v);
+                                DINO_EPI_ST16((u32x4*)((T*)p.out + (size_t)m * p.ldo + nw0 + slot * 8), v, nt_out);
                         }
                     }
                     __builtin_amdgcn_wave_barrier();
@@ -617,9 +589,7 @@ static __device__ __forceinline__ void gemm4_body(const GemmArgs& p, char* smem)
                         if (q * 4 + i >= NI) continue;
                         const int row = i * 16 + (el & 15);
                         const int slot = (4 * j + (el >> 4)) ^ (row & 7);  // 4 columns (16 B) per slot
-                        const f32x4 a = DINO4_ACC(q, b, i, j);
-                        *(float4*)(ep + row * 128 + slot * 16) =
-                            make_float4((a[0] + b4.x) * ls.x, (a[1] + b4.y) * ls.y, (a[2] + b4.z) * ls.z, (a[3] + b4.w) * ls.w);
+                        *(float4*)(ep + row * 128 + slot * 16) = epi_layerscale(DINO4_ACC(q, b, i, j), b4, ls);
                     }
                 }
                 if (ps8 + PF < 8) issue_loads(ps8 + PF);  // ahead of this pass's stores
@@ -628,8 +598,7 @@ static __device__ __forceinline__ void gemm4_body(const GemmArgs& p, char* smem)
                 for (int it = 0; it < 8; ++it) {
                     const int row = it * 8 + (el >> 3), slot = el & 7;
                     float4 v = *(const float4*)(ep + row * 128 + ((slot ^ (row & 7)) << 4));
-                    if constexpr (EPI == EPI_RESID)
-                        v = make_float4(v.x + add[ps8][it].x, v.y + add[ps8][it].y, v.z + add[ps8][it].z, v.w + add[ps8][it].w);
+                    if constexpr (EPI == EPI_RESID) v = epi_residual(v, add[ps8][it]);
                     const int m = mbase + q * 64 + row;
                     if (m < M && (NI == 8 || q * 64 + row < 16 * NI)) *(float4*)((float*)p.out + (size_t)m * p.ldo + nb) = v;
                 }
@@ -692,9 +661,7 @@ static __device__ __forceinline__ void gemm4_body(const GemmArgs& p, char* smem)
                             if (q * 4 + ih * 2 + ii >= NI) continue;
                             const int row = ii * 16 + (el & 15);
                             const int slot = (b * 8 + j * 4 + (el >> 4)) ^ (row & 15);
-                            const f32x4 a = DINO4_ACC(q, b, ih * 2 + ii, j);
-                            *(float4*)(ep + row * 256 + slot * 16) =
-                                make_float4((a[0] + b4.x) * ls.x, (a[1] + b4.y) * ls.y, (a[2] + b4.z) * ls.z, (a[3] + b4.w) * ls.w);
+                            *(float4*)(ep + row * 256 + slot * 16) = epi_layerscale(DINO4_ACC(q, b, ih * 2 + ii, j), b4, ls);
                         }
                     }
                 const float4 gam = *(const float4*)(p.ln_gamma + nb);
@@ -710,18 +677,12 @@ static __device__ __forceinline__ void gemm4_body(const GemmArgs& p, char* smem)
                 for (int it = 0; it < 8; ++it) {
                     const int row = it * 4 + (el >> 4), slot = el & 15;
                     float4 v = *(const float4*)(ep + row * 256 + ((slot ^ (row & 15)) << 4));
-                    v = make_float4(v.x + add[ps8][it].x, v.y + add[ps8][it].y, v.z + add[ps8][it].z, v.w + add[ps8][it].w);
+                    v = epi_residual(v, add[ps8][it]);
                     const int rl = q * 64 + ih * 32 + row;
                     const int m = mbase + rl;
                     const bool live = m < M && (NI == 8 || rl < 16 * NI);
                     if (live) *(float4*)((float*)p.out + (size_t)m * p.ldo + nb) = v;
-                    vec4 og;
-                    float g0 = v.x * gam.x, g1 = v.y * gam.y, g2 = v.z * gam.z, g3 = v.w * gam.w;
-                    asm("" : "+v"(g0), "+v"(g1), "+v"(g2), "+v"(g3));  // f32 products first, then the rounding
-                    og[0] = E::from_f32(g0);
-                    og[1] = E::from_f32(g1);
-                    og[2] = E::from_f32(g2);
-                    og[3] = E::from_f32(g3);
+                    const vec4 og = epi_xg<E>(v, gam);
                     if (live) *(vec4*)((T*)p.xg + (size_t)m * p.ldo + nb) = og;
                     float s4, q4;
                     ln_leaf4(v.x, v.y, v.z, v.w, s4, q4);

@@ -179,3 +179,22 @@ def test_misc_kernels_keep_their_rounding_points(tmp_path):
     fused, n = fused_kernels(*compile_misc_both_ways(src, str(tmp_path)))
     assert n == 10, n  # preprocess_u8_kernel + layernorm_kernel<f32 | f16 | bf16, MAXV 2 | 4 | 8>
     assert not fused, "contracted into FMAs: %s" % fused
+
+
+# ------------------------------------------------------------------------------------------------------------- gemm_epilogue.h
+def test_gemm_epilogue_arithmetic_has_a_single_source():
+    """The three GEMM kernel files must give an accumulator the same bits, so the epilogue arithmetic is written once, in
+    csrc/gemm_epilogue.h, and gemm.hip, gemm2.hip and gemm4.hip include it.  Its fingerprints -- the two GELU constants, the SwiGLU's
+    `__expf(`, the 16-byte store macro -- may not reappear in any other file of csrc/.  (attention.hip's softmax has exponentials of its
+    own, `__expf(` among them; it includes nothing of this and is the one file the `__expf(` count leaves out.)"""
+    csrc = os.path.join(ROOT, "dinov2.cpp_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if os.path.isfile(os.path.join(csrc, f))}
+    assert "gemm_epilogue.h" in text
+    for needle in ("0.1029432397", "2.302208199", "__expf("):
+        holders = [f for f, t in text.items() if needle in t and not (needle == "__expf(" and f == "attention.hip")]
+        assert holders == ["gemm_epilogue.h"], (needle, holders)
+    for f in ("gemm.hip", "gemm2.hip", "gemm4.hip"):
+        assert re.search(r'^#include "gemm_epilogue\.h"', text[f], re.M), f
+    assert "gemm_epilogue.h" not in text["attention.hip"]
+    for needle in ("#define DINO2_ST16", "#define DINO4_ST16"):
+        assert not [f for f, t in text.items() if needle in t], needle
