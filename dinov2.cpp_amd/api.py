@@ -71,6 +71,16 @@ class Layers(C.Structure):
 LAYERS_TOKENS, LAYERS_CHW = 0, 1
 
 
+class Attention(C.Structure):
+    """dinov2_hip_attention (include/dinov2_hip.h)."""
+    _fields_ = [("layers", C.POINTER(C.c_int32)), ("n_layers", C.c_int32), ("queries", C.POINTER(C.c_int32)), ("n_queries", C.c_int32),
+                ("keys", C.c_int32), ("probs", C.c_void_p), ("on_device", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+ATTN_KEYS_ALL, ATTN_KEYS_PATCHES = 0, 1
+_ATTN_KEYS = {"all": ATTN_KEYS_ALL, "patches": ATTN_KEYS_PATCHES}
+
+
 class GroupOpts(C.Structure):
     _fields_ = [("load", LoadOpts), ("n_devices", C.c_int32), ("devices", C.POINTER(C.c_int32)), ("broadcast", C.c_int32),
                 ("streams_per_device", C.c_int32), ("reserved", C.c_int32 * 7)]
@@ -149,6 +159,26 @@ def op_layer_tap(x, w, b, eps, R, h0, w0, *, norm, chw, want=("patch", "cls", "r
     return out
 
 
+def op_attn_rows(dtype, qkv, B, T, nh, queries, key0=0, nkeys=None, lds_budget=0):
+    """attn_rows_kernel alone (dinov2_hip_op_attn_rows[_ex]): qkv [B*T, 3*64*nh] f32 (q pre-scaled by log2(e)/8) -> [B, nh, nq, nkeys] f32, columns
+    [key0, key0 + nkeys) of the softmax rows of the tokens `queries` over all T keys.  lds_budget > 0: the LDS the scores may take, in bytes
+    (below 4 T: the two-pass form).  Raises on a HIP error or a changed guard band."""
+    H = 64 * nh
+    qkv = np.ascontiguousarray(qkv, np.float32)
+    assert qkv.shape == (B * T, 3 * H), qkv.shape
+    q = np.ascontiguousarray(queries, np.int32)
+    nkeys = T - key0 if nkeys is None else int(nkeys)
+    out = np.zeros((B, nh, len(q), nkeys), np.float32)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    rc = lib().dinov2_hip_op_attn_rows_ex(int(dtype), qkv.ctypes.data_as(fp), B, T, H, nh, q.ctypes.data_as(ip), len(q), int(key0), nkeys,
+                                          out.ctypes.data_as(fp), int(lds_budget))
+    if rc == OP_GUARD_CHANGED:
+        raise AssertionError("attn_rows wrote outside its output (guard band changed)")
+    if rc != 0:
+        raise RuntimeError(f"dinov2_hip_op_attn_rows failed ({rc})")
+    return out
+
+
 def lib():
     """Load libdinov2_hip.so; raise loudly if it is not built (no CPU fallback exists)."""
     global _lib
@@ -188,6 +218,7 @@ def lib():
     L.dinov2_hip_session_stream.restype = vp
     L.dinov2_hip_predict.argtypes = [vp, C.POINTER(Input), C.POINTER(Output), u32, cp, sz]
     L.dinov2_hip_predict_layers.argtypes = [vp, C.POINTER(Input), C.POINTER(Output), C.POINTER(Layers), u32, cp, sz]
+    L.dinov2_hip_predict_attention.argtypes = [vp, C.POINTER(Input), C.POINTER(Output), C.POINTER(Layers), C.POINTER(Attention), u32, cp, sz]
     L.dinov2_hip_default_group_opts.argtypes = [C.POINTER(GroupOpts)]
     L.dinov2_hip_default_group_opts.restype = None
     L.dinov2_hip_group_create.argtypes = [cp, C.POINTER(GroupOpts), C.POINTER(vp), cp, sz]
@@ -228,6 +259,8 @@ def lib():
     L.dinov2_hip_op_attention_ex.argtypes = [i32, fp, fp, i32, i32, i32, i32, i32]
     L.dinov2_hip_op_layernorm.argtypes = [i32, fp, fp, fp, fp, i32, i32, C.c_float]
     L.dinov2_hip_op_layer_tap.argtypes = [fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp]
+    L.dinov2_hip_op_attn_rows.argtypes = [i32, fp, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, i32, fp]
+    L.dinov2_hip_op_attn_rows_ex.argtypes = [i32, fp, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, i32, fp, C.c_int64]
     L.dinov2_hip_op_convert_weight.argtypes = [i32, vp, C.c_uint64, u32, fp, i32, i32, i32, i32]
     L.dinov2_hip_op_permute_bias.argtypes = [fp, fp, i32, i32]
     L.dinov2_hip_op_head.argtypes = [i32, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, C.c_float]
@@ -641,6 +674,66 @@ class Session:
         o = Output(cls_ptr or None, patch_ptr or None, logits_ptr or None, probs_ptr or None, None, None, 0, 1)
         err = _errbuf()
         rc = lib().dinov2_hip_predict_layers(self._h, C.byref(i), C.byref(o), C.byref(ly), CLASSIFY if classify else 0, err, len(err))
+        if rc != 0:
+            raise DinoError(rc, err.value.decode(errors="replace"))
+
+    def _attention_request(self, layers, queries, keys):
+        """(layer ids, their C array, query ids, their C array or None, keys value) of a dinov2_hip_attention."""
+        if keys not in _ATTN_KEYS:
+            raise ValueError(f"keys = {keys!r}: 'all' or 'patches'")
+        ids = [int(layers)] if isinstance(layers, (int, np.integer)) else [int(v) for v in layers]
+        qs = [] if queries is None else [int(v) for v in queries]
+        return ids, (C.c_int32 * max(len(ids), 1))(*ids), qs, ((C.c_int32 * len(qs))(*qs) if qs else None), _ATTN_KEYS[keys]
+
+    def predict_attention(self, images: np.ndarray, layers, queries=None, keys: str = "all", taps=None, *, classify: bool = False,
+                          layout: int = RGB_CHW, topk: int = 0, want=("cls", "patch_tokens", "logits", "probs"), norm: bool = True,
+                          return_outputs: bool = False):
+        """Softmax rows of chosen query tokens from the same forward as predict() (dinov2_hip_predict_attention; upstream DINOv2's
+        get_last_selfattention, HuggingFace's output_attentions).  `layers`: ascending list of k (or one k) = the attention inside block k,
+        1 .. L (HuggingFace attentions[k - 1]).  `queries`: ascending token indices (0 CLS, 1 .. R registers, then patches row-major); None: the
+        CLS row.  keys: "all" (T columns) or "patches" (the P patch columns, the same bits, not re-normalised).  Returns [n, B, heads, Q, T | P]
+        float32.  taps: a list of layer numbers for predict_layers' patch tokens [n_taps, B, P, H] (through the final LayerNorm if `norm`) from
+        the same forward.  With taps or return_outputs the result is (rows, dict): predict's outputs, plus "layers" when taps were asked for."""
+        img = np.ascontiguousarray(images, dtype=np.uint8 if layout == U8_BGR_HWC else np.float32)
+        if img.ndim == 3:
+            img = img[None]
+        B = img.shape[0]
+        hh, ww = (img.shape[2], img.shape[3]) if layout == RGB_CHW else (img.shape[1], img.shape[2])
+        hp = self.model.hparams
+        out, o = _alloc_outputs(hp, B, hh, ww, layout, classify, topk, want)
+        ps, R, Hd = hp.patch_size, hp.num_register_tokens, hp.hidden_size
+        nh, nw = preprocess_size(1 if classify else 0, hh, ww, ps) if layout == U8_BGR_HWC else (hh, ww)
+        P = (nh // ps) * (nw // ps)
+        ids, arr, qs, qarr, kv = self._attention_request(layers, queries, keys)
+        rows = np.empty((len(ids), B, hp.num_attention_heads, max(1, len(qs)), P if kv == ATTN_KEYS_PATCHES else 1 + R + P), np.float32)
+        at = Attention(arr, len(ids), qarr, len(qs), kv, rows.ctypes.data, 0)
+        ly, patch = None, None
+        if taps is not None:
+            tids = self._layer_list(taps)
+            tarr = (C.c_int32 * max(len(tids), 1))(*tids)
+            patch = np.empty((len(tids), B, P, Hd), np.float32)
+            ly = Layers(tarr, len(tids), int(bool(norm)), LAYERS_TOKENS, patch.ctypes.data, None, None, 0)
+        i = Input(img.ctypes.data, B, hh, ww, layout, 0)
+        err = _errbuf()
+        rc = lib().dinov2_hip_predict_attention(self._h, C.byref(i), C.byref(o), C.byref(ly) if ly is not None else None, C.byref(at),
+                                                CLASSIFY if classify else 0, err, len(err))
+        if rc != 0:
+            raise DinoError(rc, err.value.decode(errors="replace"))
+        if ly is not None:
+            out["layers"] = [{"layer": layer, "patch_tokens": patch[k]} for k, layer in enumerate(tids)]
+        return (rows, out) if (ly is not None or return_outputs) else rows
+
+    def predict_attention_device(self, img_ptr: int, B: int, hh: int, ww: int, layers, probs: "DeviceArray", queries=None, keys: str = "all", *,
+                                 classify: bool = False, layout: int = RGB_CHW, logits_ptr: int = 0, probs_ptr: int = 0, cls_ptr: int = 0,
+                                 patch_ptr: int = 0):
+        """Asynchronous predict_attention on device-resident input: attn_rows_kernel writes straight into `probs`, a DeviceArray (or a raw
+        device pointer, 16-byte aligned) of [n, B, heads, Q, T | P] float32, on the session's stream."""
+        ids, arr, qs, qarr, kv = self._attention_request(layers, queries, keys)
+        at = Attention(arr, len(ids), qarr, len(qs), kv, int(getattr(probs, "ptr", probs)) or None, 1)
+        i = Input(img_ptr, B, hh, ww, layout, 1)
+        o = Output(cls_ptr or None, patch_ptr or None, logits_ptr or None, probs_ptr or None, None, None, 0, 1)
+        err = _errbuf()
+        rc = lib().dinov2_hip_predict_attention(self._h, C.byref(i), C.byref(o), None, C.byref(at), CLASSIFY if classify else 0, err, len(err))
         if rc != 0:
             raise DinoError(rc, err.value.decode(errors="replace"))
 

@@ -146,6 +146,14 @@ hipError_t launch_ln_fold_vectors(DType dt, const void* W, const float* bias, co
 // log2_scores: q was scaled by log2(e)/sqrt(hd) instead of 1/sqrt(hd), so softmax uses exp2 directly.
 hipError_t launch_attention(DType dt, const void* qkv, void* out, int B, int T, int H, int nh, bool log2_scores,
                             hipStream_t stream);
+// Attention rows (dinov2_hip_predict_attention; attn_rows.hip): out [B, nh, nq, nkeys] f32 = columns [key0, key0 + nkeys) of the softmax rows of
+// the query tokens queries[0 .. nq) (DEVICE pointer, each in [0, T)), from the same token-major qkv (row stride ld elements, q pre-scaled by
+// log2(e)/sqrt(hd): exp2).  The softmax runs over all T keys whatever the columns; a row's bits depend on T and on its own q and k only.
+hipError_t launch_attn_rows(DType dt, const void* qkv, int ld, float* out, int B, int T, int H, int nh, const int32_t* queries, int nq, int key0,
+                            int nkeys, hipStream_t stream);
+// same with the LDS the scores may take (bytes) given by the caller: below 4 T the two-pass form runs (a testing aid; same bits)
+hipError_t launch_attn_rows_budget(DType dt, const void* qkv, int ld, float* out, int B, int T, int H, int nh, const int32_t* queries, int nq,
+                                   int key0, int nkeys, size_t lds_budget, hipStream_t stream);
 
 // im2col of conv_2d_sk_p0: img f32 (layout 0 = BGR HWC interleaved, 1 = RGB CHW planar) -> col [B*P, Kpad] T,
 // patch vector order (c_rgb, ky, kx), zero padded to Kpad

@@ -652,8 +652,10 @@ int prepare_pos(dinov2_hip_session* s, int B, int h, int w, char* err, size_t er
 
 // `img` is a DEVICE pointer.  Leaves final-LN tokens in s->fin, logits/probs in s->logits/s->probs.
 // `taps` (dinov2_hip_predict_layers): one layer_tap launch per requested layer, on x as it stands after that many layers; nullptr: none.
+// `attn` (dinov2_hip_predict_attention): one attn_rows launch per requested block, on that block's qkv right after its QKV GEMM (the next
+// block overwrites qkv; attention only reads it); nullptr: none.  Without either, the launches are those of a plain forward.
 int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int layout, bool classify, int nlayers,
-            bool finalize, char* err, size_t errlen, const TapRun* taps = nullptr) {
+            bool finalize, char* err, size_t errlen, const TapRun* taps = nullptr, const AttnRun* attn = nullptr) {
     const dinov2_hip_model* m = s->model;
     const int H = (int)m->hp.hidden_size, F = (int)m->hp.ffn_hidden, R = (int)m->hp.num_register_tokens;
     const int nh = (int)m->hp.num_attention_heads, ps = (int)m->hp.patch_size;
@@ -693,6 +695,7 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
                                 taps->reg ? taps->reg + k * taps->reg_stride : nullptr, st);
     };
     HIP_TRY(tap(0));
+    int next_attn = 0;
     // LN fold (dinov2_hip_load_opts.ln_fold; kernels.h EPI_RESID_LN): no LayerNorm launches inside the layers.  `ln` holds T(gamma x) for the
     // NEXT LayerNorm and `stats` the row sums behind it, both written by whoever wrote x last: ln_prepare before layer 0, the residual
     // epilogues afterwards; the QKV / FFN-in epilogues apply mean, rstd and beta.
@@ -708,6 +711,7 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
             Scope sc(s, K_LAYERNORM);
             HIP_TRY(launch_layernorm(dt, s->x, ly.norm1_w, ly.norm1_b, s->ln, d.M, H, eps, st));
         }
+        int ldq = 3 * H;
         {
             Scope sc(s, K_QKV_GEMM);
             GemmArgs a{};
@@ -721,6 +725,13 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
                 a.stats = s->stats; a.ln_gs = gs; a.ln_s = ly.qkv_s; a.ln_c = ly.qkv_c; a.ln_eps = eps;
             }
             HIP_TRY(launch_gemm(dt, fold ? EPI_QKV_LN : EPI_QKV, a, st));
+            ldq = a.ldo;
+        }
+        if (attn && next_attn < attn->n && attn->layers[next_attn] == il + 1) {  // booked as a tap: a tap of the attention
+            const size_t k = (size_t)next_attn++;
+            Scope sc(s, K_LAYER_TAP);
+            HIP_TRY(launch_attn_rows(dt, s->qkv, ldq, attn->probs + k * attn->stride, B, d.T, H, nh, attn->queries, attn->nq, attn->key0,
+                                     attn->nkeys, st));
         }
         {
             Scope sc(s, K_ATTENTION);
@@ -933,6 +944,8 @@ extern "C" void dinov2_hip_session_free(dinov2_hip_session* s) {
     if (s->raw) (void)hipFree(s->raw);
     if (s->pca_buf) (void)hipFree(s->pca_buf);
     if (s->tap_buf) (void)hipFree(s->tap_buf);
+    if (s->attn_buf) (void)hipFree(s->attn_buf);
+    if (s->attn_q) (void)hipFree(s->attn_q);
     if (s->own_stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
@@ -989,9 +1002,10 @@ size_t dinov2_max_pass_batch(const dinov2_hip_model* m, int h, int w) {
 // =============================================================================================================
 // predict
 // =============================================================================================================
-// `taps`: the layer taps of dinov2_hip_predict_layers (device pointers), nullptr for a plain predict
+// `taps`: the layer taps of dinov2_hip_predict_layers, `attn`: the attention rows of dinov2_hip_predict_attention (device pointers); nullptr
+// for a plain predict
 static int predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out, uint32_t flags, const TapRun* taps,
-                        char* err, size_t errlen) {
+                        const AttnRun* attn, char* err, size_t errlen) {
     int rc = check_input(s, in, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
     const dinov2_hip_model* m = s->model;
@@ -1051,7 +1065,12 @@ static int predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dinov
                     if (ct.cls) ct.cls += b0 * H;
                     if (ct.reg) ct.reg += b0 * Rn * H;
                 }
-                rc = predict_impl(s, &ci, out ? &co : nullptr, flags, taps ? &ct : nullptr, err, errlen);
+                AttnRun ca;
+                if (attn) {
+                    ca = *attn;
+                    ca.probs += b0 * (size_t)m->hp.num_attention_heads * (size_t)ca.nq * (size_t)ca.nkeys;
+                }
+                rc = predict_impl(s, &ci, out ? &co : nullptr, flags, taps ? &ct : nullptr, attn ? &ca : nullptr, err, errlen);
                 if (rc != DINOV2_HIP_OK) return rc;
             }
             s->last_b = 0;  // the workspace holds chunk 0 only: nothing for dinov2_hip_fetch
@@ -1088,8 +1107,8 @@ static int predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dinov
     rc = prepare_pos(s, B, h, w, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
     // (a tapped forward runs eagerly, past the graph cache: its key knows nothing of the caller's tap pointers)
-    rc = taps ? forward(s, img, B, h, w, layout, classify, (int)m->hp.num_hidden_layers, true, err, errlen, taps)
-              : forward_maybe_graph(s, img, B, h, w, layout, classify, err, errlen);
+    rc = taps || attn ? forward(s, img, B, h, w, layout, classify, (int)m->hp.num_hidden_layers, true, err, errlen, taps, attn)
+                      : forward_maybe_graph(s, img, B, h, w, layout, classify, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
     {  // what dinov2_hip_pca3(tokens = NULL) works on: the patch rows of image 0 in `fin`
         const Dims dd = dims_of(m, B, h, w);
@@ -1106,17 +1125,14 @@ static int predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dinov
 
 extern "C" int dinov2_hip_predict(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out,
                                   uint32_t flags, char* err, size_t errlen) {
-    return predict_impl(s, in, out, flags, nullptr, err, errlen);
+    return predict_impl(s, in, out, flags, nullptr, nullptr, err, errlen);
 }
 
 // =============================================================================================================
 // predict + intermediate layers (no reference counterpart; upstream DINOv2: get_intermediate_layers, HuggingFace: output_hidden_states)
 // =============================================================================================================
-extern "C" int dinov2_hip_predict_layers(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out,
-                                         const dinov2_hip_layers* ly, uint32_t flags, char* err, size_t errlen) {
-    int rc = check_input(s, in, err, errlen);
-    if (rc != DINOV2_HIP_OK) return rc;
-    const dinov2_hip_model* m = s->model;
+// the argument checks of a dinov2_hip_layers, before anything runs
+static int check_layers(const dinov2_hip_model* m, const dinov2_hip_layers* ly, char* err, size_t errlen) {
     const int L = (int)m->hp.num_hidden_layers, R = (int)m->hp.num_register_tokens;
     if (!ly || !ly->layers) {
         set_err(err, errlen, "null layers / layer list");
@@ -1152,9 +1168,12 @@ extern "C" int dinov2_hip_predict_layers(dinov2_hip_session* s, const dinov2_hip
                 return DINOV2_HIP_ERR_INVALID;
             }
     }
-    // dinov2_hip_predict's own argument checks, here as well: nothing below may run for a call that is refused
-    const bool classify = (flags & DINOV2_HIP_CLASSIFY) != 0;
-    if (classify && !m->hp.has_classifier) {
+    return DINOV2_HIP_OK;
+}
+
+// dinov2_hip_predict's own argument checks, for the calls that allocate or copy before they reach it: nothing may run for a call that is refused
+static int check_predict_args(const dinov2_hip_model* m, const dinov2_hip_output* out, uint32_t flags, char* err, size_t errlen) {
+    if ((flags & DINOV2_HIP_CLASSIFY) != 0 && !m->hp.has_classifier) {
         set_err(err, errlen, "classify requested but the model was loaded without a classifier head");
         return DINOV2_HIP_ERR_NO_HEAD;
     }
@@ -1162,58 +1181,197 @@ extern "C" int dinov2_hip_predict_layers(dinov2_hip_session* s, const dinov2_hip
         set_err(err, errlen, "top-k outputs are host-only");
         return DINOV2_HIP_ERR_INVALID;
     }
-    int h = in->height, w = in->width;
+    return DINOV2_HIP_OK;
+}
+
+// the network input size of `in` (raw 8-bit input: after the preprocessing)
+static void network_size(const dinov2_hip_model* m, const dinov2_hip_input* in, uint32_t flags, int* h, int* w) {
+    *h = in->height;
+    *w = in->width;
     if (in->layout == DINOV2_HIP_U8_BGR_HWC) {
         int32_t oh, ow;
-        dinov2_hip_preprocess_size(classify ? 1 : 0, in->height, in->width, (int32_t)m->hp.patch_size, &oh, &ow);
-        h = oh;
-        w = ow;
+        dinov2_hip_preprocess_size((flags & DINOV2_HIP_CLASSIFY) ? 1 : 0, in->height, in->width, (int32_t)m->hp.patch_size, &oh, &ow);
+        *h = oh;
+        *w = ow;
     }
-    const size_t B = (size_t)in->batch, H = m->hp.hidden_size, P = (size_t)dims_of(m, 1, h, w).P, n = (size_t)ly->n_layers;
-    TapRun t;
-    t.layers = ly->layers;
-    t.n = ly->n_layers;
-    t.norm = ly->norm != 0;
-    t.chw = ly->layout == DINOV2_HIP_LAYERS_CHW;
-    t.patch_stride = B * P * H;
-    t.cls_stride = B * H;
-    t.reg_stride = B * (size_t)R * H;
-    if (ly->on_device) {  // the kernel writes straight into the caller's buffers
-        t.patch = ly->patch_tokens;
-        t.cls = ly->cls;
-        t.reg = ly->registers;
-        return predict_impl(s, in, out, flags, &t, err, errlen);
-    }
-    // host outputs: the kernel writes into the session's tap buffer (its own allocation, like pca_buf), which leaves by asynchronous copies
-    const size_t np = ly->patch_tokens ? n * t.patch_stride : 0, nc = ly->cls ? n * t.cls_stride : 0,
-                 nr = ly->registers ? n * t.reg_stride : 0;
-    const size_t need = sizeof(float) * (np + nc + nr);
+}
+
+// a session-owned device buffer, grown on demand (after a wait: the stream may still be using the old one)
+static int grow(dinov2_hip_session* s, float** buf, size_t* have, size_t need, char* err, size_t errlen) {
+    if (need <= *have) return DINOV2_HIP_OK;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (*buf) HIP_TRY(hipFree(*buf));
+    *buf = nullptr;
+    *have = 0;
+    HIP_TRY(hipMalloc((void**)buf, need));
+    *have = need;
+    return DINOV2_HIP_OK;
+}
+
+// One forward with layer taps (`ly`) and / or attention rows (`at`), either of which may be nullptr; every argument has been checked.
+static int predict_tapped(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out, const dinov2_hip_layers* ly,
+                          const dinov2_hip_attention* at, uint32_t flags, char* err, size_t errlen) {
+    const dinov2_hip_model* m = s->model;
+    const int R = (int)m->hp.num_register_tokens;
+    int h, w;
+    network_size(m, in, flags, &h, &w);
+    const Dims d1 = dims_of(m, 1, h, w);
+    const size_t B = (size_t)in->batch, H = m->hp.hidden_size, P = (size_t)d1.P, nh = m->hp.num_attention_heads;
     HIP_TRY(hipSetDevice(m->device));
-    if (need > s->tap_bytes) {
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        if (s->tap_buf) HIP_TRY(hipFree(s->tap_buf));
-        s->tap_buf = nullptr;
-        s->tap_bytes = 0;
-        HIP_TRY(hipMalloc((void**)&s->tap_buf, need));
-        s->tap_bytes = need;
+    TapRun t;
+    size_t np = 0, nc = 0, nr = 0;
+    if (ly) {
+        const size_t n = (size_t)ly->n_layers;
+        t.layers = ly->layers;
+        t.n = ly->n_layers;
+        t.norm = ly->norm != 0;
+        t.chw = ly->layout == DINOV2_HIP_LAYERS_CHW;
+        t.patch_stride = B * P * H;
+        t.cls_stride = B * H;
+        t.reg_stride = B * (size_t)R * H;
+        if (ly->on_device) {  // the kernel writes straight into the caller's buffers
+            t.patch = ly->patch_tokens;
+            t.cls = ly->cls;
+            t.reg = ly->registers;
+        } else {  // host outputs: the kernel writes into the session's tap buffer (its own allocation, like pca_buf), which leaves by asynchronous copies
+            np = ly->patch_tokens ? n * t.patch_stride : 0;
+            nc = ly->cls ? n * t.cls_stride : 0;
+            nr = ly->registers ? n * t.reg_stride : 0;
+            const int rc = grow(s, &s->tap_buf, &s->tap_bytes, sizeof(float) * (np + nc + nr), err, errlen);
+            if (rc != DINOV2_HIP_OK) return rc;
+            if (np) t.patch = s->tap_buf;  // (every block is a multiple of H floats, H % 4 == 0: all three stay 16-byte aligned)
+            if (nc) t.cls = s->tap_buf + np;
+            if (nr) t.reg = s->tap_buf + np + nc;
+        }
     }
-    if (np) t.patch = s->tap_buf;  // (every block is a multiple of H floats, H % 4 == 0: all three stay 16-byte aligned)
-    if (nc) t.cls = s->tap_buf + np;
-    if (nr) t.reg = s->tap_buf + np + nc;
-    // One synchronise for the whole call: the forward alone first, then the taps' copies, then `out`'s copies (fetch_outputs, which waits
+    AttnRun a;
+    size_t na = 0;
+    if (at) {
+        static const int32_t cls_only[1] = {0};
+        const int32_t* q = at->n_queries ? at->queries : cls_only;
+        const size_t nq = at->n_queries ? (size_t)at->n_queries : 1;
+        a.layers = at->layers;
+        a.n = at->n_layers;
+        a.nq = (int)nq;
+        a.key0 = at->keys == DINOV2_HIP_ATTN_KEYS_PATCHES ? 1 + R : 0;
+        a.nkeys = d1.T - a.key0;
+        a.stride = B * nh * nq * (size_t)a.nkeys;
+        // the query list on the device: kept from call to call, replaced (after a wait: a forward in flight may be reading it) when it changes
+        if (s->attn_q_host.size() != nq || !std::equal(q, q + nq, s->attn_q_host.begin())) {
+            HIP_TRY(hipStreamSynchronize(s->stream));
+            s->attn_q_host.clear();
+            if (nq > s->attn_q_cap) {
+                if (s->attn_q) HIP_TRY(hipFree(s->attn_q));
+                s->attn_q = nullptr;
+                s->attn_q_cap = 0;
+                HIP_TRY(hipMalloc((void**)&s->attn_q, sizeof(int32_t) * nq));
+                s->attn_q_cap = nq;
+            }
+            HIP_TRY(hipMemcpy(s->attn_q, q, sizeof(int32_t) * nq, hipMemcpyHostToDevice));
+            s->attn_q_host.assign(q, q + nq);
+        }
+        a.queries = s->attn_q;
+        if (at->on_device) {
+            a.probs = at->probs;
+        } else {
+            na = (size_t)at->n_layers * a.stride;
+            const int rc = grow(s, &s->attn_buf, &s->attn_bytes, sizeof(float) * na, err, errlen);
+            if (rc != DINOV2_HIP_OK) return rc;
+            a.probs = s->attn_buf;
+        }
+    }
+    const TapRun* tp = ly ? &t : nullptr;
+    const AttnRun* ap = at ? &a : nullptr;
+    if (np + nc + nr + na == 0) return predict_impl(s, in, out, flags, tp, ap, err, errlen);  // nothing staged: asynchronous, as predict
+    // One synchronise for the whole call: the forward alone first, then the staged copies, then `out`'s copies (fetch_outputs, which waits
     // when `out` is host memory).  A batch that is split into passes hands `out` to the passes instead, which wait once each.
     const bool split = B > dinov2_max_pass_batch(m, h, w);
-    rc = predict_impl(s, in, split ? out : nullptr, flags, &t, err, errlen);
+    int rc = predict_impl(s, in, split ? out : nullptr, flags, tp, ap, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
     if (np) HIP_TRY(hipMemcpyAsync(ly->patch_tokens, t.patch, sizeof(float) * np, hipMemcpyDeviceToHost, s->stream));
     if (nc) HIP_TRY(hipMemcpyAsync(ly->cls, t.cls, sizeof(float) * nc, hipMemcpyDeviceToHost, s->stream));
     if (nr) HIP_TRY(hipMemcpyAsync(ly->registers, t.reg, sizeof(float) * nr, hipMemcpyDeviceToHost, s->stream));
+    if (na) HIP_TRY(hipMemcpyAsync(at->probs, a.probs, sizeof(float) * na, hipMemcpyDeviceToHost, s->stream));
     if (out && !split) {
         rc = fetch_outputs(s, out, err, errlen);
         if (rc != DINOV2_HIP_OK || !out->on_device) return rc;  // (host `out`: fetch_outputs has waited for the stream)
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
     return DINOV2_HIP_OK;
+}
+
+extern "C" int dinov2_hip_predict_layers(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out,
+                                         const dinov2_hip_layers* ly, uint32_t flags, char* err, size_t errlen) {
+    int rc = check_input(s, in, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    rc = check_layers(s->model, ly, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    rc = check_predict_args(s->model, out, flags, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    return predict_tapped(s, in, out, ly, nullptr, flags, err, errlen);
+}
+
+// =============================================================================================================
+// predict + attention rows (no reference counterpart; upstream DINOv2: get_last_selfattention, HuggingFace: output_attentions)
+// =============================================================================================================
+extern "C" int dinov2_hip_predict_attention(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out,
+                                            const dinov2_hip_layers* taps, const dinov2_hip_attention* at, uint32_t flags, char* err,
+                                            size_t errlen) {
+    int rc = check_input(s, in, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    const dinov2_hip_model* m = s->model;
+    const int L = (int)m->hp.num_hidden_layers;
+    if (!at || !at->layers || !at->probs) {
+        set_err(err, errlen, "null attention request / layer list / probs");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (at->n_layers < 1 || at->n_layers > L) {
+        set_err(err, errlen, "attention n_layers %d outside 1 .. %d", (int)at->n_layers, L);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    for (int i = 0; i < at->n_layers; ++i) {
+        if (at->layers[i] < 1 || at->layers[i] > L) {
+            set_err(err, errlen, "attention layer %d outside 1 .. %d (k = the attention inside block k; there is none before block 1)",
+                    (int)at->layers[i], L);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+        if (i > 0 && at->layers[i] <= at->layers[i - 1]) {
+            set_err(err, errlen, "the attention layer list must be strictly ascending");
+            return DINOV2_HIP_ERR_INVALID;
+        }
+    }
+    if (at->keys != DINOV2_HIP_ATTN_KEYS_ALL && at->keys != DINOV2_HIP_ATTN_KEYS_PATCHES) {
+        set_err(err, errlen, "unknown attention keys value %d", (int)at->keys);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    int h, w;
+    network_size(m, in, flags, &h, &w);
+    const int T = dims_of(m, 1, h, w).T;
+    if (at->n_queries < 0 || at->n_queries > T || (at->n_queries > 0 && !at->queries)) {
+        set_err(err, errlen, "n_queries %d outside 0 .. %d, or a null query list", (int)at->n_queries, T);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    for (int i = 0; i < at->n_queries; ++i) {
+        if (at->queries[i] < 0 || at->queries[i] >= T) {
+            set_err(err, errlen, "query token %d outside 0 .. %d for this input", (int)at->queries[i], T - 1);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+        if (i > 0 && at->queries[i] <= at->queries[i - 1]) {
+            set_err(err, errlen, "the query list must be strictly ascending");
+            return DINOV2_HIP_ERR_INVALID;
+        }
+    }
+    if (at->on_device && (reinterpret_cast<uintptr_t>(at->probs) & 15)) {
+        set_err(err, errlen, "the device pointer of dinov2_hip_attention must be 16-byte aligned");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (taps) {
+        rc = check_layers(m, taps, err, errlen);
+        if (rc != DINOV2_HIP_OK) return rc;
+    }
+    rc = check_predict_args(m, out, flags, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    return predict_tapped(s, in, out, taps, at, flags, err, errlen);
 }
 
 extern "C" int dinov2_hip_fetch(dinov2_hip_session* s, dinov2_hip_output* out, char* err, size_t errlen) {

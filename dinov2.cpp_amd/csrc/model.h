@@ -30,6 +30,17 @@ struct TapRun {
     size_t patch_stride = 0, cls_stride = 0, reg_stride = 0;
 };
 
+// The attention rows of ONE pass of dinov2_hip_predict_attention: a device pointer to where image 0 of this pass goes in the first requested
+// layer's block [B, heads, nq, nkeys], and the distance (in floats) from one requested layer's block to the next -- the caller's WHOLE batch.
+struct AttnRun {
+    const int32_t* layers = nullptr;   // [n] strictly ascending, each in [1, L]: the attention inside block layers[i]
+    int n = 0;
+    const int32_t* queries = nullptr;  // DEVICE [nq]
+    int nq = 0, key0 = 0, nkeys = 0;
+    float* probs = nullptr;
+    size_t stride = 0;
+};
+
 }  // namespace dinov2
 
 // replaces `struct dino_model` (/root/reference/dinov2.h:49-55): hparams + one device buffer + name->tensor map
@@ -69,6 +80,11 @@ struct dinov2_hip_session {
     size_t pca_bytes = 0;
     float* tap_buf = nullptr;  // dinov2_hip_predict_layers with host outputs: where the tap kernel writes before the copy-out; grown on demand
     size_t tap_bytes = 0;
+    float* attn_buf = nullptr;  // dinov2_hip_predict_attention with a host output: where attn_rows_kernel writes before the copy-out; grown on demand
+    size_t attn_bytes = 0;
+    int32_t* attn_q = nullptr;  // the query list of the last dinov2_hip_predict_attention on the device, and what it holds
+    std::vector<int32_t> attn_q_host;
+    size_t attn_q_cap = 0;
     int last_b = 0, last_h = 0, last_w = 0;  // shape of the last un-split forward (0: none): what dinov2_hip_fetch copies out
     bool last_classify = false;
     int last_first = 0, last_patches = 0;  // rows [last_first, last_first + last_patches) of image 0 in `fin`: its patch tokens

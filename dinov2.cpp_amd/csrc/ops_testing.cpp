@@ -317,6 +317,41 @@ extern "C" int dinov2_hip_op_layer_tap(const float* x, const float* w, const flo
     return 0;
 }
 
+extern "C" int dinov2_hip_op_attn_rows_ex(int32_t dtype, const float* qkv, int32_t B, int32_t T, int32_t H, int32_t nh, const int32_t* queries,
+                                          int32_t nq, int32_t key0, int32_t nkeys, float* out, int64_t lds_budget) {
+    const DType dt = dtype == 1 ? DT_BF16 : DT_F16;
+    if (!qkv || !queries || !out || B <= 0 || T <= 0 || nh <= 0 || H != nh * 64 || nq < 1 || nq > T || key0 < 0 || nkeys < 1 || key0 > T - nkeys)
+        return -1;
+    for (int i = 0; i < nq; ++i)
+        if (queries[i] < 0 || queries[i] >= T || (i > 0 && queries[i] <= queries[i - 1])) return -1;
+    // the output between two guard bands, the whole buffer 0xff bytes (NaN): an element the kernel never wrote comes back as NaN and a write
+    // outside the output changes a guard
+    const size_t no = (size_t)B * nh * nq * nkeys, ng = (size_t)DINOV2_HIP_OP_GUARD_ROWS * nkeys;
+    DevBuf dQ, dI, dO;
+    OP_TRY(upload_as(dt, qkv, (size_t)B * T * 3 * H, dQ));
+    OP_TRY(dI.alloc(sizeof(int32_t) * (size_t)nq));
+    OP_TRY(hipMemcpy(dI.p, queries, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice));
+    OP_TRY(dO.alloc((no + 2 * ng) * 4));
+    OP_TRY(hipMemset(dO.p, 0xff, (no + 2 * ng) * 4));
+    float* dev = (float*)dO.p + ng;
+    if (lds_budget > 0)
+        OP_TRY(launch_attn_rows_budget(dt, dQ.p, 3 * H, dev, B, T, H, nh, (const int32_t*)dI.p, nq, key0, nkeys, (size_t)lds_budget, nullptr));
+    else
+        OP_TRY(launch_attn_rows(dt, dQ.p, 3 * H, dev, B, T, H, nh, (const int32_t*)dI.p, nq, key0, nkeys, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    std::vector<uint32_t> raw(no + 2 * ng);
+    OP_TRY(hipMemcpy(raw.data(), dO.p, raw.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < ng; ++k)
+        if (raw[k] != 0xffffffffu || raw[ng + no + k] != 0xffffffffu) return DINOV2_HIP_OP_GUARD_CHANGED;
+    std::memcpy(out, raw.data() + ng, no * 4);
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_attn_rows(int32_t dtype, const float* qkv, int32_t B, int32_t T, int32_t H, int32_t nh, const int32_t* queries,
+                                       int32_t nq, int32_t key0, int32_t nkeys, float* out) {
+    return dinov2_hip_op_attn_rows_ex(dtype, qkv, B, T, H, nh, queries, nq, key0, nkeys, out, 0);
+}
+
 extern "C" int dinov2_hip_op_convert_weight(int32_t dtype, const void* src, uint64_t src_bytes, uint32_t ggml_type,
                                             float* out, int32_t N, int32_t K, int32_t Kpad, int32_t interleaveF) {
     const DType dt = dtype == 1 ? DT_BF16 : DT_F16;

@@ -272,6 +272,57 @@ inline std::vector<dino_layer_output> dino_get_intermediate_layers(const dino_mo
     return out;
 }
 
+// No reference counterpart: upstream DINOv2's get_last_selfattention / HuggingFace's output_attentions on the shim's types, through
+// dinov2_hip_predict_attention -- one forward, one extra kernel launch per layer.  `layers`: strictly ascending, k = the attention INSIDE
+// block k, 1 .. num_hidden_layers (HuggingFace attentions[k - 1]).  `queries`: strictly ascending token indices (0 CLS, 1 .. R registers, then
+// the patches row-major); empty = the CLS row.  patches_only: the h0 * w0 patch columns instead of all T (the same bits, not re-normalised).
+// The rows are the f32 softmax of the stored q and k, not the rounded, un-normalised P inside the attention kernel (dinov2_hip.h).
+struct dino_attention_output {
+    int layer = 0;
+    int heads = 0, queries = 0, keys = 0;  // probs is [heads][queries][keys]
+    int grid_h = 0, grid_w = 0;            // h0, w0: with patches_only a row reshapes to the grid
+    std::vector<float> probs;
+    const float* row(int head, int query) const { return probs.data() + ((size_t)head * queries + query) * keys; }
+};
+inline std::vector<dino_attention_output> dino_get_attention(const dino_model& model, const Mat32f& img, const std::vector<int>& layers,
+                                                             const std::vector<int>& queries = {}, bool patches_only = false,
+                                                             dinov2_hip_session* allocr = nullptr) {
+    dinov2_hip_session* s = allocr ? allocr : model.default_session;
+    if (!s || !img.data || img.channels != 3 || !img.isContinuous()) {
+        fprintf(stderr, "%s: need a continuous 3-channel float image\n", __func__);
+        return {};
+    }
+    const int ps = (int)model.hparams.patch_size, nh = (int)model.hparams.num_attention_heads, R = (int)model.hparams.num_register_tokens;
+    const int h0 = img.rows / ps, w0 = img.cols / ps, P = h0 * w0, keys = patches_only ? P : 1 + R + P;
+    const size_t n = layers.size(), Q = queries.empty() ? 1 : queries.size(), per = (size_t)nh * Q * keys;
+    std::vector<int32_t> ids(layers.begin(), layers.end()), qs(queries.begin(), queries.end());
+    std::vector<float> probs(n * per);
+    dinov2_hip_input in{img.data, 1, img.rows, img.cols, DINOV2_HIP_BGR_HWC, 0};
+    dinov2_hip_attention at{};
+    at.layers = ids.data();
+    at.n_layers = (int32_t)n;
+    at.queries = qs.empty() ? nullptr : qs.data();
+    at.n_queries = (int32_t)qs.size();
+    at.keys = patches_only ? DINOV2_HIP_ATTN_KEYS_PATCHES : DINOV2_HIP_ATTN_KEYS_ALL;
+    at.probs = probs.data();
+    char err[512] = {0};
+    if (dinov2_hip_predict_attention(s, &in, nullptr, nullptr, &at, 0, err, sizeof err) != DINOV2_HIP_OK) {
+        fprintf(stderr, "%s: %s\n", __func__, err);
+        return {};
+    }
+    std::vector<dino_attention_output> out(n);
+    for (size_t k = 0; k < n; ++k) {
+        out[k].layer = layers[k];
+        out[k].heads = nh;
+        out[k].queries = (int)Q;
+        out[k].keys = keys;
+        out[k].grid_h = h0;
+        out[k].grid_w = w0;
+        out[k].probs.assign(probs.begin() + (long)(k * per), probs.begin() + (long)((k + 1) * per));
+    }
+    return out;
+}
+
 // 8-bit BGR interleaved image view, as cv::imread returns it (CV_8UC3, continuous)
 struct Mat8u {
     int rows = 0, cols = 0;

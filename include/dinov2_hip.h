@@ -177,6 +177,53 @@ typedef struct dinov2_hip_layers {
 int dinov2_hip_predict_layers(dinov2_hip_session *session, const dinov2_hip_input *in, dinov2_hip_output *out,
                               const dinov2_hip_layers *layers, uint32_t flags, char *err, size_t errlen);
 
+/* -- predict + attention rows (no reference counterpart: the CLS-to-patch maps of the last block are the model's signature visualisation,
+ *    register papers plot what registers and patches give each other, token-pruning code reads CLS rows of several blocks; upstream DINOv2:
+ *    get_last_selfattention, HuggingFace: output_attentions).  ONE ordinary forward -- the attention kernels of the forward are the same and
+ *    keep their probabilities in registers; each requested block costs one more kernel launch (attn_rows_kernel, csrc/attn_rows.hip) right
+ *    after that block's QKV GEMM, which reads the q of the chosen query tokens and every k from the qkv buffer and writes
+ *        probs[l][b][head][i][j] = exp2(s_ij - m_i) / sum_{j' < T} exp2(s_ij'  - m_i),   s_ij = q[queries[i]] . k[j],  m_i = max_j s_ij
+ *    (q carries 0.125 log2(e): this is softmax(q k^T / 8)).  Index convention -- `layers[i]` = k is the attention INSIDE block k, the numbering
+ *    of dinov2_hip_predict_layers (number of blocks applied):
+ *        this library        HuggingFace              upstream DINOv2
+ *        k, 1 <= k <= L      attentions[k - 1]        blocks[k - 1].attn;  k = L: get_last_selfattention
+ *    (there is no layer 0: no attention runs before block 1).  Token indices: 0 CLS, 1 .. R registers, 1 + R + y*w0 + x patches.
+ *    Contract: the stored f16 / bf16 q and k are the operands (their products are exact in f32); scores, maximum, exponentials, sum,
+ *    reciprocal and product are f32, in summation orders that depend on nothing but T -- so a row is bit-identical whether it is asked for
+ *    alone or with every other token, in a batch of 1 or of 32, whole or split into passes, and whichever columns are kept.  These are NOT
+ *    the bits of the P the flash-style attention kernel feeds its PV product (un-normalised, rounded to the compute type, under a deferred
+ *    maximum): they are the f32 softmax of the same stored q and k.
+ *    Cost: per requested block one read of that block's K (B T H 2 bytes) per 8 queries or part thereof, e.g. the CLS rows of
+ *    all 24 blocks of ViT-L at 518 px; a full T x T map is T / 8 such reads (profiles/attention_rows.md).  In dinov2_hip_session_profile the
+ *    launches are booked under "layer_tap" (a tap of the attention): that kind reads taps + attention layers.
+ *    Out of scope: the device group (dinov2_hip_group_*) has no such call. */
+enum dinov2_hip_attention_keys { DINOV2_HIP_ATTN_KEYS_ALL = 0, DINOV2_HIP_ATTN_KEYS_PATCHES = 1 };
+
+typedef struct dinov2_hip_attention {
+    const int32_t *layers;  /* [n_layers] strictly ascending, each in [1, L]: the attention INSIDE block k -- the index convention
+                               of dinov2_hip_predict_layers (number of blocks applied), HuggingFace attentions[k - 1],
+                               upstream blocks[k - 1]; L = get_last_selfattention */
+    int32_t n_layers;       /* 1 .. L */
+    const int32_t *queries; /* [n_queries] token indices, strictly ascending, in [0, T): 0 CLS, 1 .. R registers, 1 + R + y*w0 + x patches.
+                               NULL with n_queries == 0: the CLS row alone */
+    int32_t n_queries;      /* 0 (CLS) or 1 .. T */
+    int32_t keys;           /* ALL: rows of T columns; PATCHES: the P = h0*w0 patch columns only (same bits, not re-normalised) */
+    float *probs;           /* [n_layers, B, heads, Q, T or P], Q = max(1, n_queries) */
+    int32_t on_device;      /* as in dinov2_hip_layers: 0 host (staged through a session-owned device buffer, one stream wait),
+                               1 device pointer, 16-byte aligned, written by the kernel itself, asynchronously on the session's stream */
+    int32_t reserved[4];
+} dinov2_hip_attention;
+
+/* `out` (may be NULL) and `flags` as for dinov2_hip_predict; `taps` (may be NULL) as for dinov2_hip_predict_layers: one call returns logits,
+ * layer taps and attention rows of the same forward.  Argument errors (NULL `attn`, layer list or probs; n_layers or a layer out of range,
+ * layer 0 among them; a layer or query list not strictly ascending; a query >= T for this input's shape; an unknown `keys`; a device pointer
+ * that is not 16-byte aligned; those of `taps` and of dinov2_hip_predict) return their status before anything is launched, allocated or
+ * copied.  Split batches, dinov2_hip_fetch, dinov2_hip_pca3(tokens = NULL) and DINOV2_HIP_GRAPHS=1 as for dinov2_hip_predict_layers.  The
+ * query list is kept on the device from call to call; a call with another list waits for the session's stream first. */
+int dinov2_hip_predict_attention(dinov2_hip_session *session, const dinov2_hip_input *in, dinov2_hip_output *out,
+                                 const dinov2_hip_layers *taps /* may be NULL */, const dinov2_hip_attention *attn,
+                                 uint32_t flags, char *err, size_t errlen);
+
 /* Copy-out half of dinov2_hip_predict on its own: the outputs of the session's LAST predict (which may have been called with
  * out = NULL, i.e. forward only) into the caller's buffers.  Lets a host overlap the device -> host copy of batch k with the
  * forward of batch k + 1 on another session (this is what the group's lanes do).  Not available after a predict that had to
@@ -270,7 +317,8 @@ int dinov2_hip_interpolate_pos_embed(const dinov2_hip_model *model, int32_t h_ne
 /* -- measurement hooks (no reference counterpart; the reference times the whole call, inference.cpp:64-68) */
 /* Per-kernel-kind HIP-event timing of subsequent predicts on this session (adds two events per launch). */
 int dinov2_hip_session_profile(dinov2_hip_session *session, int32_t enable);
-/* Accumulated since enable: for kind k in [0, n): name, total ms, launches.  Returns n (<= max). */
+/* Accumulated since enable: for kind k in [0, n): name, total ms, launches.  Returns n (<= max).  The kind "layer_tap" holds the launches of
+ * dinov2_hip_predict_layers (one per layer) AND those of dinov2_hip_predict_attention (one per attention layer: a tap of the attention). */
 int dinov2_hip_session_profile_read(dinov2_hip_session *session, int32_t max, const char **names, float *total_ms,
                                     int32_t *launches);
 /* Debug/parity: copy the f32 token stream [B, T, H] as it stands after `layer` layers (0 = embeddings) of the

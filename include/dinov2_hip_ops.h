@@ -64,6 +64,17 @@ int dinov2_hip_op_layernorm(int32_t dtype, const float *x, const float *w, const
 int dinov2_hip_op_layer_tap(const float *x, const float *w, const float *b, float eps, int32_t B, int32_t T, int32_t R, int32_t H, int32_t h0,
                             int32_t w0, int32_t norm, int32_t layout, float *patch_out, float *cls_out, float *reg_out);
 
+/* attn_rows_kernel alone (the kernel behind dinov2_hip_predict_attention, csrc/attn_rows.hip): qkv [B*T, 3H] host f32, rounded to the compute
+ * type on the way in (q already scaled by log2(e)/8, as the forward's QKV epilogue leaves it); queries [nq] host, strictly ascending token
+ * indices in [0, T) -> out [B, nh, nq, nkeys] f32 = columns [key0, key0 + nkeys) of the softmax rows over ALL T keys.  The device output is
+ * framed by guard bands of DINOV2_HIP_OP_GUARD_ROWS * nkeys floats and starts as NaN; a changed guard returns DINOV2_HIP_OP_GUARD_CHANGED.
+ * _ex: lds_budget = the bytes of LDS the scores may take; 0 = the library's own (what the forward uses).  Below 4 T bytes the two-pass form of
+ * the kernel runs, which keeps no scores -- the path of sequences too long for the LDS, reachable at test sizes this way.  Same bits. */
+int dinov2_hip_op_attn_rows(int32_t dtype, const float *qkv, int32_t B, int32_t T, int32_t H, int32_t nh, const int32_t *queries, int32_t nq,
+                            int32_t key0, int32_t nkeys, float *out);
+int dinov2_hip_op_attn_rows_ex(int32_t dtype, const float *qkv, int32_t B, int32_t T, int32_t H, int32_t nh, const int32_t *queries, int32_t nq,
+                               int32_t key0, int32_t nkeys, float *out, int64_t lds_budget);
+
 /* load-time tensor conversion / dequantisation (F32,F16,BF16,Q4_0,Q4_1,Q5_0,Q5_1,Q8_0 -> compute dtype).  interleaveF > 0: N = 2F rows
  * of a SwiGLU weights_in [x1 (F rows); x2 (F rows)] come out as alternating 32-row blocks x1 | x2 (csrc/model.cpp).  The output
  * starts as NaN (as do those of the layernorm, preprocess_u8, permute_bias and head entry points). */
