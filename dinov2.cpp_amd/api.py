@@ -77,6 +77,13 @@ class Attention(C.Structure):
                 ("keys", C.c_int32), ("probs", C.c_void_p), ("on_device", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class Match(C.Structure):
+    """dinov2_hip_match (include/dinov2_hip.h)."""
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("na", C.c_int32), ("nb", C.c_int32), ("H", C.c_int32), ("image_a", C.c_int32),
+                ("image_b", C.c_int32), ("on_device", C.c_int32), ("idx_ab", C.c_void_p), ("sim_ab", C.c_void_p), ("idx_ba", C.c_void_p),
+                ("sim_ba", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
 ATTN_KEYS_ALL, ATTN_KEYS_PATCHES = 0, 1
 _ATTN_KEYS = {"all": ATTN_KEYS_ALL, "patches": ATTN_KEYS_PATCHES}
 
@@ -179,6 +186,22 @@ def op_attn_rows(dtype, qkv, B, T, nh, queries, key0=0, nkeys=None, lds_budget=0
     return out
 
 
+def op_match(a, b):
+    """The kernels of csrc/match.hip alone (dinov2_hip_op_match): a [na, H], b [nb, H] f32 -> dict of idx_ab, sim_ab [na], idx_ba, sim_ba [nb].
+    No model, no session."""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    assert a.ndim == 2 and b.ndim == 2 and a.shape[1] == b.shape[1], (a.shape, b.shape)
+    na, nb = a.shape[0], b.shape[0]
+    out = {"idx_ab": np.full(na, -1, np.int32), "sim_ab": np.full(na, np.nan, np.float32),
+           "idx_ba": np.full(nb, -1, np.int32), "sim_ba": np.full(nb, np.nan, np.float32)}
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    rc = lib().dinov2_hip_op_match(a.ctypes.data_as(fp), na, b.ctypes.data_as(fp), nb, a.shape[1], out["idx_ab"].ctypes.data_as(ip),
+                                   out["sim_ab"].ctypes.data_as(fp), out["idx_ba"].ctypes.data_as(ip), out["sim_ba"].ctypes.data_as(fp))
+    if rc != 0:
+        raise RuntimeError(f"dinov2_hip_op_match failed ({rc})")
+    return out
+
+
 def lib():
     """Load libdinov2_hip.so; raise loudly if it is not built (no CPU fallback exists)."""
     global _lib
@@ -245,6 +268,7 @@ def lib():
     L.dinov2_hip_session_profile_read.argtypes = [vp, i32, C.POINTER(cp), C.POINTER(C.c_float), C.POINTER(i32)]
     L.dinov2_hip_debug_hidden.argtypes = [vp, C.POINTER(Input), i32, vp, cp, sz]
     L.dinov2_hip_pca3.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, cp, sz]
+    L.dinov2_hip_match_tokens.argtypes = [vp, C.POINTER(Match), cp, sz]
     # diagnostic ops (include/dinov2_hip_ops.h)
     fp = C.POINTER(C.c_float)
     L.dinov2_hip_op_gemm.argtypes = [i32, i32, fp, fp, fp, fp, C.c_int64, fp, i32, i32, i32, i32, i32, i32, i32, i32, i32,
@@ -265,6 +289,7 @@ def lib():
     L.dinov2_hip_op_permute_bias.argtypes = [fp, fp, i32, i32]
     L.dinov2_hip_op_head.argtypes = [i32, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, C.c_float]
     L.dinov2_hip_op_pca_ritz.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.dinov2_hip_op_match.argtypes = [fp, i32, fp, i32, i32, C.POINTER(i32), fp, C.POINTER(i32), fp]
     L.dinov2_hip_op_clock_probe.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.dinov2_hip_op_clock_slots.argtypes = [C.POINTER(C.c_uint64)]
     L.dinov2_hip_op_probe_tr16.argtypes = [C.POINTER(C.c_int16)]
@@ -772,6 +797,42 @@ class Session:
         if rc != 0:
             raise DinoError(rc, err.value.decode(errors="replace"))
         return comp, mean, proj
+
+    def match(self, a=None, b=None, *, image_a: int = 0, image_b: int = 1, shape: tuple[int, int] | None = None):
+        """Nearest rows by cosine similarity in both directions (dinov2_hip_match_tokens): for every row of a [na, H] the most similar row of
+        b [nb, H] and the reverse, from one pass over the similarity matrix on the device (never written, never moved).  A side left None is
+        the patch tokens of image `image_a` / `image_b` of the session's last un-split predict, which stay on the device; `shape` = their
+        (P, H), needed only when both sides are None.  The sides that are given are both numpy arrays or both DeviceArrays.
+        Returns a dict: idx_ab, sim_ab [na], idx_ba, sim_ba [nb] and mutual [na] bool = (idx_ba[idx_ab[i]] == i)."""
+        given = [x for x in (a, b) if x is not None]
+        dev = [isinstance(x, DeviceArray) for x in given]
+        if any(dev) and not all(dev):
+            raise ValueError("match: a and b must both be host arrays or both DeviceArrays")
+        on_device = bool(dev) and all(dev)
+        if not on_device:
+            given = [np.ascontiguousarray(x, dtype=np.float32) for x in given]
+        if any(len(x.shape) != 2 for x in given):
+            raise ValueError("match: a and b must be [n, H]")
+        if not given and shape is None:
+            raise ValueError("match: with both sides resident, give shape = (P, H) of the last predict's patch tokens")
+        res = tuple(int(v) for v in shape) if shape is not None else (int(given[0].shape[0]), int(given[0].shape[1]))
+        it = iter(given)
+        xa = next(it) if a is not None else None
+        xb = next(it) if b is not None else None
+        (na, Ha), (nb, Hb) = (res if x is None else (int(x.shape[0]), int(x.shape[1])) for x in (xa, xb))
+        if Ha != Hb:
+            raise ValueError(f"match: a has H = {Ha}, b has H = {Hb}")
+        ptr = (lambda x: None if x is None else int(x.ptr)) if on_device else (lambda x: None if x is None else x.ctypes.data)
+        out = {"idx_ab": np.empty(na, np.int32), "sim_ab": np.empty(na, np.float32), "idx_ba": np.empty(nb, np.int32),
+               "sim_ba": np.empty(nb, np.float32)}
+        m = Match(ptr(xa), ptr(xb), na, nb, Ha, int(image_a), int(image_b), int(on_device), out["idx_ab"].ctypes.data, out["sim_ab"].ctypes.data,
+                  out["idx_ba"].ctypes.data, out["sim_ba"].ctypes.data)
+        err = _errbuf()
+        rc = lib().dinov2_hip_match_tokens(self._h, C.byref(m), err, len(err))
+        if rc != 0:
+            raise DinoError(rc, err.value.decode(errors="replace"))
+        out["mutual"] = out["idx_ba"][out["idx_ab"]] == np.arange(na, dtype=np.int32)
+        return out
 
     def sync(self):
         lib().dinov2_hip_session_sync(self._h)

@@ -227,6 +227,46 @@ hipError_t launch_pca_power(const float* cov, const double* yprev, const double*
 hipError_t launch_pca_project(const float* tok, const float* mean, const float* comp, float* proj, int P, int H,
                               hipStream_t stream);
 
+// Nearest rows by cosine similarity, both directions from one pass (csrc/match.hip; contract in include/dinov2_hip.h, dinov2_hip_match).
+// Tile of match_kernel, and the tiles per side of one pass: a longer side is walked in passes of MATCH_PASS tiles, which bounds the
+// partials at 2 * MATCH_PASS * (MATCH_PASS * 128) * 8 bytes = 32 MiB whatever na and nb.
+constexpr int MATCH_TM = 128, MATCH_TN = 128, MATCH_PASS = 128;
+// Where everything sits in the caller's workspace (256-byte aligned offsets; `bytes` = its size).  The four results are DEVICE arrays there.
+struct MatchPlan {
+    int na_pad, nb_pad, hpad;  // rows to whole tiles, H to a multiple of 64
+    size_t a16, b16;           // normalised f16 operands [na_pad, hpad], [nb_pad, hpad]
+    size_t prow_v, prow_i;     // per (column tile of the pass, row of the pass): best value / column
+    size_t pcol_v, pcol_i;     // per (row tile of the pass, column of the pass): best value / row
+    size_t idx_ab, sim_ab, idx_ba, sim_ba;  // [na], [na], [nb], [nb]
+    size_t bytes;
+};
+inline MatchPlan match_plan(int na, int nb, int H) {
+    MatchPlan p{};
+    p.na_pad = (na + MATCH_TM - 1) / MATCH_TM * MATCH_TM;
+    p.nb_pad = (nb + MATCH_TN - 1) / MATCH_TN * MATCH_TN;
+    p.hpad = (H + 63) / 64 * 64;
+    const size_t pr = (size_t)(p.na_pad < MATCH_PASS * MATCH_TM ? p.na_pad : MATCH_PASS * MATCH_TM);  // rows / columns of one pass
+    const size_t pc = (size_t)(p.nb_pad < MATCH_PASS * MATCH_TN ? p.nb_pad : MATCH_PASS * MATCH_TN);
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t off = need; need += (bytes + 255) / 256 * 256; return off; };
+    p.a16 = take((size_t)p.na_pad * p.hpad * 2);
+    p.b16 = take((size_t)p.nb_pad * p.hpad * 2);
+    p.prow_v = take(pc / MATCH_TN * pr * 4);
+    p.prow_i = take(pc / MATCH_TN * pr * 4);
+    p.pcol_v = take(pr / MATCH_TM * pc * 4);
+    p.pcol_i = take(pr / MATCH_TM * pc * 4);
+    p.idx_ab = take((size_t)na * 4);
+    p.sim_ab = take((size_t)na * 4);
+    p.idx_ba = take((size_t)nb * 4);
+    p.sim_ba = take((size_t)nb * 4);
+    p.bytes = need;
+    return p;
+}
+// a [na, H] / b [nb, H]: DEVICE f32 rows with row strides lda / ldb (floats); ws: DEVICE workspace of plan.bytes (256-byte aligned).
+// Normalises both sides, runs the tile grid pass by pass and folds the partials: afterwards ws + plan.idx_ab etc. hold the results.
+hipError_t launch_match(const float* a, size_t lda, const float* b, size_t ldb, int na, int nb, int H, char* ws, const MatchPlan& plan,
+                        hipStream_t stream);
+
 // clock probe (device_types.h): per translation unit, [CLK_SLOTS][4] = running sums of shader cycles and 100 MHz ticks of workgroup 0 over
 // all launches of each kernel kind on the current device, the 100 MHz end stamp of the last one, the launch count
 hipError_t gemm_clock_probe_read(unsigned long long* out);

@@ -943,6 +943,7 @@ extern "C" void dinov2_hip_session_free(dinov2_hip_session* s) {
     if (s->ws) (void)hipFree(s->ws);
     if (s->raw) (void)hipFree(s->raw);
     if (s->pca_buf) (void)hipFree(s->pca_buf);
+    if (s->match_buf) (void)hipFree(s->match_buf);
     if (s->tap_buf) (void)hipFree(s->tap_buf);
     if (s->attn_buf) (void)hipFree(s->attn_buf);
     if (s->attn_q) (void)hipFree(s->attn_q);
@@ -1114,6 +1115,7 @@ static int predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dinov
         const Dims dd = dims_of(m, B, h, w);
         s->last_first = classify ? 1 : 1 + (int)m->hp.num_register_tokens;
         s->last_patches = dd.T - s->last_first;
+        s->last_t = dd.T;
     }
     s->last_b = B;
     s->last_h = h;
@@ -1611,5 +1613,93 @@ extern "C" int dinov2_hip_pca3(dinov2_hip_session* s, const float* tokens, int32
     if (trace)
         fprintf(stderr, "pca3: P %d H %d: means + covariance %.3f ms, %d steps %.3f ms, total %.3f ms (eigenvalues %.4g %.4g %.4g)\n", P, H,
                 t_setup, n_steps, t_iter - t_setup, since(), ev[0], ev[1], ev[2]);
+    return DINOV2_HIP_OK;
+}
+
+// =============================================================================================================
+// nearest rows by cosine similarity, both directions (csrc/match.hip; no reference counterpart)
+// =============================================================================================================
+extern "C" int dinov2_hip_match_tokens(dinov2_hip_session* s, const dinov2_hip_match* m, char* err, size_t errlen) {
+    if (!s || !m) {
+        set_err(err, errlen, "match: null session / request");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    constexpr int NMAX = 1 << 20;
+    if (m->na < 1 || m->na > NMAX || m->nb < 1 || m->nb > NMAX || m->H < 8 || m->H > 4096) {
+        set_err(err, errlen, "match: need 1 <= na, nb <= %d and 8 <= H <= 4096", NMAX);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (!m->idx_ab && !m->sim_ab && !m->idx_ba && !m->sim_ba) {
+        set_err(err, errlen, "match: no output requested");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    const int na = m->na, nb = m->nb, H = m->H;
+    // a NULL side: the patch rows of one image of the last un-split forward -- rows 1 + R .. T - 1 whatever last_first says (under
+    // DINOV2_HIP_CLASSIFY that one includes the registers)
+    const int R = (int)s->model->hp.num_register_tokens;
+    const int P = s->last_t - 1 - R;
+    const struct { const float* p; int n, image; const char* name; } side[2] = {{m->a, na, m->image_a, "a"}, {m->b, nb, m->image_b, "b"}};
+    for (const auto& sd : side) {
+        if (sd.p) {
+            if (m->on_device && ((size_t)sd.p & 15) != 0) {
+                set_err(err, errlen, "match: device pointer %s is not 16-byte aligned", sd.name);
+                return DINOV2_HIP_ERR_INVALID;
+            }
+            continue;
+        }
+        if (s->last_b <= 0 || !s->fin) {
+            set_err(err, errlen, "match: %s == NULL means the patch tokens of the session's last un-split forward, and there is none", sd.name);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+        if (sd.n != P || H != (int)s->model->hp.hidden_size) {
+            set_err(err, errlen, "match: %s == NULL means the last forward's patch tokens, which are [%d, %d]", sd.name, P,
+                    (int)s->model->hp.hidden_size);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+        if (sd.image < 0 || sd.image >= s->last_b) {
+            set_err(err, errlen, "match: image_%s %d outside the last batch of %d", sd.name, sd.image, s->last_b);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+    }
+    HIP_TRY(hipSetDevice(s->model->device));
+    hipStream_t st = s->stream;
+    const MatchPlan plan = match_plan(na, nb, H);
+    const bool stage_a = m->a && !m->on_device, stage_b = m->b && !m->on_device;
+    const size_t n_a = (size_t)na * H * 4, n_b = (size_t)nb * H * 4;
+    const size_t o_a = plan.bytes, o_b = o_a + align_up(stage_a ? n_a : 0, 256), need = o_b + align_up(stage_b ? n_b : 0, 256);
+    if (need > s->match_bytes) {
+        HIP_TRY(hipStreamSynchronize(st));
+        if (s->match_buf) HIP_TRY(hipFree(s->match_buf));
+        s->match_buf = nullptr;
+        s->match_bytes = 0;
+        const hipError_t e = hipMalloc((void**)&s->match_buf, need);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();  // (not left behind for the next launch to report)
+            s->match_buf = nullptr;
+            set_err(err, errlen, "match: %zu bytes of scratch refused: %s", need, hipGetErrorString(e));
+            return DINOV2_HIP_ERR_HIP;
+        }
+        s->match_bytes = need;
+    }
+    char* buf = s->match_buf;
+    const float* src[2];
+    for (int k = 0; k < 2; ++k) {
+        const auto& sd = side[k];
+        if (!sd.p) {
+            src[k] = s->fin + ((size_t)sd.image * s->last_t + 1 + R) * H;
+        } else if (!m->on_device) {
+            float* dst = (float*)(buf + (k == 0 ? o_a : o_b));
+            HIP_TRY(hipMemcpyAsync(dst, sd.p, k == 0 ? n_a : n_b, hipMemcpyHostToDevice, st));
+            src[k] = dst;
+        } else {
+            src[k] = sd.p;
+        }
+    }
+    HIP_TRY(launch_match(src[0], (size_t)H, src[1], (size_t)H, na, nb, H, buf, plan, st));
+    if (m->idx_ab) HIP_TRY(hipMemcpyAsync(m->idx_ab, buf + plan.idx_ab, (size_t)na * 4, hipMemcpyDeviceToHost, st));
+    if (m->sim_ab) HIP_TRY(hipMemcpyAsync(m->sim_ab, buf + plan.sim_ab, (size_t)na * 4, hipMemcpyDeviceToHost, st));
+    if (m->idx_ba) HIP_TRY(hipMemcpyAsync(m->idx_ba, buf + plan.idx_ba, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+    if (m->sim_ba) HIP_TRY(hipMemcpyAsync(m->sim_ba, buf + plan.sim_ba, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return DINOV2_HIP_OK;
 }

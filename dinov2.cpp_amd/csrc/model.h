@@ -78,6 +78,8 @@ struct dinov2_hip_session {
     size_t raw_bytes = 0;
     char* pca_buf = nullptr;  // dinov2_hip_pca3's device scratch, grown on demand
     size_t pca_bytes = 0;
+    char* match_buf = nullptr;  // dinov2_hip_match_tokens' device scratch, grown on demand
+    size_t match_bytes = 0;
     float* tap_buf = nullptr;  // dinov2_hip_predict_layers with host outputs: where the tap kernel writes before the copy-out; grown on demand
     size_t tap_bytes = 0;
     float* attn_buf = nullptr;  // dinov2_hip_predict_attention with a host output: where attn_rows_kernel writes before the copy-out; grown on demand
@@ -88,6 +90,7 @@ struct dinov2_hip_session {
     int last_b = 0, last_h = 0, last_w = 0;  // shape of the last un-split forward (0: none): what dinov2_hip_fetch copies out
     bool last_classify = false;
     int last_first = 0, last_patches = 0;  // rows [last_first, last_first + last_patches) of image 0 in `fin`: its patch tokens
+    int last_t = 0;  // tokens per image of that forward: image i of last_b starts at row i * last_t of `fin` (dinov2_hip_match_tokens)
     // carved views (valid for cur_* shape)
     int cur_b = 0, cur_h = 0, cur_w = 0;
     float *img = nullptr, *x = nullptr, *fin = nullptr, *feat = nullptr, *logits = nullptr, *probs = nullptr,

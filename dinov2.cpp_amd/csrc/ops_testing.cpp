@@ -653,3 +653,26 @@ extern "C" int dinov2_hip_op_preprocess_u8(int32_t mode, const uint8_t* bgr, int
     OP_TRY(hipMemcpy(out, dD.p, ndst * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
+
+// match_normalise_kernel + match_kernel + match_reduce_kernel (csrc/match.hip) on host data, as dinov2_hip_match_tokens runs them
+extern "C" int dinov2_hip_op_match(const float* a, int32_t na, const float* b, int32_t nb, int32_t H, int32_t* idx_ab, float* sim_ab,
+                                   int32_t* idx_ba, float* sim_ba) {
+    if (!a || !b || !idx_ab || !sim_ab || !idx_ba || !sim_ba || na < 1 || na > (1 << 20) || nb < 1 || nb > (1 << 20) || H < 8 || H > 4096)
+        return DINOV2_HIP_ERR_INVALID;
+    const MatchPlan plan = match_plan(na, nb, H);
+    DevBuf dA, dB, dW;
+    OP_TRY(dA.alloc((size_t)na * H * 4));
+    OP_TRY(dB.alloc((size_t)nb * H * 4));
+    OP_TRY(dW.alloc(plan.bytes));
+    OP_TRY(hipMemset(dW.p, 0xff, plan.bytes));
+    OP_TRY(hipMemcpy(dA.p, a, (size_t)na * H * 4, hipMemcpyHostToDevice));
+    OP_TRY(hipMemcpy(dB.p, b, (size_t)nb * H * 4, hipMemcpyHostToDevice));
+    OP_TRY(launch_match((const float*)dA.p, (size_t)H, (const float*)dB.p, (size_t)H, na, nb, H, (char*)dW.p, plan, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    char* ws = (char*)dW.p;
+    OP_TRY(hipMemcpy(idx_ab, ws + plan.idx_ab, (size_t)na * 4, hipMemcpyDeviceToHost));
+    OP_TRY(hipMemcpy(sim_ab, ws + plan.sim_ab, (size_t)na * 4, hipMemcpyDeviceToHost));
+    OP_TRY(hipMemcpy(idx_ba, ws + plan.idx_ba, (size_t)nb * 4, hipMemcpyDeviceToHost));
+    OP_TRY(hipMemcpy(sim_ba, ws + plan.sim_ba, (size_t)nb * 4, hipMemcpyDeviceToHost));
+    return 0;
+}

@@ -306,6 +306,49 @@ int dinov2_hip_preprocess(int32_t mode, const uint8_t *bgr, int32_t height, int3
 int dinov2_hip_pca3(dinov2_hip_session *session, const float *tokens, int32_t P, int32_t H, int32_t on_device,
                     float *components, float *mean, float *projection, char *err, size_t errlen);
 
+/* -- dense correspondence (no reference counterpart: for every patch of image A the most similar patch of image B by cosine similarity, the
+ *    reverse, and the mutual nearest neighbours kept -- the matching figure of the DINOv2 paper, the "sparse matching" notebooks built on
+ *    upstream's get_intermediate_layers / x_norm_patchtokens; with CLS vectors as rows the same call is retrieval / k-NN with k = 1).  Either
+ *    side is a caller's [n, H] f32 matrix (host or device) or, with a NULL pointer, the PATCH tokens of one image of the session's last
+ *    un-split forward, which never leave the device: only the two index / similarity vectors cross PCIe.  On the device (csrc/match.hip): rows
+ *    to unit length in f16, one pass over the 128 x 128 tiles of the na x nb similarity matrix on the matrix cores -- the matrix is never
+ *    written; each tile's epilogue reduces its accumulators per row and per column -- and a fold of the per-tile partials.
+ *    Contract:
+ *    1. Normalisation.  Per row ss = sum x^2 in f32, r = 1.0f / sqrtf(ss) with a correctly rounded square root and division, x^ = f16(x r);
+ *       a row with ss == 0 gives x^ = 0, so all its similarities are 0.  The operands are f16 whatever the model's compute type (like the
+ *       covariance GEMM of dinov2_hip_pca3).  Inputs must be finite; the result for non-finite input is unspecified.
+ *    2. Similarity.  sim(i, j) = sum_k a^_ik b^_jk: the f16 products are exact in f32, the accumulation is f32 on the matrix cores in an order
+ *       that depends on H alone -- not on na, nb or the tile a pair falls in -- so sim_ab[i] is bit-identical whatever other rows travel
+ *       with row i.
+ *    3. Argmax over the real rows and columns only (padding never wins); equal f32 values (-0 and +0 are equal) go to the LOWEST index; the
+ *       result depends neither on launch geometry nor on the order in which tiles finish.
+ *    4. Both directions come from the SAME products, so sim_ab[i] == sim_ba[idx_ab[i]] bit for bit whenever the pair is mutual
+ *       (idx_ba[idx_ab[i]] == i).
+ *    Out of scope: k > 1 and ratio tests, a persistent normalised bank, the device group, device-side outputs, bf16 operands.
+ *    Times against the vendor GEMM + max: profiles/match.md. */
+typedef struct dinov2_hip_match {
+    const float *a;    /* [na, H] f32, or NULL = the PATCH tokens (rows 1 + R .. T - 1 of the final-LayerNorm tokens: never CLS or registers,
+                          with or without DINOV2_HIP_CLASSIFY) of image `image_a` of the session's last un-split forward; then na must be P */
+    const float *b;    /* [nb, H], or NULL likewise with `image_b` (a and b may name the same or different images, or one of them a
+                          caller's buffer: matching the live frame against a stored template) */
+    int32_t na, nb;    /* 1 .. 1 048 576 each */
+    int32_t H;         /* 8 .. 4096; with a NULL side it must be the model's hidden size */
+    int32_t image_a, image_b; /* in [0, last batch); read only for a NULL side */
+    int32_t on_device; /* of the non-NULL a / b: 0 host, 1 device pointers (16-byte aligned) on the model's device */
+    int32_t *idx_ab;   /* [na] argmax_j sim(a_i, b_j); HOST; any of the four may be NULL, not all */
+    float   *sim_ab;   /* [na] that similarity */
+    int32_t *idx_ba;   /* [nb] argmax_i sim(a_i, b_j) */
+    float   *sim_ba;   /* [nb] */
+    int32_t reserved[4];
+} dinov2_hip_match;
+/* Synchronous: returns after the copy-out, like dinov2_hip_pca3.  Argument errors (NULL session or `m`; na, nb or H out of range; all four
+ * outputs NULL; a NULL side when the session holds no un-split forward -- none yet, or the last predict was split into passes; na / nb / H
+ * that are not P / P / the hidden size for a NULL side; an image index outside the last batch; a device pointer that is not 16-byte aligned)
+ * return DINOV2_HIP_ERR_INVALID before anything is launched, allocated or copied.  The scratch (the two f16 operands, (na + nb) rounded up to
+ * tiles x H rounded up to 64 x 2 bytes, a host side's staging copy, at most 32 MiB of partials, the results) is a session-owned buffer
+ * grown on demand; an allocation the device refuses returns DINOV2_HIP_ERR_HIP. */
+int dinov2_hip_match_tokens(dinov2_hip_session *session, const dinov2_hip_match *m, char *err, size_t errlen);
+
 /* -- quantise a GGUF (replaces dino_model_quantize, dinov2.h:118 / dinov2.cpp:355-453).  Host only.
  *    itype: ggml type id 2 q4_0, 3 q4_1, 6 q5_0, 7 q5_1, 8 q8_0.  2-D tensors named `*weight` are re-encoded, the rest copied. */
 int dinov2_hip_quantize(const char *fname_inp, const char *fname_out, int32_t itype, char *err, size_t errlen);

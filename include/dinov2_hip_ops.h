@@ -137,6 +137,12 @@ int dinov2_hip_op_gemm_plan_parts(int32_t dtype, int32_t epilogue, int32_t M, in
  * unit Ritz vectors, each with its largest loading positive (H >= 8) */
 int dinov2_hip_op_pca_ritz(const double *yprev, const double *ynext, const double *gram, int32_t H, double *evals, double *comp);
 
+/* the three kernels behind dinov2_hip_match_tokens (csrc/match.hip) without a model or session: host a [na, H], b [nb, H] in; host idx_ab [na],
+ * sim_ab [na], idx_ba [nb], sim_ba [nb] out (all four required).  Same ranges and contract as dinov2_hip_match.  The workspace is filled
+ * with 0xff bytes first, so padding that the kernels fail to zero shows up as NaN. */
+int dinov2_hip_op_match(const float *a, int32_t na, const float *b, int32_t nb, int32_t H, int32_t *idx_ab, float *sim_ab, int32_t *idx_ba,
+                        float *sim_ba);
+
 #ifdef __cplusplus
 }
 #endif
