@@ -202,6 +202,75 @@ def op_match(a, b):
     return out
 
 
+def _op_rc(rc, name):
+    if rc == OP_GUARD_CHANGED:
+        raise AssertionError(f"{name} wrote outside its output (guard band changed)")
+    if rc != 0:
+        raise RuntimeError(f"dinov2_hip_op_{name} failed ({rc})")
+
+
+def pca_ppad(P):
+    """Ppad of dinov2_hip_pca3: the token count padded to the K of its covariance GEMM (no device needed)."""
+    return int(lib().dinov2_hip_op_pca_ppad(int(P)))
+
+
+def pca_blocks(H):
+    """Workgroups of pca_power_kernel = rows of its Gram partials (no device needed)."""
+    return int(lib().dinov2_hip_op_pca_blocks(int(H)))
+
+
+def op_pca_prepare(tok):
+    """pca_mean_kernel + pca_center_transpose_kernel (dinov2_hip_op_pca_prepare): tok [P, H] f32 -> (mean [H] f32, xt [H, Ppad] f32 values of
+    the f16 matrix, padded columns included).  Raises on a HIP error or a changed guard band."""
+    tok = np.ascontiguousarray(tok, np.float32)
+    P, H = tok.shape
+    mean, xt = np.zeros(H, np.float32), np.zeros((H, pca_ppad(P)), np.float32)
+    _op_rc(lib().dinov2_hip_op_pca_prepare(tok.ctypes.data, P, H, mean.ctypes.data, xt.ctypes.data), "pca_prepare")
+    return mean, xt
+
+
+def op_pca_cov(tok):
+    """prepare + the driver's aliased covariance GEMM (dinov2_hip_op_pca_cov): tok [P, H] f32 -> cov [H, H] f32 = Xt Xt^T."""
+    tok = np.ascontiguousarray(tok, np.float32)
+    P, H = tok.shape
+    cov = np.zeros((H, H), np.float32)
+    _op_rc(lib().dinov2_hip_op_pca_cov(tok.ctypes.data, P, H, cov.ctypes.data), "pca_cov")
+    return cov
+
+
+def op_pca_power(cov, yprev, gprev_parts):
+    """One pca_power_kernel launch (dinov2_hip_op_pca_power): cov [H, H] f32, yprev [H, 8] f64, gprev_parts [pca_blocks(H), 64] f64 ->
+    (ynext [H, 8], gnext_parts [pca_blocks(H), 64]) f64."""
+    cov = np.ascontiguousarray(cov, np.float32)
+    H = cov.shape[0]
+    yprev, gprev_parts = np.ascontiguousarray(yprev, np.float64), np.ascontiguousarray(gprev_parts, np.float64)
+    nb = pca_blocks(H)
+    assert cov.shape == (H, H) and yprev.shape == (H, 8) and gprev_parts.shape == (nb, 64), (cov.shape, yprev.shape, gprev_parts.shape)
+    ynext, gnext = np.zeros((H, 8), np.float64), np.zeros((nb, 64), np.float64)
+    _op_rc(lib().dinov2_hip_op_pca_power(cov.ctypes.data, yprev.ctypes.data, gprev_parts.ctypes.data, H, ynext.ctypes.data, gnext.ctypes.data),
+           "pca_power")
+    return ynext, gnext
+
+
+def op_pca_project(tok, mean, comp):
+    """pca_project_kernel (dinov2_hip_op_pca_project): tok [P, H], mean [H], comp [3, H] f32 -> proj [P, 3] f32."""
+    tok, mean, comp = (np.ascontiguousarray(a, np.float32) for a in (tok, mean, comp))
+    P, H = tok.shape
+    assert mean.shape == (H,) and comp.shape == (3, H), (mean.shape, comp.shape)
+    proj = np.zeros((P, 3), np.float32)
+    _op_rc(lib().dinov2_hip_op_pca_project(tok.ctypes.data, mean.ctypes.data, comp.ctypes.data, P, H, proj.ctypes.data), "pca_project")
+    return proj
+
+
+def pca_chol_rinv(gram):
+    """pca_chol_rinv of csrc/kernels.h on the host: gram [8, 8] f64 -> rinv [8, 8] f64."""
+    gram = np.ascontiguousarray(gram, np.float64)
+    assert gram.shape == (8, 8), gram.shape
+    rinv = np.zeros((8, 8), np.float64)
+    _op_rc(lib().dinov2_hip_op_pca_chol_rinv(gram.ctypes.data, rinv.ctypes.data), "pca_chol_rinv")
+    return rinv
+
+
 def lib():
     """Load libdinov2_hip.so; raise loudly if it is not built (no CPU fallback exists)."""
     global _lib
@@ -289,6 +358,13 @@ def lib():
     L.dinov2_hip_op_permute_bias.argtypes = [fp, fp, i32, i32]
     L.dinov2_hip_op_head.argtypes = [i32, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, C.c_float]
     L.dinov2_hip_op_pca_ritz.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.dinov2_hip_op_pca_ppad.argtypes = [i32]
+    L.dinov2_hip_op_pca_blocks.argtypes = [i32]
+    L.dinov2_hip_op_pca_prepare.argtypes = [vp, i32, i32, vp, vp]
+    L.dinov2_hip_op_pca_cov.argtypes = [vp, i32, i32, vp]
+    L.dinov2_hip_op_pca_power.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.dinov2_hip_op_pca_project.argtypes = [vp, vp, vp, i32, i32, vp]
+    L.dinov2_hip_op_pca_chol_rinv.argtypes = [vp, vp]
     L.dinov2_hip_op_match.argtypes = [fp, i32, fp, i32, i32, C.POINTER(i32), fp, C.POINTER(i32), fp]
     L.dinov2_hip_op_clock_probe.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.dinov2_hip_op_clock_slots.argtypes = [C.POINTER(C.c_uint64)]

@@ -183,6 +183,14 @@ hipError_t launch_head(DType dt, const float* fin, const void* W, const float* b
 
 // PCA support: mean[h] = column mean of tok [P, H]; xt [H, Ppad] f16 = (tok - mean)^T, zero padded in P
 hipError_t launch_pca_prepare(const float* tok, float* mean, void* xt, int P, int H, int Ppad, hipStream_t stream);
+// Ppad: the K of the covariance GEMM, a multiple of 64 with an even K / 64
+inline int pca_ppad(int P) { return (P + 127) / 128 * 128; }
+// cov [H, H] f32 = Xt Xt^T (= P times the covariance): one plain GEMM whose two operands are the same [H, Ppad] f16 matrix
+inline hipError_t launch_pca_cov(const void* xt, float* cov, int H, int Ppad, hipStream_t stream) {
+    GemmArgs a{};
+    a.A = xt; a.W = xt; a.out = cov; a.M = H; a.N = H; a.K = Ppad; a.ldo = H;
+    return launch_gemm(DT_F16, EPI_PLAIN_F32, a, stream);
+}
 
 // Block iteration for the leading eigenvectors of cov [H, H] (see pca_power_kernel): block width, rows per workgroup, grid size
 constexpr int PCA_NB = 8, PCA_ROWS = 16;

@@ -1519,7 +1519,7 @@ extern "C" int dinov2_hip_pca3(dinov2_hip_session* s, const float* tokens, int32
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
     double t_setup = 0, t_iter = 0;
     int n_steps = 0;
-    const int Ppad = (P + 127) / 128 * 128;  // K of the covariance GEMM: multiple of 64 with an even K / 64
+    const int Ppad = pca_ppad(P);
     const int nb = pca_blocks(H);
     const size_t n_tok = (size_t)P * H * 4, n_xt = (size_t)H * Ppad * 2, n_cov = (size_t)H * H * 4, n_mean = (size_t)H * 4;
     const size_t n_y = (size_t)H * PCA_NB * 8, n_g = (size_t)nb * 64 * 8, n_comp = (size_t)3 * H * 4, n_proj = (size_t)P * 3 * 4;
@@ -1551,9 +1551,7 @@ extern "C" int dinov2_hip_pca3(dinov2_hip_session* s, const float* tokens, int32
         tok = (const float*)(buf + o_tok);
     }
     HIP_TRY(launch_pca_prepare(tok, d_mean, buf + o_xt, P, H, Ppad, st));
-    GemmArgs a{};  // P * C = Xt Xt^T: both operands are the same [H, Ppad] matrix
-    a.A = buf + o_xt; a.W = buf + o_xt; a.out = d_cov; a.M = H; a.N = H; a.K = Ppad; a.ldo = H;
-    HIP_TRY(launch_gemm(DT_F16, EPI_PLAIN_F32, a, st));
+    HIP_TRY(launch_pca_cov(buf + o_xt, d_cov, H, Ppad, st));  // P * C = Xt Xt^T: both operands are the same [H, Ppad] matrix
 
     // start block (slot 2): a fixed, well-conditioned pattern; its Gram matrix goes into workgroup 0's partial slot
     std::vector<double> y0((size_t)H * PCA_NB), g0((size_t)nb * 64, 0.0);

@@ -676,3 +676,110 @@ extern "C" int dinov2_hip_op_match(const float* a, int32_t na, const float* b, i
     OP_TRY(hipMemcpy(sim_ba, ws + plan.sim_ba, (size_t)nb * 4, hipMemcpyDeviceToHost));
     return 0;
 }
+
+// ---- the device stages of dinov2_hip_pca3 (csrc/model.cpp), each through the launch function the driver calls, on host data ----
+namespace {
+// A device output of n elements of esz bytes between two guard bands of DINOV2_HIP_OP_GUARD_ROWS rows of `row` elements; the whole buffer
+// starts as 0xff bytes (NaN in f16, f32 and f64), so an element the kernel never wrote comes back as NaN and a write outside changes a guard.
+struct Guarded {
+    DevBuf d;
+    size_t n = 0, ng = 0, esz = 0;
+    hipError_t alloc(size_t n_, size_t row, size_t esz_) {
+        n = n_; ng = (size_t)DINOV2_HIP_OP_GUARD_ROWS * row; esz = esz_;
+        hipError_t e = d.alloc((n + 2 * ng) * esz);
+        return e != hipSuccess ? e : hipMemset(d.p, 0xff, (n + 2 * ng) * esz);
+    }
+    void* ptr() const { return (char*)d.p + ng * esz; }
+    // the payload to `host` (n * esz bytes): 0, -1 on a HIP error, DINOV2_HIP_OP_GUARD_CHANGED
+    int fetch(void* host) const {
+        std::vector<unsigned char> raw((n + 2 * ng) * esz);
+        if (hipMemcpy(raw.data(), d.p, raw.size(), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        for (size_t k = 0; k < ng * esz; ++k)
+            if (raw[k] != 0xffu || raw[(ng + n) * esz + k] != 0xffu) return DINOV2_HIP_OP_GUARD_CHANGED;
+        std::memcpy(host, raw.data() + ng * esz, n * esz);
+        return 0;
+    }
+};
+bool pca_shape_ok(int P, int H) { return P >= 4 && H >= 8 && H <= 4096; }  // the range dinov2_hip_pca3 accepts
+hipError_t upload(const void* src, size_t bytes, DevBuf& d) {
+    hipError_t e = d.alloc(bytes);
+    return e != hipSuccess ? e : hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice);
+}
+}  // namespace
+
+extern "C" int dinov2_hip_op_pca_ppad(int32_t P) { return pca_ppad(P); }
+extern "C" int dinov2_hip_op_pca_blocks(int32_t H) { return pca_blocks(H); }
+
+extern "C" int dinov2_hip_op_pca_prepare(const float* tok, int32_t P, int32_t H, float* mean_out, float* xt_out) {
+    if (!tok || !mean_out || !xt_out || !pca_shape_ok(P, H)) return DINOV2_HIP_ERR_INVALID;
+    const int Ppad = pca_ppad(P);
+    const size_t nxt = (size_t)H * Ppad;
+    DevBuf dT;
+    Guarded gM, gX;
+    OP_TRY(upload(tok, (size_t)P * H * 4, dT));
+    OP_TRY(gM.alloc((size_t)H, (size_t)H, 4));
+    OP_TRY(gX.alloc(nxt, (size_t)Ppad, 2));
+    OP_TRY(launch_pca_prepare((const float*)dT.p, (float*)gM.ptr(), gX.ptr(), P, H, Ppad, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    int rc = gM.fetch(mean_out);
+    if (rc != 0) return rc;
+    std::vector<_Float16> raw(nxt);
+    rc = gX.fetch(raw.data());
+    if (rc != 0) return rc;
+    for (size_t i = 0; i < nxt; ++i) xt_out[i] = (float)raw[i];
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_pca_cov(const float* tok, int32_t P, int32_t H, float* cov_out) {
+    if (!tok || !cov_out || !pca_shape_ok(P, H)) return DINOV2_HIP_ERR_INVALID;
+    if (gemm_init() != hipSuccess) return -1;
+    const int Ppad = pca_ppad(P);
+    DevBuf dT, dM, dX;
+    Guarded gC;
+    OP_TRY(upload(tok, (size_t)P * H * 4, dT));
+    OP_TRY(dM.alloc((size_t)H * 4));
+    OP_TRY(dX.alloc((size_t)H * Ppad * 2));
+    OP_TRY(hipMemset(dX.p, 0xff, (size_t)H * Ppad * 2));  // (the driver's xt is reused scratch: whatever prepare leaves unwritten is read as it is)
+    OP_TRY(gC.alloc((size_t)H * H, (size_t)H, 4));
+    OP_TRY(launch_pca_prepare((const float*)dT.p, (float*)dM.p, dX.p, P, H, Ppad, nullptr));
+    OP_TRY(launch_pca_cov(dX.p, (float*)gC.ptr(), H, Ppad, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    return gC.fetch(cov_out);
+}
+
+extern "C" int dinov2_hip_op_pca_power(const float* cov, const double* yprev, const double* gprev_parts, int32_t H, double* ynext,
+                                       double* gnext_parts) {
+    if (!cov || !yprev || !gprev_parts || !ynext || !gnext_parts || H < 8 || H > 4096) return DINOV2_HIP_ERR_INVALID;
+    const size_t ny = (size_t)H * PCA_NB, ng = (size_t)pca_blocks(H) * 64;
+    DevBuf dC, dY, dG;
+    Guarded gY, gG;
+    OP_TRY(upload(cov, (size_t)H * H * 4, dC));
+    OP_TRY(upload(yprev, ny * 8, dY));
+    OP_TRY(upload(gprev_parts, ng * 8, dG));
+    OP_TRY(gY.alloc(ny, PCA_NB, 8));
+    OP_TRY(gG.alloc(ng, 64, 8));
+    OP_TRY(launch_pca_power((const float*)dC.p, (const double*)dY.p, (const double*)dG.p, (double*)gY.ptr(), (double*)gG.ptr(), H, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    const int rc = gY.fetch(ynext);
+    return rc != 0 ? rc : gG.fetch(gnext_parts);
+}
+
+extern "C" int dinov2_hip_op_pca_project(const float* tok, const float* mean, const float* comp, int32_t P, int32_t H, float* proj) {
+    if (!tok || !mean || !comp || !proj || !pca_shape_ok(P, H)) return DINOV2_HIP_ERR_INVALID;
+    DevBuf dT, dM, dC;
+    Guarded gP;
+    OP_TRY(upload(tok, (size_t)P * H * 4, dT));
+    OP_TRY(upload(mean, (size_t)H * 4, dM));
+    OP_TRY(upload(comp, (size_t)3 * H * 4, dC));
+    OP_TRY(gP.alloc((size_t)P * 3, 3, 4));
+    OP_TRY(launch_pca_project((const float*)dT.p, (const float*)dM.p, (const float*)dC.p, (float*)gP.ptr(), P, H, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    return gP.fetch(proj);
+}
+
+// host-only: pca_chol_rinv (csrc/kernels.h), the factorisation the power kernel and pca_ritz share
+extern "C" int dinov2_hip_op_pca_chol_rinv(const double* gram, double* rinv) {
+    if (!gram || !rinv) return DINOV2_HIP_ERR_INVALID;
+    pca_chol_rinv(gram, rinv);
+    return DINOV2_HIP_OK;
+}

@@ -5,7 +5,9 @@
  * data (converted to the compute dtype on the way in, back to f32 on the way out) so the parity tests can check each
  * kernel against the oracle in isolation -- the per-op granularity the reference gets from ggml's own op tests and
  * that /root/reference itself never had (it holds no tests at all).  All return 0 on success, -1 on a HIP error
- * (dinov2_hip_op_attention_ex: also DINOV2_HIP_OP_GUARD_CHANGED).
+ * (the entry points with guard bands -- attention_ex, layer_tap, attn_rows, pca_prepare / pca_cov / pca_power / pca_project -- also
+ * DINOV2_HIP_OP_GUARD_CHANGED).  Each family has its cases in tests/*_cases.py, CPU probes of those cases and a GPU file; for the
+ * pca_* entry points: tests/pca_cases.py, tests/test_pca_probes.py, tests/test_gpu_pca_kernels.py.
  */
 #ifndef DINOV2_HIP_OPS_H
 #define DINOV2_HIP_OPS_H
@@ -136,6 +138,27 @@ int dinov2_hip_op_gemm_plan_parts(int32_t dtype, int32_t epilogue, int32_t M, in
  * ynext [H][8] = cov * (yprev R^-1) with gram = R^T R  ->  evals [3] largest Ritz values of cov on span(yprev), comp [3][H] their
  * unit Ritz vectors, each with its largest loading positive (H >= 8) */
 int dinov2_hip_op_pca_ritz(const double *yprev, const double *ynext, const double *gram, int32_t H, double *evals, double *comp);
+
+/* The device stages of dinov2_hip_pca3 (csrc/model.cpp), one at a time and without a model or session, each through the launch function
+ * the driver itself calls (csrc/kernels.h: launch_pca_prepare, launch_pca_cov, launch_pca_power, launch_pca_project).  P >= 4, 8 <= H <= 4096
+ * as the driver requires.  Every device output is framed by guard bands of DINOV2_HIP_OP_GUARD_ROWS rows of its own row width and the whole
+ * buffer starts as 0xff bytes (NaN in f16, f32 and f64); a changed guard returns DINOV2_HIP_OP_GUARD_CHANGED, bad arguments
+ * DINOV2_HIP_ERR_INVALID.  Cases, emulations and bounds: tests/pca_cases.py; tests/test_pca_probes.py (CPU), tests/test_gpu_pca_kernels.py.
+ *   pca_ppad / pca_blocks: Ppad (the padded token count, K of the covariance GEMM) and the power kernel's grid size, as the driver computes them
+ *   pca_prepare: pca_mean_kernel + pca_center_transpose_kernel: tok [P, H] -> mean_out [H], xt_out [H, Ppad] = the f32 values of the f16 matrix
+ *                (tok - mean)^T, the padded columns p >= P included (they must be 0)
+ *   pca_cov:     prepare (into an xt that starts as NaN) + the covariance GEMM with A == W aliased: cov_out [H, H] = Xt Xt^T, f32
+ *   pca_power:   one pca_power_kernel launch: cov [H, H] f32, yprev [H][8], gprev_parts [pca_blocks(H)][64] (partial Gram sums of yprev; only
+ *                their sum matters) -> ynext [H][8] = cov (yprev R^-1), gnext_parts [pca_blocks(H)][64] = the Gram of each workgroup's 16 rows
+ *   pca_project: pca_project_kernel: proj [P, 3] = (tok - mean) comp^T, comp [3, H]
+ *   pca_chol_rinv (host-only): gram [8][8] -> rinv [8][8], the CholeskyQR factor shared by the power kernel and pca_ritz (csrc/kernels.h) */
+int dinov2_hip_op_pca_ppad(int32_t P);
+int dinov2_hip_op_pca_blocks(int32_t H);
+int dinov2_hip_op_pca_prepare(const float *tok, int32_t P, int32_t H, float *mean_out, float *xt_out);
+int dinov2_hip_op_pca_cov(const float *tok, int32_t P, int32_t H, float *cov_out);
+int dinov2_hip_op_pca_power(const float *cov, const double *yprev, const double *gprev_parts, int32_t H, double *ynext, double *gnext_parts);
+int dinov2_hip_op_pca_project(const float *tok, const float *mean, const float *comp, int32_t P, int32_t H, float *proj);
+int dinov2_hip_op_pca_chol_rinv(const double *gram, double *rinv);
 
 /* the three kernels behind dinov2_hip_match_tokens (csrc/match.hip) without a model or session: host a [na, H], b [nb, H] in; host idx_ab [na],
  * sim_ab [na], idx_ba [nb], sim_ba [nb] out (all four required).  Same ranges and contract as dinov2_hip_match.  The workspace is filled

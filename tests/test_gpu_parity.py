@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+import pca_cases as pc
 from oracle.oracle import OracleModel, bgr_hwc_to_rgb_chw
 
 pytestmark = pytest.mark.gpu
@@ -416,6 +417,50 @@ def test_pca3_matches_svd(api, golden_dir, P, H):
     # degenerate input (all tokens equal: zero covariance) stays finite: zero projection, like cv::PCA on constant data
     comp0, mean0, proj0 = sess.pca3(np.full((P, H), 2.5, np.float32))
     assert np.isfinite(comp0).all() and np.array_equal(proj0, np.zeros_like(proj0)) and np.allclose(mean0, 2.5)
+
+
+@pytest.fixture(scope="module")
+def pca_session(api, golden_dir):
+    return api.Session(api.Model(os.path.join(golden_dir, "tiny_gelu_reg4.gguf"), classify=False))
+
+
+@pytest.mark.parametrize("name", list(pc.E2E_INPUTS))
+def test_pca3_within_16x_of_its_emulation(api, pca_session, name):
+    """The whole call against the float64 SVD, held to 16 x the error the numpy emulation of the algorithm (tests/pca_cases.py pca3_emulate:
+    the same f16 rounding of the centred tokens, start block, CholeskyQR steps, check cadence and stopping rule) shows on the same input,
+    floored at 1e-7 -- a thousand to a million times tighter than test_pca3_matches_svd.  Inputs: the structured one of that test, the same
+    scaled by 1e-4 and 1e3, flat spectra (80 .. 112 steps: the 16-step check cadence), a tie of components 1 and 2 (compared as a subspace),
+    a near-tie of 3 and 4, eleven slowly decaying directions, mean 1000, and 4 x 8, 4 x 64, 5 x 200 (rank below the block width).  The mean is
+    the kernel's bit for bit; the projection is held to the projection kernel's own bound on the returned components."""
+    x, tied, (emu_cos, emu_proj), emu_steps = pc.e2e_case(name)
+    comp, mean, proj = pca_session.pca3(x)
+    assert np.isfinite(comp).all() and np.isfinite(proj).all()
+    cos_err, proj_err = pc.e2e_errors(x, comp, proj, tied)
+    print(f"\n{name}: 1 - |cos| {cos_err:.2e} (emulation {emu_cos:.2e}, allowed {pc.e2e_tolerance(emu_cos):.2e}); projection {proj_err:.2e} "
+          f"(emulation {emu_proj:.2e}, allowed {pc.e2e_tolerance(emu_proj):.2e}); emulation steps {emu_steps}")
+    ok, msg = pc.check_exact(mean, pc.mean_emulate(x), name + " mean")
+    assert ok, msg
+    assert np.abs(np.linalg.norm(comp.astype(np.float64), axis=1) - 1.0).max() <= 2.0 ** -23  # unit in double, each entry rounded once to f32
+    for k in range(3):
+        assert comp[k][np.abs(comp[k]).argmax()] > 0
+    fails = pc.check_project(lambda *_: proj, x, mean, comp, name)
+    assert not fails, fails
+    assert cos_err <= pc.e2e_tolerance(emu_cos), (cos_err, emu_cos)
+    assert proj_err <= pc.e2e_tolerance(emu_proj), (proj_err, emu_proj)
+
+
+def test_pca3_refuses_tokens_beyond_the_f16_range(api, pca_session):
+    """A centred token beyond 65504 makes the f16 operand of the covariance infinite: DINOV2_HIP_ERR_INVALID with the driver's message, and
+    the session goes on working."""
+    x, tied, _, _ = pc.e2e_case("structured_256x384")
+    before = pca_session.pca3(x)
+    big = x.copy()
+    big[3, 5] = 2.0e5
+    with pytest.raises(api.DinoError) as e:
+        pca_session.pca3(big)
+    assert e.value.status == 4 and "non-finite covariance" in str(e.value)
+    for a, b in zip(pca_session.pca3(x), before):
+        assert np.array_equal(a, b)
 
 
 def test_pca3_on_resident_tokens(api, golden_dir):
