@@ -84,6 +84,20 @@ class Match(C.Structure):
                 ("sim_ba", C.c_void_p), ("reserved", C.c_int32 * 4)]
 
 
+class Rows(C.Structure):
+    """dinov2_hip_rows (include/dinov2_hip.h)."""
+    _fields_ = [("source", C.c_int32), ("data", C.c_void_p), ("n", C.c_int32), ("H", C.c_int32), ("image", C.c_int32), ("on_device", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class TopK(C.Structure):
+    """dinov2_hip_topk (include/dinov2_hip.h)."""
+    _fields_ = [("queries", Rows), ("k", C.c_int32), ("idx", C.c_void_p), ("sim", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+ROWS_GIVEN, ROWS_LAST_CLS, ROWS_LAST_PATCHES = 0, 1, 2
+_ROWS_SOURCE = {"given": ROWS_GIVEN, "last_cls": ROWS_LAST_CLS, "last_patches": ROWS_LAST_PATCHES}
+
 ATTN_KEYS_ALL, ATTN_KEYS_PATCHES = 0, 1
 _ATTN_KEYS = {"all": ATTN_KEYS_ALL, "patches": ATTN_KEYS_PATCHES}
 
@@ -200,6 +214,32 @@ def op_match(a, b):
     if rc != 0:
         raise RuntimeError(f"dinov2_hip_op_match failed ({rc})")
     return out
+
+
+def op_bank_topk(q, b, k, chunk_tiles=0):
+    """The kernels of csrc/bank.hip alone (dinov2_hip_op_bank_topk): q [nq, H] against the bank built from b [nb, H] -> dict of idx, sim
+    [nq, k].  chunk_tiles: column tiles per workgroup, 0 = the planner's choice.  No model, no session."""
+    q, b = np.ascontiguousarray(q, np.float32), np.ascontiguousarray(b, np.float32)
+    assert q.ndim == 2 and b.ndim == 2 and q.shape[1] == b.shape[1], (q.shape, b.shape)
+    nq, nb = q.shape[0], b.shape[0]
+    out = {"idx": np.full((nq, k), -7, np.int32), "sim": np.full((nq, k), np.nan, np.float32)}
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    rc = lib().dinov2_hip_op_bank_topk(q.ctypes.data_as(fp), nq, b.ctypes.data_as(fp), nb, q.shape[1], int(k), int(chunk_tiles),
+                                       out["idx"].ctypes.data_as(ip), out["sim"].ctypes.data_as(fp))
+    if rc != 0:
+        raise RuntimeError(f"dinov2_hip_op_bank_topk failed ({rc})")
+    return out
+
+
+BANK_PLAN_FIELDS = ("chunk_tiles", "nchunks", "pass_tiles", "ntiles", "partial_bytes", "bytes")
+
+
+def bank_plan(nq, nb, H, k, chunk_tiles=0):
+    """bank_topk_plan (csrc/kernels.h) as a dict; no device needed."""
+    buf = (C.c_int64 * len(BANK_PLAN_FIELDS))()
+    if lib().dinov2_hip_op_bank_plan(int(nq), int(nb), int(H), int(k), int(chunk_tiles), buf) != 0:
+        raise ValueError(f"bank_topk refuses nq={nq} nb={nb} H={H} k={k}")
+    return dict(zip(BANK_PLAN_FIELDS, [int(v) for v in buf]))
 
 
 def _op_rc(rc, name):
@@ -338,6 +378,13 @@ def lib():
     L.dinov2_hip_debug_hidden.argtypes = [vp, C.POINTER(Input), i32, vp, cp, sz]
     L.dinov2_hip_pca3.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, cp, sz]
     L.dinov2_hip_match_tokens.argtypes = [vp, C.POINTER(Match), cp, sz]
+    L.dinov2_hip_bank_create.argtypes = [vp, i32, i32, C.POINTER(vp), cp, sz]
+    L.dinov2_hip_bank_free.argtypes = [vp]
+    L.dinov2_hip_bank_free.restype = None
+    L.dinov2_hip_bank_count.argtypes = [vp]
+    L.dinov2_hip_bank_clear.argtypes = [vp]
+    L.dinov2_hip_bank_add.argtypes = [vp, vp, C.POINTER(Rows), C.POINTER(i32), cp, sz]
+    L.dinov2_hip_bank_topk.argtypes = [vp, vp, C.POINTER(TopK), cp, sz]
     # diagnostic ops (include/dinov2_hip_ops.h)
     fp = C.POINTER(C.c_float)
     L.dinov2_hip_op_gemm.argtypes = [i32, i32, fp, fp, fp, fp, C.c_int64, fp, i32, i32, i32, i32, i32, i32, i32, i32, i32,
@@ -366,6 +413,9 @@ def lib():
     L.dinov2_hip_op_pca_project.argtypes = [vp, vp, vp, i32, i32, vp]
     L.dinov2_hip_op_pca_chol_rinv.argtypes = [vp, vp]
     L.dinov2_hip_op_match.argtypes = [fp, i32, fp, i32, i32, C.POINTER(i32), fp, C.POINTER(i32), fp]
+    L.dinov2_hip_op_bank_topk.argtypes = [fp, i32, fp, i32, i32, i32, i32, C.POINTER(i32), fp]
+    L.dinov2_hip_op_bank_plan.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64)]
+    L.dinov2_hip_op_bank_bench.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, fp]
     L.dinov2_hip_op_clock_probe.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.dinov2_hip_op_clock_slots.argtypes = [C.POINTER(C.c_uint64)]
     L.dinov2_hip_op_probe_tr16.argtypes = [C.POINTER(C.c_int16)]
@@ -587,6 +637,82 @@ class DeviceArray:
             pass
 
 
+class Bank:
+    """dinov2_hip_bank: a device-resident bank of unit-length f16 rows and its top-k cosine search (include/dinov2_hip.h).  Rows come from
+    host arrays, DeviceArrays, or -- source="last_cls" / "last_patches" -- from the session's last un-split predict without leaving the device."""
+
+    def __init__(self, model: "Model", H: int, capacity: int):
+        h = C.c_void_p()
+        err = _errbuf()
+        rc = lib().dinov2_hip_bank_create(model._h, int(H), int(capacity), C.byref(h), err, len(err))
+        if rc != 0:
+            raise DinoError(rc, err.value.decode(errors="replace"))
+        self._h = h
+        self.H, self.capacity = int(H), int(capacity)
+
+    def _rows(self, sess, rows, source, image, n):
+        """(Rows struct, the array it points into: kept alive by the caller)."""
+        if source is None:
+            source = "given" if rows is not None else None
+        if source not in _ROWS_SOURCE or (source == "given") != (rows is not None):
+            raise ValueError("bank: give rows, or source = 'last_cls' / 'last_patches' without rows")
+        if source != "given":
+            if n is None:  # what the session's last Session.predict left behind (n=...: after another kind of predict)
+                n = getattr(sess, "_last_rows", {}).get(source, 0)
+            return Rows(_ROWS_SOURCE[source], None, int(n), self.H, int(image), 0), None
+        if isinstance(rows, DeviceArray):
+            if len(rows.shape) != 2:
+                raise ValueError("bank: rows must be [n, H]")
+            return Rows(ROWS_GIVEN, rows.ptr, rows.shape[0], rows.shape[1], 0, 1), rows
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        if x.ndim != 2:
+            raise ValueError("bank: rows must be [n, H]")
+        return Rows(ROWS_GIVEN, x.ctypes.data, x.shape[0], x.shape[1], 0, 0), x
+
+    def add(self, sess: "Session", rows=None, *, source=None, image: int = 0, n: int | None = None) -> int:
+        """Normalises rows into the bank and returns the index of the first one.  rows: [n, H] host array or DeviceArray; or rows=None with
+        source="last_cls" (the CLS row of every image of the session's last predict; n = that batch) or "last_patches" (the patch rows of
+        image `image`; n = P); `n` is taken from the session's last predict() unless given."""
+        r, keep = self._rows(sess, rows, source, image, n)
+        first = C.c_int32(-1)
+        err = _errbuf()
+        rc = lib().dinov2_hip_bank_add(sess._h, self._h, C.byref(r), C.byref(first), err, len(err))
+        if rc != 0:
+            raise DinoError(rc, err.value.decode(errors="replace"))
+        return int(first.value)
+
+    def topk(self, sess: "Session", queries=None, k: int = 1, *, source=None, image: int = 0, n: int | None = None) -> dict:
+        """The k most similar bank rows of every query, best first: dict of idx [nq, k] int32 (insertion indices; -1 past the bank's count)
+        and sim [nq, k] f32 (-inf there).  queries as the rows of add()."""
+        r, keep = self._rows(sess, queries, source, image, n)
+        nq = max(int(r.n), 0)
+        out = {"idx": np.empty((nq, int(k)), np.int32), "sim": np.empty((nq, int(k)), np.float32)}
+        t = TopK(r, int(k), out["idx"].ctypes.data, out["sim"].ctypes.data)
+        err = _errbuf()
+        rc = lib().dinov2_hip_bank_topk(sess._h, self._h, C.byref(t), err, len(err))
+        if rc != 0:
+            raise DinoError(rc, err.value.decode(errors="replace"))
+        return out
+
+    @property
+    def count(self) -> int:
+        return int(lib().dinov2_hip_bank_count(self._h))
+
+    def clear(self):
+        lib().dinov2_hip_bank_clear(self._h)
+
+    def free(self):
+        if getattr(self, "_h", None):
+            lib().dinov2_hip_bank_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Group:
     """dinov2_hip_group: N devices behind one handle -- host threads + sessions per device inside the library (two lanes per
     device by default: one lane's PCIe copies run under the other's kernels), the global batch split contiguously, outputs
@@ -701,6 +827,9 @@ class Session:
         rc = lib().dinov2_hip_predict(self._h, C.byref(i), C.byref(o), CLASSIFY if classify else 0, err, len(err))
         if rc != 0:
             raise DinoError(rc, err.value.decode(errors="replace"))
+        hp = self.model.hparams  # the resident rows a Bank may name: one CLS row per image, P patch rows per image
+        nh, nw = preprocess_size(1 if classify else 0, hh, ww, hp.patch_size) if layout == U8_BGR_HWC else (hh, ww)
+        self._last_rows = {"last_cls": B, "last_patches": (nh // hp.patch_size) * (nw // hp.patch_size)}
         return out
 
     def predict_device(self, img_ptr: int, B: int, hh: int, ww: int, *, classify: bool, layout: int = RGB_CHW,

@@ -275,6 +275,64 @@ inline MatchPlan match_plan(int na, int nb, int H) {
 hipError_t launch_match(const float* a, size_t lda, const float* b, size_t ldb, int na, int nb, int H, char* ws, const MatchPlan& plan,
                         hipStream_t stream);
 
+// match_normalise_kernel on its own (contract 1 of dinov2_hip_match): rows [n] of x (row stride ld floats) -> out [nout, hpad] f16, rows n ..
+// nout - 1 zero, rows >= nout not touched.  The one normaliser of match.hip and bank.hip.
+hipError_t launch_match_normalise(const float* x, size_t ld, _Float16* out, int n, int nout, int H, int hpad, hipStream_t stream);
+
+// Top-k rows of a resident f16 bank by cosine similarity (csrc/bank.hip; contract in include/dinov2_hip.h, dinov2_hip_bank_topk).
+// bank_topk_kernel has match_kernel's tile; workgroup (x, y) walks the `chunk_tiles` column tiles of chunk x for query row tile y and leaves
+// one sorted list of k (value, index) pairs per query row; bank_merge_kernel merges the lists of a row over the chunks.  The queries are
+// walked in passes of at most BANK_PASS_TILES row tiles, and the chunk count is capped, so that the partials of one pass
+// (chunks x rows of the pass x k x 8 bytes) never exceed BANK_PARTIAL_MAX whatever nq, count and k.
+constexpr int BANK_K_MAX = 64, BANK_PASS_TILES = 32, BANK_TARGET_WGS = 256;
+constexpr size_t BANK_PARTIAL_MAX = (size_t)32 << 20;
+struct BankEntry {  // one element of a list; an empty slot is (-inf, INT_MAX)
+    float v;
+    int i;
+};
+struct BankTopkPlan {
+    int nq_pad, hpad;            // queries to whole tiles, H to a multiple of 64
+    int ntiles;                  // column tiles that hold rows < count
+    int chunk_tiles, nchunks;    // column tiles per workgroup, workgroups per query row tile
+    int pass_tiles;              // query row tiles per pass
+    size_t q16;                  // normalised queries [nq_pad, hpad] f16
+    size_t part;                 // BankEntry [nchunks][pass_tiles * 128][k]
+    size_t idx, sim;             // results [nq, k]
+    size_t bytes;
+};
+// chunk_tiles = 0: as many chunks as fill BANK_TARGET_WGS workgroups; a given value is raised where the partials would pass BANK_PARTIAL_MAX
+inline BankTopkPlan bank_topk_plan(int nq, int count, int H, int k, int chunk_tiles) {
+    BankTopkPlan p{};
+    p.nq_pad = (nq + MATCH_TM - 1) / MATCH_TM * MATCH_TM;
+    p.hpad = (H + 63) / 64 * 64;
+    p.ntiles = (count + MATCH_TN - 1) / MATCH_TN;
+    const int rt = p.nq_pad / MATCH_TM < BANK_PASS_TILES ? p.nq_pad / MATCH_TM : BANK_PASS_TILES;
+    const int want = (BANK_TARGET_WGS + rt - 1) / rt;
+    if (chunk_tiles <= 0) chunk_tiles = (p.ntiles + want - 1) / want;
+    const size_t per_chunk_tile = (size_t)MATCH_TM * k * sizeof(BankEntry);  // partials of one (chunk, row tile)
+    const int max_chunks = (int)(BANK_PARTIAL_MAX / per_chunk_tile);
+    const int floor_tiles = (p.ntiles + max_chunks - 1) / max_chunks;
+    if (chunk_tiles < floor_tiles) chunk_tiles = floor_tiles;
+    if (chunk_tiles > p.ntiles) chunk_tiles = p.ntiles;
+    p.chunk_tiles = chunk_tiles;
+    p.nchunks = (p.ntiles + chunk_tiles - 1) / chunk_tiles;
+    const int fit = (int)(BANK_PARTIAL_MAX / (per_chunk_tile * p.nchunks));
+    p.pass_tiles = rt < fit ? rt : fit;
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t off = need; need += (bytes + 255) / 256 * 256; return off; };
+    p.q16 = take((size_t)p.nq_pad * p.hpad * 2);
+    p.part = take(per_chunk_tile * p.nchunks * p.pass_tiles);
+    p.idx = take((size_t)nq * k * 4);
+    p.sim = take((size_t)nq * k * 4);
+    p.bytes = need;
+    return p;
+}
+// q [nq, H]: DEVICE f32 rows with row stride ldq (floats); bank: the normalised f16 rows [>= ntiles * 128, hpad], of which the first `count`
+// are searched; ws: DEVICE workspace of plan.bytes.  Afterwards ws + plan.idx / plan.sim hold [nq, k]; slots past `count` are (-1, -inf).
+// `floor_only`: the sweep without its selection epilogue (a measuring aid: the results are meaningless).
+hipError_t launch_bank_topk(const float* q, size_t ldq, int nq, const _Float16* bank, int count, int H, int k, char* ws, const BankTopkPlan& plan,
+                            bool floor_only, hipStream_t stream);
+
 // clock probe (device_types.h): per translation unit, [CLK_SLOTS][4] = running sums of shader cycles and 100 MHz ticks of workgroup 0 over
 // all launches of each kernel kind on the current device, the 100 MHz end stamp of the last one, the launch count
 hipError_t gemm_clock_probe_read(unsigned long long* out);

@@ -41,14 +41,15 @@ __device__ __forceinline__ void fold_lane(Best& b) {
 
 }  // namespace
 
-// x: rows [n] of H floats, row stride ld.  out [npad, hpad] f16: row / sqrt(sum of squares), 0 for an all-zero row, for rows >= n and for
-// columns >= H.  Four rows per workgroup, one wave each; lane l owns the 4-float chunks l, l + 64, ... (16-byte loads when `vec`: H, ld
+// x: rows [n] of H floats, row stride ld.  out [nout, hpad] f16: row / sqrt(sum of squares), 0 for an all-zero row, for rows >= n and for
+// columns >= H; rows >= nout are not touched (the grid covers nout rounded up to 4).  Four rows per workgroup, one wave each; lane l owns the 4-float chunks l, l + 64, ... (16-byte loads when `vec`: H, ld
 // multiples of 4 and an aligned base; the summation order is the same either way, so it depends on H alone).
 __global__ __launch_bounds__(256) void match_normalise_kernel(const float* __restrict__ x, size_t ld, _Float16* __restrict__ out, int n,
-                                                              int H, int hpad, int vec) {
+                                                              int nout, int H, int hpad, int vec) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63;
     const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= (size_t)nout) return;
     f16x4* const o = (f16x4*)(out + row * hpad);
     const int nch = hpad / 4;
     if (row >= (size_t)n) {
@@ -231,13 +232,20 @@ __global__ __launch_bounds__(256) void match_reduce_kernel(const float* __restri
     idx[e] = b.i;
 }
 
+hipError_t launch_match_normalise(const float* x, size_t ld, _Float16* out, int n, int nout, int H, int hpad, hipStream_t st) {
+    const int vec = H % 4 == 0 && ld % 4 == 0 && ((size_t)x & 15) == 0;
+    hipLaunchKernelGGL(match_normalise_kernel, dim3((nout + 3) / 4), dim3(256), 0, st, x, ld, out, n, nout, H, hpad, vec);
+    return hipGetLastError();
+}
+
 hipError_t launch_match(const float* a, size_t lda, const float* b, size_t ldb, int na, int nb, int H, char* ws, const MatchPlan& p,
                         hipStream_t st) {
     _Float16* const a16 = (_Float16*)(ws + p.a16);
     _Float16* const b16 = (_Float16*)(ws + p.b16);
-    const int veca = H % 4 == 0 && lda % 4 == 0 && ((size_t)a & 15) == 0, vecb = H % 4 == 0 && ldb % 4 == 0 && ((size_t)b & 15) == 0;
-    hipLaunchKernelGGL(match_normalise_kernel, dim3(p.na_pad / 4), dim3(256), 0, st, a, lda, a16, na, H, p.hpad, veca);
-    hipLaunchKernelGGL(match_normalise_kernel, dim3(p.nb_pad / 4), dim3(256), 0, st, b, ldb, b16, nb, H, p.hpad, vecb);
+    hipError_t e = launch_match_normalise(a, lda, a16, na, p.na_pad, H, p.hpad, st);
+    if (e != hipSuccess) return e;
+    e = launch_match_normalise(b, ldb, b16, nb, p.nb_pad, H, p.hpad, st);
+    if (e != hipSuccess) return e;
     float *prow_v = (float*)(ws + p.prow_v), *pcol_v = (float*)(ws + p.pcol_v), *sim_ab = (float*)(ws + p.sim_ab), *sim_ba = (float*)(ws + p.sim_ba);
     int *prow_i = (int*)(ws + p.prow_i), *pcol_i = (int*)(ws + p.pcol_i), *idx_ab = (int*)(ws + p.idx_ab), *idx_ba = (int*)(ws + p.idx_ba);
     constexpr int PR = MATCH_PASS * MATCH_TM, PC = MATCH_PASS * MATCH_TN;

@@ -944,6 +944,7 @@ extern "C" void dinov2_hip_session_free(dinov2_hip_session* s) {
     if (s->raw) (void)hipFree(s->raw);
     if (s->pca_buf) (void)hipFree(s->pca_buf);
     if (s->match_buf) (void)hipFree(s->match_buf);
+    if (s->bank_buf) (void)hipFree(s->bank_buf);
     if (s->tap_buf) (void)hipFree(s->tap_buf);
     if (s->attn_buf) (void)hipFree(s->attn_buf);
     if (s->attn_q) (void)hipFree(s->attn_q);
@@ -1698,6 +1699,224 @@ extern "C" int dinov2_hip_match_tokens(dinov2_hip_session* s, const dinov2_hip_m
     if (m->sim_ab) HIP_TRY(hipMemcpyAsync(m->sim_ab, buf + plan.sim_ab, (size_t)na * 4, hipMemcpyDeviceToHost, st));
     if (m->idx_ba) HIP_TRY(hipMemcpyAsync(m->idx_ba, buf + plan.idx_ba, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
     if (m->sim_ba) HIP_TRY(hipMemcpyAsync(m->sim_ba, buf + plan.sim_ba, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DINOV2_HIP_OK;
+}
+
+// =============================================================================================================
+// a resident bank of normalised rows and its top-k search (csrc/bank.hip; no reference counterpart)
+// =============================================================================================================
+extern "C" int dinov2_hip_bank_create(dinov2_hip_model* model, int32_t H, int32_t capacity, dinov2_hip_bank** out, char* err, size_t errlen) {
+    if (!model || !out) {
+        set_err(err, errlen, "bank_create: null model / out");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (H < 8 || H > 4096 || capacity < 1 || capacity > (1 << 24)) {
+        set_err(err, errlen, "bank_create: need 8 <= H <= 4096 and 1 <= capacity <= %d", 1 << 24);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    HIP_TRY(hipSetDevice(model->device));
+    std::unique_ptr<dinov2_hip_bank> b(new dinov2_hip_bank);
+    b->device = model->device;
+    b->H = H;
+    b->hpad = (H + 63) / 64 * 64;
+    b->capacity = capacity;
+    b->cap_pad = (capacity + MATCH_TN - 1) / MATCH_TN * MATCH_TN;
+    const size_t bytes = (size_t)b->cap_pad * b->hpad * 2;
+    hipError_t e = hipMalloc((void**)&b->rows, bytes);
+    if (e == hipSuccess) {
+        e = hipMemset(b->rows, 0, bytes);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) (void)hipFree(b->rows);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // (not left behind for the next launch to report)
+        set_err(err, errlen, "bank_create: %zu bytes refused: %s", bytes, hipGetErrorString(e));
+        return DINOV2_HIP_ERR_HIP;
+    }
+    *out = b.release();
+    return DINOV2_HIP_OK;
+}
+
+extern "C" void dinov2_hip_bank_free(dinov2_hip_bank* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    (void)hipDeviceSynchronize();  // a session's stream may still be reading the rows
+    if (b->rows) (void)hipFree(b->rows);
+    delete b;
+}
+
+extern "C" int dinov2_hip_bank_count(const dinov2_hip_bank* b) { return b ? b->count : 0; }
+
+extern "C" int dinov2_hip_bank_clear(dinov2_hip_bank* b) {
+    if (!b) return DINOV2_HIP_ERR_INVALID;
+    b->count = 0;  // the memory stays as it is: the sweep masks on count
+    return DINOV2_HIP_OK;
+}
+
+namespace {
+// Checks a dinov2_hip_rows against the session and the bank's H; on success *src / *ld are the device view of a resident source (nullptr
+// for DINOV2_HIP_ROWS_GIVEN).  Touches nothing.
+int check_rows(const char* who, const dinov2_hip_session* s, const dinov2_hip_bank* b, const dinov2_hip_rows* r, const float** src, size_t* ld,
+               char* err, size_t errlen) {
+    *src = nullptr;
+    *ld = (size_t)b->H;
+    if (s->model->device != b->device) {
+        set_err(err, errlen, "%s: the session is on device %d, the bank on device %d", who, s->model->device, b->device);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (r->H != b->H) {
+        set_err(err, errlen, "%s: rows have H = %d, the bank %d", who, r->H, b->H);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (r->n < 1 || r->n > (1 << 24)) {
+        set_err(err, errlen, "%s: need 1 <= n <= %d", who, 1 << 24);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (r->source == DINOV2_HIP_ROWS_GIVEN) {
+        if (!r->data) {
+            set_err(err, errlen, "%s: DINOV2_HIP_ROWS_GIVEN with data == NULL", who);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+        if (r->on_device && ((size_t)r->data & 15) != 0) {
+            set_err(err, errlen, "%s: the device pointer is not 16-byte aligned", who);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+        return DINOV2_HIP_OK;
+    }
+    if (r->source != DINOV2_HIP_ROWS_LAST_CLS && r->source != DINOV2_HIP_ROWS_LAST_PATCHES) {
+        set_err(err, errlen, "%s: unknown rows source %d", who, r->source);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (s->last_b <= 0 || !s->fin) {
+        set_err(err, errlen, "%s: a resident source means rows of the session's last un-split forward, and there is none", who);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    const int Hm = (int)s->model->hp.hidden_size, R = (int)s->model->hp.num_register_tokens, T = s->last_t, P = T - 1 - R;
+    if (r->H != Hm) {
+        set_err(err, errlen, "%s: a resident source has the model's hidden size %d, not %d", who, Hm, r->H);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (r->source == DINOV2_HIP_ROWS_LAST_CLS) {
+        if (r->n != s->last_b) {
+            set_err(err, errlen, "%s: LAST_CLS has one row per image of the last batch: n must be %d", who, s->last_b);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+        *src = s->fin;  // row 0 of every image
+        *ld = (size_t)T * Hm;
+    } else {
+        if (r->n != P) {
+            set_err(err, errlen, "%s: LAST_PATCHES has the last forward's %d patch rows: n must be %d", who, P, P);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+        if (r->image < 0 || r->image >= s->last_b) {
+            set_err(err, errlen, "%s: image %d outside the last batch of %d", who, r->image, s->last_b);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+        *src = s->fin + ((size_t)r->image * T + 1 + R) * Hm;
+        *ld = (size_t)Hm;
+    }
+    return DINOV2_HIP_OK;
+}
+
+// the session's bank scratch, at least `need` bytes (after a wait: the stream may still be using the old one)
+int bank_scratch(dinov2_hip_session* s, size_t need, const char* who, char* err, size_t errlen) {
+    if (need <= s->bank_bytes) return DINOV2_HIP_OK;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (s->bank_buf) HIP_TRY(hipFree(s->bank_buf));
+    s->bank_buf = nullptr;
+    s->bank_bytes = 0;
+    const hipError_t e = hipMalloc((void**)&s->bank_buf, need);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        s->bank_buf = nullptr;
+        set_err(err, errlen, "%s: %zu bytes of scratch refused: %s", who, need, hipGetErrorString(e));
+        return DINOV2_HIP_ERR_HIP;
+    }
+    s->bank_bytes = need;
+    return DINOV2_HIP_OK;
+}
+}  // namespace
+
+extern "C" int dinov2_hip_bank_add(dinov2_hip_session* s, dinov2_hip_bank* b, const dinov2_hip_rows* rows, int32_t* first, char* err,
+                                   size_t errlen) {
+    if (!s || !b || !rows) {
+        set_err(err, errlen, "bank_add: null session / bank / rows");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    const float* src;
+    size_t ld;
+    const int rc = check_rows("bank_add", s, b, rows, &src, &ld, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    if (rows->n > b->capacity - b->count) {
+        set_err(err, errlen, "bank_add: %d rows do not fit: the bank holds %d of %d", rows->n, b->count, b->capacity);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t st = s->stream;
+    const int n = rows->n;
+    if (rows->source == DINOV2_HIP_ROWS_GIVEN) {
+        src = rows->data;
+        if (!rows->on_device) {
+            const size_t bytes = (size_t)n * b->H * 4;
+            const int rs = bank_scratch(s, align_up(bytes, 256), "bank_add", err, errlen);
+            if (rs != DINOV2_HIP_OK) return rs;
+            HIP_TRY(hipMemcpyAsync(s->bank_buf, rows->data, bytes, hipMemcpyHostToDevice, st));
+            src = (const float*)s->bank_buf;
+        }
+    }
+    // rows [count, count + n) only: what lies past them is not touched (it is masked, not assumed zero)
+    HIP_TRY(launch_match_normalise(src, ld, b->rows + (size_t)b->count * b->hpad, n, n, b->H, b->hpad, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (first) *first = b->count;
+    b->count += n;
+    return DINOV2_HIP_OK;
+}
+
+extern "C" int dinov2_hip_bank_topk(dinov2_hip_session* s, const dinov2_hip_bank* b, const dinov2_hip_topk* q, char* err, size_t errlen) {
+    if (!s || !b || !q) {
+        set_err(err, errlen, "bank_topk: null session / bank / request");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (q->k < 1 || q->k > BANK_K_MAX) {
+        set_err(err, errlen, "bank_topk: need 1 <= k <= %d", BANK_K_MAX);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (!q->idx && !q->sim) {
+        set_err(err, errlen, "bank_topk: no output requested");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    const float* src;
+    size_t ld;
+    const int rc = check_rows("bank_topk", s, b, &q->queries, &src, &ld, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    if (q->queries.n > (1 << 20)) {
+        set_err(err, errlen, "bank_topk: at most %d queries a call", 1 << 20);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (b->count < 1) {
+        set_err(err, errlen, "bank_topk: the bank is empty");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t st = s->stream;
+    const int nq = q->queries.n, k = q->k;
+    const BankTopkPlan plan = bank_topk_plan(nq, b->count, b->H, k, 0);
+    const bool stage = q->queries.source == DINOV2_HIP_ROWS_GIVEN && !q->queries.on_device;
+    const size_t n_q = (size_t)nq * b->H * 4;
+    const int rs = bank_scratch(s, plan.bytes + align_up(stage ? n_q : 0, 256), "bank_topk", err, errlen);
+    if (rs != DINOV2_HIP_OK) return rs;
+    char* const buf = s->bank_buf;
+    if (q->queries.source == DINOV2_HIP_ROWS_GIVEN) {
+        src = q->queries.data;
+        if (stage) {
+            HIP_TRY(hipMemcpyAsync(buf + plan.bytes, q->queries.data, n_q, hipMemcpyHostToDevice, st));
+            src = (const float*)(buf + plan.bytes);
+        }
+    }
+    HIP_TRY(launch_bank_topk(src, ld, nq, b->rows, b->count, b->H, k, buf, plan, false, st));
+    if (q->idx) HIP_TRY(hipMemcpyAsync(q->idx, buf + plan.idx, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+    if (q->sim) HIP_TRY(hipMemcpyAsync(q->sim, buf + plan.sim, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return DINOV2_HIP_OK;
 }

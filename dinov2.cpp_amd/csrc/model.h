@@ -80,6 +80,8 @@ struct dinov2_hip_session {
     size_t pca_bytes = 0;
     char* match_buf = nullptr;  // dinov2_hip_match_tokens' device scratch, grown on demand
     size_t match_bytes = 0;
+    char* bank_buf = nullptr;  // scratch of dinov2_hip_bank_add / dinov2_hip_bank_topk (staged host rows, f16 queries, partials, results)
+    size_t bank_bytes = 0;
     float* tap_buf = nullptr;  // dinov2_hip_predict_layers with host outputs: where the tap kernel writes before the copy-out; grown on demand
     size_t tap_bytes = 0;
     float* attn_buf = nullptr;  // dinov2_hip_predict_attention with a host output: where attn_rows_kernel writes before the copy-out; grown on demand
@@ -114,6 +116,14 @@ struct dinov2_hip_session {
     std::vector<hipEvent_t> free_events;
     std::vector<double> prof_ms;
     std::vector<int> prof_n;
+};
+
+// A resident bank of normalised f16 rows (dinov2_hip_bank_*): one device allocation [cap_pad, hpad], never moved; rows [0, count) are valid.
+// It keeps the device ordinal only, so it may outlive the model it was created with.
+struct dinov2_hip_bank {
+    int device = 0;
+    int H = 0, hpad = 0, capacity = 0, cap_pad = 0, count = 0;
+    _Float16* rows = nullptr;
 };
 
 // Internal (not C-ABI) helpers shared by model.cpp and group.cpp.

@@ -677,6 +677,73 @@ extern "C" int dinov2_hip_op_match(const float* a, int32_t na, const float* b, i
     return 0;
 }
 
+// ---- dinov2_hip_bank_topk's kernels (csrc/bank.hip) on host data: the bank is built by the shared normaliser, then swept and merged ----
+namespace {
+bool bank_shape_ok(int nq, int nb, int H, int k) {
+    return nq >= 1 && nq <= (1 << 20) && nb >= 1 && nb <= (1 << 24) && H >= 8 && H <= 4096 && k >= 1 && k <= BANK_K_MAX;
+}
+}  // namespace
+extern "C" int dinov2_hip_op_bank_plan(int32_t nq, int32_t nb, int32_t H, int32_t k, int32_t chunk_tiles, int64_t* out) {
+    if (!out || !bank_shape_ok(nq, nb, H, k) || chunk_tiles < 0) return DINOV2_HIP_ERR_INVALID;
+    const BankTopkPlan p = bank_topk_plan(nq, nb, H, k, chunk_tiles);
+    out[0] = p.chunk_tiles;
+    out[1] = p.nchunks;
+    out[2] = p.pass_tiles;
+    out[3] = p.ntiles;
+    out[4] = (int64_t)((size_t)p.nchunks * p.pass_tiles * MATCH_TM * k * sizeof(BankEntry));
+    out[5] = (int64_t)p.bytes;
+    return 0;
+}
+extern "C" int dinov2_hip_op_bank_topk(const float* q, int32_t nq, const float* b, int32_t nb, int32_t H, int32_t k, int32_t chunk_tiles,
+                                       int32_t* idx, float* sim) {
+    if (!q || !b || !idx || !sim || !bank_shape_ok(nq, nb, H, k) || chunk_tiles < 0) return DINOV2_HIP_ERR_INVALID;
+    const BankTopkPlan plan = bank_topk_plan(nq, nb, H, k, chunk_tiles);
+    const size_t bank_bytes = (size_t)plan.ntiles * MATCH_TN * plan.hpad * 2;
+    DevBuf dQ, dB, dBank, dW;
+    OP_TRY(dQ.alloc((size_t)nq * H * 4));
+    OP_TRY(dB.alloc((size_t)nb * H * 4));
+    OP_TRY(dBank.alloc(bank_bytes));
+    OP_TRY(dW.alloc(plan.bytes));
+    OP_TRY(hipMemset(dBank.p, 0xff, bank_bytes));  // rows past nb stay NaN: the sweep must mask them
+    OP_TRY(hipMemset(dW.p, 0xff, plan.bytes));
+    OP_TRY(hipMemcpy(dQ.p, q, (size_t)nq * H * 4, hipMemcpyHostToDevice));
+    OP_TRY(hipMemcpy(dB.p, b, (size_t)nb * H * 4, hipMemcpyHostToDevice));
+    OP_TRY(launch_match_normalise((const float*)dB.p, (size_t)H, (_Float16*)dBank.p, nb, nb, H, plan.hpad, nullptr));
+    OP_TRY(launch_bank_topk((const float*)dQ.p, (size_t)H, nq, (const _Float16*)dBank.p, nb, H, k, (char*)dW.p, plan, false, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    OP_TRY(hipMemcpy(idx, (char*)dW.p + plan.idx, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    OP_TRY(hipMemcpy(sim, (char*)dW.p + plan.sim, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int dinov2_hip_op_bank_bench(const float* q_dev, int32_t nq, const float* b_dev, int32_t nb, int32_t H, int32_t k,
+                                        int32_t chunk_tiles, int32_t warmup, int32_t iters, int32_t floor_only, float* ms) {
+    if (!q_dev || !b_dev || !ms || !bank_shape_ok(nq, nb, H, k) || chunk_tiles < 0 || warmup < 0 || iters < 1) return DINOV2_HIP_ERR_INVALID;
+    const BankTopkPlan plan = bank_topk_plan(nq, nb, H, k, chunk_tiles);
+    DevBuf dBank, dW;
+    OP_TRY(dBank.alloc((size_t)plan.ntiles * MATCH_TN * plan.hpad * 2));
+    OP_TRY(dW.alloc(plan.bytes));
+    OP_TRY(hipMemset(dBank.p, 0, (size_t)plan.ntiles * MATCH_TN * plan.hpad * 2));
+    OP_TRY(launch_match_normalise(b_dev, (size_t)H, (_Float16*)dBank.p, nb, nb, H, plan.hpad, nullptr));
+    hipEvent_t e0, e1;
+    OP_TRY(hipEventCreate(&e0));
+    OP_TRY(hipEventCreate(&e1));
+    int rc = 0;
+    for (int i = 0; i < warmup + iters && rc == 0; ++i) {
+        if (i == warmup && hipEventRecord(e0, nullptr) != hipSuccess) rc = -1;
+        if (launch_bank_topk(q_dev, (size_t)H, nq, (const _Float16*)dBank.p, nb, H, k, (char*)dW.p, plan, floor_only != 0, nullptr) != hipSuccess)
+            rc = -1;
+    }
+    float t = 0.0f;
+    if (rc == 0 && (hipEventRecord(e1, nullptr) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                    hipEventElapsedTime(&t, e0, e1) != hipSuccess))
+        rc = -1;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    (void)hipDeviceSynchronize();
+    *ms = t / (float)iters;
+    return rc;
+}
+
 // ---- the device stages of dinov2_hip_pca3 (csrc/model.cpp), each through the launch function the driver calls, on host data ----
 namespace {
 // A device output of n elements of esz bytes between two guard bands of DINOV2_HIP_OP_GUARD_ROWS rows of `row` elements; the whole buffer

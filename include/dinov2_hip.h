@@ -324,7 +324,8 @@ int dinov2_hip_pca3(dinov2_hip_session *session, const float *tokens, int32_t P,
  *       result depends neither on launch geometry nor on the order in which tiles finish.
  *    4. Both directions come from the SAME products, so sim_ab[i] == sim_ba[idx_ab[i]] bit for bit whenever the pair is mutual
  *       (idx_ba[idx_ab[i]] == i).
- *    Out of scope: k > 1 and ratio tests, a persistent normalised bank, the device group, device-side outputs, bf16 operands.
+ *    Out of scope: k > 1 and ratio tests, a persistent normalised bank (both: dinov2_hip_bank_topk below), the device group, device-side
+ *    outputs, bf16 operands.
  *    Times against the vendor GEMM + max: profiles/match.md. */
 typedef struct dinov2_hip_match {
     const float *a;    /* [na, H] f32, or NULL = the PATCH tokens (rows 1 + R .. T - 1 of the final-LayerNorm tokens: never CLS or registers,
@@ -348,6 +349,77 @@ typedef struct dinov2_hip_match {
  * tiles x H rounded up to 64 x 2 bytes, a host side's staging copy, at most 32 MiB of partials, the results) is a session-owned buffer
  * grown on demand; an allocation the device refuses returns DINOV2_HIP_ERR_HIP. */
 int dinov2_hip_match_tokens(dinov2_hip_session *session, const dinov2_hip_match *m, char *err, size_t errlen);
+
+/* -- a resident feature bank with top-k cosine search (no reference counterpart: k-NN classification -- the evaluation protocol of the
+ *    DINOv2 paper, k = 10, 20, ... with votes weighted by exp(sim / 0.07) --, retrieval against a gallery, Lowe's ratio test (k = 2), template
+ *    memories for the realtime loop).  The other half of dinov2_hip_match_tokens: the gallery is normalised ONCE into a device-resident f16
+ *    bank, and every query batch gets its k best rows back; only the queries (unless they are resident too) and [nq, k] results cross PCIe.
+ *    The bank is one device allocation on the model's device, made at create and never moved: f16 rows [capacity rounded up to the 128-row
+ *    tile, H rounded up to 64], zeroed at create.  It keeps only the device ordinal, so it may outlive the model; a session of another device
+ *    is refused.  One host thread at a time uses a bank.  On the device (csrc/bank.hip): dinov2_hip_match's normalisation kernel, then
+ *    workgroups that each sweep one chunk of the bank's 128-column tiles for one 128-row tile of queries on the matrix cores, keeping a sorted
+ *    list of k (value, index) pairs per query row in LDS, and a merge of the chunk lists.  The similarity matrix is never written.
+ *    Contract:
+ *    1. Normalisation.  Contract 1 of dinov2_hip_match, word for word: per row ss = sum x^2 in f32 in the same order, r = 1.0f / sqrtf(ss)
+ *       with a correctly rounded square root and division, x^ = f16(x r); a row with ss == 0 gives x^ = 0, so all its similarities are 0.
+ *       It is the same kernel.  Inputs must be finite.
+ *    2. Similarity.  Contract 2 of dinov2_hip_match: the same MFMA shape with k-steps of 32 in ascending order, an order that depends on H
+ *       alone.  Hence sim[i][0] and idx[i][0] equal sim_ab[i] and idx_ab[i] of dinov2_hip_match_tokens on the same rows bit for bit, and a
+ *       row's result is independent of the queries that travel with it.
+ *    3. Order.  One strict total order: the larger f32 value first (-0 is read as +0), among equal values the LOWEST index.  Row i of the
+ *       result is the first k of the bank's `count` rows in that order, best first.  Indices are distinct, so this list is unique: it does not
+ *       depend on launch geometry, on the chunking of the bank, on the insertion or merge order, or on which rows were added in which call.
+ *       The index is the insertion index (what dinov2_hip_bank_add reported as `first`, counting on).  Rows past `count` never win: the sweep
+ *       masks on count and assumes nothing about the memory behind it (dinov2_hip_bank_clear does not touch it).
+ *    4. Short banks.  When k > count, slots count .. k - 1 hold idx = -1 and sim = -INFINITY.
+ *    Out of scope: weighted voting -- a caller writes it from idx, sim and its own label array:
+ *        for (j = 0; j < k && idx[i * k + j] >= 0; ++j)
+ *            votes[label[idx[i * k + j]]] += expf(sim[i * k + j] / 0.07f);
+ *        predicted[i] = argmax(votes);
+ *    -- removal of single rows, bf16 operands, the device group, device-side outputs, k > 64.
+ *    Times: profiles/bank_topk.md. */
+typedef struct dinov2_hip_bank dinov2_hip_bank;
+
+enum dinov2_hip_rows_source { DINOV2_HIP_ROWS_GIVEN = 0, DINOV2_HIP_ROWS_LAST_CLS = 1, DINOV2_HIP_ROWS_LAST_PATCHES = 2 };
+typedef struct dinov2_hip_rows {
+    int32_t source;     /* GIVEN: `data` is [n, H] f32.  LAST_CLS: the final-LayerNorm CLS row of every image of the session's last
+                           un-split forward (n must be that batch).  LAST_PATCHES: the patch rows 1 + R .. T - 1 of image `image`
+                           (n must be P) -- the rows a NULL side of dinov2_hip_match stands for.  Resident rows never leave the device. */
+    const float *data;  /* GIVEN only; host, or device (16-byte aligned) with on_device = 1 */
+    int32_t n, H, image, on_device;
+    int32_t reserved[4];
+} dinov2_hip_rows;
+
+/* 8 <= H <= 4096, 1 <= capacity <= 2^24 (16 777 216) rows, else DINOV2_HIP_ERR_INVALID.  An allocation the device refuses returns
+ * DINOV2_HIP_ERR_HIP and leaves nothing behind for the next launch to report. */
+int  dinov2_hip_bank_create(dinov2_hip_model *model, int32_t H, int32_t capacity, dinov2_hip_bank **out, char *err, size_t errlen);
+/* waits for the device first: a session's stream may still be reading the rows */
+void dinov2_hip_bank_free(dinov2_hip_bank *bank);
+/* rows added since create / the last clear (0 for NULL) */
+int  dinov2_hip_bank_count(const dinov2_hip_bank *bank);
+/* count = 0; the memory is not touched */
+int  dinov2_hip_bank_clear(dinov2_hip_bank *bank);
+/* Normalises `rows` into rows [count, count + n) of the bank, reports *first = the old count (first may be NULL) and returns after the
+ * stream has finished: a returned bank is always complete.  More rows than fit returns DINOV2_HIP_ERR_INVALID and changes nothing.
+ * Argument errors (NULLs; n out of range; H unequal to the bank's; a resident source when the session holds no un-split forward -- none
+ * yet, or the last predict was split into passes; n that is not the batch (LAST_CLS) or P (LAST_PATCHES); an image index outside the last
+ * batch; an unknown source; a misaligned device pointer; a session of another device) return DINOV2_HIP_ERR_INVALID before anything is
+ * launched, allocated or copied, with *first and the bank untouched.  Host rows are staged in a session-owned scratch grown on demand. */
+int  dinov2_hip_bank_add(dinov2_hip_session *s, dinov2_hip_bank *bank, const dinov2_hip_rows *rows, int32_t *first, char *err, size_t errlen);
+
+typedef struct dinov2_hip_topk {
+    dinov2_hip_rows queries; /* 1 .. 1 048 576 rows */
+    int32_t k;          /* 1 .. 64 */
+    int32_t *idx;       /* [nq, k] HOST; either may be NULL, not both */
+    float   *sim;       /* [nq, k] HOST */
+    int32_t reserved[4];
+} dinov2_hip_topk;
+/* Synchronous: returns after the copy-out.  Argument errors (those of dinov2_hip_bank_add for `queries`; k out of range; both outputs NULL;
+ * an empty bank) return DINOV2_HIP_ERR_INVALID before anything is launched, allocated or copied, with the outputs untouched.  The scratch
+ * (the f16 queries, host queries' staging copy, the partial lists, the results) is the same session-owned buffer; the queries are walked
+ * in passes of at most 4 096 and the bank in at most as many chunks that the partial lists of one pass stay within 32 MiB whatever nq,
+ * count and k.  An allocation the device refuses returns DINOV2_HIP_ERR_HIP. */
+int  dinov2_hip_bank_topk(dinov2_hip_session *s, const dinov2_hip_bank *bank, const dinov2_hip_topk *q, char *err, size_t errlen);
 
 /* -- quantise a GGUF (replaces dino_model_quantize, dinov2.h:118 / dinov2.cpp:355-453).  Host only.
  *    itype: ggml type id 2 q4_0, 3 q4_1, 6 q5_0, 7 q5_1, 8 q8_0.  2-D tensors named `*weight` are re-encoded, the rest copied. */

@@ -166,6 +166,22 @@ int dinov2_hip_op_pca_chol_rinv(const double *gram, double *rinv);
 int dinov2_hip_op_match(const float *a, int32_t na, const float *b, int32_t nb, int32_t H, int32_t *idx_ab, float *sim_ab, int32_t *idx_ba,
                         float *sim_ba);
 
+/* the two kernels behind dinov2_hip_bank_topk (csrc/bank.hip) and the shared normaliser, without a model or session: host q [nq, H] against
+ * host b [nb, H] (all of them counted); host idx / sim [nq, k] out (both required).  1 <= nq <= 2^20, 1 <= nb <= 2^24, 8 <= H <= 4096,
+ * 1 <= k <= 64.  chunk_tiles: column tiles per workgroup, 0 = the planner's choice (a value that would take the partial lists past their
+ * bound is raised).  The workspace and the bank are filled with 0xff bytes first, so anything the kernels read without having written it
+ * shows up as NaN. */
+int dinov2_hip_op_bank_topk(const float *q, int32_t nq, const float *b, int32_t nb, int32_t H, int32_t k, int32_t chunk_tiles, int32_t *idx,
+                            float *sim);
+/* the plan of such a call (bank_topk_plan, csrc/kernels.h; no device): out[0 .. 5] = chunk_tiles, nchunks, pass_tiles, ntiles, bytes of the
+ * partial lists, bytes of the whole workspace.  Returns 0, or DINOV2_HIP_ERR_INVALID for sizes out of range. */
+int dinov2_hip_op_bank_plan(int32_t nq, int32_t nb, int32_t H, int32_t k, int32_t chunk_tiles, int64_t *out);
+/* measuring aid (tools/bank_bench.py): DEVICE f32 queries q_dev [nq, H] against a bank built here from the DEVICE f32 rows b_dev [nb, H];
+ * `warmup` + `iters` searches (normalise the queries, sweep, merge) on the null stream, the mean milliseconds of the timed ones by HIP events
+ * in *ms.  floor_only = 1: the sweep with its selection epilogue compiled out (the kernel's own floor; its results mean nothing). */
+int dinov2_hip_op_bank_bench(const float *q_dev, int32_t nq, const float *b_dev, int32_t nb, int32_t H, int32_t k, int32_t chunk_tiles,
+                             int32_t warmup, int32_t iters, int32_t floor_only, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
