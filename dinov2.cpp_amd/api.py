@@ -95,6 +95,22 @@ class TopK(C.Structure):
     _fields_ = [("queries", Rows), ("k", C.c_int32), ("idx", C.c_void_p), ("sim", C.c_void_p), ("reserved", C.c_int32 * 4)]
 
 
+class DenseDesc(C.Structure):
+    """dinov2_hip_dense_desc (include/dinov2_hip.h)."""
+    _fields_ = [("layers", C.POINTER(C.c_int32)), ("n_layers", C.c_int32), ("norm", C.c_int32), ("concat_cls", C.c_int32),
+                ("num_classes", C.c_int32), ("weight", C.c_void_p), ("bias", C.c_void_p), ("reduce", C.c_int32), ("bin_centers", C.c_void_p),
+                ("bins_eps", C.c_float), ("reserved", C.c_int32 * 6)]
+
+
+class DenseOut(C.Structure):
+    """dinov2_hip_dense_out (include/dinov2_hip.h)."""
+    _fields_ = [("out_h", C.c_int32), ("out_w", C.c_int32), ("labels", C.c_void_p), ("value", C.c_void_p), ("logits", C.c_void_p),
+                ("on_device", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+DENSE_ARGMAX, DENSE_BINS = 0, 1
+_DENSE_REDUCE = {"argmax": DENSE_ARGMAX, "bins": DENSE_BINS}
+
 ROWS_GIVEN, ROWS_LAST_CLS, ROWS_LAST_PATCHES = 0, 1, 2
 _ROWS_SOURCE = {"given": ROWS_GIVEN, "last_cls": ROWS_LAST_CLS, "last_patches": ROWS_LAST_PATCHES}
 
@@ -229,6 +245,69 @@ def op_bank_topk(q, b, k, chunk_tiles=0):
     if rc != 0:
         raise RuntimeError(f"dinov2_hip_op_bank_topk failed ({rc})")
     return out
+
+
+def op_dense_reduce(logits, h0, w0, out_h, out_w, reduce="argmax", centers=None, eps=0.0, want=("labels", "value")):
+    """dense_reduce_kernel alone (dinov2_hip_op_dense_reduce): logits [h0 * w0, C] of one image -> dict of labels [out_h, out_w] uint8 (argmax
+    only) and value [out_h, out_w] f32.  Raises on a HIP error or a changed guard band."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    if lg.ndim != 2 or lg.shape[0] != h0 * w0:
+        raise ValueError("op_dense_reduce: logits must be [h0 * w0, C]")
+    red = _DENSE_REDUCE[reduce]
+    out = {}
+    if red == DENSE_ARGMAX and "labels" in want:
+        out["labels"] = np.empty((int(out_h), int(out_w)), np.uint8)
+    if "value" in want:
+        out["value"] = np.empty((int(out_h), int(out_w)), np.float32)
+    cen = np.ascontiguousarray(centers, dtype=np.float32) if centers is not None else None
+    fp, ptr = C.POINTER(C.c_float), lambda a, t: a.ctypes.data_as(t) if a is not None else None
+    rc = lib().dinov2_hip_op_dense_reduce(ptr(lg, fp), int(h0), int(w0), lg.shape[1], int(out_h), int(out_w), red, ptr(cen, fp), float(eps),
+                                          ptr(out.get("labels"), C.POINTER(C.c_uint8)), ptr(out.get("value"), fp))
+    if rc == OP_GUARD_CHANGED:
+        raise RuntimeError("dinov2_hip_op_dense_reduce: a guard band around an output was written")
+    if rc != 0:
+        raise RuntimeError(f"dinov2_hip_op_dense_reduce failed ({rc})")
+    return out
+
+
+def op_dense_pack(x, w, b, eps, R, *, norm, concat_cls, slot=0, nslots=1):
+    """dense_pack_kernel alone (dinov2_hip_op_dense_pack): x [B, T, H] f32 -> [B * P, nslots * H * (1 + concat_cls)] f32, the values of the f16
+    operand after one launch into column block `slot` (the other blocks come back as NaN)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    B, T, H = x.shape
+    P = T - 1 - R
+    out = np.empty((B * P, nslots * H * (2 if concat_cls else 1)), np.float32)
+    w = np.ascontiguousarray(w, dtype=np.float32) if w is not None else None
+    b = np.ascontiguousarray(b, dtype=np.float32) if b is not None else None
+    fp, ptr = C.POINTER(C.c_float), lambda a: a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else None
+    rc = lib().dinov2_hip_op_dense_pack(ptr(x), ptr(w), ptr(b), float(eps), B, T, int(R), H, int(bool(norm)), int(bool(concat_cls)), int(slot),
+                                        int(nslots), ptr(out))
+    if rc == OP_GUARD_CHANGED:
+        raise RuntimeError("dinov2_hip_op_dense_pack: a guard band around the operand was written")
+    if rc != 0:
+        raise RuntimeError(f"dinov2_hip_op_dense_pack failed ({rc})")
+    return out
+
+
+DENSE_PLAN_FIELDS = ("tile_y", "tile_x", "span_y", "span_x", "pitch", "lds_bytes")
+
+
+def dense_reduce_plan(h0, w0, C_, out_h, out_w):
+    """dense_reduce_plan (csrc/kernels.h) as a dict; no device.  ValueError for sizes out of range."""
+    buf = (C.c_int64 * 6)()
+    if lib().dinov2_hip_op_dense_reduce_plan(int(h0), int(w0), int(C_), int(out_h), int(out_w), buf) != 0:
+        raise ValueError(f"dense_reduce_plan: {(h0, w0, C_, out_h, out_w)} out of range")
+    return dict(zip(DENSE_PLAN_FIELDS, (int(v) for v in buf)))
+
+
+def fold_batchnorm(weight, bias, gamma, beta, mean, var, eps=1e-5):
+    """The BatchNorm in front of a linear head folded into it (float64 arithmetic, float32 results): s = gamma / sqrt(var + eps),
+    W' = W diag(s), b' = b + W (beta - mean * s).  weight [C, K]; bias [C] or None; the four BatchNorm vectors [K]."""
+    W = np.asarray(weight, np.float64)
+    g, bt, mu, v = (np.asarray(a, np.float64) for a in (gamma, beta, mean, var))
+    s = g / np.sqrt(v + float(eps))
+    b0 = np.zeros(W.shape[0]) if bias is None else np.asarray(bias, np.float64)
+    return (W * s[None, :]).astype(np.float32), (b0 + W @ (bt - mu * s)).astype(np.float32)
 
 
 BANK_PLAN_FIELDS = ("chunk_tiles", "nchunks", "pass_tiles", "ntiles", "partial_bytes", "bytes")
@@ -385,6 +464,10 @@ def lib():
     L.dinov2_hip_bank_clear.argtypes = [vp]
     L.dinov2_hip_bank_add.argtypes = [vp, vp, C.POINTER(Rows), C.POINTER(i32), cp, sz]
     L.dinov2_hip_bank_topk.argtypes = [vp, vp, C.POINTER(TopK), cp, sz]
+    L.dinov2_hip_dense_head_create.argtypes = [vp, C.POINTER(DenseDesc), C.POINTER(vp), cp, sz]
+    L.dinov2_hip_dense_head_free.argtypes = [vp]
+    L.dinov2_hip_dense_head_free.restype = None
+    L.dinov2_hip_predict_dense.argtypes = [vp, C.POINTER(Input), C.POINTER(Output), vp, C.POINTER(DenseOut), u32, cp, sz]
     # diagnostic ops (include/dinov2_hip_ops.h)
     fp = C.POINTER(C.c_float)
     L.dinov2_hip_op_gemm.argtypes = [i32, i32, fp, fp, fp, fp, C.c_int64, fp, i32, i32, i32, i32, i32, i32, i32, i32, i32,
@@ -415,6 +498,9 @@ def lib():
     L.dinov2_hip_op_match.argtypes = [fp, i32, fp, i32, i32, C.POINTER(i32), fp, C.POINTER(i32), fp]
     L.dinov2_hip_op_bank_topk.argtypes = [fp, i32, fp, i32, i32, i32, i32, C.POINTER(i32), fp]
     L.dinov2_hip_op_bank_plan.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64)]
+    L.dinov2_hip_op_dense_reduce.argtypes = [fp, i32, i32, i32, i32, i32, i32, fp, C.c_float, C.POINTER(C.c_uint8), fp]
+    L.dinov2_hip_op_dense_pack.argtypes = [fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32, fp]
+    L.dinov2_hip_op_dense_reduce_plan.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64)]
     L.dinov2_hip_op_bank_bench.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, fp]
     L.dinov2_hip_op_clock_probe.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.dinov2_hip_op_clock_slots.argtypes = [C.POINTER(C.c_uint64)]
@@ -713,6 +799,46 @@ class Bank:
             pass
 
 
+class DenseHead:
+    """dinov2_hip_dense_head: a resident linear segmentation (reduce="argmax") or depth (reduce="bins") head over the patch tokens of `layers`
+    (include/dinov2_hip.h).  weight [C, K], K = len(layers) * H * (1 + concat_cls), column order layer-major, patch then cls; a BatchNorm in
+    front of it is folded first (fold_batchnorm)."""
+
+    def __init__(self, model: "Model", layers, weight, bias=None, *, norm: bool = True, concat_cls: bool = False, reduce: str = "argmax",
+                 bin_centers=None, bins_eps: float = 0.1):
+        ids = [int(v) for v in layers]
+        W = np.ascontiguousarray(weight, dtype=np.float32)
+        hp = model.hparams
+        K = len(ids) * int(hp.hidden_size) * (2 if concat_cls else 1)
+        if W.ndim != 2 or W.shape[1] != K:
+            raise ValueError(f"DenseHead: weight must be [C, {K}]")
+        b = np.ascontiguousarray(bias, dtype=np.float32) if bias is not None else None
+        cen = np.ascontiguousarray(bin_centers, dtype=np.float32) if bin_centers is not None else None
+        if (b is not None and b.shape != (W.shape[0],)) or (cen is not None and cen.shape != (W.shape[0],)):
+            raise ValueError("DenseHead: bias and bin_centers must be [C]")
+        arr = (C.c_int32 * max(len(ids), 1))(*ids)
+        d = DenseDesc(arr, len(ids), int(bool(norm)), int(bool(concat_cls)), W.shape[0], W.ctypes.data, b.ctypes.data if b is not None else None,
+                      _DENSE_REDUCE[reduce], cen.ctypes.data if cen is not None else None, float(bins_eps))
+        h = C.c_void_p()
+        err = _errbuf()
+        rc = lib().dinov2_hip_dense_head_create(model._h, C.byref(d), C.byref(h), err, len(err))
+        if rc != 0:
+            raise DinoError(rc, err.value.decode(errors="replace"))
+        self._h = h
+        self.layers, self.num_classes, self.reduce, self.K = ids, int(W.shape[0]), reduce, K
+
+    def free(self):
+        if getattr(self, "_h", None):
+            lib().dinov2_hip_dense_head_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Group:
     """dinov2_hip_group: N devices behind one handle -- host threads + sessions per device inside the library (two lanes per
     device by default: one lane's PCIe copies run under the other's kernels), the global batch split contiguously, outputs
@@ -904,6 +1030,53 @@ class Session:
         o = Output(cls_ptr or None, patch_ptr or None, logits_ptr or None, probs_ptr or None, None, None, 0, 1)
         err = _errbuf()
         rc = lib().dinov2_hip_predict_layers(self._h, C.byref(i), C.byref(o), C.byref(ly), CLASSIFY if classify else 0, err, len(err))
+        if rc != 0:
+            raise DinoError(rc, err.value.decode(errors="replace"))
+
+    def predict_dense(self, images: np.ndarray, head: "DenseHead", out_size=None, want=("labels", "value", "logits"), *, classify: bool = False,
+                      layout: int = RGB_CHW, topk: int = 0, predict_want=()) -> dict:
+        """One forward plus a linear dense head (dinov2_hip_predict_dense): dict of "labels" [B, oh, ow] uint8 (argmax heads), "value"
+        [B, oh, ow] f32 (the winning logit, or the bins' expectation) and "logits" [B, P, C] f32, whichever of `want` the head has, plus
+        "predict": predict()'s outputs named in `predict_want`, if any.  out_size: (out_h, out_w), None = the network input size."""
+        img = np.ascontiguousarray(images, dtype=np.uint8 if layout == U8_BGR_HWC else np.float32)
+        if img.ndim == 3:
+            img = img[None]
+        B = img.shape[0]
+        hh, ww = (img.shape[2], img.shape[3]) if layout == RGB_CHW else (img.shape[1], img.shape[2])
+        hp = self.model.hparams
+        nh, nw = preprocess_size(1 if classify else 0, hh, ww, hp.patch_size) if layout == U8_BGR_HWC else (hh, ww)
+        oh, ow = (nh, nw) if out_size is None else (int(out_size[0]), int(out_size[1]))
+        P = (nh // hp.patch_size) * (nw // hp.patch_size)
+        res = {}
+        if "labels" in want and head.reduce == "argmax":
+            res["labels"] = np.empty((B, oh, ow), np.uint8)
+        if "value" in want:
+            res["value"] = np.empty((B, oh, ow), np.float32)
+        if "logits" in want:
+            res["logits"] = np.empty((B, P, head.num_classes), np.float32)
+        ptr = lambda k: res[k].ctypes.data if k in res else None
+        do = DenseOut(0 if out_size is None else oh, 0 if out_size is None else ow, ptr("labels"), ptr("value"), ptr("logits"), 0)
+        out, o = _alloc_outputs(hp, B, hh, ww, layout, classify, topk, predict_want) if predict_want else ({}, None)
+        i = Input(img.ctypes.data, B, hh, ww, layout, 0)
+        err = _errbuf()
+        rc = lib().dinov2_hip_predict_dense(self._h, C.byref(i), C.byref(o) if o is not None else None, head._h, C.byref(do),
+                                            CLASSIFY if classify else 0, err, len(err))
+        if rc != 0:
+            raise DinoError(rc, err.value.decode(errors="replace"))
+        self._last_rows = {"last_cls": B, "last_patches": P}
+        if predict_want:
+            res["predict"] = out
+        return res
+
+    def predict_dense_device(self, img_ptr: int, B: int, hh: int, ww: int, head: "DenseHead", out_size=None, *, labels_ptr: int = 0,
+                             value_ptr: int = 0, logits_ptr: int = 0, classify: bool = False, layout: int = RGB_CHW):
+        """Asynchronous predict_dense on device-resident input and outputs (raw device pointers, 16-byte aligned): labels [B, oh, ow] uint8,
+        value [B, oh, ow] f32, logits [B, P, C] f32, any of them 0."""
+        oh, ow = (0, 0) if out_size is None else (int(out_size[0]), int(out_size[1]))
+        do = DenseOut(oh, ow, labels_ptr or None, value_ptr or None, logits_ptr or None, 1)
+        i = Input(img_ptr, B, hh, ww, layout, 1)
+        err = _errbuf()
+        rc = lib().dinov2_hip_predict_dense(self._h, C.byref(i), None, head._h, C.byref(do), CLASSIFY if classify else 0, err, len(err))
         if rc != 0:
             raise DinoError(rc, err.value.decode(errors="replace"))
 

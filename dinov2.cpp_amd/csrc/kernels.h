@@ -333,6 +333,80 @@ inline BankTopkPlan bank_topk_plan(int nq, int count, int H, int k, int chunk_ti
 hipError_t launch_bank_topk(const float* q, size_t ldq, int nq, const _Float16* bank, int count, int H, int k, char* ws, const BankTopkPlan& plan,
                             bool floor_only, hipStream_t stream);
 
+// Dense linear heads (csrc/dense.hip; contract in include/dinov2_hip.h, dinov2_hip_predict_dense): dense_pack_kernel builds the f16 operand
+// A [B P, K] of the logits GEMM straight from the residual stream at each tapped layer, launch_gemm(DT_F16, EPI_PLAIN_F32) gives the
+// low-resolution logits [B P, Cpad] f32, dense_reduce_kernel resamples them to out_h x out_w and reduces over the classes per pixel.
+constexpr int DENSE_C_MIN = 2, DENSE_C_MAX = 256, DENSE_LAYERS_MAX = 8, DENSE_OUT_MAX = 8192;
+constexpr size_t DENSE_LDS_BUDGET = (size_t)64 << 10;  // what a workgroup of dense_reduce_kernel may take (the limit no attribute has to raise)
+enum DenseReduce : int { DENSE_ARGMAX = 0, DENSE_BINS = 1 };
+// columns of the logits the GEMM writes: the weight is stored [Cpad, K] with zero rows, so that every 128- or 256-column tile reads real memory
+inline int dense_cpad(int C) { return (C + 127) / 128 * 128; }
+// floats from one staged logit row to the next in LDS: C to a multiple of 4, then an ODD number of 16-byte units, so that up to 16 neighbouring
+// rows start in 16 different 16-byte bank groups (256 classes: 260 floats)
+inline int dense_pitch(int C) { return (((C + 3) / 4) | 1) * 4; }
+// Contract 3, one axis: where output coordinate dst samples the n_in inputs.  scale = (float)n_in / (float)n_out, computed ONCE on the host.
+// Every operation rounds on its own (nothing contracted); the one source of these bits for the kernel, the planner and the host.
+__host__ __device__ inline void dense_axis(float scale, int dst, int n_in, int& i0, int& i1, float& lam) {
+#pragma clang fp contract(off)
+    const float t = scale * ((float)dst + 0.5f);
+    float src = t - 0.5f;
+    src = src < 0.0f ? 0.0f : src;
+    i0 = (int)src;
+    i0 = i0 < n_in - 1 ? i0 : n_in - 1;
+    i1 = i0 + 1 < n_in - 1 ? i0 + 1 : n_in - 1;
+    lam = src - (float)i0;
+}
+// The launch geometry of dense_reduce_kernel, decided without the device: a workgroup owns tile_y x tile_x output pixels and stages the
+// span_y x span_x low-resolution rows between the first pixel's i0 and the last pixel's i1 (per axis, the widest over all tiles) into LDS --
+// the largest tile of the list whose rows, centres and label tile fit DENSE_LDS_BUDGET.  A 1 x 1 tile needs 2 x 2 rows: some tile always fits.
+struct DenseReducePlan {
+    int tile_y, tile_x;  // 0, 0: refused arguments
+    int span_y, span_x;
+    int pitch;
+    int grid_x, grid_y;
+    float scale_y, scale_x;
+    size_t lds_bytes;
+};
+inline int dense_axis_span(float scale, int n_in, int n_out, int tile) {
+    int span = 0;
+    for (int d0 = 0; d0 < n_out; d0 += tile) {
+        const int d1 = d0 + tile < n_out ? d0 + tile - 1 : n_out - 1;
+        int lo, hi, t;
+        float lam;
+        dense_axis(scale, d0, n_in, lo, t, lam);
+        dense_axis(scale, d1, n_in, t, hi, lam);
+        span = hi - lo + 1 > span ? hi - lo + 1 : span;
+    }
+    return span;
+}
+inline DenseReducePlan dense_reduce_plan(int h0, int w0, int C, int out_h, int out_w) {
+    DenseReducePlan p{};
+    if (h0 < 1 || w0 < 1 || C < 1 || C > DENSE_C_MAX || out_h < 1 || out_w < 1 || out_h > DENSE_OUT_MAX || out_w > DENSE_OUT_MAX) return p;
+    static const int tiles[8][2] = {{16, 64}, {16, 32}, {16, 16}, {8, 16}, {8, 8}, {4, 4}, {2, 2}, {1, 1}};
+    p.scale_y = (float)h0 / (float)out_h;
+    p.scale_x = (float)w0 / (float)out_w;
+    p.pitch = dense_pitch(C);
+    for (const auto& t : tiles) {
+        const int sy = dense_axis_span(p.scale_y, h0, out_h, t[0]), sx = dense_axis_span(p.scale_x, w0, out_w, t[1]);
+        const size_t lds = (size_t)sy * sx * p.pitch * 4 + (size_t)(C + 3) / 4 * 16 + ((size_t)t[0] * t[1] + 15) / 16 * 16;
+        if (lds > DENSE_LDS_BUDGET) continue;
+        p.tile_y = t[0]; p.tile_x = t[1]; p.span_y = sy; p.span_x = sx; p.lds_bytes = lds;
+        p.grid_y = (out_h + t[0] - 1) / t[0];
+        p.grid_x = (out_w + t[1] - 1) / t[1];
+        break;
+    }
+    return p;
+}
+// x [B*T, H] f32 (the residual stream): for every PATCH row (b, p) the f16 (round to nearest even) of the row launch_layer_tap gives with the
+// same `norm` goes to A[(b P + p) lda + col0 .. + H), and with `concat_cls` that image's CLS row behind it (.. + 2 H).  16-byte stores:
+// H, lda and col0 multiples of 8, A 16-byte aligned.  H <= 2 048.
+hipError_t launch_dense_pack(const float* x, const float* w, const float* b, float eps, int B, int T, int R, int H, bool norm, bool concat_cls,
+                             _Float16* A, size_t lda, int col0, hipStream_t stream);
+// logits [B, h0 w0, ldl] f32 DEVICE (token-major, ldl % 4 == 0, 16-byte aligned) -> labels [B, out_h, out_w] u8 (ARGMAX only) and / or value
+// [B, out_h, out_w] f32, either may be nullptr; centers [C] DEVICE (BINS).  plan = dense_reduce_plan(h0, w0, C, out_h, out_w).
+hipError_t launch_dense_reduce(const float* logits, int ldl, int B, int h0, int w0, int C, int out_h, int out_w, int reduce, const float* centers,
+                               float eps, uint8_t* labels, float* value, const DenseReducePlan& plan, hipStream_t stream);
+
 // clock probe (device_types.h): per translation unit, [CLK_SLOTS][4] = running sums of shader cycles and 100 MHz ticks of workgroup 0 over
 // all launches of each kernel kind on the current device, the 100 MHz end stamp of the last one, the launch count
 hipError_t gemm_clock_probe_read(unsigned long long* out);

@@ -653,9 +653,11 @@ int prepare_pos(dinov2_hip_session* s, int B, int h, int w, char* err, size_t er
 // `img` is a DEVICE pointer.  Leaves final-LN tokens in s->fin, logits/probs in s->logits/s->probs.
 // `taps` (dinov2_hip_predict_layers): one layer_tap launch per requested layer, on x as it stands after that many layers; nullptr: none.
 // `attn` (dinov2_hip_predict_attention): one attn_rows launch per requested block, on that block's qkv right after its QKV GEMM (the next
-// block overwrites qkv; attention only reads it); nullptr: none.  Without either, the launches are those of a plain forward.
+// block overwrites qkv; attention only reads it); nullptr: none.  `dense` (dinov2_hip_predict_dense): one dense_pack launch per requested layer,
+// beside the tap; nullptr: none.  Without any of them, the launches are those of a plain forward.
 int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int layout, bool classify, int nlayers,
-            bool finalize, char* err, size_t errlen, const TapRun* taps = nullptr, const AttnRun* attn = nullptr) {
+            bool finalize, char* err, size_t errlen, const TapRun* taps = nullptr, const AttnRun* attn = nullptr,
+            const DenseRun* dense = nullptr) {
     const dinov2_hip_model* m = s->model;
     const int H = (int)m->hp.hidden_size, F = (int)m->hp.ffn_hidden, R = (int)m->hp.num_register_tokens;
     const int nh = (int)m->hp.num_attention_heads, ps = (int)m->hp.patch_size;
@@ -695,6 +697,15 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
                                 taps->reg ? taps->reg + k * taps->reg_stride : nullptr, st);
     };
     HIP_TRY(tap(0));
+    int next_pack = 0;
+    auto pack = [&](int layer) -> hipError_t {  // the same point as `tap`: this layer's patch rows as f16 into their columns of the dense operand
+        if (!dense || next_pack >= dense->n || dense->layers[next_pack] != layer) return hipSuccess;
+        const int slot = next_pack++;
+        Scope sc(s, K_LAYER_TAP);
+        return launch_dense_pack(s->x, m->ln_w, m->ln_b, eps, B, d.T, R, H, dense->norm, dense->concat_cls, dense->A, dense->lda,
+                                 slot * dense->hblk, st);
+    };
+    HIP_TRY(pack(0));
     int next_attn = 0;
     // LN fold (dinov2_hip_load_opts.ln_fold; kernels.h EPI_RESID_LN): no LayerNorm launches inside the layers.  `ln` holds T(gamma x) for the
     // NEXT LayerNorm and `stats` the row sums behind it, both written by whoever wrote x last: ln_prepare before layer 0, the residual
@@ -773,6 +784,7 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
             HIP_TRY(launch_gemm(dt, feeds_ln1 ? EPI_RESID_LN : EPI_RESID, a, st));
         }
         HIP_TRY(tap(il + 1));
+        HIP_TRY(pack(il + 1));
     }
     if (!finalize) return DINOV2_HIP_OK;
     {
@@ -945,6 +957,7 @@ extern "C" void dinov2_hip_session_free(dinov2_hip_session* s) {
     if (s->pca_buf) (void)hipFree(s->pca_buf);
     if (s->match_buf) (void)hipFree(s->match_buf);
     if (s->bank_buf) (void)hipFree(s->bank_buf);
+    if (s->dense_buf) (void)hipFree(s->dense_buf);
     if (s->tap_buf) (void)hipFree(s->tap_buf);
     if (s->attn_buf) (void)hipFree(s->attn_buf);
     if (s->attn_q) (void)hipFree(s->attn_q);
@@ -1004,10 +1017,56 @@ size_t dinov2_max_pass_batch(const dinov2_hip_model* m, int h, int w) {
 // =============================================================================================================
 // predict
 // =============================================================================================================
-// `taps`: the layer taps of dinov2_hip_predict_layers, `attn`: the attention rows of dinov2_hip_predict_attention (device pointers); nullptr
-// for a plain predict
+// One pass of dinov2_hip_predict_dense: the head, the caller's request, the first image of this pass within the caller's batch, the output grid
+// and where one pass's operand, logits and staged host outputs sit in the session's dense scratch.
+struct DenseCall {
+    const dinov2_hip_dense_head* head = nullptr;
+    const dinov2_hip_dense_out* out = nullptr;
+    size_t b0 = 0;
+    int oh = 0, ow = 0;
+    size_t a16 = 0, lg = 0, lab = 0, val = 0;
+};
+
+// The dense stage of one pass of B images at network input size h x w, after its forward: the logits GEMM over the packed operand, the
+// copy-out of the low-resolution logits, the resampling reduction, each output at this pass's image offset.  Enqueues only.
+static int dense_stage(dinov2_hip_session* s, const DenseCall& dc, int B, int h, int w, char* err, size_t errlen) {
+    const dinov2_hip_model* m = s->model;
+    const dinov2_hip_dense_head* hd = dc.head;
+    const dinov2_hip_dense_out* o = dc.out;
+    const int ps = (int)m->hp.patch_size, h0 = h / ps, w0 = w / ps;
+    const size_t P = (size_t)h0 * w0, M = (size_t)B * P, K = (size_t)hd->K, C = (size_t)hd->C, cpad = (size_t)hd->cpad;
+    hipStream_t st = s->stream;
+    _Float16* const A = (_Float16*)(s->dense_buf + dc.a16);
+    float* const lg = (float*)(s->dense_buf + dc.lg);
+    Scope sc(s, K_HEAD);
+    // (the GEMM's staging cursors are 32-bit byte offsets from A: row chunks below 2^31 bytes.  A row's bits do not depend on the chunking.)
+    const size_t chunk = std::max<size_t>(256, (((size_t)1 << 31) / (K * 2)) / 256 * 256);
+    for (size_t r0 = 0; r0 < M; r0 += chunk) {
+        GemmArgs a{};
+        a.A = A + r0 * K; a.W = hd->w16; a.bias = hd->bias; a.out = lg + r0 * cpad;
+        a.M = (int)std::min(chunk, M - r0); a.N = (int)cpad; a.K = (int)K; a.ldo = (int)cpad;
+        HIP_TRY(launch_gemm(DT_F16, EPI_PLAIN_F32, a, st));
+    }
+    const hipMemcpyKind kind = o->on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (o->logits)
+        HIP_TRY(hipMemcpy2DAsync(o->logits + dc.b0 * P * C, C * 4, lg, cpad * 4, C * 4, M, kind, st));
+    if (!o->labels && !o->value) return DINOV2_HIP_OK;
+    const size_t npx = (size_t)dc.oh * dc.ow;
+    uint8_t* lab = o->labels ? (o->on_device ? o->labels + dc.b0 * npx : (uint8_t*)(s->dense_buf + dc.lab)) : nullptr;
+    float* val = o->value ? (o->on_device ? o->value + dc.b0 * npx : (float*)(s->dense_buf + dc.val)) : nullptr;
+    const DenseReducePlan plan = dense_reduce_plan(h0, w0, hd->C, dc.oh, dc.ow);
+    HIP_TRY(launch_dense_reduce(lg, (int)cpad, B, h0, w0, hd->C, dc.oh, dc.ow, hd->reduce, hd->centers, hd->eps, lab, val, plan, st));
+    if (!o->on_device) {
+        if (lab) HIP_TRY(hipMemcpyAsync(o->labels + dc.b0 * npx, lab, (size_t)B * npx, hipMemcpyDeviceToHost, st));
+        if (val) HIP_TRY(hipMemcpyAsync(o->value + dc.b0 * npx, val, (size_t)B * npx * 4, hipMemcpyDeviceToHost, st));
+    }
+    return DINOV2_HIP_OK;
+}
+
+// `taps`: the layer taps of dinov2_hip_predict_layers, `attn`: the attention rows of dinov2_hip_predict_attention (device pointers), `dense`:
+// the head and outputs of dinov2_hip_predict_dense; nullptr for a plain predict
 static int predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out, uint32_t flags, const TapRun* taps,
-                        const AttnRun* attn, char* err, size_t errlen) {
+                        const AttnRun* attn, char* err, size_t errlen, const DenseCall* dense = nullptr) {
     int rc = check_input(s, in, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
     const dinov2_hip_model* m = s->model;
@@ -1072,7 +1131,13 @@ static int predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dinov
                     ca = *attn;
                     ca.probs += b0 * (size_t)m->hp.num_attention_heads * (size_t)ca.nq * (size_t)ca.nkeys;
                 }
-                rc = predict_impl(s, &ci, out ? &co : nullptr, flags, taps ? &ct : nullptr, attn ? &ca : nullptr, err, errlen);
+                DenseCall cd;
+                if (dense) {  // this pass's images at their offset in every output; the scratch is one pass's and is reused
+                    cd = *dense;
+                    cd.b0 = dense->b0 + b0;
+                }
+                rc = predict_impl(s, &ci, out ? &co : nullptr, flags, taps ? &ct : nullptr, attn ? &ca : nullptr, err, errlen,
+                                  dense ? &cd : nullptr);
                 if (rc != DINOV2_HIP_OK) return rc;
             }
             s->last_b = 0;  // the workspace holds chunk 0 only: nothing for dinov2_hip_fetch
@@ -1109,9 +1174,25 @@ static int predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dinov
     rc = prepare_pos(s, B, h, w, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
     // (a tapped forward runs eagerly, past the graph cache: its key knows nothing of the caller's tap pointers)
-    rc = taps || attn ? forward(s, img, B, h, w, layout, classify, (int)m->hp.num_hidden_layers, true, err, errlen, taps, attn)
-                      : forward_maybe_graph(s, img, B, h, w, layout, classify, err, errlen);
+    DenseRun dr;
+    if (dense) {
+        const dinov2_hip_dense_head* hd = dense->head;
+        dr.layers = hd->layers;
+        dr.n = hd->n_layers;
+        dr.norm = hd->norm;
+        dr.concat_cls = hd->concat_cls;
+        dr.A = (_Float16*)(s->dense_buf + dense->a16);
+        dr.lda = (size_t)hd->K;
+        dr.hblk = hd->H * (hd->concat_cls ? 2 : 1);
+    }
+    rc = taps || attn || dense
+             ? forward(s, img, B, h, w, layout, classify, (int)m->hp.num_hidden_layers, true, err, errlen, taps, attn, dense ? &dr : nullptr)
+             : forward_maybe_graph(s, img, B, h, w, layout, classify, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
+    if (dense) {
+        rc = dense_stage(s, *dense, B, h, w, err, errlen);
+        if (rc != DINOV2_HIP_OK) return rc;
+    }
     {  // what dinov2_hip_pca3(tokens = NULL) works on: the patch rows of image 0 in `fin`
         const Dims dd = dims_of(m, B, h, w);
         s->last_first = classify ? 1 : 1 + (int)m->hp.num_register_tokens;
@@ -1918,5 +1999,163 @@ extern "C" int dinov2_hip_bank_topk(dinov2_hip_session* s, const dinov2_hip_bank
     if (q->idx) HIP_TRY(hipMemcpyAsync(q->idx, buf + plan.idx, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
     if (q->sim) HIP_TRY(hipMemcpyAsync(q->sim, buf + plan.sim, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return DINOV2_HIP_OK;
+}
+
+// =============================================================================================================
+// linear dense-prediction heads (csrc/dense.hip; no reference counterpart; upstream DINOv2: BNHead of eval/segmentation and eval/depth)
+// =============================================================================================================
+extern "C" int dinov2_hip_dense_head_create(dinov2_hip_model* model, const dinov2_hip_dense_desc* d, dinov2_hip_dense_head** out, char* err,
+                                            size_t errlen) {
+    if (!model || !d || !out || !d->layers || !d->weight) {
+        set_err(err, errlen, "dense_head_create: null model / desc / out / layer list / weight");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    const int L = (int)model->hp.num_hidden_layers, H = (int)model->hp.hidden_size;
+    if (d->n_layers < 1 || d->n_layers > DENSE_LAYERS_MAX) {
+        set_err(err, errlen, "dense_head_create: n_layers %d outside 1 .. %d", (int)d->n_layers, DENSE_LAYERS_MAX);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    for (int i = 0; i < d->n_layers; ++i)
+        if (d->layers[i] < 0 || d->layers[i] > L || (i > 0 && d->layers[i] <= d->layers[i - 1])) {
+            set_err(err, errlen, "dense_head_create: the layer list must be strictly ascending, each layer in 0 .. %d", L);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+    if (d->num_classes < DENSE_C_MIN || d->num_classes > DENSE_C_MAX) {
+        set_err(err, errlen, "dense_head_create: num_classes %d outside %d .. %d", (int)d->num_classes, DENSE_C_MIN, DENSE_C_MAX);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (d->reduce != DINOV2_HIP_DENSE_ARGMAX && d->reduce != DINOV2_HIP_DENSE_BINS) {
+        set_err(err, errlen, "dense_head_create: unknown reduce %d", (int)d->reduce);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (d->reduce == DINOV2_HIP_DENSE_BINS && (!d->bin_centers || !(d->bins_eps > 0.0f))) {
+        set_err(err, errlen, "dense_head_create: DINOV2_HIP_DENSE_BINS needs bin_centers and bins_eps > 0");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (H % 64 != 0 || H > 2048) {
+        set_err(err, errlen, "dense_head_create: hidden size %d is not a multiple of 64 up to 2048", H);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    std::unique_ptr<dinov2_hip_dense_head> hd(new dinov2_hip_dense_head);
+    hd->device = model->device;
+    hd->H = H;
+    hd->L = L;
+    hd->n_layers = d->n_layers;
+    for (int i = 0; i < d->n_layers; ++i) hd->layers[i] = d->layers[i];
+    hd->norm = d->norm != 0;
+    hd->concat_cls = d->concat_cls != 0;
+    hd->C = d->num_classes;
+    hd->cpad = dense_cpad(hd->C);
+    hd->K = d->n_layers * H * (hd->concat_cls ? 2 : 1);
+    hd->reduce = d->reduce;
+    hd->eps = d->reduce == DINOV2_HIP_DENSE_BINS ? d->bins_eps : 0.0f;
+    const size_t C = (size_t)hd->C, cpad = (size_t)hd->cpad, K = (size_t)hd->K;
+    const size_t wbytes = align_up(cpad * K * 2, 256), vbytes = align_up(cpad * 4, 256), bytes = wbytes + 2 * vbytes;
+    std::vector<char> host(bytes, 0);  // rows past C of the weight, the bias and the centres stay zero
+    _Float16* const w16 = (_Float16*)host.data();
+    for (size_t i = 0; i < C * K; ++i) w16[i] = (_Float16)d->weight[i];  // round to nearest even
+    if (d->bias) std::memcpy(host.data() + wbytes, d->bias, C * 4);
+    if (d->reduce == DINOV2_HIP_DENSE_BINS) std::memcpy(host.data() + wbytes + vbytes, d->bin_centers, C * 4);
+    HIP_TRY(hipSetDevice(model->device));
+    hipError_t e = hipMalloc((void**)&hd->dev, bytes);
+    if (e == hipSuccess) {
+        e = hipMemcpy(hd->dev, host.data(), bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) (void)hipFree(hd->dev);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // (not left behind for the next launch to report)
+        set_err(err, errlen, "dense_head_create: %zu bytes refused: %s", bytes, hipGetErrorString(e));
+        return DINOV2_HIP_ERR_HIP;
+    }
+    hd->w16 = (_Float16*)hd->dev;
+    hd->bias = (float*)(hd->dev + wbytes);
+    hd->centers = (float*)(hd->dev + wbytes + vbytes);
+    *out = hd.release();
+    return DINOV2_HIP_OK;
+}
+
+extern "C" void dinov2_hip_dense_head_free(dinov2_hip_dense_head* hd) {
+    if (!hd) return;
+    (void)hipSetDevice(hd->device);
+    (void)hipDeviceSynchronize();  // a session's stream may still be reading the weight
+    if (hd->dev) (void)hipFree(hd->dev);
+    delete hd;
+}
+
+extern "C" int dinov2_hip_predict_dense(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out,
+                                        const dinov2_hip_dense_head* hd, const dinov2_hip_dense_out* o, uint32_t flags, char* err,
+                                        size_t errlen) {
+    int rc = check_input(s, in, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    const dinov2_hip_model* m = s->model;
+    if (!hd || !o) {
+        set_err(err, errlen, "predict_dense: null head / outputs");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (hd->device != m->device) {
+        set_err(err, errlen, "predict_dense: the session is on device %d, the head on device %d", m->device, hd->device);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (hd->H != (int)m->hp.hidden_size || hd->L != (int)m->hp.num_hidden_layers) {
+        set_err(err, errlen, "predict_dense: the head was created for hidden size %d and %d layers, the session's model has %d and %d", hd->H, hd->L,
+                (int)m->hp.hidden_size, (int)m->hp.num_hidden_layers);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (!o->labels && !o->value && !o->logits) {
+        set_err(err, errlen, "predict_dense: no output requested");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (o->labels && hd->reduce == DINOV2_HIP_DENSE_BINS) {
+        set_err(err, errlen, "predict_dense: labels requested from a DINOV2_HIP_DENSE_BINS head");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    int h, w;
+    network_size(m, in, flags, &h, &w);
+    const bool own_size = o->out_h == 0 && o->out_w == 0;
+    const int oh = own_size ? h : o->out_h, ow = own_size ? w : o->out_w;
+    if (oh < 1 || ow < 1 || oh > DENSE_OUT_MAX || ow > DENSE_OUT_MAX) {
+        set_err(err, errlen, "predict_dense: output size %d x %d outside 1 .. %d (0, 0 = the network input size)", oh, ow, DENSE_OUT_MAX);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (o->on_device && ((reinterpret_cast<uintptr_t>(o->labels) | reinterpret_cast<uintptr_t>(o->value) | reinterpret_cast<uintptr_t>(o->logits)) & 15)) {
+        set_err(err, errlen, "device pointers of dinov2_hip_dense_out must be 16-byte aligned");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    rc = check_predict_args(m, out, flags, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    HIP_TRY(hipSetDevice(m->device));
+    // the scratch of ONE pass: operand, logits (rows to whole 256-row tiles), and what host outputs are staged in
+    const Dims d1 = dims_of(m, 1, h, w);
+    const size_t B = (size_t)in->batch, Bp = std::min(B, dinov2_max_pass_batch(m, h, w));
+    const size_t rows = align_up(Bp * (size_t)d1.P, 256), npx = (size_t)oh * ow;
+    DenseCall dc;
+    dc.head = hd;
+    dc.out = o;
+    dc.oh = oh;
+    dc.ow = ow;
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t off = need; need += align_up(bytes, 256); return off; };
+    dc.a16 = take(rows * (size_t)hd->K * 2);
+    dc.lg = take(rows * (size_t)hd->cpad * 4);
+    dc.lab = take(!o->on_device && o->labels ? Bp * npx : 0);
+    dc.val = take(!o->on_device && o->value ? Bp * npx * 4 : 0);
+    if (need > s->dense_bytes) {
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        if (s->dense_buf) HIP_TRY(hipFree(s->dense_buf));
+        s->dense_buf = nullptr;
+        s->dense_bytes = 0;
+        const hipError_t e = hipMalloc((void**)&s->dense_buf, need);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            s->dense_buf = nullptr;
+            set_err(err, errlen, "predict_dense: %zu bytes of scratch refused: %s", need, hipGetErrorString(e));
+            return DINOV2_HIP_ERR_HIP;
+        }
+        s->dense_bytes = need;
+    }
+    rc = predict_impl(s, in, out, flags, nullptr, nullptr, err, errlen, &dc);
+    if (rc != DINOV2_HIP_OK) return rc;
+    if (!o->on_device) HIP_TRY(hipStreamSynchronize(s->stream));  // host outputs are complete on return
     return DINOV2_HIP_OK;
 }

@@ -41,6 +41,17 @@ struct AttnRun {
     size_t stride = 0;
 };
 
+// The operand packing of ONE pass of dinov2_hip_predict_dense: at requested layer i (slot i) dense_pack_kernel writes the f16 patch rows of this
+// pass's images into columns [i * hblk, (i + 1) * hblk) of A [B P, lda] -- the operand of the logits GEMM, in the session's dense scratch.
+struct DenseRun {
+    const int32_t* layers = nullptr;  // [n] strictly ascending, each in [0, L]
+    int n = 0;
+    bool norm = false, concat_cls = false;
+    _Float16* A = nullptr;
+    size_t lda = 0;
+    int hblk = 0;  // H * (1 + concat_cls)
+};
+
 }  // namespace dinov2
 
 // replaces `struct dino_model` (/root/reference/dinov2.h:49-55): hparams + one device buffer + name->tensor map
@@ -82,6 +93,8 @@ struct dinov2_hip_session {
     size_t match_bytes = 0;
     char* bank_buf = nullptr;  // scratch of dinov2_hip_bank_add / dinov2_hip_bank_topk (staged host rows, f16 queries, partials, results)
     size_t bank_bytes = 0;
+    char* dense_buf = nullptr;  // scratch of dinov2_hip_predict_dense (the f16 operand and the logits of one pass, host outputs' staging)
+    size_t dense_bytes = 0;
     float* tap_buf = nullptr;  // dinov2_hip_predict_layers with host outputs: where the tap kernel writes before the copy-out; grown on demand
     size_t tap_bytes = 0;
     float* attn_buf = nullptr;  // dinov2_hip_predict_attention with a host output: where attn_rows_kernel writes before the copy-out; grown on demand
@@ -124,6 +137,22 @@ struct dinov2_hip_bank {
     int device = 0;
     int H = 0, hpad = 0, capacity = 0, cap_pad = 0, count = 0;
     _Float16* rows = nullptr;
+};
+
+// A resident linear dense-prediction head (dinov2_hip_dense_head_*): one device allocation made at create -- the f16 weight [cpad, K] with zero
+// rows past C, the bias [cpad] (zeros without one) and the bin centres [cpad] -- never moved.  It keeps the device ordinal and the two sizes of
+// the model it was created for, so it may outlive that model.
+struct dinov2_hip_dense_head {
+    int device = 0;
+    int H = 0, L = 0;  // hidden size and number of blocks of the model it was created for
+    int n_layers = 0;
+    int32_t layers[dinov2::DENSE_LAYERS_MAX] = {};
+    bool norm = false, concat_cls = false;
+    int C = 0, cpad = 0, K = 0, reduce = 0;
+    float eps = 0.0f;
+    char* dev = nullptr;
+    _Float16* w16 = nullptr;
+    float *bias = nullptr, *centers = nullptr;
 };
 
 // Internal (not C-ABI) helpers shared by model.cpp and group.cpp.

@@ -850,3 +850,89 @@ extern "C" int dinov2_hip_op_pca_chol_rinv(const double* gram, double* rinv) {
     pca_chol_rinv(gram, rinv);
     return DINOV2_HIP_OK;
 }
+
+// ---- the kernels of csrc/dense.hip (dinov2_hip_predict_dense) on host data ----
+extern "C" int dinov2_hip_op_dense_reduce_plan(int32_t h0, int32_t w0, int32_t C, int32_t out_h, int32_t out_w, int64_t* out) {
+    const DenseReducePlan p = dense_reduce_plan(h0, w0, C, out_h, out_w);
+    if (!out || p.tile_y == 0) return DINOV2_HIP_ERR_INVALID;
+    out[0] = p.tile_y;
+    out[1] = p.tile_x;
+    out[2] = p.span_y;
+    out[3] = p.span_x;
+    out[4] = p.pitch;
+    out[5] = (int64_t)p.lds_bytes;
+    return 0;
+}
+extern "C" int dinov2_hip_op_dense_reduce(const float* logits, int32_t h0, int32_t w0, int32_t C, int32_t out_h, int32_t out_w, int32_t reduce,
+                                          const float* centers, float eps, uint8_t* labels, float* value) {
+    const DenseReducePlan plan = dense_reduce_plan(h0, w0, C, out_h, out_w);
+    if (!logits || plan.tile_y == 0 || (reduce != DENSE_ARGMAX && reduce != DENSE_BINS)) return DINOV2_HIP_ERR_INVALID;
+    if (reduce == DENSE_BINS ? (!centers || !(eps > 0.0f) || labels || !value) : (!labels && !value)) return DINOV2_HIP_ERR_INVALID;
+    const size_t P = (size_t)h0 * w0, ldl = (size_t)dense_cpad(C), npx = (size_t)out_h * out_w, ng = (size_t)DINOV2_HIP_OP_GUARD_ROWS * out_w;
+    DevBuf dL, dC, dLab, dVal;
+    OP_TRY(dL.alloc(P * ldl * 4));
+    OP_TRY(hipMemset(dL.p, 0xff, P * ldl * 4));  // the columns past C stay NaN: the kernel must not let them into a result
+    OP_TRY(hipMemcpy2D(dL.p, ldl * 4, logits, (size_t)C * 4, (size_t)C * 4, P, hipMemcpyHostToDevice));
+    if (reduce == DENSE_BINS) {
+        OP_TRY(dC.alloc((size_t)C * 4));
+        OP_TRY(hipMemcpy(dC.p, centers, (size_t)C * 4, hipMemcpyHostToDevice));
+    }
+    if (labels) {
+        OP_TRY(dLab.alloc(npx + 2 * ng));
+        OP_TRY(hipMemset(dLab.p, 0xff, npx + 2 * ng));
+    }
+    if (value) {
+        OP_TRY(dVal.alloc((npx + 2 * ng) * 4));
+        OP_TRY(hipMemset(dVal.p, 0xff, (npx + 2 * ng) * 4));
+    }
+    OP_TRY(launch_dense_reduce((const float*)dL.p, (int)ldl, 1, h0, w0, C, out_h, out_w, reduce, (const float*)dC.p, eps,
+                               labels ? (uint8_t*)dLab.p + ng : nullptr, value ? (float*)dVal.p + ng : nullptr, plan, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    if (labels) {
+        std::vector<uint8_t> raw(npx + 2 * ng);
+        OP_TRY(hipMemcpy(raw.data(), dLab.p, raw.size(), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < ng; ++k)
+            if (raw[k] != 0xff || raw[ng + npx + k] != 0xff) return DINOV2_HIP_OP_GUARD_CHANGED;
+        std::memcpy(labels, raw.data() + ng, npx);
+    }
+    if (value) {
+        std::vector<uint32_t> raw(npx + 2 * ng);
+        OP_TRY(hipMemcpy(raw.data(), dVal.p, raw.size() * 4, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < ng; ++k)
+            if (raw[k] != 0xffffffffu || raw[ng + npx + k] != 0xffffffffu) return DINOV2_HIP_OP_GUARD_CHANGED;
+        std::memcpy(value, raw.data() + ng, npx * 4);
+    }
+    return 0;
+}
+extern "C" int dinov2_hip_op_dense_pack(const float* x, const float* ln_w, const float* ln_b, float eps, int32_t B, int32_t T, int32_t R, int32_t H,
+                                        int32_t norm, int32_t concat_cls, int32_t slot, int32_t nslots, float* out) {
+    if (!x || !out || B <= 0 || H <= 0 || H % 8 != 0 || R < 0 || T < 2 + R || nslots < 1 || nslots > DENSE_LAYERS_MAX || slot < 0 || slot >= nslots)
+        return DINOV2_HIP_ERR_INVALID;
+    if (norm && (!ln_w || !ln_b)) return DINOV2_HIP_ERR_INVALID;
+    const size_t P = (size_t)(T - 1 - R), hblk = (size_t)H * (concat_cls ? 2 : 1), K = hblk * nslots, n = (size_t)B * P * K;
+    const size_t nx = (size_t)B * T * H, ng = (size_t)DINOV2_HIP_OP_GUARD_ROWS * K;
+    DevBuf dX, dW, dB, dA;
+    OP_TRY(dX.alloc(nx * 4));
+    OP_TRY(hipMemcpy(dX.p, x, nx * 4, hipMemcpyHostToDevice));
+    if (norm) {
+        OP_TRY(dW.alloc((size_t)H * 4));
+        OP_TRY(dB.alloc((size_t)H * 4));
+        OP_TRY(hipMemcpy(dW.p, ln_w, (size_t)H * 4, hipMemcpyHostToDevice));
+        OP_TRY(hipMemcpy(dB.p, ln_b, (size_t)H * 4, hipMemcpyHostToDevice));
+    }
+    OP_TRY(dA.alloc((n + 2 * ng) * 2));
+    OP_TRY(hipMemset(dA.p, 0xff, (n + 2 * ng) * 2));
+    OP_TRY(launch_dense_pack((const float*)dX.p, (const float*)dW.p, (const float*)dB.p, eps, B, T, R, H, norm != 0, concat_cls != 0,
+                             (_Float16*)dA.p + ng, K, (int)(slot * hblk), nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    std::vector<uint16_t> raw(n + 2 * ng);
+    OP_TRY(hipMemcpy(raw.data(), dA.p, raw.size() * 2, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < ng; ++k)
+        if (raw[k] != 0xffffu || raw[ng + n + k] != 0xffffu) return DINOV2_HIP_OP_GUARD_CHANGED;
+    for (size_t i = 0; i < n; ++i) {
+        _Float16 hv;
+        std::memcpy(&hv, &raw[ng + i], 2);
+        out[i] = (float)hv;
+    }
+    return 0;
+}

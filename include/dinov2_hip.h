@@ -421,6 +421,94 @@ typedef struct dinov2_hip_topk {
  * count and k.  An allocation the device refuses returns DINOV2_HIP_ERR_HIP. */
 int  dinov2_hip_bank_topk(dinov2_hip_session *s, const dinov2_hip_bank *bank, const dinov2_hip_topk *q, char *err, size_t errlen);
 
+/* -- linear dense-prediction heads (no reference counterpart: semantic segmentation and depth estimation with a linear head on frozen
+ *    patch features, two of the evaluation protocols of the DINOv2 paper; upstream: BNHead of
+ *    dinov2/eval/segmentation/models/decode_heads/linear_head.py and of dinov2/eval/depth/models/decode_heads/linear_head.py).  A resident head
+ *    -- a 1x1 convolution over the concatenated patch tokens of up to 8 layers -- and ONE call that runs the forward and returns a label map
+ *    or a depth map [B, out_h, out_w]: the tapped tokens, the low-resolution logits and the resampling all stay on the device, and the
+ *    full-resolution logit planes never exist.  On the device (csrc/dense.hip): at each requested layer one kernel writes the patch rows as
+ *    f16 into their columns of the operand A [B P, K]; one plain GEMM on the matrix cores gives the low-resolution logits; one kernel
+ *    interpolates them per output pixel and reduces over the classes.  The head is one device allocation made at create (f16 weight, bias,
+ *    centres) and never moved; it keeps the device ordinal, the hidden size and the number of layers only, so it may outlive the model; one
+ *    host thread at a time uses a session with it.
+ *    BatchNorm (upstream's BNHead normalises the concatenated features before the convolution) is folded by the caller: with
+ *        s = gamma / sqrt(var + eps)      (per input channel k)
+ *        W' = W diag(s)                   W'[c][k] = W[c][k] s[k]
+ *        b' = b + W (beta - mean * s)
+ *    pass W' and b' (the Python binding has fold_batchnorm).
+ *    Contract:
+ *    1. Operands.  Row (b, p) of A is, per requested layer in list order, f16 (round to nearest even) of exactly the f32 bits
+ *       dinov2_hip_predict_layers gives for that patch row with the same `norm`; with concat_cls that image's CLS row of the same layer
+ *       follows (so K = n_layers * H * (1 + concat_cls), layer-major, patch then cls).  W^ = f16(W).  The operands are f16 whatever the
+ *       model's compute type, as for dinov2_hip_pca3 and dinov2_hip_match.  Values must lie within the f16 range; outside it the result is
+ *       unspecified.
+ *    2. Low-resolution logits.  L[b][p][c] = sum_k A^ W^ + bias[c]: the products are exact in f32, the accumulation is f32 on the matrix
+ *       cores in an order that depends on K alone, the bias is added last.  An image's logits are bit-identical whatever batch it travels
+ *       in, and whether or not the batch is split into passes.
+ *    3. Resampling.  Bilinear, half-pixel centres, PyTorch's align_corners=False, all in f32, per axis (n_in = h0 or w0, n_out = out_h or out_w):
+ *           scale = (float)n_in / (float)n_out
+ *           src   = max(scale * (dst + 0.5f) - 0.5f, 0)
+ *           i0 = min((int)src, n_in - 1),  i1 = min(i0 + 1, n_in - 1),  lambda = src - i0
+ *       and with the four neighbours v00 (y i0, x i0), v01 (y i0, x i1), v10, v11 of class c:
+ *           t = (1 - lx) * v00 + lx * v01,   u = (1 - lx) * v10 + lx * v11,   val = (1 - ly) * t + ly * u
+ *       Every multiplication and addition is rounded on its own; nothing is contracted into a fused multiply-add.  A numpy float32
+ *       restatement gives the same bits (tests/dense_cases.py).
+ *    4. ARGMAX.  labels = the argmax over c of val_c; equal values go to the LOWEST class (-0 equals +0); `value` is that val.  The argmax
+ *       is taken after the interpolation, never before it.
+ *    5. BINS.  r_c = max(val_c, 0) + eps,  S = sum_c r_c,  D = sum_c r_c * center_c, both sums in f32, sequential in ascending c (an order
+ *       that depends on C alone), uncontracted;  value = D / S with a correctly rounded division.
+ *    6. Independence.  A pixel's result does not depend on launch geometry, on how out_h x out_w is tiled, or on the other images.
+ *    Out of scope: the device group (dinov2_hip_group_*); dinov2_compat.hpp; C > 256; softmax probabilities; the final scalar resize of a
+ *    depth map to the image size (upstream reduces over the bins at 4 h0 x 4 w0: pass that as out_h, out_w); multi-scale or sliding-window
+ *    inference; reading head weights from GGUF or mmseg checkpoints; hidden sizes that are not a multiple of 64.
+ *    Times: profiles/dense_head.md. */
+enum dinov2_hip_dense_reduce { DINOV2_HIP_DENSE_ARGMAX = 0, DINOV2_HIP_DENSE_BINS = 1 };
+typedef struct dinov2_hip_dense_head dinov2_hip_dense_head;
+typedef struct dinov2_hip_dense_desc {
+    const int32_t *layers;    /* as dinov2_hip_layers: strictly ascending, each in [0, L] (number of blocks applied) */
+    int32_t n_layers;         /* 1 .. 8 */
+    int32_t norm;             /* 1: the model's final LayerNorm on the tapped rows (upstream default) */
+    int32_t concat_cls;       /* 1: every layer's block is [patch row ; CLS row of that image] (upstream's depth heads) */
+    int32_t num_classes;      /* C, 2 .. 256 */
+    const float *weight;      /* HOST [C, K] f32, K = n_layers * H * (1 + concat_cls); column order: layer-major, patch then cls */
+    const float *bias;        /* HOST [C] or NULL */
+    int32_t reduce;           /* DINOV2_HIP_DENSE_ARGMAX | DINOV2_HIP_DENSE_BINS */
+    const float *bin_centers; /* HOST [C], BINS only */
+    float bins_eps;           /* BINS only, > 0 (upstream 0.1) */
+    int32_t reserved[6];
+} dinov2_hip_dense_desc;
+/* Copies what `desc` points to: the caller's arrays may go afterwards.  Argument errors (NULL model, desc, out, layer list or weight; a bad
+ * layer list; num_classes out of range; an unknown reduce; BINS without centres or with bins_eps <= 0; a hidden size that is not a
+ * multiple of 64) return DINOV2_HIP_ERR_INVALID before anything is launched, allocated or copied.  An allocation the device refuses returns
+ * DINOV2_HIP_ERR_HIP. */
+int  dinov2_hip_dense_head_create(dinov2_hip_model *model, const dinov2_hip_dense_desc *desc, dinov2_hip_dense_head **out, char *err,
+                                  size_t errlen);
+/* waits for the device first: a session's stream may still be reading the weight */
+void dinov2_hip_dense_head_free(dinov2_hip_dense_head *head);
+
+typedef struct dinov2_hip_dense_out {
+    int32_t out_h, out_w;  /* the grid on which the reduction over C runs; 0, 0 = the network input size; otherwise each 1 .. 8192 */
+    uint8_t *labels;       /* [B, out_h, out_w], ARGMAX only */
+    float   *value;        /* [B, out_h, out_w]; ARGMAX: the winning interpolated logit, BINS: the expectation D / S */
+    float   *logits;       /* [B, P, C] token-major low-resolution logits (contract 2); any of the three may be NULL, not all */
+    int32_t on_device;     /* as dinov2_hip_layers: 0 host (staged in the session's scratch, one stream wait at the end), 1 device pointers,
+                              16-byte aligned, written asynchronously on the session's stream */
+    int32_t reserved[4];
+} dinov2_hip_dense_out;
+/* `out` (may be NULL) and `flags` as for dinov2_hip_predict: one call returns the classifier's logits and the dense prediction of the same
+ * forward.  The patch rows are rows 1 + R .. T - 1, with or without DINOV2_HIP_CLASSIFY.  Argument errors (NULL session, input, head or
+ * `dense`; out_h or out_w out of range, the network input size with 0, 0 included; `labels` requested from a BINS head; all three outputs
+ * NULL; a device pointer that is not 16-byte aligned; a head created for a model with another hidden size or number of layers; a session
+ * on another device than the head; those of dinov2_hip_predict) return their status before anything is launched, allocated or copied, with
+ * the outputs untouched.  A batch that is split into passes runs the dense stage once per pass, each pass writing at its image offset.  The
+ * call runs eagerly under DINOV2_HIP_GRAPHS=1.  dinov2_hip_fetch, dinov2_hip_pca3(tokens = NULL), dinov2_hip_match_tokens and the
+ * dinov2_hip_bank_* calls behave afterwards as after a dinov2_hip_predict of the same shape.  The scratch (the f16 operand and the logits
+ * of one pass, rows rounded up to 256, and host outputs' staging) is a session-owned buffer grown on demand; an allocation the device
+ * refuses returns DINOV2_HIP_ERR_HIP.  In dinov2_hip_session_profile the packing launches are booked under "layer_tap", the GEMM and the
+ * reduction under "head". */
+int dinov2_hip_predict_dense(dinov2_hip_session *session, const dinov2_hip_input *in, dinov2_hip_output *out /* may be NULL */,
+                             const dinov2_hip_dense_head *head, const dinov2_hip_dense_out *dense, uint32_t flags, char *err, size_t errlen);
+
 /* -- quantise a GGUF (replaces dino_model_quantize, dinov2.h:118 / dinov2.cpp:355-453).  Host only.
  *    itype: ggml type id 2 q4_0, 3 q4_1, 6 q5_0, 7 q5_1, 8 q8_0.  2-D tensors named `*weight` are re-encoded, the rest copied. */
 int dinov2_hip_quantize(const char *fname_inp, const char *fname_out, int32_t itype, char *err, size_t errlen);

@@ -182,6 +182,22 @@ int dinov2_hip_op_bank_plan(int32_t nq, int32_t nb, int32_t H, int32_t k, int32_
 int dinov2_hip_op_bank_bench(const float *q_dev, int32_t nq, const float *b_dev, int32_t nb, int32_t H, int32_t k, int32_t chunk_tiles,
                              int32_t warmup, int32_t iters, int32_t floor_only, float *ms);
 
+/* the two kernels of csrc/dense.hip (behind dinov2_hip_predict_dense) without a model or session; cases and the numpy restatement:
+ * tests/dense_cases.py.
+ * dense_reduce: host logits [h0 * w0, C] f32 (one image, token-major) -> labels [out_h, out_w] u8 (ARGMAX only; NULL otherwise) and / or value
+ *               [out_h, out_w] f32, contracts 3 - 5 of dinov2_hip_predict_dense.  reduce 0 ARGMAX, 1 BINS (centers [C], eps > 0).  1 <= C <= 256,
+ *               out_h, out_w 1 .. 8192.  Each device output is framed by guard bands of DINOV2_HIP_OP_GUARD_ROWS * out_w elements and starts as
+ *               0xff bytes; a changed guard returns DINOV2_HIP_OP_GUARD_CHANGED.
+ * dense_pack:   x [B, T, H] f32, T = 1 + R + P -> out_f16_as_f32 [B * P, nslots * H * (1 + concat_cls)]: the f32 values of the f16 operand after
+ *               ONE dense_pack launch into column block `slot`; the other blocks come back as NaN (the operand starts as 0xff bytes and is
+ *               framed by guard bands).  norm = 1: LayerNorm (w, b, eps); H % 8 == 0.
+ * dense_reduce_plan (no device): out[0 .. 5] = tile_y, tile_x, span_y, span_x, pitch, LDS bytes of dense_reduce_plan (csrc/kernels.h). */
+int dinov2_hip_op_dense_reduce(const float *logits, int32_t h0, int32_t w0, int32_t C, int32_t out_h, int32_t out_w, int32_t reduce,
+                               const float *centers, float eps, uint8_t *labels, float *value);
+int dinov2_hip_op_dense_pack(const float *x, const float *ln_w, const float *ln_b, float eps, int32_t B, int32_t T, int32_t R, int32_t H,
+                             int32_t norm, int32_t concat_cls, int32_t slot, int32_t nslots, float *out_f16_as_f32);
+int dinov2_hip_op_dense_reduce_plan(int32_t h0, int32_t w0, int32_t C, int32_t out_h, int32_t out_w, int64_t *out);
+
 #ifdef __cplusplus
 }
 #endif
