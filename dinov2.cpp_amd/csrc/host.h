@@ -1,0 +1,72 @@
+// Internal helpers of the host files behind the C-ABI (load.cpp, model.cpp, extras.cpp, pca.cpp, resident.cpp): error text, HIP_TRY, sizes, the session's
+// scratch buffers.  Not for group.cpp, which talks to the sessions through the C-ABI and has an error macro of its own.
+#pragma once
+#include <cstdarg>
+#include <cstdio>
+
+#include "model.h"
+
+namespace dinov2 {
+
+inline void set_err(char* err, size_t n, const char* fmt, ...) {
+    if (!err || n == 0) return;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(err, n, fmt, ap);
+    va_end(ap);
+}
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e__ = (expr);                                                                   \
+        if (e__ != hipSuccess) {                                                                   \
+            dinov2::set_err(err, errlen, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+            return DINOV2_HIP_ERR_HIP;                                                             \
+        }                                                                                          \
+    } while (0)
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+struct Dims {
+    int P, T, M;
+};
+
+inline Dims dims_of(const dinov2_hip_model* m, int B, int h, int w) {
+    Dims d;
+    d.P = (h / (int)m->hp.patch_size) * (w / (int)m->hp.patch_size);
+    d.T = 1 + (int)m->hp.num_register_tokens + d.P;
+    d.M = B * d.T;
+    return d;
+}
+
+// Session scratch `buf`, at least `need` bytes: the one place that allocates it (model.cpp).  Returns at once when it is large enough; otherwise
+// waits for the session's stream (which may still be using the old allocation), frees it and allocates anew -- the contents are not kept.  A
+// refused allocation leaves `buf` empty and HIP's last error cleared (not left behind for the next launch to report), and reports
+// "<who>: <n> bytes of scratch refused: <hip error string>".
+int reserve(dinov2_hip_session* s, DevBuf& buf, size_t need, const char* who, char* err, size_t errlen);
+
+// A layer list has to be strictly ascending with every entry in [lo, hi].  0 when it is; otherwise *bad is the first offending entry and the
+// return value says what is wrong with it -- entry by entry, the range before the order.  The callers word the refusal.
+enum LayerListFault : int { LAYER_LIST_OK = 0, LAYER_OUT_OF_RANGE, LAYER_NOT_ASCENDING };
+inline LayerListFault check_layer_list(const int32_t* layers, int n, int lo, int hi, int* bad) {
+    for (int i = 0; i < n; ++i) {
+        *bad = (int)layers[i];
+        if (layers[i] < lo || layers[i] > hi) return LAYER_OUT_OF_RANGE;
+        if (i > 0 && layers[i] <= layers[i - 1]) return LAYER_NOT_ASCENDING;
+    }
+    return LAYER_LIST_OK;
+}
+
+// interpolate_pos_embed of the reference (load.cpp).  pos: [1 + M*M, H]; out: [1 + h_new*w_new, H].
+void interpolate_pos_embed(const float* pos, int M, int H, int h_new, int w_new, float* out);
+
+// model.cpp, for extras.cpp: the argument checks of every predict (null session / dinov2_check_input; classify without a head, top-k on the
+// device), the network input size of `in` (raw 8-bit input: after the preprocessing), the passes themselves, and the copy-out of the last one.
+int check_input(const dinov2_hip_session* s, const dinov2_hip_input* in, char* err, size_t errlen);
+int check_predict_args(const dinov2_hip_model* m, const dinov2_hip_output* out, uint32_t flags, char* err, size_t errlen);
+void network_size(const dinov2_hip_model* m, const dinov2_hip_input* in, uint32_t flags, int* h, int* w);
+int predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out, uint32_t flags, const PassExtras& ex, char* err,
+                 size_t errlen);
+int fetch_outputs(dinov2_hip_session* s, dinov2_hip_output* out, char* err, size_t errlen);
+
+}  // namespace dinov2

@@ -19,19 +19,36 @@ struct LayerWeights {
     float *qkv_s = nullptr, *qkv_c = nullptr, *fc1_s = nullptr, *fc1_c = nullptr;
 };
 
-// The taps of ONE pass of dinov2_hip_predict_layers: device pointers to where image 0 of this pass goes in the first requested layer's
-// block, and the distance (in floats) from one requested layer's block to the next -- that of the caller's WHOLE batch, so the passes of a
-// split batch fill one set of buffers.
+// A device allocation that a session owns and grows on demand through reserve() (host.h).
+struct DevBuf {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    template <class T>
+    T* as() const { return static_cast<T*>(ptr); }
+};
+
+// The side outputs of ONE pass of the forward.  Every run descriptor points at where image 0 of this pass goes; the distance from one requested
+// layer's block to the next is that of the caller's WHOLE batch, so the passes of a split batch fill one set of buffers.  at_image(b0, ...) is
+// the descriptor of the pass that starts at image b0 of the batch this one describes.  n == 0: off.
+
+// The taps of dinov2_hip_predict_layers: device pointers into the first requested layer's block, and the strides (in floats) between blocks.
 struct TapRun {
     const int32_t* layers = nullptr;  // [n] strictly ascending, each in [0, L]
     int n = 0;
     bool norm = false, chw = false;
     float *patch = nullptr, *cls = nullptr, *reg = nullptr;
     size_t patch_stride = 0, cls_stride = 0, reg_stride = 0;
+    TapRun at_image(size_t b0, size_t P, size_t R, size_t H) const {  // an image is [P, H] / [H] / [R, H] of its layer's block
+        TapRun t = *this;
+        if (t.patch) t.patch += b0 * P * H;
+        if (t.cls) t.cls += b0 * H;
+        if (t.reg) t.reg += b0 * R * H;
+        return t;
+    }
 };
 
-// The attention rows of ONE pass of dinov2_hip_predict_attention: a device pointer to where image 0 of this pass goes in the first requested
-// layer's block [B, heads, nq, nkeys], and the distance (in floats) from one requested layer's block to the next -- the caller's WHOLE batch.
+// The attention rows of dinov2_hip_predict_attention: a device pointer into the first requested layer's block [B, heads, nq, nkeys], and the
+// stride (in floats) between blocks.
 struct AttnRun {
     const int32_t* layers = nullptr;   // [n] strictly ascending, each in [1, L]: the attention inside block layers[i]
     int n = 0;
@@ -39,17 +56,57 @@ struct AttnRun {
     int nq = 0, key0 = 0, nkeys = 0;
     float* probs = nullptr;
     size_t stride = 0;
+    AttnRun at_image(size_t b0, size_t heads) const {
+        AttnRun a = *this;
+        if (a.probs) a.probs += b0 * heads * (size_t)nq * (size_t)nkeys;
+        return a;
+    }
 };
 
-// The operand packing of ONE pass of dinov2_hip_predict_dense: at requested layer i (slot i) dense_pack_kernel writes the f16 patch rows of this
-// pass's images into columns [i * hblk, (i + 1) * hblk) of A [B P, lda] -- the operand of the logits GEMM, in the session's dense scratch.
+// dinov2_hip_predict_dense.  During the forward, at requested layer i (slot i) dense_pack_kernel writes the f16 patch rows of this pass's images
+// into columns [i * hblk, (i + 1) * hblk) of A [B P, K], hblk = H * (1 + concat_cls): the operand of the logits GEMM.  After it, dense_stage
+// runs that GEMM into `lg` and reduces to the caller's outputs at image b0.  A, lg, lab and val are ONE pass's, in the session's dense scratch,
+// reused by every pass; lab / val are where host labels / values are staged.
 struct DenseRun {
-    const int32_t* layers = nullptr;  // [n] strictly ascending, each in [0, L]
+    const dinov2_hip_dense_head* head = nullptr;
+    const int32_t* layers = nullptr;  // the head's: [n] strictly ascending, each in [0, L]
     int n = 0;
-    bool norm = false, concat_cls = false;
+    const dinov2_hip_dense_out* out = nullptr;
+    size_t b0 = 0;  // first image of this pass within the caller's batch
+    int oh = 0, ow = 0;
     _Float16* A = nullptr;
-    size_t lda = 0;
-    int hblk = 0;  // H * (1 + concat_cls)
+    float* lg = nullptr;
+    uint8_t* lab = nullptr;
+    float* val = nullptr;
+    DenseRun at_image(size_t b) const {
+        DenseRun d = *this;
+        d.b0 += b;
+        return d;
+    }
+};
+
+struct PassExtras {
+    TapRun taps;
+    AttnRun attn;
+    DenseRun dense;
+    bool any() const { return taps.n > 0 || attn.n > 0 || dense.n > 0; }
+    PassExtras at_image(size_t b0, size_t P, size_t R, size_t H, size_t heads) const {
+        return PassExtras{taps.at_image(b0, P, R, H), attn.at_image(b0, heads), dense.at_image(b0)};
+    }
+};
+
+// The scratch buffers of a session, one DevBuf each in dinov2_hip_session::scratch: dinov2_hip_session_free frees them all.
+enum Scratch : int {
+    SCRATCH_WS = 0,  // the forward's workspace, carved into the views below
+    SCRATCH_RAW,     // raw 8-bit images of DINOV2_HIP_U8_BGR_HWC host inputs
+    SCRATCH_PCA,     // dinov2_hip_pca3
+    SCRATCH_MATCH,   // dinov2_hip_match_tokens
+    SCRATCH_BANK,    // dinov2_hip_bank_add / dinov2_hip_bank_topk (staged host rows, f16 queries, partials, results)
+    SCRATCH_DENSE,   // dinov2_hip_predict_dense (the f16 operand and the logits of one pass, host outputs' staging)
+    SCRATCH_TAP,     // dinov2_hip_predict_layers with host outputs: where the tap kernel writes before the copy-out
+    SCRATCH_ATTN,    // dinov2_hip_predict_attention with a host output: where attn_rows_kernel writes before the copy-out
+    SCRATCH_ATTN_Q,  // the query list of the last dinov2_hip_predict_attention on the device (attn_q_host: what it holds)
+    SCRATCH_COUNT
 };
 
 }  // namespace dinov2
@@ -83,25 +140,8 @@ struct dinov2_hip_session {
     dinov2_hip_model* model = nullptr;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    char* ws = nullptr;
-    size_t ws_bytes = 0;
-    uint8_t* raw = nullptr;  // raw 8-bit images for DINOV2_HIP_U8_BGR_HWC inputs
-    size_t raw_bytes = 0;
-    char* pca_buf = nullptr;  // dinov2_hip_pca3's device scratch, grown on demand
-    size_t pca_bytes = 0;
-    char* match_buf = nullptr;  // dinov2_hip_match_tokens' device scratch, grown on demand
-    size_t match_bytes = 0;
-    char* bank_buf = nullptr;  // scratch of dinov2_hip_bank_add / dinov2_hip_bank_topk (staged host rows, f16 queries, partials, results)
-    size_t bank_bytes = 0;
-    char* dense_buf = nullptr;  // scratch of dinov2_hip_predict_dense (the f16 operand and the logits of one pass, host outputs' staging)
-    size_t dense_bytes = 0;
-    float* tap_buf = nullptr;  // dinov2_hip_predict_layers with host outputs: where the tap kernel writes before the copy-out; grown on demand
-    size_t tap_bytes = 0;
-    float* attn_buf = nullptr;  // dinov2_hip_predict_attention with a host output: where attn_rows_kernel writes before the copy-out; grown on demand
-    size_t attn_bytes = 0;
-    int32_t* attn_q = nullptr;  // the query list of the last dinov2_hip_predict_attention on the device, and what it holds
-    std::vector<int32_t> attn_q_host;
-    size_t attn_q_cap = 0;
+    dinov2::DevBuf scratch[dinov2::SCRATCH_COUNT];  // every device allocation of the session, by dinov2::Scratch
+    std::vector<int32_t> attn_q_host;               // what scratch[SCRATCH_ATTN_Q] holds
     int last_b = 0, last_h = 0, last_w = 0;  // shape of the last un-split forward (0: none): what dinov2_hip_fetch copies out
     bool last_classify = false;
     int last_first = 0, last_patches = 0;  // rows [last_first, last_first + last_patches) of image 0 in `fin`: its patch tokens
@@ -155,7 +195,7 @@ struct dinov2_hip_dense_head {
     float *bias = nullptr, *centers = nullptr;
 };
 
-// Internal (not C-ABI) helpers shared by model.cpp and group.cpp.
+// Internal (not C-ABI) helpers shared by model.cpp and group.cpp (host.h has those of the other host files).
 // Argument checks of dinov2_hip_predict that need no session: layout, batch, height / width against the patch size.
 int dinov2_check_input(const dinov2_hip_model* m, const dinov2_hip_input* in, char* err, size_t errlen);
 // Largest batch ONE pass of the forward takes at network input size h x w (32-bit activation offsets; DINOV2_HIP_MAX_CHUNK lowers it for

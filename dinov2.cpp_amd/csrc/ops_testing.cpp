@@ -744,7 +744,7 @@ extern "C" int dinov2_hip_op_bank_bench(const float* q_dev, int32_t nq, const fl
     return rc;
 }
 
-// ---- the device stages of dinov2_hip_pca3 (csrc/model.cpp), each through the launch function the driver calls, on host data ----
+// ---- the device stages of dinov2_hip_pca3 (csrc/pca.cpp), each through the launch function the driver calls, on host data ----
 namespace {
 // A device output of n elements of esz bytes between two guard bands of DINOV2_HIP_OP_GUARD_ROWS rows of `row` elements; the whole buffer
 // starts as 0xff bytes (NaN in f16, f32 and f64), so an element the kernel never wrote comes back as NaN and a write outside changes a guard.

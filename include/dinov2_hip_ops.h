@@ -139,7 +139,7 @@ int dinov2_hip_op_gemm_plan_parts(int32_t dtype, int32_t epilogue, int32_t M, in
  * unit Ritz vectors, each with its largest loading positive (H >= 8) */
 int dinov2_hip_op_pca_ritz(const double *yprev, const double *ynext, const double *gram, int32_t H, double *evals, double *comp);
 
-/* The device stages of dinov2_hip_pca3 (csrc/model.cpp), one at a time and without a model or session, each through the launch function
+/* The device stages of dinov2_hip_pca3 (csrc/pca.cpp), one at a time and without a model or session, each through the launch function
  * the driver itself calls (csrc/kernels.h: launch_pca_prepare, launch_pca_cov, launch_pca_power, launch_pca_project).  P >= 4, 8 <= H <= 4096
  * as the driver requires.  Every device output is framed by guard bands of DINOV2_HIP_OP_GUARD_ROWS rows of its own row width and the whole
  * buffer starts as 0xff bytes (NaN in f16, f32 and f64); a changed guard returns DINOV2_HIP_OP_GUARD_CHANGED, bad arguments

@@ -1,5 +1,5 @@
 """Cases for the device half of dinov2_hip_pca3 (csrc/kernels_misc.hip: pca_mean_kernel, pca_center_transpose_kernel, pca_power_kernel,
-pca_project_kernel; the covariance GEMM with A == W aliased; csrc/model.cpp: the driver), shared by tests/test_pca_probes.py (CPU: the numpy
+pca_project_kernel; the covariance GEMM with A == W aliased; csrc/pca.cpp: the driver), shared by tests/test_pca_probes.py (CPU: the numpy
 emulations pass every check, planted bugs do not), tests/test_gpu_pca_kernels.py (each kernel alone through dinov2_hip_op_pca_*) and
 tests/test_gpu_parity.py (the whole call).  Plain module, no fixtures.
 
@@ -330,7 +330,7 @@ def gram_parts_spread(g, H):
 
 
 def start_block(H):
-    """The driver's start block (csrc/model.cpp): y0[j][c] = sin(0.37 (j + 1) (c + 1)) + (c == j % 8 ? 0.5 : 0)."""
+    """The driver's start block (csrc/pca.cpp): y0[j][c] = sin(0.37 (j + 1) (c + 1)) + (c == j % 8 ? 0.5 : 0)."""
     j, c = np.arange(H)[:, None], np.arange(NB)[None, :]
     return np.sin(0.37 * (j + 1) * (c + 1)) + np.where(c == j % NB, 0.5, 0.0)
 
@@ -512,7 +512,7 @@ def emulated_ops(mutant=None):
 
 # ------------------------------------------------------------------------------------------------------------------- the whole call
 def ritz(yprev, ynext, g, vectors=True):
-    """The Rayleigh-Ritz step of csrc/model.cpp pca_ritz in numpy (eigh in place of its Jacobi sweeps): (3 largest Ritz values, comp [3, H])."""
+    """The Rayleigh-Ritz step of csrc/pca.cpp pca_ritz in numpy (eigh in place of its Jacobi sweeps): (3 largest Ritz values, comp [3, H])."""
     rinv = chol_rinv(g)
     q = yprev @ rinv
     b = q.T @ ynext

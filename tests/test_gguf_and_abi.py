@@ -357,7 +357,7 @@ def test_native_quantize_equals_python_tool(api, pkg, golden_dir, tmp_path, ityp
 
 @pytest.mark.parametrize("H", [8, 33, 384, 1024])
 def test_pca_ritz_step_matches_eigh(pkg, H):
-    """The host half of dinov2_hip_pca3 (CholeskyQR of the block + 8 x 8 Rayleigh-Ritz by Jacobi, csrc/model.cpp pca_ritz): a
+    """The host half of dinov2_hip_pca3 (CholeskyQR of the block + 8 x 8 Rayleigh-Ritz by Jacobi, csrc/pca.cpp pca_ritz): a
     block spanning the top-8 eigenspace of a symmetric matrix, arbitrarily mixed, must give back its three leading
     eigenvectors and eigenvalues -- unit length, sign convention 'largest loading positive'.  No device call."""
     api = import_module(pkg.__name__ + ".api")

@@ -120,7 +120,7 @@ def test_log2_kernel1_bitwise_repeatable(api, dt):
 
 @pytest.mark.parametrize("dt", [ac.F16, ac.BF16], ids=["f16", "bf16"])
 def test_qkv_gemm_then_log2_attention(api, dt):
-    """The forward's pair: the QKV GEMM epilogue with qscale = 0.125 * log2(e) (csrc/model.cpp:707), then attention with
+    """The forward's pair: the QKV GEMM epilogue with qscale = 0.125 * log2(e) (csrc/model.cpp forward()), then attention with
     log2_scores = 1, against a float64 softmax(Q K^T / 8) V of the unrounded x W^T + b: the log2(e) fold is applied exactly once.
     x, W and b lie on grids that make x W^T + b exact in f32, so the only input error is the rounding of q, k, v to T:
     q relative <= u + 2^-22 (scale product and rounding), k, v <= u; per query |ds| <= sum_d |q_d k_d| ((1 + e_q)(1 + e_k) - 1) in
@@ -132,7 +132,7 @@ def test_qkv_gemm_then_log2_attention(api, dt):
     x = rng.integers(-16, 17, (M, H)) / 8.0                 # multiples of 1/8, |x| <= 2
     W = rng.integers(-8, 9, (3 * H, H)) / 64.0              # multiples of 1/64, |W| <= 1/8
     bias = rng.integers(-256, 257, 3 * H) / 512.0
-    qscale = 0.125 * math.log2(math.e)                      # csrc/model.cpp:707
+    qscale = 0.125 * math.log2(math.e)                      # csrc/model.cpp forward()
     qkv = np.zeros((M, 3 * H), np.float32)
     rc = api.lib().dinov2_hip_op_gemm(dt, EPI_QKV, _p(x.astype(np.float32)), _p(W.astype(np.float32)), _p(bias.astype(np.float32)),
                                       fp(), 0, _p(qkv), M, 3 * H, M, 3 * H, H, 0, 0, 0, H, qscale)

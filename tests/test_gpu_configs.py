@@ -355,3 +355,56 @@ def test_distance_to_exact_arithmetic(api, pkg, ggufs, head_std, seed):
     assert rec["hip_abs"] <= 1e-3 * max(1.0, big)            # the stated bound also holds against exact arithmetic
     assert rec["hip_abs"] <= 1.18 * worst_ggml, rec          # and the HIP path is as good an approximation as a ggml-style one
     assert rec["hip_tokens_abs"] <= 1.10 * worst_ggml_tok, rec
+
+
+# ------------------------------------------------------------------------------------------------- session scratch growing mid-session
+def _scratch_round(api, pkg, model, head, sess, B, hh, ww, seed):
+    """One call of everything that owns session scratch, at batch B and network input size hh x ww, all with host inputs and outputs (the staged
+    paths): {name: array}."""
+    hp = model.hparams
+    H, P = int(hp.hidden_size), (hh // hp.patch_size) * (ww // hp.patch_size)
+    rng = np.random.default_rng(seed)
+    img = pkg.synth.synthetic_images(B, hh, ww, seed=seed)
+    raw = rng.integers(0, 256, (B, hh - 8, ww - 8, 3), dtype=np.uint8)  # features preprocessing: up to the next multiple of 14, hh x ww again
+    rows = rng.standard_normal((B * P, H)).astype(np.float32)
+    res = {}
+    taps = sess.predict_layers(img, [0, 2], return_class_token=True, return_registers=True)
+    for d in taps["layers"]:
+        for k in ("patch_tokens", "cls", "registers"):
+            res[f"layers.{d['layer']}.{k}"] = d[k]
+    res["layers.out.patch_tokens"] = taps["patch_tokens"]
+    res["attention.2q"] = sess.predict_attention(img, [1, 2], queries=[0, 5])
+    res["attention.3q"] = sess.predict_attention(img, [2], queries=[1, 2, 7], keys="patches")
+    dense = sess.predict_dense(img, head, want=("labels", "value"))
+    res["dense.labels"], res["dense.value"] = dense["labels"], dense["value"]
+    u8 = sess.predict(raw, layout=api.U8_BGR_HWC)
+    assert u8["patch_tokens"].shape == (B, P, H)
+    res["raw_u8.cls"], res["raw_u8.patch_tokens"] = u8["cls"], u8["patch_tokens"]
+    res["pca3.components"], res["pca3.mean"], res["pca3.projection"] = sess.pca3(rows)
+    for k, v in sess.match(rows, rows[::-1] + np.float32(0.25) * rows).items():
+        res["match." + k] = v
+    bank = api.Bank(model, H, B * P)
+    res["bank.first"] = np.array([bank.add(sess, rows)])
+    for k, v in bank.topk(sess, rows[: B * P // 2] + np.float32(0.5), k=3).items():
+        res["bank.topk." + k] = v
+    bank.free()
+    return res
+
+
+def test_every_session_scratch_regrows_mid_session(api, pkg, golden_dir):
+    """ONE session goes small (28 x 42, batch 1) -> large (56 x 84, batch 3) -> small again through every call that keeps scratch in the
+    session -- the workspace, the tap, attention-row and query-list buffers, the dense operand, the raw-image buffer, the PCA, match and bank
+    scratch -- so each of them is allocated, outgrown and reallocated, then reused with room to spare.  Every output of every round is, bit for
+    bit, what the same call gives on a session that has done nothing else."""
+    model = api.Model(os.path.join(golden_dir, "tiny_gelu_reg4.gguf"), classify=True)
+    H = int(model.hparams.hidden_size)
+    rng = np.random.default_rng(7)
+    head = api.DenseHead(model, [1, 2], rng.standard_normal((5, 2 * H)).astype(np.float32) / np.float32(8), rng.standard_normal(5).astype(np.float32))
+    one = api.Session(model)
+    for n, (B, hh, ww) in enumerate([(1, 28, 42), (3, 56, 84), (1, 28, 42)]):
+        got = _scratch_round(api, pkg, model, head, one, B, hh, ww, seed=30 + n)
+        ref = _scratch_round(api, pkg, model, head, api.Session(model), B, hh, ww, seed=30 + n)
+        assert set(got) == set(ref)
+        for k in sorted(ref):
+            assert got[k].shape == ref[k].shape and got[k].dtype == ref[k].dtype, (n, k)
+            assert got[k].tobytes() == ref[k].tobytes(), f"round {n} ({B} x {hh} x {ww}): {k} differs from a fresh session's"

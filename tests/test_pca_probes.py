@@ -139,7 +139,7 @@ def test_new_symbols_are_declared_and_exported(api):
     out = subprocess.check_output(["nm", "-D", "--defined-only", api.LIB_PATH], text=True)
     assert names <= set(re.findall(r" T (dinov2_hip_[a-z0-9_]+)", out))
     # the driver and the testing entry points share the padding rule and the aliased launch: one definition each
-    model = open(os.path.join(ROOT, "dinov2.cpp_amd", "csrc", "model.cpp")).read()
+    model = open(os.path.join(ROOT, "dinov2.cpp_amd", "csrc", "pca.cpp")).read()
     testing = open(os.path.join(ROOT, "dinov2.cpp_amd", "csrc", "ops_testing.cpp")).read()
     for src in (model, testing):
         assert "pca_ppad(P)" in src and "launch_pca_cov(" in src and "/ 128 * 128" not in src
