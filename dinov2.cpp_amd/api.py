@@ -170,13 +170,28 @@ def gemm_plan_parts(dtype, epilogue, M, N, K):
     return [dict(zip(PLAN_PART_FIELDS, buf[i * nf:(i + 1) * nf])) for i in range(n)]
 
 
+def _op_rc(rc, name):
+    if rc == OP_GUARD_CHANGED:
+        raise AssertionError(f"{name} wrote outside its output (guard band changed)")
+    if rc != 0:
+        raise RuntimeError(f"dinov2_hip_op_{name} failed ({rc})")
+
+
+def _ptr(a):
+    """A numpy array as the typed pointer an op's argtypes ask for (its own dtype's; also taken where they say void *); None stays NULL."""
+    return None if a is None else a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
+
+
+def _f32(a):
+    return None if a is None else np.ascontiguousarray(a, np.float32)
+
+
 def op_layer_tap(x, w, b, eps, R, h0, w0, *, norm, chw, want=("patch", "cls", "reg")):
     """layer_tap_kernel alone (dinov2_hip_op_layer_tap): x [B, T, H] f32 -> dict of the destinations in `want`.  Raises on a HIP error or a
     changed guard band."""
-    x = np.ascontiguousarray(x, np.float32)
+    x = _f32(x)
     B, T, H = x.shape
     P = h0 * w0
-    fp = C.POINTER(C.c_float)
     out = {}
     if "patch" in want:
         out["patch"] = np.zeros((B, H, h0, w0) if chw else (B, P, H), np.float32)
@@ -184,15 +199,8 @@ def op_layer_tap(x, w, b, eps, R, h0, w0, *, norm, chw, want=("patch", "cls", "r
         out["cls"] = np.zeros((B, H), np.float32)
     if "reg" in want:
         out["reg"] = np.zeros((B, R, H), np.float32)
-    ptr = lambda a: a.ctypes.data_as(fp) if a is not None else None  # noqa: E731
-    w = None if w is None else np.ascontiguousarray(w, np.float32)
-    b = None if b is None else np.ascontiguousarray(b, np.float32)
-    rc = lib().dinov2_hip_op_layer_tap(ptr(x), ptr(w), ptr(b), float(eps), B, T, R, H, h0, w0, int(norm), int(chw), ptr(out.get("patch")),
-                                       ptr(out.get("cls")), ptr(out.get("reg")))
-    if rc == OP_GUARD_CHANGED:
-        raise AssertionError("layer_tap wrote outside its output (guard band changed)")
-    if rc != 0:
-        raise RuntimeError(f"dinov2_hip_op_layer_tap failed ({rc})")
+    _op_rc(lib().dinov2_hip_op_layer_tap(_ptr(x), _ptr(_f32(w)), _ptr(_f32(b)), float(eps), B, T, R, H, h0, w0, int(norm), int(chw),
+                                         _ptr(out.get("patch")), _ptr(out.get("cls")), _ptr(out.get("reg"))), "layer_tap")
     return out
 
 
@@ -201,56 +209,45 @@ def op_attn_rows(dtype, qkv, B, T, nh, queries, key0=0, nkeys=None, lds_budget=0
     [key0, key0 + nkeys) of the softmax rows of the tokens `queries` over all T keys.  lds_budget > 0: the LDS the scores may take, in bytes
     (below 4 T: the two-pass form).  Raises on a HIP error or a changed guard band."""
     H = 64 * nh
-    qkv = np.ascontiguousarray(qkv, np.float32)
+    qkv = _f32(qkv)
     assert qkv.shape == (B * T, 3 * H), qkv.shape
     q = np.ascontiguousarray(queries, np.int32)
     nkeys = T - key0 if nkeys is None else int(nkeys)
     out = np.zeros((B, nh, len(q), nkeys), np.float32)
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
-    rc = lib().dinov2_hip_op_attn_rows_ex(int(dtype), qkv.ctypes.data_as(fp), B, T, H, nh, q.ctypes.data_as(ip), len(q), int(key0), nkeys,
-                                          out.ctypes.data_as(fp), int(lds_budget))
-    if rc == OP_GUARD_CHANGED:
-        raise AssertionError("attn_rows wrote outside its output (guard band changed)")
-    if rc != 0:
-        raise RuntimeError(f"dinov2_hip_op_attn_rows failed ({rc})")
+    _op_rc(lib().dinov2_hip_op_attn_rows_ex(int(dtype), _ptr(qkv), B, T, H, nh, _ptr(q), len(q), int(key0), nkeys, _ptr(out), int(lds_budget)),
+           "attn_rows")
     return out
 
 
 def op_match(a, b):
     """The kernels of csrc/match.hip alone (dinov2_hip_op_match): a [na, H], b [nb, H] f32 -> dict of idx_ab, sim_ab [na], idx_ba, sim_ba [nb].
     No model, no session."""
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    a, b = _f32(a), _f32(b)
     assert a.ndim == 2 and b.ndim == 2 and a.shape[1] == b.shape[1], (a.shape, b.shape)
     na, nb = a.shape[0], b.shape[0]
     out = {"idx_ab": np.full(na, -1, np.int32), "sim_ab": np.full(na, np.nan, np.float32),
            "idx_ba": np.full(nb, -1, np.int32), "sim_ba": np.full(nb, np.nan, np.float32)}
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
-    rc = lib().dinov2_hip_op_match(a.ctypes.data_as(fp), na, b.ctypes.data_as(fp), nb, a.shape[1], out["idx_ab"].ctypes.data_as(ip),
-                                   out["sim_ab"].ctypes.data_as(fp), out["idx_ba"].ctypes.data_as(ip), out["sim_ba"].ctypes.data_as(fp))
-    if rc != 0:
-        raise RuntimeError(f"dinov2_hip_op_match failed ({rc})")
+    _op_rc(lib().dinov2_hip_op_match(_ptr(a), na, _ptr(b), nb, a.shape[1], _ptr(out["idx_ab"]), _ptr(out["sim_ab"]), _ptr(out["idx_ba"]),
+                                     _ptr(out["sim_ba"])), "match")
     return out
 
 
 def op_bank_topk(q, b, k, chunk_tiles=0):
     """The kernels of csrc/bank.hip alone (dinov2_hip_op_bank_topk): q [nq, H] against the bank built from b [nb, H] -> dict of idx, sim
     [nq, k].  chunk_tiles: column tiles per workgroup, 0 = the planner's choice.  No model, no session."""
-    q, b = np.ascontiguousarray(q, np.float32), np.ascontiguousarray(b, np.float32)
+    q, b = _f32(q), _f32(b)
     assert q.ndim == 2 and b.ndim == 2 and q.shape[1] == b.shape[1], (q.shape, b.shape)
     nq, nb = q.shape[0], b.shape[0]
     out = {"idx": np.full((nq, k), -7, np.int32), "sim": np.full((nq, k), np.nan, np.float32)}
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
-    rc = lib().dinov2_hip_op_bank_topk(q.ctypes.data_as(fp), nq, b.ctypes.data_as(fp), nb, q.shape[1], int(k), int(chunk_tiles),
-                                       out["idx"].ctypes.data_as(ip), out["sim"].ctypes.data_as(fp))
-    if rc != 0:
-        raise RuntimeError(f"dinov2_hip_op_bank_topk failed ({rc})")
+    _op_rc(lib().dinov2_hip_op_bank_topk(_ptr(q), nq, _ptr(b), nb, q.shape[1], int(k), int(chunk_tiles), _ptr(out["idx"]), _ptr(out["sim"])),
+           "bank_topk")
     return out
 
 
 def op_dense_reduce(logits, h0, w0, out_h, out_w, reduce="argmax", centers=None, eps=0.0, want=("labels", "value")):
     """dense_reduce_kernel alone (dinov2_hip_op_dense_reduce): logits [h0 * w0, C] of one image -> dict of labels [out_h, out_w] uint8 (argmax
     only) and value [out_h, out_w] f32.  Raises on a HIP error or a changed guard band."""
-    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    lg = _f32(logits)
     if lg.ndim != 2 or lg.shape[0] != h0 * w0:
         raise ValueError("op_dense_reduce: logits must be [h0 * w0, C]")
     red = _DENSE_REDUCE[reduce]
@@ -259,33 +256,20 @@ def op_dense_reduce(logits, h0, w0, out_h, out_w, reduce="argmax", centers=None,
         out["labels"] = np.empty((int(out_h), int(out_w)), np.uint8)
     if "value" in want:
         out["value"] = np.empty((int(out_h), int(out_w)), np.float32)
-    cen = np.ascontiguousarray(centers, dtype=np.float32) if centers is not None else None
-    fp, ptr = C.POINTER(C.c_float), lambda a, t: a.ctypes.data_as(t) if a is not None else None
-    rc = lib().dinov2_hip_op_dense_reduce(ptr(lg, fp), int(h0), int(w0), lg.shape[1], int(out_h), int(out_w), red, ptr(cen, fp), float(eps),
-                                          ptr(out.get("labels"), C.POINTER(C.c_uint8)), ptr(out.get("value"), fp))
-    if rc == OP_GUARD_CHANGED:
-        raise RuntimeError("dinov2_hip_op_dense_reduce: a guard band around an output was written")
-    if rc != 0:
-        raise RuntimeError(f"dinov2_hip_op_dense_reduce failed ({rc})")
+    _op_rc(lib().dinov2_hip_op_dense_reduce(_ptr(lg), int(h0), int(w0), lg.shape[1], int(out_h), int(out_w), red, _ptr(_f32(centers)),
+                                            float(eps), _ptr(out.get("labels")), _ptr(out.get("value"))), "dense_reduce")
     return out
 
 
 def op_dense_pack(x, w, b, eps, R, *, norm, concat_cls, slot=0, nslots=1):
     """dense_pack_kernel alone (dinov2_hip_op_dense_pack): x [B, T, H] f32 -> [B * P, nslots * H * (1 + concat_cls)] f32, the values of the f16
-    operand after one launch into column block `slot` (the other blocks come back as NaN)."""
-    x = np.ascontiguousarray(x, dtype=np.float32)
+    operand after one launch into column block `slot` (the other blocks come back as NaN).  Raises on a HIP error or a changed guard band."""
+    x = _f32(x)
     B, T, H = x.shape
     P = T - 1 - R
     out = np.empty((B * P, nslots * H * (2 if concat_cls else 1)), np.float32)
-    w = np.ascontiguousarray(w, dtype=np.float32) if w is not None else None
-    b = np.ascontiguousarray(b, dtype=np.float32) if b is not None else None
-    fp, ptr = C.POINTER(C.c_float), lambda a: a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else None
-    rc = lib().dinov2_hip_op_dense_pack(ptr(x), ptr(w), ptr(b), float(eps), B, T, int(R), H, int(bool(norm)), int(bool(concat_cls)), int(slot),
-                                        int(nslots), ptr(out))
-    if rc == OP_GUARD_CHANGED:
-        raise RuntimeError("dinov2_hip_op_dense_pack: a guard band around the operand was written")
-    if rc != 0:
-        raise RuntimeError(f"dinov2_hip_op_dense_pack failed ({rc})")
+    _op_rc(lib().dinov2_hip_op_dense_pack(_ptr(x), _ptr(_f32(w)), _ptr(_f32(b)), float(eps), B, T, int(R), H, int(bool(norm)),
+                                          int(bool(concat_cls)), int(slot), int(nslots), _ptr(out)), "dense_pack")
     return out
 
 
@@ -321,13 +305,6 @@ def bank_plan(nq, nb, H, k, chunk_tiles=0):
     return dict(zip(BANK_PLAN_FIELDS, [int(v) for v in buf]))
 
 
-def _op_rc(rc, name):
-    if rc == OP_GUARD_CHANGED:
-        raise AssertionError(f"{name} wrote outside its output (guard band changed)")
-    if rc != 0:
-        raise RuntimeError(f"dinov2_hip_op_{name} failed ({rc})")
-
-
 def pca_ppad(P):
     """Ppad of dinov2_hip_pca3: the token count padded to the K of its covariance GEMM (no device needed)."""
     return int(lib().dinov2_hip_op_pca_ppad(int(P)))
@@ -341,43 +318,42 @@ def pca_blocks(H):
 def op_pca_prepare(tok):
     """pca_mean_kernel + pca_center_transpose_kernel (dinov2_hip_op_pca_prepare): tok [P, H] f32 -> (mean [H] f32, xt [H, Ppad] f32 values of
     the f16 matrix, padded columns included).  Raises on a HIP error or a changed guard band."""
-    tok = np.ascontiguousarray(tok, np.float32)
+    tok = _f32(tok)
     P, H = tok.shape
     mean, xt = np.zeros(H, np.float32), np.zeros((H, pca_ppad(P)), np.float32)
-    _op_rc(lib().dinov2_hip_op_pca_prepare(tok.ctypes.data, P, H, mean.ctypes.data, xt.ctypes.data), "pca_prepare")
+    _op_rc(lib().dinov2_hip_op_pca_prepare(_ptr(tok), P, H, _ptr(mean), _ptr(xt)), "pca_prepare")
     return mean, xt
 
 
 def op_pca_cov(tok):
     """prepare + the driver's aliased covariance GEMM (dinov2_hip_op_pca_cov): tok [P, H] f32 -> cov [H, H] f32 = Xt Xt^T."""
-    tok = np.ascontiguousarray(tok, np.float32)
+    tok = _f32(tok)
     P, H = tok.shape
     cov = np.zeros((H, H), np.float32)
-    _op_rc(lib().dinov2_hip_op_pca_cov(tok.ctypes.data, P, H, cov.ctypes.data), "pca_cov")
+    _op_rc(lib().dinov2_hip_op_pca_cov(_ptr(tok), P, H, _ptr(cov)), "pca_cov")
     return cov
 
 
 def op_pca_power(cov, yprev, gprev_parts):
     """One pca_power_kernel launch (dinov2_hip_op_pca_power): cov [H, H] f32, yprev [H, 8] f64, gprev_parts [pca_blocks(H), 64] f64 ->
     (ynext [H, 8], gnext_parts [pca_blocks(H), 64]) f64."""
-    cov = np.ascontiguousarray(cov, np.float32)
+    cov = _f32(cov)
     H = cov.shape[0]
     yprev, gprev_parts = np.ascontiguousarray(yprev, np.float64), np.ascontiguousarray(gprev_parts, np.float64)
     nb = pca_blocks(H)
     assert cov.shape == (H, H) and yprev.shape == (H, 8) and gprev_parts.shape == (nb, 64), (cov.shape, yprev.shape, gprev_parts.shape)
     ynext, gnext = np.zeros((H, 8), np.float64), np.zeros((nb, 64), np.float64)
-    _op_rc(lib().dinov2_hip_op_pca_power(cov.ctypes.data, yprev.ctypes.data, gprev_parts.ctypes.data, H, ynext.ctypes.data, gnext.ctypes.data),
-           "pca_power")
+    _op_rc(lib().dinov2_hip_op_pca_power(_ptr(cov), _ptr(yprev), _ptr(gprev_parts), H, _ptr(ynext), _ptr(gnext)), "pca_power")
     return ynext, gnext
 
 
 def op_pca_project(tok, mean, comp):
     """pca_project_kernel (dinov2_hip_op_pca_project): tok [P, H], mean [H], comp [3, H] f32 -> proj [P, 3] f32."""
-    tok, mean, comp = (np.ascontiguousarray(a, np.float32) for a in (tok, mean, comp))
+    tok, mean, comp = _f32(tok), _f32(mean), _f32(comp)
     P, H = tok.shape
     assert mean.shape == (H,) and comp.shape == (3, H), (mean.shape, comp.shape)
     proj = np.zeros((P, 3), np.float32)
-    _op_rc(lib().dinov2_hip_op_pca_project(tok.ctypes.data, mean.ctypes.data, comp.ctypes.data, P, H, proj.ctypes.data), "pca_project")
+    _op_rc(lib().dinov2_hip_op_pca_project(_ptr(tok), _ptr(mean), _ptr(comp), P, H, _ptr(proj)), "pca_project")
     return proj
 
 
@@ -386,7 +362,7 @@ def pca_chol_rinv(gram):
     gram = np.ascontiguousarray(gram, np.float64)
     assert gram.shape == (8, 8), gram.shape
     rinv = np.zeros((8, 8), np.float64)
-    _op_rc(lib().dinov2_hip_op_pca_chol_rinv(gram.ctypes.data, rinv.ctypes.data), "pca_chol_rinv")
+    _op_rc(lib().dinov2_hip_op_pca_chol_rinv(_ptr(gram), _ptr(rinv)), "pca_chol_rinv")
     return rinv
 
 
@@ -518,8 +494,35 @@ def lib():
     return L
 
 
-def _errbuf():
-    return C.create_string_buffer(512)
+def _errbuf(size: int = 512):
+    return C.create_string_buffer(size)
+
+
+def _call(fn, *args):
+    """One call of a C-ABI function whose last two parameters are (err, errlen): a non-zero status raises DinoError with the library's text."""
+    err = _errbuf()
+    rc = fn(*args, err, len(err))
+    if rc != 0:
+        raise DinoError(rc, err.value.decode(errors="replace"))
+
+
+class _Handle:
+    """Owner of one C-ABI handle, `_h`; the subclass names the function that frees it.  close() and free() are the same call."""
+    _free = None
+    _h = None
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._free)(self._h)
+            self._h = None
+
+    free = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 U8_BGR_HWC = 2
@@ -552,8 +555,9 @@ def _preprocess(mode, img, patch):
     return out
 
 
-class Model:
+class Model(_Handle):
     """dino_model counterpart (owning handle)."""
+    _free = "dinov2_hip_model_free"
 
     def __init__(self, path: str, *, device: int = 0, dtype: int = F16, classify: bool = True,
                  skip_tensor_data: bool = False, pool_const_divisor: bool = True, pool_includes_registers: bool = True,
@@ -568,10 +572,7 @@ class Model:
         o.batch_invariant = int(batch_invariant)
         o.ln_fold = int(ln_fold)
         h = C.c_void_p()
-        err = _errbuf()
-        rc = L.dinov2_hip_model_load(path.encode(), C.byref(o), C.byref(h), err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(L.dinov2_hip_model_load, path.encode(), C.byref(o), C.byref(h))
         self._h = h
         hp = HParams()
         L.dinov2_hip_model_hparams(h, C.byref(hp))
@@ -601,23 +602,35 @@ class Model:
         p = self.hparams.patch_size
         return 1 + self.hparams.num_register_tokens + (h // p) * (w // p)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dinov2_hip_model_free(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def _images(images, layout, dtype=None):
+    """The image argument of every predict as the C-ABI takes it: (img, B, hh, ww), img contiguous [B, 3, hh, ww] (RGB_CHW) or [B, hh, ww, 3],
+    uint8 for U8_BGR_HWC and float32 otherwise unless `dtype` says so; one image becomes a batch of one.  Any other shape is refused here:
+    the library reads B * 3 * hh * ww elements whatever the array holds."""
+    img = np.ascontiguousarray(images, dtype=dtype or (np.uint8 if layout == U8_BGR_HWC else np.float32))
+    if img.ndim == 3:
+        img = img[None]
+    if img.ndim != 4 or (img.shape[1] if layout == RGB_CHW else img.shape[3]) != 3:
+        raise ValueError(f"expected [B, 3, H, W] (RGB_CHW) or [B, H, W, 3] images, got shape {img.shape}")
+    hh, ww = (img.shape[2], img.shape[3]) if layout == RGB_CHW else (img.shape[1], img.shape[2])
+    return img, img.shape[0], hh, ww
+
+
+def _grid(hp, hh, ww, layout, classify):
+    """(nh, nw, P): the network input size of an hh x ww image (raw 8-bit input: after the preprocessing) and its number of patches."""
+    nh, nw = preprocess_size(1 if classify else 0, hh, ww, hp.patch_size) if layout == U8_BGR_HWC else (hh, ww)
+    return nh, nw, (nh // hp.patch_size) * (nw // hp.patch_size)
+
+
+def _device_output(cls_ptr, patch_ptr, logits_ptr, probs_ptr):
+    """The Output of the *_device calls: raw device pointers, 0 = not wanted; no top-k on the device."""
+    return Output(cls_ptr or None, patch_ptr or None, logits_ptr or None, probs_ptr or None, None, None, 0, 1)
 
 
 def _alloc_outputs(hp, B, hh, ww, layout, classify, topk, want):
     """Host output arrays + the filled Output struct for a predict of B images (shared by Session and Group)."""
-    Hd, R, ps = hp.hidden_size, hp.num_register_tokens, hp.patch_size
-    nh, nw = preprocess_size(1 if classify else 0, hh, ww, ps) if layout == U8_BGR_HWC else (hh, ww)
-    P = (nh // ps) * (nw // ps)
+    Hd, R = hp.hidden_size, hp.num_register_tokens
+    P = _grid(hp, hh, ww, layout, classify)[2]
     out = {}
     o = Output()
     if "cls" in want:
@@ -723,16 +736,14 @@ class DeviceArray:
             pass
 
 
-class Bank:
+class Bank(_Handle):
     """dinov2_hip_bank: a device-resident bank of unit-length f16 rows and its top-k cosine search (include/dinov2_hip.h).  Rows come from
     host arrays, DeviceArrays, or -- source="last_cls" / "last_patches" -- from the session's last un-split predict without leaving the device."""
+    _free = "dinov2_hip_bank_free"
 
     def __init__(self, model: "Model", H: int, capacity: int):
         h = C.c_void_p()
-        err = _errbuf()
-        rc = lib().dinov2_hip_bank_create(model._h, int(H), int(capacity), C.byref(h), err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_bank_create, model._h, int(H), int(capacity), C.byref(h))
         self._h = h
         self.H, self.capacity = int(H), int(capacity)
 
@@ -761,10 +772,7 @@ class Bank:
         image `image`; n = P); `n` is taken from the session's last predict() unless given."""
         r, keep = self._rows(sess, rows, source, image, n)
         first = C.c_int32(-1)
-        err = _errbuf()
-        rc = lib().dinov2_hip_bank_add(sess._h, self._h, C.byref(r), C.byref(first), err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_bank_add, sess._h, self._h, C.byref(r), C.byref(first))
         return int(first.value)
 
     def topk(self, sess: "Session", queries=None, k: int = 1, *, source=None, image: int = 0, n: int | None = None) -> dict:
@@ -774,10 +782,7 @@ class Bank:
         nq = max(int(r.n), 0)
         out = {"idx": np.empty((nq, int(k)), np.int32), "sim": np.empty((nq, int(k)), np.float32)}
         t = TopK(r, int(k), out["idx"].ctypes.data, out["sim"].ctypes.data)
-        err = _errbuf()
-        rc = lib().dinov2_hip_bank_topk(sess._h, self._h, C.byref(t), err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_bank_topk, sess._h, self._h, C.byref(t))
         return out
 
     @property
@@ -787,22 +792,12 @@ class Bank:
     def clear(self):
         lib().dinov2_hip_bank_clear(self._h)
 
-    def free(self):
-        if getattr(self, "_h", None):
-            lib().dinov2_hip_bank_free(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class DenseHead:
+class DenseHead(_Handle):
     """dinov2_hip_dense_head: a resident linear segmentation (reduce="argmax") or depth (reduce="bins") head over the patch tokens of `layers`
     (include/dinov2_hip.h).  weight [C, K], K = len(layers) * H * (1 + concat_cls), column order layer-major, patch then cls; a BatchNorm in
     front of it is folded first (fold_batchnorm)."""
+    _free = "dinov2_hip_dense_head_free"
 
     def __init__(self, model: "Model", layers, weight, bias=None, *, norm: bool = True, concat_cls: bool = False, reduce: str = "argmax",
                  bin_centers=None, bins_eps: float = 0.1):
@@ -820,29 +815,16 @@ class DenseHead:
         d = DenseDesc(arr, len(ids), int(bool(norm)), int(bool(concat_cls)), W.shape[0], W.ctypes.data, b.ctypes.data if b is not None else None,
                       _DENSE_REDUCE[reduce], cen.ctypes.data if cen is not None else None, float(bins_eps))
         h = C.c_void_p()
-        err = _errbuf()
-        rc = lib().dinov2_hip_dense_head_create(model._h, C.byref(d), C.byref(h), err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_dense_head_create, model._h, C.byref(d), C.byref(h))
         self._h = h
         self.layers, self.num_classes, self.reduce, self.K = ids, int(W.shape[0]), reduce, K
 
-    def free(self):
-        if getattr(self, "_h", None):
-            lib().dinov2_hip_dense_head_free(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class Group:
+class Group(_Handle):
     """dinov2_hip_group: N devices behind one handle -- host threads + sessions per device inside the library (two lanes per
     device by default: one lane's PCIe copies run under the other's kernels), the global batch split contiguously, outputs
     landing at the shard offsets of the caller's arrays."""
+    _free = "dinov2_hip_group_free"
 
     def __init__(self, path: str, devices=None, *, dtype: int = F16, classify: bool = True, broadcast: bool = True,
                  batch_invariant: bool = True, streams_per_device: int = 2):
@@ -857,10 +839,7 @@ class Group:
             self._devs = (C.c_int32 * len(devices))(*devices)
             o.n_devices, o.devices = len(devices), self._devs
         h = C.c_void_p()
-        err = _errbuf()
-        rc = L.dinov2_hip_group_create(path.encode(), C.byref(o), C.byref(h), err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(L.dinov2_hip_group_create, path.encode(), C.byref(o), C.byref(h))
         self._h = h
         self.size = int(L.dinov2_hip_group_size(h))
         self.hparams = HParams()
@@ -871,102 +850,57 @@ class Group:
 
     def predict(self, images: np.ndarray, *, classify: bool = False, layout: int = RGB_CHW, topk: int = 0,
                 want=("cls", "patch_tokens", "logits", "probs")) -> dict:
-        img = np.ascontiguousarray(images, dtype=np.uint8 if layout == U8_BGR_HWC else np.float32)
-        if img.ndim == 3:  # one image -> a batch of one, like Session.predict
-            img = img[None]
-        if img.ndim != 4 or (img.shape[1] if layout == RGB_CHW else img.shape[3]) != 3:
-            raise ValueError(f"expected [B, 3, H, W] (RGB_CHW) or [B, H, W, 3] images, got shape {img.shape}")
-        B = img.shape[0]
-        hh, ww = (img.shape[2], img.shape[3]) if layout == RGB_CHW else (img.shape[1], img.shape[2])
+        img, B, hh, ww = _images(images, layout)
         out, o = _alloc_outputs(self.hparams, B, hh, ww, layout, classify, topk, want)
         i = Input(img.ctypes.data, B, hh, ww, layout, 0)
-        err = _errbuf()
-        rc = lib().dinov2_hip_group_predict(self._h, C.byref(i), C.byref(o), CLASSIFY if classify else 0, err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_group_predict, self._h, C.byref(i), C.byref(o), CLASSIFY if classify else 0)
         return out
 
     def submit(self, images: np.ndarray, *, classify: bool = False, layout: int = RGB_CHW, topk: int = 0,
                want=("cls", "patch_tokens", "logits", "probs")):
         """First half of predict (dinov2_hip_group_submit): returns a pending-job handle at once; up to `streams_per_device` jobs
         may be in flight.  `images` must not be modified until wait() has returned for the handle."""
-        img = np.ascontiguousarray(images, dtype=np.uint8 if layout == U8_BGR_HWC else np.float32)
-        if img.ndim == 3:
-            img = img[None]
-        if img.ndim != 4 or (img.shape[1] if layout == RGB_CHW else img.shape[3]) != 3:
-            raise ValueError(f"expected [B, 3, H, W] (RGB_CHW) or [B, H, W, 3] images, got shape {img.shape}")
-        B = img.shape[0]
-        hh, ww = (img.shape[2], img.shape[3]) if layout == RGB_CHW else (img.shape[1], img.shape[2])
+        img, B, hh, ww = _images(images, layout)
         out, o = _alloc_outputs(self.hparams, B, hh, ww, layout, classify, topk, want)
         i = Input(img.ctypes.data, B, hh, ww, layout, 0)
         t = C.c_int64(-1)
-        err = _errbuf()
-        rc = lib().dinov2_hip_group_submit(self._h, C.byref(i), C.byref(o), CLASSIFY if classify else 0, C.byref(t), err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_group_submit, self._h, C.byref(i), C.byref(o), CLASSIFY if classify else 0, C.byref(t))
         return (t.value, img, out)  # the handle keeps the input and output arrays alive
 
     def wait(self, handle) -> dict:
         """Second half: blocks until the job's results are in the arrays; handles are waited for in submission order."""
-        err = _errbuf()
-        rc = lib().dinov2_hip_group_wait(self._h, handle[0], err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_group_wait, self._h, handle[0])
         return handle[2]
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dinov2_hip_group_free(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Session:
+class Session(_Handle):
     """ggml_gallocr_t counterpart: stream + workspace, reusable across predicts."""
+    _free = "dinov2_hip_session_free"
 
     def __init__(self, model: Model, stream: int | None = None):
         self.model = model
         h = C.c_void_p()
-        err = _errbuf()
-        rc = lib().dinov2_hip_session_create(model._h, C.c_void_p(stream) if stream else None, C.byref(h), err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_session_create, model._h, C.c_void_p(stream) if stream else None, C.byref(h))
         self._h = h
 
     def predict(self, images: np.ndarray, *, classify: bool = False, layout: int = RGB_CHW, topk: int = 0,
                 want=("cls", "patch_tokens", "logits", "probs")) -> dict:
         """images: f32 host array [B,3,H,W] (RGB_CHW) or [B,H,W,3] (BGR_HWC), or RAW uint8 [B,h,w,3] BGR with
         layout=U8_BGR_HWC (preprocessed on the device).  Returns host numpy outputs."""
-        img = np.ascontiguousarray(images, dtype=np.uint8 if layout == U8_BGR_HWC else np.float32)
-        if img.ndim == 3:
-            img = img[None]
-        B = img.shape[0]
-        hh, ww = (img.shape[2], img.shape[3]) if layout == RGB_CHW else (img.shape[1], img.shape[2])
+        img, B, hh, ww = _images(images, layout)
         out, o = _alloc_outputs(self.model.hparams, B, hh, ww, layout, classify, topk, want)
         i = Input(img.ctypes.data, B, hh, ww, layout, 0)
-        err = _errbuf()
-        rc = lib().dinov2_hip_predict(self._h, C.byref(i), C.byref(o), CLASSIFY if classify else 0, err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
-        hp = self.model.hparams  # the resident rows a Bank may name: one CLS row per image, P patch rows per image
-        nh, nw = preprocess_size(1 if classify else 0, hh, ww, hp.patch_size) if layout == U8_BGR_HWC else (hh, ww)
-        self._last_rows = {"last_cls": B, "last_patches": (nh // hp.patch_size) * (nw // hp.patch_size)}
+        _call(lib().dinov2_hip_predict, self._h, C.byref(i), C.byref(o), CLASSIFY if classify else 0)
+        # the resident rows a Bank may name: one CLS row per image, P patch rows per image
+        self._last_rows = {"last_cls": B, "last_patches": _grid(self.model.hparams, hh, ww, layout, classify)[2]}
         return out
 
     def predict_device(self, img_ptr: int, B: int, hh: int, ww: int, *, classify: bool, layout: int = RGB_CHW,
                        logits_ptr: int = 0, probs_ptr: int = 0, cls_ptr: int = 0, patch_ptr: int = 0):
         """Asynchronous predict on device-resident input/outputs (raw device pointers)."""
         i = Input(img_ptr, B, hh, ww, layout, 1)
-        o = Output(cls_ptr or None, patch_ptr or None, logits_ptr or None, probs_ptr or None, None, None, 0, 1)
-        err = _errbuf()
-        rc = lib().dinov2_hip_predict(self._h, C.byref(i), C.byref(o), CLASSIFY if classify else 0, err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        o = _device_output(cls_ptr, patch_ptr, logits_ptr, probs_ptr)
+        _call(lib().dinov2_hip_predict, self._h, C.byref(i), C.byref(o), CLASSIFY if classify else 0)
 
     def _layer_list(self, layers):
         """`layers` as the C-ABI wants it: ascending numbers of blocks applied; an int n = the last n layers, as upstream."""
@@ -985,16 +919,12 @@ class Session:
         block index i is layer i + 1, HuggingFace hidden_states[k] is layer k), or an int n = the last n layers.  norm: through the model's
         final LayerNorm; reshape: patch tokens as [B, H, h0, w0] instead of [B, P, H].  Returns predict's dict plus "layers": one dict per
         requested layer with "layer", "patch_tokens" and, if asked for, "cls" [B, H] and "registers" [B, R, H]."""
-        img = np.ascontiguousarray(images, dtype=np.uint8 if layout == U8_BGR_HWC else np.float32)
-        if img.ndim == 3:
-            img = img[None]
-        B = img.shape[0]
-        hh, ww = (img.shape[2], img.shape[3]) if layout == RGB_CHW else (img.shape[1], img.shape[2])
+        img, B, hh, ww = _images(images, layout)
         hp = self.model.hparams
         out, o = _alloc_outputs(hp, B, hh, ww, layout, classify, topk, want)
         ids = self._layer_list(layers)
         n, Hd, R, ps = len(ids), hp.hidden_size, hp.num_register_tokens, hp.patch_size
-        nh, nw = preprocess_size(1 if classify else 0, hh, ww, ps) if layout == U8_BGR_HWC else (hh, ww)
+        nh, nw, _ = _grid(hp, hh, ww, layout, classify)
         h0, w0 = nh // ps, nw // ps
         arr = (C.c_int32 * max(n, 1))(*ids)
         patch = np.empty((n, B, Hd, h0, w0) if reshape else (n, B, h0 * w0, Hd), np.float32)
@@ -1003,10 +933,7 @@ class Session:
         ly = Layers(arr, n, int(bool(norm)), LAYERS_CHW if reshape else LAYERS_TOKENS, patch.ctypes.data,
                     cls.ctypes.data if cls is not None else None, reg.ctypes.data if reg is not None else None, 0)
         i = Input(img.ctypes.data, B, hh, ww, layout, 0)
-        err = _errbuf()
-        rc = lib().dinov2_hip_predict_layers(self._h, C.byref(i), C.byref(o), C.byref(ly), CLASSIFY if classify else 0, err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_predict_layers, self._h, C.byref(i), C.byref(o), C.byref(ly), CLASSIFY if classify else 0)
         out["layers"] = []
         for k, layer in enumerate(ids):
             d = {"layer": layer, "patch_tokens": patch[k]}
@@ -1027,26 +954,18 @@ class Session:
         ly = Layers(arr, len(ids), int(bool(norm)), LAYERS_CHW if reshape else LAYERS_TOKENS, layer_patch_ptr or None,
                     layer_cls_ptr or None, layer_reg_ptr or None, 1)
         i = Input(img_ptr, B, hh, ww, layout, 1)
-        o = Output(cls_ptr or None, patch_ptr or None, logits_ptr or None, probs_ptr or None, None, None, 0, 1)
-        err = _errbuf()
-        rc = lib().dinov2_hip_predict_layers(self._h, C.byref(i), C.byref(o), C.byref(ly), CLASSIFY if classify else 0, err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        o = _device_output(cls_ptr, patch_ptr, logits_ptr, probs_ptr)
+        _call(lib().dinov2_hip_predict_layers, self._h, C.byref(i), C.byref(o), C.byref(ly), CLASSIFY if classify else 0)
 
     def predict_dense(self, images: np.ndarray, head: "DenseHead", out_size=None, want=("labels", "value", "logits"), *, classify: bool = False,
                       layout: int = RGB_CHW, topk: int = 0, predict_want=()) -> dict:
         """One forward plus a linear dense head (dinov2_hip_predict_dense): dict of "labels" [B, oh, ow] uint8 (argmax heads), "value"
         [B, oh, ow] f32 (the winning logit, or the bins' expectation) and "logits" [B, P, C] f32, whichever of `want` the head has, plus
         "predict": predict()'s outputs named in `predict_want`, if any.  out_size: (out_h, out_w), None = the network input size."""
-        img = np.ascontiguousarray(images, dtype=np.uint8 if layout == U8_BGR_HWC else np.float32)
-        if img.ndim == 3:
-            img = img[None]
-        B = img.shape[0]
-        hh, ww = (img.shape[2], img.shape[3]) if layout == RGB_CHW else (img.shape[1], img.shape[2])
+        img, B, hh, ww = _images(images, layout)
         hp = self.model.hparams
-        nh, nw = preprocess_size(1 if classify else 0, hh, ww, hp.patch_size) if layout == U8_BGR_HWC else (hh, ww)
+        nh, nw, P = _grid(hp, hh, ww, layout, classify)
         oh, ow = (nh, nw) if out_size is None else (int(out_size[0]), int(out_size[1]))
-        P = (nh // hp.patch_size) * (nw // hp.patch_size)
         res = {}
         if "labels" in want and head.reduce == "argmax":
             res["labels"] = np.empty((B, oh, ow), np.uint8)
@@ -1058,11 +977,8 @@ class Session:
         do = DenseOut(0 if out_size is None else oh, 0 if out_size is None else ow, ptr("labels"), ptr("value"), ptr("logits"), 0)
         out, o = _alloc_outputs(hp, B, hh, ww, layout, classify, topk, predict_want) if predict_want else ({}, None)
         i = Input(img.ctypes.data, B, hh, ww, layout, 0)
-        err = _errbuf()
-        rc = lib().dinov2_hip_predict_dense(self._h, C.byref(i), C.byref(o) if o is not None else None, head._h, C.byref(do),
-                                            CLASSIFY if classify else 0, err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_predict_dense, self._h, C.byref(i), C.byref(o) if o is not None else None, head._h, C.byref(do),
+              CLASSIFY if classify else 0)
         self._last_rows = {"last_cls": B, "last_patches": P}
         if predict_want:
             res["predict"] = out
@@ -1075,10 +991,7 @@ class Session:
         oh, ow = (0, 0) if out_size is None else (int(out_size[0]), int(out_size[1]))
         do = DenseOut(oh, ow, labels_ptr or None, value_ptr or None, logits_ptr or None, 1)
         i = Input(img_ptr, B, hh, ww, layout, 1)
-        err = _errbuf()
-        rc = lib().dinov2_hip_predict_dense(self._h, C.byref(i), None, head._h, C.byref(do), CLASSIFY if classify else 0, err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_predict_dense, self._h, C.byref(i), None, head._h, C.byref(do), CLASSIFY if classify else 0)
 
     def _attention_request(self, layers, queries, keys):
         """(layer ids, their C array, query ids, their C array or None, keys value) of a dinov2_hip_attention."""
@@ -1097,16 +1010,11 @@ class Session:
         CLS row.  keys: "all" (T columns) or "patches" (the P patch columns, the same bits, not re-normalised).  Returns [n, B, heads, Q, T | P]
         float32.  taps: a list of layer numbers for predict_layers' patch tokens [n_taps, B, P, H] (through the final LayerNorm if `norm`) from
         the same forward.  With taps or return_outputs the result is (rows, dict): predict's outputs, plus "layers" when taps were asked for."""
-        img = np.ascontiguousarray(images, dtype=np.uint8 if layout == U8_BGR_HWC else np.float32)
-        if img.ndim == 3:
-            img = img[None]
-        B = img.shape[0]
-        hh, ww = (img.shape[2], img.shape[3]) if layout == RGB_CHW else (img.shape[1], img.shape[2])
+        img, B, hh, ww = _images(images, layout)
         hp = self.model.hparams
         out, o = _alloc_outputs(hp, B, hh, ww, layout, classify, topk, want)
-        ps, R, Hd = hp.patch_size, hp.num_register_tokens, hp.hidden_size
-        nh, nw = preprocess_size(1 if classify else 0, hh, ww, ps) if layout == U8_BGR_HWC else (hh, ww)
-        P = (nh // ps) * (nw // ps)
+        R, Hd = hp.num_register_tokens, hp.hidden_size
+        P = _grid(hp, hh, ww, layout, classify)[2]
         ids, arr, qs, qarr, kv = self._attention_request(layers, queries, keys)
         rows = np.empty((len(ids), B, hp.num_attention_heads, max(1, len(qs)), P if kv == ATTN_KEYS_PATCHES else 1 + R + P), np.float32)
         at = Attention(arr, len(ids), qarr, len(qs), kv, rows.ctypes.data, 0)
@@ -1117,11 +1025,8 @@ class Session:
             patch = np.empty((len(tids), B, P, Hd), np.float32)
             ly = Layers(tarr, len(tids), int(bool(norm)), LAYERS_TOKENS, patch.ctypes.data, None, None, 0)
         i = Input(img.ctypes.data, B, hh, ww, layout, 0)
-        err = _errbuf()
-        rc = lib().dinov2_hip_predict_attention(self._h, C.byref(i), C.byref(o), C.byref(ly) if ly is not None else None, C.byref(at),
-                                                CLASSIFY if classify else 0, err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_predict_attention, self._h, C.byref(i), C.byref(o), C.byref(ly) if ly is not None else None, C.byref(at),
+              CLASSIFY if classify else 0)
         if ly is not None:
             out["layers"] = [{"layer": layer, "patch_tokens": patch[k]} for k, layer in enumerate(tids)]
         return (rows, out) if (ly is not None or return_outputs) else rows
@@ -1134,25 +1039,15 @@ class Session:
         ids, arr, qs, qarr, kv = self._attention_request(layers, queries, keys)
         at = Attention(arr, len(ids), qarr, len(qs), kv, int(getattr(probs, "ptr", probs)) or None, 1)
         i = Input(img_ptr, B, hh, ww, layout, 1)
-        o = Output(cls_ptr or None, patch_ptr or None, logits_ptr or None, probs_ptr or None, None, None, 0, 1)
-        err = _errbuf()
-        rc = lib().dinov2_hip_predict_attention(self._h, C.byref(i), C.byref(o), None, C.byref(at), CLASSIFY if classify else 0, err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        o = _device_output(cls_ptr, patch_ptr, logits_ptr, probs_ptr)
+        _call(lib().dinov2_hip_predict_attention, self._h, C.byref(i), C.byref(o), None, C.byref(at), CLASSIFY if classify else 0)
 
     def debug_hidden(self, images: np.ndarray, layer: int, layout: int = RGB_CHW) -> np.ndarray:
-        img = np.ascontiguousarray(images, dtype=np.float32)
-        if img.ndim == 3:
-            img = img[None]
-        B = img.shape[0]
-        hh, ww = (img.shape[2], img.shape[3]) if layout == RGB_CHW else (img.shape[1], img.shape[2])
+        img, B, hh, ww = _images(images, layout, np.float32)  # (no preprocess step here: float32 whatever the layout)
         T = self.model.tokens(hh, ww)
         out = np.empty((B, T, self.model.hparams.hidden_size), np.float32)
         i = Input(img.ctypes.data, B, hh, ww, layout, 0)
-        err = _errbuf()
-        rc = lib().dinov2_hip_debug_hidden(self._h, C.byref(i), layer, out.ctypes.data, err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_debug_hidden, self._h, C.byref(i), layer, out.ctypes.data)
         return out
 
     def pca3(self, tokens: np.ndarray | None = None, shape: tuple[int, int] | None = None):
@@ -1170,10 +1065,7 @@ class Session:
             P, H = x.shape
             ptr = x.ctypes.data
         comp, mean, proj = np.empty((3, H), np.float32), np.empty(H, np.float32), np.empty((P, 3), np.float32)
-        err = _errbuf()
-        rc = lib().dinov2_hip_pca3(self._h, ptr, P, H, 0, comp.ctypes.data, mean.ctypes.data, proj.ctypes.data, err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_pca3, self._h, ptr, P, H, 0, comp.ctypes.data, mean.ctypes.data, proj.ctypes.data)
         return comp, mean, proj
 
     def match(self, a=None, b=None, *, image_a: int = 0, image_b: int = 1, shape: tuple[int, int] | None = None):
@@ -1205,10 +1097,7 @@ class Session:
                "sim_ba": np.empty(nb, np.float32)}
         m = Match(ptr(xa), ptr(xb), na, nb, Ha, int(image_a), int(image_b), int(on_device), out["idx_ab"].ctypes.data, out["sim_ab"].ctypes.data,
                   out["idx_ba"].ctypes.data, out["sim_ba"].ctypes.data)
-        err = _errbuf()
-        rc = lib().dinov2_hip_match_tokens(self._h, C.byref(m), err, len(err))
-        if rc != 0:
-            raise DinoError(rc, err.value.decode(errors="replace"))
+        _call(lib().dinov2_hip_match_tokens, self._h, C.byref(m))
         out["mutual"] = out["idx_ba"][out["idx_ab"]] == np.arange(na, dtype=np.int32)
         return out
 
@@ -1229,17 +1118,6 @@ class Session:
         cnt = (C.c_int32 * n)()
         k = lib().dinov2_hip_session_profile_read(self._h, n, names, ms, cnt)
         return {names[i].decode(): (float(ms[i]), int(cnt[i])) for i in range(k)}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dinov2_hip_session_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ------------------------------------------------------------------------------------------------

@@ -57,6 +57,9 @@ inline LayerListFault check_layer_list(const int32_t* layers, int n, int lo, int
     return LAYER_LIST_OK;
 }
 
+// pca.cpp, for ops_testing.cpp: the Rayleigh-Ritz step of dinov2_hip_pca3 on the host
+void pca_ritz(const double* yprev, const double* ynext, const double* g_parts, int nparts, int H, double* evals, double* comp);
+
 // interpolate_pos_embed of the reference (load.cpp).  pos: [1 + M*M, H]; out: [1 + h_new*w_new, H].
 void interpolate_pos_embed(const float* pos, int M, int H, int h_new, int w_new, float* out);
 
