@@ -61,6 +61,12 @@ class Output(C.Structure):
                 ("topk_ids", C.c_void_p), ("topk_probs", C.c_void_p), ("topk", C.c_int32), ("on_device", C.c_int32)]
 
 
+class ImageList(C.Structure):
+    """dinov2_hip_image_list (include/dinov2_hip.h)."""
+    _fields_ = [("data", C.POINTER(C.c_void_p)), ("height", C.POINTER(C.c_int32)), ("width", C.POINTER(C.c_int32)), ("n", C.c_int32),
+                ("layout", C.c_int32), ("on_device", C.c_int32)]
+
+
 class Layers(C.Structure):
     """dinov2_hip_layers (include/dinov2_hip.h)."""
     _fields_ = [("layers", C.POINTER(C.c_int32)), ("n_layers", C.c_int32), ("norm", C.c_int32), ("layout", C.c_int32),
@@ -201,6 +207,41 @@ def op_layer_tap(x, w, b, eps, R, h0, w0, *, norm, chw, want=("patch", "cls", "r
         out["reg"] = np.zeros((B, R, H), np.float32)
     _op_rc(lib().dinov2_hip_op_layer_tap(_ptr(x), _ptr(_f32(w)), _ptr(_f32(b)), float(eps), B, T, R, H, h0, w0, int(norm), int(chw),
                                          _ptr(out.get("patch")), _ptr(out.get("cls")), _ptr(out.get("reg"))), "layer_tap")
+    return out
+
+
+LIST_ORDER_AS_GIVEN, LIST_ORDER_LONGEST_FIRST = 0, 1
+LIST_POS_GRIDS = 64  # DINOV2_HIP_LIST_POS_GRIDS
+
+
+def list_plan(sizes, patch, R, nh, order=LIST_ORDER_AS_GIVEN):
+    """The plan of a Session.predict_list (dinov2_hip_op_list_plan; no device): `sizes` = [(h, w)] NETWORK sizes in pixels.  Returns a dict:
+    images [n, 5] int64 (row0, T, P, h0, w0), runs [nruns, 2] (first, count), items [units, 4] int32 (row0, T, head, query block) in the
+    order of the attention launch's workgroups, and the totals M, P, pixels, units."""
+    hw = np.ascontiguousarray(sizes, np.int32).reshape(-1, 2)
+    n = len(hw)
+    h, w = np.ascontiguousarray(hw[:, 0]), np.ascontiguousarray(hw[:, 1])
+    tot = np.zeros(5, np.int64)
+    images, runs = np.zeros((n, 5), np.int64), np.zeros((n, 2), np.int32)
+    args = (n, _ptr(h), _ptr(w), int(patch), int(R), int(nh), int(order))
+    if lib().dinov2_hip_op_list_plan(*args, _ptr(images), _ptr(runs), None, 0, _ptr(tot)) != 0:
+        raise ValueError(f"list_plan refuses sizes={hw.tolist()} patch={patch} R={R} nh={nh} order={order}")
+    items = np.zeros((int(tot[3]), 4), np.int32)
+    if lib().dinov2_hip_op_list_plan(*args, None, None, _ptr(items), len(items), _ptr(tot)) != 0:
+        raise ValueError("list_plan: the table does not fit")
+    return {"images": images, "runs": runs[:int(tot[4])], "items": items, "M": int(tot[0]), "P": int(tot[1]), "pixels": int(tot[2]),
+            "units": int(tot[3])}
+
+
+def op_attention_list(dtype, qkv, T, nh, log2_scores=True):
+    """launch_attention_list alone (dinov2_hip_op_attention_list): qkv [sum T, 3*64*nh] f32, segments of T[i] tokens one after the other ->
+    [sum T, 64*nh] f32 values of the compute type.  Raises on a HIP error or a changed guard band."""
+    H = 64 * nh
+    T = np.ascontiguousarray(T, np.int32)
+    qkv = _f32(qkv)
+    assert qkv.shape == (int(T.sum()), 3 * H), qkv.shape
+    out = np.zeros((int(T.sum()), H), np.float32)
+    _op_rc(lib().dinov2_hip_op_attention_list(int(dtype), _ptr(qkv), _ptr(out), len(T), _ptr(T), H, nh, int(log2_scores)), "attention_list")
     return out
 
 
@@ -406,6 +447,8 @@ def lib():
     L.dinov2_hip_predict.argtypes = [vp, C.POINTER(Input), C.POINTER(Output), u32, cp, sz]
     L.dinov2_hip_predict_layers.argtypes = [vp, C.POINTER(Input), C.POINTER(Output), C.POINTER(Layers), u32, cp, sz]
     L.dinov2_hip_predict_attention.argtypes = [vp, C.POINTER(Input), C.POINTER(Output), C.POINTER(Layers), C.POINTER(Attention), u32, cp, sz]
+    L.dinov2_hip_list_rows.argtypes = [vp, C.POINTER(ImageList), u32, C.POINTER(C.c_int64), cp, sz]
+    L.dinov2_hip_predict_list.argtypes = [vp, C.POINTER(ImageList), C.POINTER(Output), u32, cp, sz]
     L.dinov2_hip_default_group_opts.argtypes = [C.POINTER(GroupOpts)]
     L.dinov2_hip_default_group_opts.restype = None
     L.dinov2_hip_group_create.argtypes = [cp, C.POINTER(GroupOpts), C.POINTER(vp), cp, sz]
@@ -456,6 +499,9 @@ def lib():
     L.dinov2_hip_op_ln_fold_vectors.argtypes = [i32, fp, fp, fp, fp, fp, fp, i32, i32]
     L.dinov2_hip_op_attention.argtypes = [i32, fp, fp, i32, i32, i32, i32]
     L.dinov2_hip_op_attention_ex.argtypes = [i32, fp, fp, i32, i32, i32, i32, i32]
+    L.dinov2_hip_op_list_plan.argtypes = [i32, C.POINTER(i32), C.POINTER(i32), i32, i32, i32, i32, C.POINTER(C.c_int64), C.POINTER(i32),
+                                          C.POINTER(i32), C.c_int64, C.POINTER(C.c_int64)]
+    L.dinov2_hip_op_attention_list.argtypes = [i32, fp, fp, i32, C.POINTER(i32), i32, i32, i32]
     L.dinov2_hip_op_layernorm.argtypes = [i32, fp, fp, fp, fp, i32, i32, C.c_float]
     L.dinov2_hip_op_layer_tap.argtypes = [fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32, fp, fp, fp]
     L.dinov2_hip_op_attn_rows.argtypes = [i32, fp, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, i32, fp]
@@ -652,6 +698,28 @@ def _alloc_outputs(hp, B, hh, ww, layout, classify, topk, want):
             out["topk_probs"] = np.empty((B, topk), np.float32)
             o.topk_ids, o.topk_probs, o.topk = out["topk_ids"].ctypes.data, out["topk_probs"].ctypes.data, topk
     return out, o
+
+
+def _image_list(ptrs, sizes, layout, on_device):
+    """(ImageList, the ctypes arrays it points into: kept alive by the caller) of n images at `ptrs` with `sizes` = [(h, w)]."""
+    n = len(ptrs)
+    data = (C.c_void_p * max(n, 1))(*[int(p) if p else None for p in ptrs])
+    hs = (C.c_int32 * max(n, 1))(*[int(s[0]) for s in sizes])
+    ws = (C.c_int32 * max(n, 1))(*[int(s[1]) for s in sizes])
+    il = ImageList(C.cast(data, C.POINTER(C.c_void_p)), C.cast(hs, C.POINTER(C.c_int32)), C.cast(ws, C.POINTER(C.c_int32)), n, int(layout),
+                   int(on_device))
+    return il, (data, hs, ws)
+
+
+def list_rows(model: "Model", sizes, *, classify: bool = False, layout: int = RGB_CHW) -> np.ndarray:
+    """offsets [n + 1] (dinov2_hip_list_rows; no device): image i of a predict_list of images of these `sizes` = [(h, w)] (RAW sizes for
+    U8_BGR_HWC) owns rows offsets[i] .. offsets[i + 1] of the packed patch tokens."""
+    il, keep = _image_list([0] * len(sizes), sizes, layout, 0)
+    il.data = None
+    offsets = np.zeros(len(sizes) + 1, np.int64)
+    _call(lib().dinov2_hip_list_rows, model._h, C.byref(il), CLASSIFY if classify else 0, _ptr(offsets))
+    del keep
+    return offsets
 
 
 def pinned_empty(shape, dtype=np.float32) -> np.ndarray:
@@ -901,6 +969,42 @@ class Session(_Handle):
         i = Input(img_ptr, B, hh, ww, layout, 1)
         o = _device_output(cls_ptr, patch_ptr, logits_ptr, probs_ptr)
         _call(lib().dinov2_hip_predict, self._h, C.byref(i), C.byref(o), CLASSIFY if classify else 0)
+
+    def predict_list(self, images, *, classify: bool = False, layout: int = RGB_CHW, topk: int = 0,
+                     want=("cls", "patch_tokens", "logits", "probs")) -> dict:
+        """Images of different sizes in ONE forward (dinov2_hip_predict_list): `images` = a list of f32 arrays [3, h, w] (RGB_CHW) or [h, w, 3]
+        (BGR_HWC), or RAW uint8 [h, w, 3] with layout=U8_BGR_HWC.  Image i has, bit for bit, the outputs of predict() on it alone.  Returns
+        cls [n, H], logits / probs [n, C], topk_* [n, topk] as predict() does, and the patch tokens three ways: "patch_packed" [offsets[n], H],
+        "offsets" [n + 1], and "patch_tokens" = a list of views into the packed array, one [P_i (+ R), H] per image."""
+        imgs = [np.ascontiguousarray(a, dtype=np.uint8 if layout == U8_BGR_HWC else np.float32) for a in images]
+        for a in imgs:
+            if a.ndim != 3 or (a.shape[0] if layout == RGB_CHW else a.shape[2]) != 3:
+                raise ValueError(f"expected [3, h, w] (RGB_CHW) or [h, w, 3] images, got shape {a.shape}")
+        sizes = [(a.shape[1], a.shape[2]) if layout == RGB_CHW else (a.shape[0], a.shape[1]) for a in imgs]
+        il, keep = _image_list([a.ctypes.data for a in imgs], sizes, layout, 0)
+        hp, n = self.model.hparams, len(imgs)
+        offsets = np.zeros(n + 1, np.int64)
+        _call(lib().dinov2_hip_list_rows, self.model._h, C.byref(il), CLASSIFY if classify else 0, _ptr(offsets))
+        out, o = _alloc_outputs(hp, n, 0, 0, RGB_CHW, classify, topk, [k for k in want if k != "patch_tokens"])
+        if "patch_tokens" in want:
+            out["patch_packed"] = np.empty((int(offsets[-1]), hp.hidden_size), np.float32)
+            o.patch_tokens = out["patch_packed"].ctypes.data
+            out["patch_tokens"] = [out["patch_packed"][offsets[i]:offsets[i + 1]] for i in range(n)]
+        out["offsets"] = offsets
+        _call(lib().dinov2_hip_predict_list, self._h, C.byref(il), C.byref(o), CLASSIFY if classify else 0)
+        self._last_rows = {}  # a list forward leaves nothing resident for a Bank to name
+        del keep
+        return out
+
+    def predict_list_device(self, img_ptrs, sizes, *, classify: bool, layout: int = RGB_CHW, logits_ptr: int = 0, probs_ptr: int = 0,
+                            cls_ptr: int = 0, patch_ptr: int = 0):
+        """Asynchronous predict_list on device-resident inputs / outputs (raw device pointers): img_ptrs [n], sizes [(h, w)] as the layout
+        takes them; patch_ptr receives the packed rows (list_rows gives their offsets)."""
+        il, keep = _image_list(img_ptrs, sizes, layout, 1)
+        o = _device_output(cls_ptr, patch_ptr, logits_ptr, probs_ptr)
+        _call(lib().dinov2_hip_predict_list, self._h, C.byref(il), C.byref(o), CLASSIFY if classify else 0)
+        self._last_rows = {}
+        del keep
 
     def _layer_list(self, layers):
         """`layers` as the C-ABI wants it: ascending numbers of blocks applied; an int n = the last n layers, as upstream."""

@@ -131,6 +131,30 @@ static __device__ __forceinline__ float max32(const f32x16 (&s)[2]) {
     return max3f(max3f(m0, m1, m2), m3, m3);
 }
 
+// What a kernel below runs over: the type of its third parameter.  AttnUniform: B images of Ttok tokens each, the workgroup's (image, head,
+// query block) from its place in the grid -- the parameter is the int Ttok the kernels always took, so their signature, kernarg layout and
+// prologue are what they were.  AttnList (launch_attention_list): images of different lengths one after the other, the workgroup's {first
+// row, length, head, query block} from a device table (a uniform address: one scalar 16-byte load).  The policy touches three places --
+// where the workgroup's rows begin, how many there are, and where its output rows go; the key loop is one text for both.
+struct AttnUniform {
+    static constexpr bool LIST = false;
+    using Arg = int;  // Ttok
+};
+struct AttnList {
+    static constexpr bool LIST = true;
+    using Arg = const AttnItem*;  // [gridDim.x]
+};
+// The workgroup's table entry into SGPRs: read through the constant address space, the uniform-address load is one s_load_dwordx4 (as a
+// plain global load hipcc made it a vector load, and T, head and the query block -- loop bounds, wave-uniform branches -- sat in VGPRs).
+// Nothing writes the table while the kernel runs.
+static __device__ __forceinline__ AttnItem attn_item(const AttnItem* items, int i) {
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    typedef const i32x4 __attribute__((address_space(4))) * ConstItems;
+    static_assert(sizeof(AttnItem) == 16, "one 16-byte load per entry");
+    const i32x4 v = ((ConstItems)(uintptr_t)items)[i];
+    return AttnItem{v[0], v[1], v[2], v[3]};
+}
+
 #ifndef DINO_PREC
 #define DINO_PREC 0  // tuning builds: which operand roundings attention_kernel removes (gemm.hip, "DINO_PREC"); 0 in the product
 #endif
@@ -143,9 +167,9 @@ static __device__ __forceinline__ float max32(const f32x16 (&s)[2]) {
 // more per MFMA than the GEMM, and like the GEMM it is bound by what the CU can move next to the MFMAs, profiles/r02_gemm_kloop.md):
 // half the LDS bytes per MFMA for twice the registers (two waves per SIMD).  Per query the arithmetic is the same instruction
 // sequence in the same order, so QB does not change a single bit of the result.
-template <typename T, bool LOG2, int NWV, int QB = 1>
+template <typename T, bool LOG2, int NWV, int QB = 1, typename POL = AttnUniform>
 __global__ __launch_bounds__(NWV * 64, QB == 2 ? 2 : (NWV == 8 ? 4 : 2)) void attention_kernel(
-    const T* __restrict__ qkv, T* __restrict__ out, int Ttok, int H) {
+    const T* __restrict__ qkv, T* __restrict__ out, typename POL::Arg arg, int H) {
     using E = Elem<T>;
     using vec8 = typename E::vec8;
     using vec4 = typename E::vec4;
@@ -169,15 +193,26 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 2 : (NWV == 8 ? 4 : 2)) void at
     // 0.36 GB algorithmic, i.e. the kernel ran at HBM speed).  xcd_remap gives each XCD a contiguous range of logical ids,
     // so all query blocks of a head share one L2.
     constexpr int QW = 32 * QB;  // queries per wave
-    const int nqb = (Ttok + NWV * QW - 1) / (NWV * QW), nhd = H >> 6;
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);
-    const int qb = lid % nqb, h = (lid / nqb) % nhd, b = lid / (nqb * nhd);
+    int Ttok, qb, h;
+    size_t row_first;  // the first row of this workgroup's image in qkv and out
+    if constexpr (POL::LIST) {
+        static_assert(NWV * QW == ATTN_LIST_QB, "the table's query blocks are this kernel's");
+        const AttnItem it = attn_item(arg, xcd_remap(blockIdx.x, gridDim.x));
+        Ttok = it.T, qb = it.qb, h = it.head, row_first = (size_t)it.row0;
+    } else {
+        Ttok = arg;
+        const int nqb = (Ttok + NWV * QW - 1) / (NWV * QW), nhd = H >> 6;
+        const int lid = xcd_remap(blockIdx.x, gridDim.x);
+        qb = lid % nqb, h = (lid / nqb) % nhd;
+        const int b = lid / (nqb * nhd);
+        row_first = (size_t)b * Ttok;
+    }
 #if DINO_PREC & 25
     const int H3 = 6 * H;  // (tuning build) every row carries a second word of q | k | v behind the first: [q k v | q_lo k_lo v_lo]
 #else
     const int H3 = 3 * H;
 #endif
-    const char* base = (const char*)(qkv + (size_t)b * Ttok * H3);
+    const char* base = (const char*)(qkv + row_first * H3);
 
     const int ql = lane & 31, hh = lane >> 5;
     const int qrow0 = qb * (NWV * QW) + wid * QW + ql;  // + 32 u for query block u of this wave
@@ -434,7 +469,7 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 2 : (NWV == 8 ? 4 : 2)) void at
         const float l_tot = l_run[u] + __shfl_xor(l_run[u], 32);
         const float inv = 1.0f / l_tot;
         if (qrow < Ttok) {
-            T* orow = out + ((size_t)b * Ttok + qrow) * H + h * 64;
+            T* orow = out + (row_first + qrow) * H + h * 64;
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -462,8 +497,8 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 2 : (NWV == 8 ? 4 : 2)) void at
 // from LDS feeds two MFMAs (half the LDS bytes per MFMA) and the MFMA / softmax overlap happens inside the wave's own instruction
 // stream -- the design profiles/r02_attention_anatomy.md section 4 points to.  Per query the arithmetic is the same instruction
 // sequence in the same order for every (QB, NWV): results are bit-identical (test_attention_kernels_agree_bit_for_bit).
-template <typename T, bool LOG2, int QB = 1, int NWV = 4>
-__global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(const T* __restrict__ qkv, T* __restrict__ out, int Ttok, int H) {
+template <typename T, bool LOG2, int QB = 1, int NWV = 4, typename POL = AttnUniform>
+__global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(const T* __restrict__ qkv, T* __restrict__ out, typename POL::Arg arg, int H) {
     using E = Elem<T>;
     using vec8 = typename E::vec8;
     using vec4 = typename E::vec4;
@@ -481,11 +516,22 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(c
     DINO_TS_INIT
     DINO_CLK_BEGIN()
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nqb = (Ttok + WGQ - 1) / WGQ, nhd = H >> 6;
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);  // all query blocks of a head on one XCD (see attention_kernel)
-    const int qb = lid % nqb, h = (lid / nqb) % nhd, b = lid / (nqb * nhd);
+    int Ttok, qb, h;
+    size_t row_first;  // as in attention_kernel
+    if constexpr (POL::LIST) {
+        static_assert(WGQ == ATTN_LIST_QB, "the table's query blocks are this kernel's");
+        const AttnItem it = attn_item(arg, xcd_remap(blockIdx.x, gridDim.x));
+        Ttok = it.T, qb = it.qb, h = it.head, row_first = (size_t)it.row0;
+    } else {
+        Ttok = arg;
+        const int nqb = (Ttok + WGQ - 1) / WGQ, nhd = H >> 6;
+        const int lid = xcd_remap(blockIdx.x, gridDim.x);  // all query blocks of a head on one XCD (see attention_kernel)
+        qb = lid % nqb, h = (lid / nqb) % nhd;
+        const int b = lid / (nqb * nhd);
+        row_first = (size_t)b * Ttok;
+    }
     const int H3 = 3 * H;
-    const char* base = (const char*)(qkv + (size_t)b * Ttok * H3);
+    const char* base = (const char*)(qkv + row_first * H3);
     const int ql = lane & 31, hh = lane >> 5;
     const int qrow0 = qb * WGQ + wid * QW + ql;  // + 32 u for query block u of this wave
 
@@ -850,7 +896,7 @@ __global__ __launch_bounds__(NWV * 64, QB == 2 ? 1 : 2) void attention2_kernel(c
         const float inv = 1.0f / l_tot;
         const int qrow = qrow0 + 32 * u;
         if (qrow < Ttok) {
-            T* orow = out + ((size_t)b * Ttok + qrow) * H + h * 64;
+            T* orow = out + (row_first + qrow) * H + h * 64;
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -952,6 +998,25 @@ static hipError_t launch_attention_impl(DType dt, const void* qkv, void* out, in
     else { if (log2_scores) DINO_ATT_N(__bf16, true) else DINO_ATT_N(__bf16, false) }
 #undef DINO_ATT_N
 #undef DINO_ATT
+    return hipGetLastError();
+}
+
+// The list form (kernels.h): one workgroup per table entry, the four-wave 128-query instances of the two kernels above over AttnList.
+hipError_t launch_attention_list(DType dt, const void* qkv, void* out, const AttnItem* items_dev, int n_items, long units, int H, int nh,
+                                 bool log2_scores, hipStream_t st) {
+    if (H != nh * 64 || n_items <= 0 || !items_dev) return hipErrorInvalidValue;
+    const int forced_ver = tune_get(TUNE_ATTN_V);
+    const int ver = forced_ver ? forced_ver : units <= 512 ? 2 : 1;  // launch_attention's rule, on the list's total
+    if (ver != 1 && ver != 2) return hipErrorInvalidValue;           // versions 3 and 4 have no list form
+    const dim3 grid((unsigned)n_items), block(256);
+#define DINO_ATTL(TT, LG)                                                                                                             \
+    {                                                                                                                                 \
+        if (ver == 2) hipLaunchKernelGGL((attention2_kernel<TT, LG, 1, 4, AttnList>), grid, block, 0, st, (const TT*)qkv, (TT*)out, items_dev, H); \
+        else hipLaunchKernelGGL((attention_kernel<TT, LG, 4, 1, AttnList>), grid, block, 0, st, (const TT*)qkv, (TT*)out, items_dev, H);       \
+    }
+    if (dt == DT_F16) { if (log2_scores) DINO_ATTL(_Float16, true) else DINO_ATTL(_Float16, false) }
+    else { if (log2_scores) DINO_ATTL(__bf16, true) else DINO_ATTL(__bf16, false) }
+#undef DINO_ATTL
     return hipGetLastError();
 }
 

@@ -585,7 +585,7 @@ std::atomic<int> g_tune[TUNE_COUNT];
 int g_tune_env[TUNE_COUNT];  // what the environment said at first use: what a negative value restores (tests leave the process as they found it)
 std::once_flag g_tune_once;
 void tune_init() {
-    static const char* const names[TUNE_COUNT] = {"DINOV2_HIP_GEMM_GEN", "DINOV2_HIP_GEMM_TILE", "DINOV2_HIP_ATTN_V", "DINOV2_HIP_ATTN_NWV"};
+    static const char* const names[TUNE_COUNT] = {"DINOV2_HIP_GEMM_GEN", "DINOV2_HIP_GEMM_TILE", "DINOV2_HIP_ATTN_V", "DINOV2_HIP_ATTN_NWV", "DINOV2_HIP_LIST_ORDER"};
     for (int k = 0; k < TUNE_COUNT; ++k) {
         const char* e = getenv(names[k]);
         g_tune_env[k] = e ? atoi(e) : 0;

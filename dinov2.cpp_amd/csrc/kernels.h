@@ -3,7 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
+#include <utility>
+#include <vector>
 
 namespace dinov2 {
 
@@ -120,7 +123,8 @@ enum TuneKey : int {
     TUNE_GEMM_TILE = 1,  // DINOV2_HIP_GEMM_TILE: 128 | 256 (tuning builds: 129 | 192)
     TUNE_ATTN_V = 2,     // DINOV2_HIP_ATTN_V: 1 .. 4
     TUNE_ATTN_NWV = 3,   // DINOV2_HIP_ATTN_NWV: 2 | 3 | 4
-    TUNE_COUNT = 4
+    TUNE_LIST_ORDER = 4, // DINOV2_HIP_LIST_ORDER: 1 = the attention table of dinov2_hip_predict_list with the longest images first (a measuring aid; same bits)
+    TUNE_COUNT = 5
 };
 int tune_get(TuneKey k);
 void tune_set(TuneKey k, int v);
@@ -146,6 +150,71 @@ hipError_t launch_ln_fold_vectors(DType dt, const void* W, const float* bias, co
 // log2_scores: q was scaled by log2(e)/sqrt(hd) instead of 1/sqrt(hd), so softmax uses exp2 directly.
 hipError_t launch_attention(DType dt, const void* qkv, void* out, int B, int T, int H, int nh, bool log2_scores,
                             hipStream_t stream);
+// ---- a list of images of different sizes in one forward (dinov2_hip_predict_list; contract in include/dinov2_hip.h).  The residual stream
+// holds the images' token rows one after the other: image i owns rows [row0, row0 + T).  Everything but attention works per row and takes
+// M = sum T_i; attention runs over a device table with one entry per workgroup.
+struct AttnItem {  // one workgroup of launch_attention_list: 128 queries [128 qb, 128 qb + 128) of head `head` of the image at rows [row0, row0 + T)
+    int32_t row0, T, head, qb;
+};
+struct ListImage {
+    int64_t row0;     // first row of the image in the residual stream
+    int32_t T, P;     // tokens (1 + R + P) and patches (h0 w0)
+    int32_t h0, w0;   // patch grid
+};
+struct ListRun {  // a run of consecutive images of one network size: embedded and pooled by one launch each, with B = count
+    int32_t first, count;
+};
+constexpr int ATTN_LIST_QB = 128;  // queries per workgroup of the list kernels (four waves of 32)
+// The sizes of a plan; list_plan fills the arrays the caller gives it (any may be null: counts only).  Launches nothing, needs no device.
+struct ListPlan {
+    int64_t M;        // total rows, sum T_i
+    int64_t P;        // total patches
+    int64_t pixels;   // sum h_i w_i (network sizes)
+    int64_t units;    // attention work items = sum ceil(T_i / 128) nh
+    int32_t nruns;
+};
+// h[i], w[i]: NETWORK sizes in pixels (positive multiples of `patch`, the callers check).  items: [units], images: [n], runs: [<= n].
+// Table order: image-major, then head, then query block -- after xcd_remap over the table's length all query blocks of an (image, head) sit
+// on one XCD, except where the boundary between two XCD ranges falls inside one.  The images come in list order (LIST_ORDER_AS_GIVEN) or by
+// descending T, equal T in list order (LIST_ORDER_LONGEST_FIRST); the order changes no bit of any result.  The table holds row0 in 32 bits:
+// ask for it only where M < 2^31 (one pass is far below).
+enum ListOrder : int { LIST_ORDER_AS_GIVEN = 0, LIST_ORDER_LONGEST_FIRST = 1 };
+inline ListPlan list_plan(int n, const int32_t* h, const int32_t* w, int patch, int R, int nh, int order, ListImage* images, ListRun* runs,
+                          AttnItem* items) {
+    ListPlan p{};
+    std::vector<std::pair<int32_t, int64_t>> seg(items ? (size_t)n : 0);  // (T, row0) per image, for the table
+    for (int i = 0; i < n; ++i) {
+        const int h0 = h[i] / patch, w0 = w[i] / patch;
+        const int P = h0 * w0, T = 1 + R + P;
+        if (images) images[i] = ListImage{p.M, T, P, h0, w0};
+        if (items) seg[(size_t)i] = {T, p.M};
+        if (i == 0 || h[i] != h[i - 1] || w[i] != w[i - 1]) {
+            if (runs) runs[p.nruns] = ListRun{i, 0};
+            ++p.nruns;
+        }
+        if (runs) ++runs[p.nruns - 1].count;
+        p.units += (int64_t)((T + ATTN_LIST_QB - 1) / ATTN_LIST_QB) * nh;
+        p.M += T;
+        p.P += P;
+        p.pixels += (int64_t)h[i] * w[i];
+    }
+    if (!items) return p;
+    if (order == LIST_ORDER_LONGEST_FIRST)
+        std::stable_sort(seg.begin(), seg.end(), [](const std::pair<int32_t, int64_t>& a, const std::pair<int32_t, int64_t>& b) { return a.first > b.first; });
+    AttnItem* it = items;
+    for (const auto& s : seg) {
+        const int nqb = (s.first + ATTN_LIST_QB - 1) / ATTN_LIST_QB;
+        for (int hd = 0; hd < nh; ++hd)
+            for (int qb = 0; qb < nqb; ++qb) *it++ = AttnItem{(int32_t)s.second, s.first, hd, qb};
+    }
+    return p;
+}
+// The list form of launch_attention: qkv [sum T_i, 3H], out [sum T_i, H]; items_dev: DEVICE table of n_items entries (list_plan); `units` =
+// n_items picks the kernel as launch_attention does on its own count (version 2 up to 512, else 1; TUNE_ATTN_V forces 1 or 2, other values
+// are refused: versions 3 and 4 and the 2- and 3-wave workgroups have no list form).  Each image is, bit for bit, launch_attention on its
+// rows alone (B = 1).  The 32-bit staging cursors are relative to the image's first row: T_i 3H 2 < 2^32 per image (the caller checks).
+hipError_t launch_attention_list(DType dt, const void* qkv, void* out, const AttnItem* items_dev, int n_items, long units, int H, int nh,
+                                 bool log2_scores, hipStream_t stream);
 // Attention rows (dinov2_hip_predict_attention; attn_rows.hip): out [B, nh, nq, nkeys] f32 = columns [key0, key0 + nkeys) of the softmax rows of
 // the query tokens queries[0 .. nq) (DEVICE pointer, each in [0, T)), from the same token-major qkv (row stride ld elements, q pre-scaled by
 // log2(e)/sqrt(hd): exp2).  The softmax runs over all T keys whatever the columns; a row's bits depend on T and on its own q and k only.

@@ -4,8 +4,10 @@
 //   build_graph + dino_predict  /root/reference/dinov2.cpp:823-838, :900-999  -> forward() + dinov2_hip_predict
 // There is no graph builder / allocator / backend scheduler here: the forward is a fixed sequence of ~8 fused
 // kernel launches per layer on one HIP stream over a pre-carved workspace.
+// dinov2_hip_predict_list (no reference counterpart) is here too: forward_list() is forward() over images of different sizes.
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <numeric>
 
@@ -92,8 +94,9 @@ struct Carve {
     size_t img, col, x, ln, qkv, att, hid, fin, feat, logits, probs, pos, stats, stats_bytes, total;
 };
 
-Carve carve_of(const dinov2_hip_model* m, int B, int h, int w) {
-    const Dims d = dims_of(m, B, h, w);
+// The workspace of one pass over `n` images with `pixels` pixels, `patches` patches and `M` token rows in all; pos_floats: the carve's own
+// position embedding (a uniform batch has one; a list keeps its embeddings in scratch[SCRATCH_LIST_POS])
+Carve carve_sizes(const dinov2_hip_model* m, size_t n, size_t pixels, size_t patches, size_t M, size_t pos_floats) {
     const size_t H = m->hp.hidden_size, F = m->hp.ffn_hidden, C = std::max<size_t>(m->hp.num_classes, 1);
     Carve c{};
     size_t off = 0;
@@ -102,35 +105,40 @@ Carve carve_of(const dinov2_hip_model* m, int B, int h, int w) {
         off += align_up(bytes, 256);
         return o;
     };
-    c.img = put(sizeof(float) * 3 * (size_t)B * h * w);
-    c.col = put(2 * (size_t)B * d.P * m->kpe_pad);
-    c.x = put(sizeof(float) * (size_t)d.M * H);
-    c.ln = put(2 * (size_t)d.M * H);
+    c.img = put(sizeof(float) * 3 * pixels);
+    c.col = put(2 * patches * m->kpe_pad);
+    c.x = put(sizeof(float) * M * H);
+    c.ln = put(2 * M * H);
 #if defined(DINO_PREC) && (DINO_PREC & 25)
-    c.qkv = put(2 * (size_t)d.M * 6 * H);  // (tuning build, profiles/r05_parity_attribution.md) second f16 word of q | k | v behind the first
+    c.qkv = put(2 * M * 6 * H);  // (tuning build, profiles/r05_parity_attribution.md) second f16 word of q | k | v behind the first
 #else
-    c.qkv = put(2 * (size_t)d.M * 3 * H);
+    c.qkv = put(2 * M * 3 * H);
 #endif
-    c.att = put(2 * (size_t)d.M * H);
-    c.hid = put(2 * (size_t)d.M * F);
-    c.fin = put(sizeof(float) * (size_t)d.M * H);
-    c.feat = put(sizeof(float) * (size_t)B * 2 * H);
-    c.logits = put(sizeof(float) * (size_t)B * C);
-    c.probs = put(sizeof(float) * (size_t)B * C);
-    c.pos = put(sizeof(float) * (size_t)(1 + d.P) * H);
-    c.stats_bytes = m->ln_fold ? sizeof(float) * 2 * (size_t)d.M * ln_stat_slots((int)H) : 0;
+    c.att = put(2 * M * H);
+    c.hid = put(2 * M * F);
+    c.fin = put(sizeof(float) * M * H);
+    c.feat = put(sizeof(float) * n * 2 * H);
+    c.logits = put(sizeof(float) * n * C);
+    c.probs = put(sizeof(float) * n * C);
+    c.pos = put(sizeof(float) * pos_floats);
+    c.stats_bytes = m->ln_fold ? sizeof(float) * 2 * M * ln_stat_slots((int)H) : 0;
     c.stats = put(c.stats_bytes);
     c.total = off;
     return c;
 }
 
-int ensure_workspace(dinov2_hip_session* s, int B, int h, int w, char* err, size_t errlen) {
+Carve carve_of(const dinov2_hip_model* m, int B, int h, int w) {
+    const Dims d = dims_of(m, B, h, w);
+    return carve_sizes(m, (size_t)B, (size_t)B * h * w, (size_t)B * d.P, (size_t)d.M, (size_t)(1 + d.P) * m->hp.hidden_size);
+}
+
+// Makes the workspace at least c.total bytes (captured graphs point into the old one: gone before it is freed) and points the session's views
+// into it.  The caller records what the carve is for (cur_b / cur_h / cur_w, list_key).
+int apply_carve(dinov2_hip_session* s, const Carve& c, char* err, size_t errlen) {
     DevBuf& buf = s->scratch[SCRATCH_WS];
-    if (s->cur_b == B && s->cur_h == h && s->cur_w == w && buf.ptr) return DINOV2_HIP_OK;
-    const Carve c = carve_of(s->model, B, h, w);
     if (c.total > buf.bytes) {
         HIP_TRY(hipStreamSynchronize(s->stream));
-        for (auto& g : s->graphs)  // captured graphs point into the old workspace: gone before it is freed
+        for (auto& g : s->graphs)
             if (g.exec) (void)hipGraphExecDestroy(g.exec);
         s->graphs.clear();
         const int rc = reserve(s, buf, c.total, "workspace", err, errlen);
@@ -153,9 +161,32 @@ int ensure_workspace(dinov2_hip_session* s, int B, int h, int w, char* err, size
     // (the slots past hidden / 64 of every statistics row are read by the consumers and written by nobody: zero them with the carve)
     if (c.stats_bytes) HIP_TRY(hipMemsetAsync(s->stats, 0, c.stats_bytes, s->stream));
     s->pos_h = s->pos_w = -1;  // the carve moved: re-upload the pos-embed
+    return DINOV2_HIP_OK;
+}
+
+int ensure_workspace(dinov2_hip_session* s, int B, int h, int w, char* err, size_t errlen) {
+    if (s->cur_b == B && s->cur_h == h && s->cur_w == w && s->scratch[SCRATCH_WS].ptr) return DINOV2_HIP_OK;
+    s->cur_b = 0;  // (nothing valid while the carve moves)
+    s->list_key[2] = 0;
+    const int rc = apply_carve(s, carve_of(s->model, B, h, w), err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
     s->cur_b = B;
     s->cur_h = h;
     s->cur_w = w;
+    return DINOV2_HIP_OK;
+}
+
+// the same for a list (dinov2_hip_predict_list): carved by its totals; cur_b = -1 makes the next uniform predict carve anew
+int ensure_workspace_list(dinov2_hip_session* s, const ListPlan& lp, int n, char* err, size_t errlen) {
+    const int64_t key[4] = {lp.pixels, lp.P, lp.M, n};
+    if (s->cur_b == -1 && std::equal(key, key + 4, s->list_key) && s->scratch[SCRATCH_WS].ptr) return DINOV2_HIP_OK;
+    s->cur_b = 0;
+    s->list_key[2] = 0;
+    const int rc = apply_carve(s, carve_sizes(s->model, (size_t)n, (size_t)lp.pixels, (size_t)lp.P, (size_t)lp.M, 0), err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    s->cur_b = -1;
+    s->cur_h = s->cur_w = 0;
+    std::copy(key, key + 4, s->list_key);
     return DINOV2_HIP_OK;
 }
 
@@ -388,6 +419,191 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
     return DINOV2_HIP_OK;
 }
 
+// ---- dinov2_hip_predict_list: images of different sizes in one forward ------------------------------------------------------------------
+// The position embeddings of the list's patch grids, one per distinct (h0, w0), in scratch[SCRATCH_LIST_POS]; pos_of[i] = image i's (device).
+// They stay from call to call, up to DINOV2_HIP_LIST_POS_GRIDS of them: a list that would take the cache past that, or past its allocation,
+// clears it first (so a single list with more distinct grids than the bound is served, and evicts everything else).  Staging as in
+// prepare_pos: the host buffer is rewritten only after a wait for the stream, and the call returns after the copy has landed.
+int prepare_pos_list(dinov2_hip_session* s, const std::vector<ListImage>& im, std::vector<const float*>& pos_of, char* err, size_t errlen) {
+    const dinov2_hip_model* m = s->model;
+    const size_t H = m->hp.hidden_size;
+    auto find = [&](int h0, int w0) {
+        for (size_t k = 0; k < s->list_pos.size(); ++k)
+            if (s->list_pos[k].h0 == h0 && s->list_pos[k].w0 == w0) return (long)k;
+        return -1L;
+    };
+    auto missing_of = [&](std::vector<std::pair<int, int>>& miss) {  // the list's grids that are not cached, each once; their floats
+        size_t floats = 0;
+        miss.clear();
+        for (const ListImage& g : im) {
+            if (find(g.h0, g.w0) >= 0 || std::find(miss.begin(), miss.end(), std::make_pair(g.h0, g.w0)) != miss.end()) continue;
+            miss.emplace_back(g.h0, g.w0);
+            floats += (size_t)(1 + g.P) * H;
+        }
+        return floats;
+    };
+    std::vector<std::pair<int, int>> miss;
+    size_t add = missing_of(miss);
+    DevBuf& buf = s->scratch[SCRATCH_LIST_POS];
+    if (!miss.empty() && (s->list_pos.size() + miss.size() > DINOV2_HIP_LIST_POS_GRIDS || (s->list_pos_used + add) * sizeof(float) > buf.bytes)) {
+        s->list_pos.clear();  // full: cleared, not grown entry by entry (the launches that read the old entries are ahead of the copy on the stream)
+        s->list_pos_used = 0;
+        add = missing_of(miss);
+        const int rc = reserve(s, buf, add * sizeof(float), "predict_list", err, errlen);
+        if (rc != DINOV2_HIP_OK) return rc;
+    }
+    if (!miss.empty()) {
+        hipStream_t st = s->stream;
+        HIP_TRY(hipStreamSynchronize(st));  // list_pos_stage may still be in flight
+        s->list_pos_stage.resize(add);
+        size_t off = 0;
+        for (const auto& g : miss) {
+            interpolate_pos_embed(m->pos_host.data(), (int)(m->hp.img_size / m->hp.patch_size), (int)H, g.first, g.second, s->list_pos_stage.data() + off);
+            s->list_pos.push_back({g.first, g.second, s->list_pos_used + off});
+            off += (size_t)(1 + g.first * g.second) * H;
+        }
+        HIP_TRY(hipMemcpyAsync(buf.as<float>() + s->list_pos_used, s->list_pos_stage.data(), sizeof(float) * add, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        s->list_pos_used += add;
+    }
+    pos_of.resize(im.size());
+    for (size_t i = 0; i < im.size(); ++i) pos_of[i] = buf.as<float>() + s->list_pos[(size_t)find(im[i].h0, im[i].w0)].off;
+    return DINOV2_HIP_OK;
+}
+
+// The attention work table on the device; uploaded only when it differs from the one already there (a caller that repeats a list pays once).
+int prepare_items_list(dinov2_hip_session* s, const std::vector<AttnItem>& items, char* err, size_t errlen) {
+    const size_t bytes = items.size() * sizeof(AttnItem);
+    DevBuf& buf = s->scratch[SCRATCH_LIST_ITEMS];
+    if (buf.ptr && s->list_items_host.size() == items.size() && std::memcmp(s->list_items_host.data(), items.data(), bytes) == 0) return DINOV2_HIP_OK;
+    s->list_items_host.clear();  // (nothing valid on the device until the copy below has been queued)
+    const int rc = reserve(s, buf, bytes, "predict_list", err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));  // a copy from list_items_host may still be in flight
+    s->list_items_host = items;
+    HIP_TRY(hipMemcpyAsync(buf.ptr, s->list_items_host.data(), bytes, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return DINOV2_HIP_OK;
+}
+
+// forward() over a list: the residual stream holds the images' rows one after the other (image i at rows [row0, row0 + T_i)).  The embedding
+// and the head run once per run of equal size with B = run length, every layer launch is forward()'s with M = sum T_i, and attention goes
+// over the work table.  `imgs[r]`: DEVICE images of run r, contiguous.  Leaves final-LN tokens in s->fin, logits / probs [n, C] in s->logits / s->probs.
+int forward_list(dinov2_hip_session* s, const std::vector<const float*>& imgs, const std::vector<ListImage>& im, const std::vector<ListRun>& runs,
+                 const std::vector<const float*>& pos_of, const int32_t* hs, const int32_t* ws, int n_items, int layout, bool classify, char* err,
+                 size_t errlen) {
+    const dinov2_hip_model* m = s->model;
+    const int H = (int)m->hp.hidden_size, F = (int)m->hp.ffn_hidden, R = (int)m->hp.num_register_tokens;
+    const int nh = (int)m->hp.num_attention_heads, ps = (int)m->hp.patch_size, nlayers = (int)m->hp.num_hidden_layers;
+    const int M = (int)(im.back().row0 + im.back().T);
+    hipStream_t st = s->stream;
+    const DType dt = m->dt;
+    size_t patch0 = 0;  // patches before this run: its rows of `col`
+    for (size_t r = 0; r < runs.size(); ++r) {
+        const ListImage& g = im[(size_t)runs[r].first];
+        const int B = runs[r].count, i0 = runs[r].first;
+        char* const col = (char*)s->col + patch0 * (size_t)m->kpe_pad * 2;
+        float* const x = s->x + (size_t)g.row0 * H;
+        {
+            Scope sc(s, K_IM2COL);
+            HIP_TRY(launch_im2col(dt, imgs[r], col, B, hs[i0], ws[i0], ps, m->kpe_pad, layout, st));
+        }
+        {
+            Scope sc(s, K_INIT);
+            HIP_TRY(launch_init_tokens(x, m->cls, pos_of[(size_t)i0], m->reg, B, g.T, R, H, st));
+        }
+        {
+            Scope sc(s, K_PATCH_GEMM);
+            GemmArgs a{};
+            a.A = col; a.W = m->patch_w; a.bias = m->patch_b; a.out = x; a.aux = pos_of[(size_t)i0];
+            a.M = B * g.P; a.N = H; a.K = m->kpe_pad; a.ldo = H; a.P = g.P; a.T = g.T; a.R = R;
+            HIP_TRY(launch_gemm(dt, EPI_PATCH, a, st));
+        }
+        patch0 += (size_t)B * g.P;
+    }
+    const float eps = m->hp.eps;
+    const bool fold = m->ln_fold;
+    const int gs = ln_stat_slots(H);
+    if (fold && nlayers > 0) {
+        Scope sc(s, K_LAYERNORM);
+        HIP_TRY(launch_ln_prepare(dt, s->x, m->layers[0].norm1_w, s->ln, s->stats, gs, M, H, st));
+    }
+    for (int il = 0; il < nlayers; ++il) {  // forward()'s layer, launch for launch, but for the attention
+        const LayerWeights& ly = m->layers[(size_t)il];
+        if (!fold) {
+            Scope sc(s, K_LAYERNORM);
+            HIP_TRY(launch_layernorm(dt, s->x, ly.norm1_w, ly.norm1_b, s->ln, M, H, eps, st));
+        }
+        {
+            Scope sc(s, K_QKV_GEMM);
+            GemmArgs a{};
+            a.A = s->ln; a.W = ly.qkv_w; a.bias = ly.qkv_b; a.out = s->qkv;
+            a.M = M; a.N = 3 * H; a.K = H; a.ldo = 3 * H; a.qcols = H;
+            a.qscale = 0.125f * 1.44269504088896340736f;
+            if (fold) {
+                a.stats = s->stats; a.ln_gs = gs; a.ln_s = ly.qkv_s; a.ln_c = ly.qkv_c; a.ln_eps = eps;
+            }
+            HIP_TRY(launch_gemm(dt, fold ? EPI_QKV_LN : EPI_QKV, a, st));
+        }
+        {
+            Scope sc(s, K_ATTENTION);
+            HIP_TRY(launch_attention_list(dt, s->qkv, s->att, s->scratch[SCRATCH_LIST_ITEMS].as<AttnItem>(), n_items, n_items, H, nh, true, st));
+        }
+        {
+            Scope sc(s, K_OPROJ_GEMM);
+            GemmArgs a{};
+            a.A = s->att; a.W = ly.o_w; a.bias = ly.o_b; a.out = s->x; a.aux = ly.ls1;
+            a.M = M; a.N = H; a.K = H; a.ldo = H;
+            if (fold) {
+                a.ln_gamma = ly.norm2_w; a.xg = s->ln; a.stats = s->stats; a.ln_gs = gs;
+            }
+            HIP_TRY(launch_gemm(dt, fold ? EPI_RESID_LN : EPI_RESID, a, st));
+        }
+        if (!fold) {
+            Scope sc(s, K_LAYERNORM);
+            HIP_TRY(launch_layernorm(dt, s->x, ly.norm2_w, ly.norm2_b, s->ln, M, H, eps, st));
+        }
+        {
+            Scope sc(s, K_FC1_GEMM);
+            GemmArgs a{};
+            a.A = s->ln; a.W = ly.fc1_w; a.bias = ly.fc1_b; a.out = s->hid;
+            a.M = M; a.N = m->hp.swiglu ? 2 * F : F; a.K = H; a.ldo = F;
+            if (fold) {
+                a.stats = s->stats; a.ln_gs = gs; a.ln_s = ly.fc1_s; a.ln_c = ly.fc1_c; a.ln_eps = eps;
+            }
+            HIP_TRY(launch_gemm(dt, m->hp.swiglu ? (fold ? EPI_SWIGLU_LN : EPI_SWIGLU) : (fold ? EPI_GELU_LN : EPI_GELU), a, st));
+        }
+        {
+            Scope sc(s, K_FC2_GEMM);
+            GemmArgs a{};
+            a.A = s->hid; a.W = ly.fc2_w; a.bias = ly.fc2_b; a.out = s->x; a.aux = ly.ls2;
+            a.M = M; a.N = H; a.K = F; a.ldo = H;
+            const bool feeds_ln1 = fold && il + 1 < nlayers;
+            if (feeds_ln1) {
+                a.ln_gamma = m->layers[(size_t)il + 1].norm1_w; a.xg = s->ln; a.stats = s->stats; a.ln_gs = gs;
+            }
+            HIP_TRY(launch_gemm(dt, feeds_ln1 ? EPI_RESID_LN : EPI_RESID, a, st));
+        }
+    }
+    {
+        Scope sc(s, K_FINAL_LN);
+        HIP_TRY(launch_layernorm_f32(s->x, m->ln_w, m->ln_b, s->fin, M, H, eps, st));
+    }
+    if (classify) {
+        const int first = m->quirk_pool_regs ? 1 : 1 + R;
+        const int Mg = (int)(m->hp.img_size / m->hp.patch_size);
+        const size_t C = m->hp.num_classes;
+        for (const ListRun& run : runs) {  // the pooling divisor is the run's own
+            const ListImage& g = im[(size_t)run.first];
+            const float div = m->quirk_const_div ? (float)(Mg * Mg) : (float)(g.T - first);
+            Scope sc(s, K_HEAD);
+            HIP_TRY(launch_head(dt, s->fin + (size_t)g.row0 * H, m->head_w, m->head_b, s->feat + (size_t)run.first * 2 * H,
+                                s->logits + (size_t)run.first * C, s->probs + (size_t)run.first * C, run.count, g.T, H, (int)C, first, 1.0f / div, st));
+        }
+    }
+    return DINOV2_HIP_OK;
+}
+
 // Opt-in (DINOV2_HIP_GRAPHS=1): second and later forwards with the same (workspace, input pointer, shape, flags) replay a
 // captured hipGraph; the first occurrence runs eagerly (one-off shapes never pay for a capture), the second is captured.
 // Off by default because it buys nothing on an idle host: the forward is kernel-bound (178 launches, mean gap 1.0 us in the
@@ -455,6 +671,22 @@ int forward_maybe_graph(dinov2_hip_session* s, const float* img, int B, int h, i
 
 }  // namespace
 
+// out->topk_ids / topk_probs [B, topk] from host probabilities [B, C]: descending sort of all classes like dinov2.cpp:961-965
+static void topk_rows(const float* probs_host, int B, size_t C, dinov2_hip_output* out) {
+    const int k = std::min<int>(out->topk, (int)C);
+    std::vector<int> idx(C);
+    for (int b = 0; b < B; ++b) {
+        const float* p = probs_host + (size_t)b * C;
+        std::iota(idx.begin(), idx.end(), 0);
+        std::partial_sort(idx.begin(), idx.begin() + k, idx.end(),
+                          [&](int a, int c2) { return p[a] > p[c2] || (p[a] == p[c2] && a < c2); });
+        for (int i = 0; i < out->topk; ++i) {
+            if (out->topk_ids) out->topk_ids[(size_t)b * out->topk + i] = i < k ? idx[(size_t)i] : -1;
+            if (out->topk_probs) out->topk_probs[(size_t)b * out->topk + i] = i < k ? p[idx[(size_t)i]] : 0.f;
+        }
+    }
+}
+
 // Copy-out of the session's last forward (shape in s->last_*): the tail of dino_predict (dinov2.cpp:950-999).
 int dinov2::fetch_outputs(dinov2_hip_session* s, dinov2_hip_output* out, char* err, size_t errlen) {
     const dinov2_hip_model* m = s->model;
@@ -486,20 +718,7 @@ int dinov2::fetch_outputs(dinov2_hip_session* s, dinov2_hip_output* out, char* e
         HIP_TRY(hipMemcpyAsync(probs_host.data(), s->probs, sizeof(float) * B * C, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
-    if (want_topk) {  // descending sort of all classes like dinov2.cpp:961-965, ids and probabilities returned
-        const int k = std::min<int>(out->topk, (int)C);
-        std::vector<int> idx(C);
-        for (int b = 0; b < B; ++b) {
-            const float* p = probs_host.data() + (size_t)b * C;
-            std::iota(idx.begin(), idx.end(), 0);
-            std::partial_sort(idx.begin(), idx.begin() + k, idx.end(),
-                              [&](int a, int c2) { return p[a] > p[c2] || (p[a] == p[c2] && a < c2); });
-            for (int i = 0; i < out->topk; ++i) {
-                if (out->topk_ids) out->topk_ids[(size_t)b * out->topk + i] = i < k ? idx[(size_t)i] : -1;
-                if (out->topk_probs) out->topk_probs[(size_t)b * out->topk + i] = i < k ? p[idx[(size_t)i]] : 0.f;
-            }
-        }
-    }
+    if (want_topk) topk_rows(probs_host.data(), B, C, out);
     return DINOV2_HIP_OK;
 }
 
@@ -723,6 +942,196 @@ int dinov2::predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dino
 extern "C" int dinov2_hip_predict(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out,
                                   uint32_t flags, char* err, size_t errlen) {
     return predict_impl(s, in, out, flags, PassExtras{}, err, errlen);
+}
+
+// =============================================================================================================
+// predict_list
+// =============================================================================================================
+namespace {
+
+// The order of the attention work table (kernels.h ListOrder).  Shipped: as given -- profiles/predict_list.md (c) has both times.
+// DINOV2_HIP_LIST_ORDER=1 / the "list_order" switch picks the other (a measuring aid; the bits do not depend on it).
+int list_table_order() { return tune_get(TUNE_LIST_ORDER) == 1 ? (int)LIST_ORDER_LONGEST_FIRST : (int)LIST_ORDER_AS_GIVEN; }
+
+// The argument checks of dinov2_hip_list_rows and dinov2_hip_predict_list that need no device: every refusal names the image.  On success
+// hs / ws hold the network sizes.  need_data: the image pointers are checked too.
+int check_list(const dinov2_hip_model* m, const dinov2_hip_image_list* l, uint32_t flags, bool need_data, std::vector<int32_t>& hs,
+               std::vector<int32_t>& ws, char* err, size_t errlen) {
+    if (!m || !l) {
+        set_err(err, errlen, "null session / model / list");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (l->n <= 0) {
+        set_err(err, errlen, "an image list holds at least one image (n = %d)", l->n);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (!l->height || !l->width || (need_data && !l->data)) {
+        set_err(err, errlen, "null data / height / width array of the image list");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    hs.resize((size_t)l->n);
+    ws.resize((size_t)l->n);
+    // one pass, as dinov2_max_pass_batch has it for a uniform batch: the widest activation buffer stays below 2^31 bytes
+    const int64_t widest = (int64_t)std::max<size_t>({3 * (size_t)m->hp.hidden_size, (size_t)m->hp.ffn_hidden, (size_t)m->kpe_pad});
+    int64_t M = 0;
+    int first_over = -1;
+    for (int i = 0; i < l->n; ++i) {
+        if (need_data && !l->data[i]) {
+            set_err(err, errlen, "image %d: null data pointer", i);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+        dinov2_hip_input in{};
+        in.data = reinterpret_cast<const float*>(need_data ? l->data[i] : (const void*)l);  // (never dereferenced here)
+        in.batch = 1; in.height = l->height[i]; in.width = l->width[i]; in.layout = l->layout; in.on_device = l->on_device;
+        char why[256] = "";
+        const int rc = dinov2_check_input(m, &in, why, sizeof(why));
+        if (rc != DINOV2_HIP_OK) {
+            set_err(err, errlen, "image %d: %s", i, why);
+            return rc;
+        }
+        int h, w;
+        network_size(m, &in, flags, &h, &w);
+        hs[(size_t)i] = h;
+        ws[(size_t)i] = w;
+        M += dims_of(m, 1, h, w).T;
+        if (first_over < 0 && M * widest * 2 >= ((int64_t)1 << 31)) first_over = i;
+    }
+    if (first_over >= 0) {
+        set_err(err, errlen, "image %d: with it the list has too many token rows for one pass (%lld in all; rows * %lld * 2 must stay below 2^31, "
+                "the 32-bit activation offsets of dinov2_hip_predict's passes).  A list is refused, not split: hand it over in parts",
+                first_over, (long long)M, (long long)widest);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    return DINOV2_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" int dinov2_hip_list_rows(const dinov2_hip_model* m, const dinov2_hip_image_list* list, uint32_t flags, int64_t* offsets, char* err,
+                                    size_t errlen) {
+    std::vector<int32_t> hs, ws;
+    const int rc = check_list(m, list, flags, false, hs, ws, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    if (!offsets) {
+        set_err(err, errlen, "null offsets");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    const int skip = (flags & DINOV2_HIP_CLASSIFY) ? 1 : 1 + (int)m->hp.num_register_tokens;  // rows of an image that are not handed out
+    offsets[0] = 0;
+    for (int i = 0; i < list->n; ++i) offsets[i + 1] = offsets[i] + dims_of(m, 1, hs[(size_t)i], ws[(size_t)i]).T - skip;
+    return DINOV2_HIP_OK;
+}
+
+extern "C" int dinov2_hip_predict_list(dinov2_hip_session* s, const dinov2_hip_image_list* list, dinov2_hip_output* out, uint32_t flags, char* err,
+                                       size_t errlen) {
+    std::vector<int32_t> hs, ws;
+    int rc = check_list(s ? s->model : nullptr, list, flags, true, hs, ws, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    const dinov2_hip_model* m = s->model;
+    rc = check_predict_args(m, out, flags, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    const bool classify = (flags & DINOV2_HIP_CLASSIFY) != 0;
+    const int n = list->n, R = (int)m->hp.num_register_tokens, nh = (int)m->hp.num_attention_heads;
+    const size_t H = m->hp.hidden_size, C = m->hp.num_classes;
+    HIP_TRY(hipSetDevice(m->device));
+    // a list forward leaves no "last un-split forward": nothing for dinov2_hip_fetch, pca3(tokens = NULL), match / bank on resident tokens
+    s->last_b = 0;
+    s->last_patches = 0;
+    s->last_t = 0;
+
+    std::vector<ListImage> im((size_t)n);
+    std::vector<ListRun> runs((size_t)n);
+    ListPlan lp = list_plan(n, hs.data(), ws.data(), (int)m->hp.patch_size, R, nh, list_table_order(), im.data(), runs.data(), nullptr);
+    runs.resize((size_t)lp.nruns);
+    std::vector<AttnItem> items((size_t)lp.units);
+    lp = list_plan(n, hs.data(), ws.data(), (int)m->hp.patch_size, R, nh, list_table_order(), nullptr, nullptr, items.data());
+
+    rc = ensure_workspace_list(s, lp, n, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    hipStream_t st = s->stream;
+
+    // the images, run by run contiguous on the device: where the caller's device images already are, they are read in place
+    const bool raw_u8 = list->layout == DINOV2_HIP_U8_BGR_HWC;
+    const int layout = raw_u8 ? DINOV2_HIP_BGR_HWC : list->layout;
+    std::vector<size_t> pix((size_t)n + 1, 0);  // pixels before image i (network size): its place in s->img
+    for (int i = 0; i < n; ++i) pix[(size_t)i + 1] = pix[(size_t)i] + (size_t)hs[(size_t)i] * ws[(size_t)i];
+    std::vector<const float*> imgs(runs.size());
+    if (raw_u8) {
+        std::vector<const uint8_t*> src((size_t)n);
+        for (int i = 0; i < n; ++i) src[(size_t)i] = static_cast<const uint8_t*>(list->data[i]);
+        if (!list->on_device) {
+            size_t nraw = 0;
+            for (int i = 0; i < n; ++i) nraw += align_up((size_t)list->height[i] * list->width[i] * 3, 16);
+            rc = reserve(s, s->scratch[SCRATCH_RAW], nraw, "predict_list", err, errlen);
+            if (rc != DINOV2_HIP_OK) return rc;
+            uint8_t* d = s->scratch[SCRATCH_RAW].as<uint8_t>();
+            for (int i = 0; i < n; ++i) {
+                const size_t bytes = (size_t)list->height[i] * list->width[i] * 3;
+                HIP_TRY(hipMemcpyAsync(d, src[(size_t)i], bytes, hipMemcpyHostToDevice, st));
+                src[(size_t)i] = d;
+                d += align_up(bytes, 16);
+            }
+        }
+        for (int i = 0; i < n; ++i) {  // each image to its own network size
+            const int h = hs[(size_t)i], w = ws[(size_t)i], rh = classify ? 256 : h, rw = classify ? 256 : w;
+            HIP_TRY(launch_preprocess_u8(src[(size_t)i], s->img + 3 * pix[(size_t)i], 1, list->height[i], list->width[i], rh, rw, (rh - h) / 2,
+                                         (rw - w) / 2, h, w, st));
+        }
+        for (size_t r = 0; r < runs.size(); ++r) imgs[r] = s->img + 3 * pix[(size_t)runs[r].first];
+    } else {
+        for (size_t r = 0; r < runs.size(); ++r) {
+            const int i0 = runs[r].first, i1 = i0 + runs[r].count;
+            const size_t fl = 3 * (size_t)hs[(size_t)i0] * ws[(size_t)i0];  // floats of one image of the run
+            bool in_place = list->on_device != 0;
+            for (int i = i0 + 1; i < i1 && in_place; ++i)
+                in_place = static_cast<const float*>(list->data[i]) == static_cast<const float*>(list->data[i - 1]) + fl;
+            if (in_place) {
+                imgs[r] = static_cast<const float*>(list->data[i0]);
+                continue;
+            }
+            for (int i = i0; i < i1; ++i)
+                HIP_TRY(hipMemcpyAsync(s->img + 3 * pix[(size_t)i], list->data[i], sizeof(float) * fl,
+                                       list->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+            imgs[r] = s->img + 3 * pix[(size_t)i0];
+        }
+    }
+    std::vector<const float*> pos_of;
+    rc = prepare_pos_list(s, im, pos_of, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    rc = prepare_items_list(s, items, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    rc = forward_list(s, imgs, im, runs, pos_of, hs.data(), ws.data(), (int)items.size(), layout, classify, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    if (!out) return DINOV2_HIP_OK;
+
+    // copy-out, run by run: cls [n, H]; the patch rows packed, image i at rows [offsets[i], offsets[i + 1]) of dinov2_hip_list_rows
+    const hipMemcpyKind kind = out->on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const int skip = classify ? 1 : 1 + R;
+    size_t orow = 0;
+    for (const ListRun& run : runs) {
+        const ListImage& g = im[(size_t)run.first];
+        const float* fin = s->fin + (size_t)g.row0 * H;
+        const size_t pitch = sizeof(float) * (size_t)g.T * H, wbytes = sizeof(float) * (size_t)(g.T - skip) * H;
+        if (out->cls)
+            HIP_TRY(hipMemcpy2DAsync(out->cls + (size_t)run.first * H, sizeof(float) * H, fin, pitch, sizeof(float) * H, (size_t)run.count, kind, st));
+        if (out->patch_tokens)
+            HIP_TRY(hipMemcpy2DAsync(out->patch_tokens + orow * H, wbytes, fin + (size_t)skip * H, pitch, wbytes, (size_t)run.count, kind, st));
+        orow += (size_t)run.count * (size_t)(g.T - skip);
+    }
+    if (classify) {
+        if (out->logits) HIP_TRY(hipMemcpyAsync(out->logits, s->logits, sizeof(float) * n * C, kind, st));
+        if (out->probs) HIP_TRY(hipMemcpyAsync(out->probs, s->probs, sizeof(float) * n * C, kind, st));
+    }
+    if (out->on_device) return DINOV2_HIP_OK;
+    std::vector<float> probs_host;
+    const bool want_topk = classify && out->topk > 0 && (out->topk_ids || out->topk_probs);
+    if (want_topk) {
+        probs_host.resize((size_t)n * C);
+        HIP_TRY(hipMemcpyAsync(probs_host.data(), s->probs, sizeof(float) * n * C, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (want_topk) topk_rows(probs_host.data(), n, C, out);
+    return DINOV2_HIP_OK;
 }
 
 extern "C" int dinov2_hip_fetch(dinov2_hip_session* s, dinov2_hip_output* out, char* err, size_t errlen) {

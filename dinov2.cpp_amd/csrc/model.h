@@ -106,6 +106,8 @@ enum Scratch : int {
     SCRATCH_TAP,     // dinov2_hip_predict_layers with host outputs: where the tap kernel writes before the copy-out
     SCRATCH_ATTN,    // dinov2_hip_predict_attention with a host output: where attn_rows_kernel writes before the copy-out
     SCRATCH_ATTN_Q,  // the query list of the last dinov2_hip_predict_attention on the device (attn_q_host: what it holds)
+    SCRATCH_LIST_POS,    // dinov2_hip_predict_list: the interpolated position embeddings of up to LIST_POS_GRIDS patch grids (list_pos: what it holds)
+    SCRATCH_LIST_ITEMS,  // dinov2_hip_predict_list: the attention work table of the last list (list_items_host: what it holds)
     SCRATCH_COUNT
 };
 
@@ -154,6 +156,17 @@ struct dinov2_hip_session {
     float* stats = nullptr;  // LN fold: [M][ln_stat_slots(H)][2] row statistics of the residual stream (slots past H / 64 stay zero)
     int pos_h = -1, pos_w = -1;  // grid the cached interpolated pos-embed in `pos` belongs to
     std::vector<float> pos_stage;
+    // dinov2_hip_predict_list.  The workspace is carved by (pixels, patches, rows, images) instead of (B, h, w): list_key holds those four while
+    // the carve is a list's (cur_b is then -1, so the next uniform predict carves anew), and is cleared by a uniform carve.
+    int64_t list_key[4] = {0, 0, 0, 0};
+    struct ListPos {  // one cached position embedding [1 + h0 w0, H] f32 at float offset `off` of scratch[SCRATCH_LIST_POS]
+        int h0, w0;
+        size_t off;
+    };
+    std::vector<ListPos> list_pos;
+    size_t list_pos_used = 0;                      // floats of scratch[SCRATCH_LIST_POS] taken by list_pos
+    std::vector<float> list_pos_stage;             // host side of the uploads (never rewritten while a copy from it may be in flight)
+    std::vector<dinov2::AttnItem> list_items_host;  // what scratch[SCRATCH_LIST_ITEMS] holds
     // hipGraph cache (the "allocr reuse" of the reference taken one step further): a forward that repeats with the same
     // shape, input pointer and workspace is captured once and replayed; 178 launches become one graph launch
     struct GraphEntry {

@@ -263,6 +263,58 @@ extern "C" int dinov2_hip_op_attention_ex(int32_t dtype, const float* qkv, float
     return dO.fetch_as(dt, out);
 }
 
+// ---- dinov2_hip_predict_list: its plan (no device) and the list form of the attention kernels over segments of given lengths ----
+extern "C" int dinov2_hip_op_list_plan(int32_t n, const int32_t* h, const int32_t* w, int32_t patch, int32_t R, int32_t nh, int32_t order,
+                                       int64_t* images, int32_t* runs, int32_t* items, int64_t cap_items, int64_t* totals) {
+    if (n <= 0 || !h || !w || patch <= 0 || R < 0 || nh <= 0 || !totals || (order != LIST_ORDER_AS_GIVEN && order != LIST_ORDER_LONGEST_FIRST))
+        return DINOV2_HIP_ERR_INVALID;
+    for (int i = 0; i < n; ++i)
+        if (h[i] < 0 || w[i] < 0) return DINOV2_HIP_ERR_INVALID;
+    std::vector<ListImage> im((size_t)n);
+    std::vector<ListRun> rn((size_t)n);
+    const ListPlan p = list_plan(n, h, w, patch, R, nh, order, im.data(), rn.data(), nullptr);
+    totals[0] = p.M; totals[1] = p.P; totals[2] = p.pixels; totals[3] = p.units; totals[4] = p.nruns;
+    if (p.M > (int64_t)INT32_MAX) return DINOV2_HIP_ERR_INVALID;  // (the table holds row0 in 32 bits)
+    for (int i = 0; images && i < n; ++i) {
+        const int64_t rec[5] = {im[(size_t)i].row0, im[(size_t)i].T, im[(size_t)i].P, im[(size_t)i].h0, im[(size_t)i].w0};
+        std::copy(rec, rec + 5, images + (size_t)i * 5);
+    }
+    for (int r = 0; runs && r < p.nruns; ++r) {
+        runs[2 * r] = rn[(size_t)r].first;
+        runs[2 * r + 1] = rn[(size_t)r].count;
+    }
+    if (items) {
+        if (cap_items < p.units) return DINOV2_HIP_ERR_INVALID;
+        static_assert(sizeof(AttnItem) == 4 * sizeof(int32_t), "an item is four int32: row0, T, head, query block");
+        (void)list_plan(n, h, w, patch, R, nh, order, nullptr, nullptr, reinterpret_cast<AttnItem*>(items));
+    }
+    return DINOV2_HIP_OK;
+}
+
+extern "C" int dinov2_hip_op_attention_list(int32_t dtype, const float* qkv, float* out, int32_t n, const int32_t* T, int32_t H, int32_t nh,
+                                            int32_t log2_scores) {
+    const DType dt = dtype_of(dtype);
+    if (!qkv || !out || n <= 0 || !T || nh <= 0 || H != nh * 64) return -1;
+    // a segment of T tokens as a 1-pixel-patch image of (T - 1) x 1 patches without registers: the table is the forward's own
+    std::vector<int32_t> hh((size_t)n), ww((size_t)n, 1);
+    for (int i = 0; i < n; ++i) {
+        if (T[i] <= 0 || (size_t)T[i] * 3 * H * 2 >= ((size_t)1 << 32)) return -1;  // the per-image bound of the 32-bit staging cursors
+        hh[(size_t)i] = T[i] - 1;
+    }
+    const int order = tune_get(TUNE_LIST_ORDER) == 1 ? LIST_ORDER_LONGEST_FIRST : LIST_ORDER_AS_GIVEN;
+    ListPlan p = list_plan(n, hh.data(), ww.data(), 1, 0, nh, order, nullptr, nullptr, nullptr);
+    if (p.M > (int64_t)INT32_MAX) return -1;
+    std::vector<AttnItem> items((size_t)p.units);
+    p = list_plan(n, hh.data(), ww.data(), 1, 0, nh, order, nullptr, nullptr, items.data());
+    OpBuf dQ, dI, dO;
+    OP_TRY(dQ.upload_as(dt, qkv, (size_t)p.M * 3 * H));
+    OP_TRY(dI.upload(items.data(), items.size() * sizeof(AttnItem)));
+    OP_TRY(dO.alloc((size_t)p.M * H, 2, OpBuf::nans(), (size_t)H));  // a write outside rows [0, sum T) changes a guard
+    OP_TRY(launch_attention_list(dt, dQ.p, dO.as<void>(), dI.as<AttnItem>(), (int)items.size(), (long)p.units, H, nh, log2_scores != 0, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    return dO.fetch_as(dt, out);
+}
+
 extern "C" int dinov2_hip_op_layernorm(int32_t dtype, const float* x, const float* w, const float* b, float* out,
                                        int32_t rows, int32_t H, float eps) {
     const size_t n = (size_t)rows * H;
@@ -473,7 +525,7 @@ extern "C" float dinov2_hip_op_attention_bench(int32_t dtype, int32_t B, int32_t
 // ---- testing aids: the tuning switches (read from the environment once) and the dispatcher's plan for a shape ----
 namespace {
 int tune_key(const char* key) {  // the TuneKey of a switch's name, -1 if there is none
-    static const char* const names[TUNE_COUNT] = {"gemm_gen", "gemm_tile", "attn_v", "attn_nwv"};
+    static const char* const names[TUNE_COUNT] = {"gemm_gen", "gemm_tile", "attn_v", "attn_nwv", "list_order"};
     for (int k = 0; key && k < TUNE_COUNT; ++k)
         if (std::strcmp(key, names[k]) == 0) return k;
     return -1;

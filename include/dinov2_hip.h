@@ -230,6 +230,46 @@ int dinov2_hip_predict_attention(dinov2_hip_session *session, const dinov2_hip_i
  * split an over-long batch into passes. */
 int dinov2_hip_fetch(dinov2_hip_session *session, dinov2_hip_output *out, char *err, size_t errlen);
 
+/* -- predict over a list of images of different sizes (no reference counterpart: dino_preprocess resizes every image to (dim / patch + 1) patch
+ *    per side, so the network size follows the raw image, and a folder of photographs, a set of crops or the levels of a pyramid is a list of
+ *    different sizes -- each its own batch-1 forward through dinov2_hip_predict.  Upstream DINOv2: forward_features_list with a block-diagonal
+ *    attention mask).  ONE forward: the token rows of all images stand one after the other in the residual stream (M = sum T_i rows); the patch
+ *    embedding and the head run once per run of consecutive images of one size, every per-row kernel (LayerNorm, the four GEMMs of a block)
+ *    runs once over the M rows, and attention runs once per block over a work table of {first row, length, head, query block} -- the list
+ *    form of the two attention kernels (csrc/attention.hip, launch_attention_list), which never stages a key of a neighbouring image.
+ *    Contract: image i of a list has, BIT FOR BIT, the outputs dinov2_hip_predict gives for that image alone (every kernel plan is
+ *    batch-invariant, and the order of the list and of the work table changes nothing).
+ *    Outputs: the ordinary dinov2_hip_output with B = n -- cls [n, H], logits / probs [n, C], topk_* [n, topk] -- and patch_tokens PACKED,
+ *    [offsets[n], H]: image i owns rows offsets[i] .. offsets[i + 1] (dinov2_hip_list_rows), P_i of them, or R + P_i with DINOV2_HIP_CLASSIFY,
+ *    in dinov2_hip_predict's row order.  Host and device outputs as in dinov2_hip_predict.
+ *    The position embeddings of up to DINOV2_HIP_LIST_POS_GRIDS distinct patch grids ((1 + P) H floats each: 5.6 MB for ViT-L at 518 px) stay on the device from call to call; a list that would
+ *    take the cache past that clears it first (a single list may hold more distinct grids than that: it is served, and evicts the rest).
+ *    Argument errors -- n <= 0, a NULL array or image pointer, a size dinov2_hip_predict would refuse for that image, classify without a
+ *    head, device top-k, a list with too many rows for one pass -- return their status, naming the image, before anything is allocated, copied
+ *    or launched.
+ *    Afterwards there is no "last un-split forward": until the next dinov2_hip_predict, dinov2_hip_fetch, dinov2_hip_pca3(tokens = NULL),
+ *    dinov2_hip_match_tokens on resident tokens and the bank's LAST_CLS / LAST_PATCHES are refused as they are before the first predict.
+ *    Out of scope: lists longer than one pass (rows * max(3 H, ffn, patch K) * 2 >= 2^31 bytes: refused, not split); layer taps, attention
+ *    rows and dense heads on a list; the device group; graph capture (a list call runs eagerly); masks (upstream's masks_list); list forms
+ *    of the attention variants that are never auto-selected (DINOV2_HIP_ATTN_V=3|4 make the call fail; DINOV2_HIP_ATTN_NWV is not looked at).
+ *    Times against batch-1 calls: profiles/predict_list.md. */
+#define DINOV2_HIP_LIST_POS_GRIDS 64
+typedef struct dinov2_hip_image_list {
+    const void *const *data; /* [n] one pointer per image: f32, or uint8_t for DINOV2_HIP_U8_BGR_HWC                                  */
+    const int32_t *height;   /* [n] as dinov2_hip_input.height: the network size, or the RAW size for DINOV2_HIP_U8_BGR_HWC (each image
+                                is then preprocessed on the device to its own network size)                                           */
+    const int32_t *width;    /* [n]                                                                                                   */
+    int32_t n;               /* >= 1                                                                                                  */
+    int32_t layout;          /* enum dinov2_hip_layout, one for the whole list                                                        */
+    int32_t on_device;       /* as dinov2_hip_input.on_device, one for the whole list.  Device images of equal size that already stand
+                                one after the other in memory are read in place; others are gathered with device copies              */
+} dinov2_hip_image_list;
+/* rows of out->patch_tokens that image i occupies: offsets[i] .. offsets[i + 1]; offsets has n + 1 entries.  Needs no device; `data` may be NULL. */
+int dinov2_hip_list_rows(const dinov2_hip_model *model, const dinov2_hip_image_list *list, uint32_t flags, int64_t *offsets, char *err,
+                         size_t errlen);
+int dinov2_hip_predict_list(dinov2_hip_session *session, const dinov2_hip_image_list *list, dinov2_hip_output *out, uint32_t flags,
+                            char *err, size_t errlen);
+
 /* -- multi-device group (no reference counterpart: the reference is one backend, batch 1) -----------------
  *    Host threads + sessions per device inside the library; dinov2_hip_group_predict splits the caller's global batch
  *    contiguously (device g owns images [g*B/G, (g+1)*B/G), remainder to the low ranks) and every device writes its results
@@ -553,6 +593,8 @@ const char *dinov2_hip_build_id(void);
  *   DINOV2_HIP_GEMM_GEN=2|4  which generation of the persistent GEMM runs the 256-row / mixed / one-tile-per-workgroup plans -- 2 = gemm2.hip
  *                            (eight waves, barrier-separated sections), 4 = gemm4.hip (four waves, hand-ordered K loop; the default for
  *                            K >= 1 024).  Both give every row the same bits.  (The LN-fold epilogues exist in gemm4.hip and the small-tile kernel only.)
+ *   DINOV2_HIP_LIST_ORDER=1  (a fifth switch of that kind, "list_order") the attention work table of dinov2_hip_predict_list with the longest
+ *                            images first instead of in list order; a measuring aid (profiles/predict_list.md), same bits.
  *   DINOV2_HIP_LN_FOLD=0|1   what dinov2_hip_load_opts.ln_fold = 0 ("the library's choice") resolves to; unset: off.
  *   DINOV2_HIP_GROUP_NO_AFFINITY=1  the group's worker threads are not bound to the CPUs local to their device.
  *   DINOV2_HIP_GROUP_REQUIRE_RCCL=1  dinov2_hip_group_create fails when librccl cannot be loaded instead of letting every device

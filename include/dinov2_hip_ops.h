@@ -54,6 +54,23 @@ int dinov2_hip_op_attention(int32_t dtype, const float *qkv, float *out, int32_t
 int dinov2_hip_op_attention_ex(int32_t dtype, const float *qkv, float *out, int32_t B, int32_t T, int32_t H, int32_t nh,
                                int32_t log2_scores);
 
+/* dinov2_hip_predict_list (include/dinov2_hip.h).  Cases, the numpy restatement of the plan and the per-segment emulation: tests/list_cases.py;
+ * tests/test_list_probes.py (CPU), tests/test_gpu_attention_list.py, tests/test_gpu_predict_list.py.
+ * list_plan (no device; list_plan of csrc/kernels.h): n images of NETWORK size h[i] x w[i] pixels, `patch` pixels per patch side, R register
+ *   tokens, nh heads; order 0 = the work table in list order, 1 = longest images first (equal lengths in list order).
+ *   images [n][5] int64 = row0, T, P, h0, w0;  runs [n][2] int32 = first image, count of each run of consecutive images of one size (totals[4]
+ *   of them are written);  items [cap_items][4] int32 = row0, T, head, query block (128 queries) of every workgroup of the attention launch,
+ *   image-major, then head, then query block;  totals [5] = M (rows), patches, pixels, units (table entries), runs.  images / runs / items may
+ *   be NULL.  DINOV2_HIP_ERR_INVALID for bad arguments, cap_items < units, or M >= 2^31.
+ * attention_list: launch_attention_list on host data: qkv [sum T, 3H] (q already scaled), n segments of T[i] tokens one after the other ->
+ *   out [sum T, H]; each segment is, bit for bit, dinov2_hip_op_attention_ex on it alone (B = 1).  The kernel follows "attn_v" (1 | 2; other
+ *   forced values fail) and otherwise the forward's rule on the table's length; the table's order follows "list_order".  Guard bands and NaN
+ *   fill as for attention_ex. */
+int dinov2_hip_op_list_plan(int32_t n, const int32_t *h, const int32_t *w, int32_t patch, int32_t R, int32_t nh, int32_t order, int64_t *images,
+                            int32_t *runs, int32_t *items, int64_t cap_items, int64_t *totals);
+int dinov2_hip_op_attention_list(int32_t dtype, const float *qkv, float *out, int32_t n, const int32_t *T, int32_t H, int32_t nh,
+                                 int32_t log2_scores);
+
 /* ggml_norm * w + b (dinov2.cpp:694-700); dtype -1 = f32 output (final layernorm), 0/1 = f16/bf16 output */
 int dinov2_hip_op_layernorm(int32_t dtype, const float *x, const float *w, const float *b, float *out, int32_t rows,
                             int32_t H, float eps);
@@ -115,7 +132,7 @@ int dinov2_hip_op_clock_slots(uint64_t *out18);
 
 /* Testing aids.  The switches the library used to read from the environment on every launch (DINOV2_HIP_GEMM_GEN, DINOV2_HIP_GEMM_TILE,
  * DINOV2_HIP_ATTN_V, DINOV2_HIP_ATTN_NWV; include/dinov2_hip.h, "Environment") are read ONCE, on first use; a test that wants to flip one
- * inside a process calls the setter: key = "gemm_gen" | "gemm_tile" | "attn_v" | "attn_nwv", value 0 = the library's own choice,
+ * inside a process calls the setter: key = "gemm_gen" | "gemm_tile" | "attn_v" | "attn_nwv" | "list_order", value 0 = the library's own choice,
  * a negative value = back to what the environment said when the library first looked (so a test leaves a `DINOV2_HIP_GEMM_GEN=2 pytest`
  * run as it found it).
  * Not thread-safe against concurrent forwards on other threads in the sense that they may see either value. */

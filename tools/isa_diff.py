@@ -61,14 +61,28 @@ def main():
     ap.add_argument("--flags", default="", help="extra compiler flags for both sides, e.g. '-DDINO_PREC=31'")
     ap.add_argument("--jobs", type=int, default=6)
     ap.add_argument("--show", type=int, default=0, metavar="N", help="print the first N lines of each differing function's diff")
+    ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPL",
+                    help="rewrite function names on both sides before they are matched (repeatable): for a change that alters mangled names "
+                         "but must not alter bodies, e.g. a defaulted template parameter")
     a = ap.parse_args()
     extra = a.flags.split()
+
+    def renamed(fns):
+        out = {}
+        for n, ins in fns.items():
+            for r in a.rename:
+                pat, _, repl = r.partition("=")
+                n = re.sub(pat, repl, n)
+            if n in out:
+                sys.exit("--rename maps two functions to %s" % n)
+            out[n] = ins
+        return out
     differing = 0
     with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(a.jobs) as pool:
         jobs = {(side, rel): pool.submit(compile_asm, tree, rel, a.arch, extra, os.path.join(tmp, "%s_%s.s" % (side, os.path.basename(rel))))
                 for rel in a.files for side, tree in (("a", a.tree_a), ("b", a.tree_b))}
         for rel in a.files:
-            fa, fb = jobs["a", rel].result(), jobs["b", rel].result()
+            fa, fb = renamed(jobs["a", rel].result()), renamed(jobs["b", rel].result())
             names = sorted(set(fa) | set(fb))
             diff = [n for n in names if fa.get(n) != fb.get(n)]
             differing += len(diff)
