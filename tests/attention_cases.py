@@ -341,6 +341,10 @@ def build_probe(kind, B, T, nh, dt, seed):
 
 # ------------------------------------------------------------------------------------------------------------- emulation
 MUTANTS = ("drop_last_key", "drop_key_64", "leak_tail", "exp_swapped", "q_scaled_twice", "heads_swapped", "ragged_rows_shifted")
+# Planted bugs that finite data cannot show (every check above passes them): only a NaN tracer does (tests/tracer_cases.py).
+#   mask_by_multiply: the key tail is staged from the rows that FOLLOW the image (the next image's first keys; the last image's tail from
+#                     its own last key) and its weights are forced to 0 by a product, p * 0, instead of the select to -inf
+TRACER_MUTANTS = ("mask_by_multiply",)
 
 
 def emulate(qkv, B, T, nh, dt, log2, mutant=None, qblock=128):
@@ -362,6 +366,11 @@ def emulate(qkv, B, T, nh, dt, log2, mutant=None, qblock=128):
     for jt in range(ntiles):
         idx = np.minimum(np.arange(jt * KT, jt * KT + KT), T - 1)  # the staging clamps the tail to key T-1
         kt, vt = k[:, :, idx], v[:, :, idx]
+        if mutant == "mask_by_multiply" and jt == ntiles - 1 and B > 1:
+            over = np.minimum(np.arange(jt * KT, jt * KT + KT) - T, T - 1)  # >= 0: position of a tail key among the next image's rows
+            kt, vt = kt.copy(), vt.copy()
+            kt[:-1, :, over >= 0] = k[1:, :, over[over >= 0]]
+            vt[:-1, :, over >= 0] = v[1:, :, over[over >= 0]]
         s = np.matmul(q, kt.transpose(0, 1, 3, 2)) - m[..., None]
         keys = np.arange(jt * KT, jt * KT + KT)
         dead = keys >= T
@@ -381,6 +390,9 @@ def emulate(qkv, B, T, nh, dt, log2, mutant=None, qblock=128):
         o = o * alpha[..., None]
         s = s - d[..., None]
         p = ex(s)
+        if mutant == "mask_by_multiply":  # the scores were masked for the maximum only: p = 2^(q.k - m) * 0 for the tail
+            with np.errstate(invalid="ignore", over="ignore"):
+                p = np.where(dead, ex(np.matmul(q, kt.transpose(0, 1, 3, 2)) - m[..., None]) * f(0), p)
         l = l + p.sum(-1, dtype=f)
         o = o + np.matmul(round_t(p, dt), vt)
     with np.errstate(invalid="ignore", divide="ignore"):
