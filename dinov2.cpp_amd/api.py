@@ -101,6 +101,16 @@ class TopK(C.Structure):
     _fields_ = [("queries", Rows), ("k", C.c_int32), ("idx", C.c_void_p), ("sim", C.c_void_p), ("reserved", C.c_int32 * 4)]
 
 
+class KMeans(C.Structure):
+    """dinov2_hip_kmeans (include/dinov2_hip.h)."""
+    _fields_ = [("rows", Rows), ("all_images", C.c_int32), ("K", C.c_int32), ("max_iter", C.c_int32), ("init", C.c_int32),
+                ("init_centers", C.c_void_p), ("init_rows", C.c_void_p), ("labels", C.c_void_p), ("sim", C.c_void_p), ("centers", C.c_void_p),
+                ("counts", C.c_void_p), ("iterations", C.c_void_p), ("converged", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+KMEANS_INIT_GIVEN, KMEANS_INIT_ROWS = 0, 1
+
+
 class DenseDesc(C.Structure):
     """dinov2_hip_dense_desc (include/dinov2_hip.h)."""
     _fields_ = [("layers", C.POINTER(C.c_int32)), ("n_layers", C.c_int32), ("norm", C.c_int32), ("concat_cls", C.c_int32),
@@ -282,6 +292,75 @@ def op_bank_topk(q, b, k, chunk_tiles=0):
     out = {"idx": np.full((nq, k), -7, np.int32), "sim": np.full((nq, k), np.nan, np.float32)}
     _op_rc(lib().dinov2_hip_op_bank_topk(_ptr(q), nq, _ptr(b), nb, q.shape[1], int(k), int(chunk_tiles), _ptr(out["idx"]), _ptr(out["sim"])),
            "bank_topk")
+    return out
+
+
+KMEANS_PLAN_FIELDS = ("npad", "kpad", "hpad", "hpad128", "chunk", "nsplit", "partial_bytes", "bytes")
+
+
+def op_kmeans_plan(n, K, H, nsplit=0):
+    """kmeans_plan (csrc/kernels.h) as a dict; no device needed."""
+    buf = (C.c_int64 * len(KMEANS_PLAN_FIELDS))()
+    if lib().dinov2_hip_op_kmeans_plan(int(n), int(K), int(H), int(nsplit), buf) != 0:
+        raise ValueError(f"kmeans refuses n={n} K={K} H={H} nsplit={nsplit}")
+    return dict(zip(KMEANS_PLAN_FIELDS, [int(v) for v in buf]))
+
+
+def op_kmeans_assign(rows, centers):
+    """kmeans_assign_kernel alone (dinov2_hip_op_kmeans_assign): rows [n, H] against centers [K, H] -> dict of labels [n] int32, sim [n] f32.
+    No model, no session.  Raises on a HIP error or a changed guard band."""
+    x, c = _f32(rows), _f32(centers)
+    assert x.ndim == 2 and c.ndim == 2 and x.shape[1] == c.shape[1], (x.shape, c.shape)
+    n = x.shape[0]
+    out = {"labels": np.full(n, -7, np.int32), "sim": np.full(n, np.nan, np.float32)}
+    _op_rc(lib().dinov2_hip_op_kmeans_assign(_ptr(x), n, _ptr(c), c.shape[0], x.shape[1], _ptr(out["labels"]), _ptr(out["sim"])), "kmeans_assign")
+    return out
+
+
+def op_kmeans_update(rows, labels, K, prev_centers, nsplit=0):
+    """Transpose, update and finish of csrc/kmeans.hip for given labels (dinov2_hip_op_kmeans_update): dict of centers [K, H] (prev_centers
+    where a cluster is empty), counts [K] and xhat [n, H], the f32 values of the f16 rows that were summed."""
+    x, prev = _f32(rows), _f32(prev_centers)
+    lab = np.ascontiguousarray(labels, np.int32)
+    n, H = x.shape
+    assert lab.shape == (n,) and prev.shape == (int(K), H), (lab.shape, prev.shape)
+    out = {"centers": np.full((int(K), H), np.nan, np.float32), "counts": np.full(int(K), -7, np.int32), "xhat": np.full((n, H), np.nan, np.float32)}
+    _op_rc(lib().dinov2_hip_op_kmeans_update(_ptr(x), n, _ptr(lab), int(K), H, int(nsplit), _ptr(prev), _ptr(out["centers"]), _ptr(out["counts"]),
+                                             _ptr(out["xhat"])), "kmeans_update")
+    return out
+
+
+def _kmeans_init(init, n, K, H, seed):
+    """(init id, centres or None, row indices or None) of the `init` argument of Session.kmeans / op_kmeans."""
+    if init is None:
+        if K > n:
+            raise ValueError(f"kmeans: K = {K} distinct rows cannot be drawn from n = {n}")
+        return KMEANS_INIT_ROWS, None, np.sort(np.random.default_rng(seed).choice(n, int(K), replace=False)).astype(np.int32)
+    a = np.asarray(init)
+    if a.ndim == 1 and np.issubdtype(a.dtype, np.integer):
+        if a.shape != (int(K),):
+            raise ValueError("kmeans: init row indices must be [K]")
+        return KMEANS_INIT_ROWS, None, np.ascontiguousarray(a, np.int32)
+    if a.shape != (int(K), int(H)):
+        raise ValueError("kmeans: init must be None, [K] row indices or [K, H] centres")
+    return KMEANS_INIT_GIVEN, _f32(a), None
+
+
+def _kmeans_out(n, K, H):
+    return {"labels": np.full(n, -7, np.int32), "sim": np.full(n, np.nan, np.float32), "centers": np.full((K, H), np.nan, np.float32),
+            "counts": np.full(K, -7, np.int32)}
+
+
+def op_kmeans(rows, K, max_iter=20, init=None, seed=0):
+    """The whole loop of dinov2_hip_kmeans_tokens on host rows without a model or session (dinov2_hip_op_kmeans); the dict of Session.kmeans."""
+    x = _f32(rows)
+    n, H = x.shape
+    _, cen, idx = _kmeans_init(init, n, int(K), H, seed)
+    out = _kmeans_out(n, int(K), H)
+    it, conv = C.c_int32(-1), C.c_int32(-1)
+    _op_rc(lib().dinov2_hip_op_kmeans(_ptr(x), n, int(K), H, int(max_iter), _ptr(cen), _ptr(idx), _ptr(out["labels"]), _ptr(out["sim"]),
+                                      _ptr(out["centers"]), _ptr(out["counts"]), C.byref(it), C.byref(conv)), "kmeans")
+    out.update(iterations=int(it.value), converged=bool(conv.value))
     return out
 
 
@@ -476,6 +555,7 @@ def lib():
     L.dinov2_hip_debug_hidden.argtypes = [vp, C.POINTER(Input), i32, vp, cp, sz]
     L.dinov2_hip_pca3.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, cp, sz]
     L.dinov2_hip_match_tokens.argtypes = [vp, C.POINTER(Match), cp, sz]
+    L.dinov2_hip_kmeans_tokens.argtypes = [vp, C.POINTER(KMeans), cp, sz]
     L.dinov2_hip_bank_create.argtypes = [vp, i32, i32, C.POINTER(vp), cp, sz]
     L.dinov2_hip_bank_free.argtypes = [vp]
     L.dinov2_hip_bank_free.restype = None
@@ -519,6 +599,12 @@ def lib():
     L.dinov2_hip_op_pca_chol_rinv.argtypes = [vp, vp]
     L.dinov2_hip_op_match.argtypes = [fp, i32, fp, i32, i32, C.POINTER(i32), fp, C.POINTER(i32), fp]
     L.dinov2_hip_op_bank_topk.argtypes = [fp, i32, fp, i32, i32, i32, i32, C.POINTER(i32), fp]
+    ip = C.POINTER(i32)
+    L.dinov2_hip_op_kmeans_assign.argtypes = [fp, i32, fp, i32, i32, ip, fp]
+    L.dinov2_hip_op_kmeans_update.argtypes = [fp, i32, ip, i32, i32, i32, fp, fp, ip, fp]
+    L.dinov2_hip_op_kmeans_plan.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int64)]
+    L.dinov2_hip_op_kmeans.argtypes = [fp, i32, i32, i32, i32, fp, ip, ip, fp, fp, ip, ip, ip]
+    L.dinov2_hip_op_kmeans_bench.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, fp]
     L.dinov2_hip_op_bank_plan.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64)]
     L.dinov2_hip_op_dense_reduce.argtypes = [fp, i32, i32, i32, i32, i32, i32, fp, C.c_float, C.POINTER(C.c_uint8), fp]
     L.dinov2_hip_op_dense_pack.argtypes = [fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32, fp]
@@ -1203,6 +1289,44 @@ class Session(_Handle):
                   out["idx_ba"].ctypes.data, out["sim_ba"].ctypes.data)
         _call(lib().dinov2_hip_match_tokens, self._h, C.byref(m))
         out["mutual"] = out["idx_ba"][out["idx_ab"]] == np.arange(na, dtype=np.int32)
+        return out
+
+    def kmeans(self, rows=None, K: int = 8, max_iter: int = 20, init=None, seed: int = 0, *, source=None, image: int = 0,
+               all_images: bool = False, n: int | None = None, H: int | None = None):
+        """Spherical k-means on the device (dinov2_hip_kmeans_tokens).  rows: [n, H] host array or DeviceArray; or rows=None with
+        source="last_patches" (the patch rows of image `image` of the last un-split predict, or of every image with all_images=True) or
+        "last_cls"; `n` and `H` are taken from the session's last predict() unless given.  init: None (K distinct rows drawn by
+        numpy.random.default_rng(seed), sorted), [K] row indices or [K, H] centre vectors.  max_iter=0 only assigns.
+        Returns a dict: labels [n] int32, sim [n] f32, centers [K, H] f32 (cluster sums: right direction, not unit length), counts [K],
+        iterations, converged."""
+        if source is None:
+            source = "given" if rows is not None else None
+        if source not in _ROWS_SOURCE or (source == "given") != (rows is not None):
+            raise ValueError("kmeans: give rows, or source = 'last_cls' / 'last_patches' without rows")
+        if source != "given":
+            last = getattr(self, "_last_rows", {})
+            if n is None:
+                n = last.get(source, 0) * (last.get("last_cls", 0) if all_images else 1)
+            r = Rows(_ROWS_SOURCE[source], None, int(n), int(H if H is not None else self.model.hparams.hidden_size), int(image), 0)
+            keep = None
+        elif isinstance(rows, DeviceArray):
+            if len(rows.shape) != 2:
+                raise ValueError("kmeans: rows must be [n, H]")
+            r, keep = Rows(ROWS_GIVEN, rows.ptr, rows.shape[0], rows.shape[1], 0, 1), rows
+        else:
+            keep = np.ascontiguousarray(rows, dtype=np.float32)
+            if keep.ndim != 2:
+                raise ValueError("kmeans: rows must be [n, H]")
+            r = Rows(ROWS_GIVEN, keep.ctypes.data, keep.shape[0], keep.shape[1], 0, 0)
+        nn, HH, K = max(int(r.n), 0), int(r.H), int(K)
+        kind, cen, idx = _kmeans_init(init, nn, K, HH, seed)
+        out = _kmeans_out(nn, max(K, 0), HH)
+        it, conv = C.c_int32(-1), C.c_int32(-1)
+        km = KMeans(r, int(bool(all_images)), K, int(max_iter), kind, None if cen is None else cen.ctypes.data,
+                    None if idx is None else idx.ctypes.data, out["labels"].ctypes.data, out["sim"].ctypes.data, out["centers"].ctypes.data,
+                    out["counts"].ctypes.data, C.addressof(it), C.addressof(conv))
+        _call(lib().dinov2_hip_kmeans_tokens, self._h, C.byref(km))
+        out.update(iterations=int(it.value), converged=bool(conv.value))
         return out
 
     def sync(self):

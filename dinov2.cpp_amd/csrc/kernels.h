@@ -402,6 +402,81 @@ inline BankTopkPlan bank_topk_plan(int nq, int count, int H, int k, int chunk_ti
 hipError_t launch_bank_topk(const float* q, size_t ldq, int nq, const _Float16* bank, int count, int H, int k, char* ws, const BankTopkPlan& plan,
                             bool floor_only, hipStream_t stream);
 
+// Spherical k-means of token rows (csrc/kmeans.hip; contract in include/dinov2_hip.h, dinov2_hip_kmeans).  The assignment has match_kernel's
+// tile; the update is a GEMM X^T [hpad128, npad] x one-hot [npad, kpad] with the same tile, its rows split into `nsplit` chunks (a multiple of
+// 64 rows each, the last one possibly shorter) whose f32 partials [nsplit][kpad][hpad128] never exceed KMEANS_PARTIAL_MAX.
+constexpr int KMEANS_K_MAX = 1024, KMEANS_ITER_MAX = 1000, KMEANS_N_MAX = 1 << 20, KMEANS_TARGET_WGS = 256;
+constexpr size_t KMEANS_PARTIAL_MAX = (size_t)32 << 20;
+struct KmeansPlan {
+    int npad, kpad, hpad, hpad128;  // rows and centres to whole 128-tiles, H to a multiple of 64 (assignment) and of 128 (update)
+    int chunk, nsplit;              // rows per chunk of the update, chunks: chunk i covers rows [i chunk, min((i + 1) chunk, npad))
+    size_t x16, xt, c16;            // f16: X^ [npad, hpad], X^T [hpad128, npad], normalised centres [kpad, hpad]
+    size_t cvec;                    // the centre vectors [K, H] f32
+    size_t labels, sim;             // [npad] int32 (-1 on padding rows), [npad] f32
+    size_t part, cpart, counts;     // f32 [nsplit][kpad][hpad128], int32 [nsplit][kpad], int32 [kpad]
+    size_t chpart, changed;         // int32 [npad / 128], int32 [1]
+    size_t init;                    // int32 [K]: the row indices of DINOV2_HIP_KMEANS_INIT_ROWS
+    size_t part_bytes, bytes;
+};
+// nsplit = 0: as many chunks as bring the update grid to about KMEANS_TARGET_WGS workgroups; the chunk of a given value is raised where the
+// partials would pass KMEANS_PARTIAL_MAX.  Pure: (n, K, H, nsplit) alone decide every summation order of the update.
+inline KmeansPlan kmeans_plan(int n, int K, int H, int nsplit) {
+    KmeansPlan p{};
+    p.npad = (n + 127) / 128 * 128;
+    p.kpad = (K + 127) / 128 * 128;
+    p.hpad = (H + 63) / 64 * 64;
+    p.hpad128 = (H + 127) / 128 * 128;
+    const int nt = p.npad / 64;  // K-tiles of the update
+    const int tiles = (p.hpad128 / 128) * (p.kpad / 128);
+    const size_t per_split = (size_t)p.kpad * p.hpad128 * 4;  // <= 16 MiB
+    if (nsplit <= 0) nsplit = (KMEANS_TARGET_WGS + tiles - 1) / tiles;
+    const int cap = (int)(KMEANS_PARTIAL_MAX / per_split);
+    if (nsplit > cap) nsplit = cap;
+    if (nsplit > nt) nsplit = nt;
+    const int chunk_tiles = (nt + nsplit - 1) / nsplit;
+    p.chunk = chunk_tiles * 64;
+    p.nsplit = (nt + chunk_tiles - 1) / chunk_tiles;  // no empty chunk
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t off = need; need += (bytes + 255) / 256 * 256; return off; };
+    p.x16 = take((size_t)p.npad * p.hpad * 2);
+    p.xt = take((size_t)p.hpad128 * p.npad * 2);
+    p.c16 = take((size_t)p.kpad * p.hpad * 2);
+    p.cvec = take((size_t)K * H * 4);
+    p.labels = take((size_t)p.npad * 4);
+    p.sim = take((size_t)p.npad * 4);
+    p.part_bytes = per_split * p.nsplit;
+    p.part = take(p.part_bytes);
+    p.cpart = take((size_t)p.nsplit * p.kpad * 4);
+    p.counts = take((size_t)p.kpad * 4);
+    p.chpart = take((size_t)(p.npad / 128) * 4);
+    p.changed = take(4);
+    p.init = take((size_t)K * 4);
+    p.bytes = need;
+    return p;
+}
+struct KmeansBufs {  // the device arrays of one run: views of a workspace (kmeans_bufs) or buffers of their own
+    _Float16 *x16, *xt, *c16;
+    float* cvec;
+    int* labels;
+    float* sim;
+    float* part;
+    int *cpart, *counts, *chpart, *changed;
+};
+KmeansBufs kmeans_bufs(char* ws, const KmeansPlan& plan);
+// x16 and c16 normalised (launch_match_normalise with nout = npad / kpad) -> labels [npad] (read unless `first`; padding rows -1), sim [n],
+// *changed = the rows whose label differs from what labels held (`first`: n)
+hipError_t launch_kmeans_assign(const KmeansBufs& b, int n, int K, const KmeansPlan& plan, bool first, hipStream_t stream);
+// x16 -> xt, every element of it written
+hipError_t launch_kmeans_transpose(const KmeansBufs& b, const KmeansPlan& plan, hipStream_t stream);
+// xt, labels (values in [0, K) or -1) -> counts [K]; cvec rows of the clusters with members = their sums; c16 = normalise(cvec)
+hipError_t launch_kmeans_update(const KmeansBufs& b, int K, int H, const KmeansPlan& plan, hipStream_t stream);
+hipError_t launch_kmeans_count(const KmeansBufs& b, int K, const KmeansPlan& plan, hipStream_t stream);
+// cvec [K, H] = rows idx[j] (DEVICE indices) of src, where row r lives at src + (r / per) * outer + (r % per) * ld floats
+hipError_t launch_kmeans_gather(const float* src, int per, size_t outer, size_t ld, const int* idx, int K, int H, float* cvec, hipStream_t stream);
+// The loop (contract 5): b.x16 = the normalised rows, b.cvec = the init vectors on entry; synchronises the stream once per assignment.
+hipError_t kmeans_run(const KmeansBufs& b, int n, int K, int H, int max_iter, const KmeansPlan& plan, hipStream_t stream, int* iterations,
+                      int* converged);
+
 // Dense linear heads (csrc/dense.hip; contract in include/dinov2_hip.h, dinov2_hip_predict_dense): dense_pack_kernel builds the f16 operand
 // A [B P, K] of the logits GEMM straight from the residual stream at each tapped layer, launch_gemm(DT_F16, EPI_PLAIN_F32) gives the
 // low-resolution logits [B P, Cpad] f32, dense_reduce_kernel resamples them to out_h x out_w and reduces over the classes per pixel.

@@ -108,6 +108,7 @@ enum Scratch : int {
     SCRATCH_ATTN_Q,  // the query list of the last dinov2_hip_predict_attention on the device (attn_q_host: what it holds)
     SCRATCH_LIST_POS,    // dinov2_hip_predict_list: the interpolated position embeddings of up to LIST_POS_GRIDS patch grids (list_pos: what it holds)
     SCRATCH_LIST_ITEMS,  // dinov2_hip_predict_list: the attention work table of the last list (list_items_host: what it holds)
+    SCRATCH_KMEANS,      // dinov2_hip_kmeans_tokens (staged host rows, the f16 operands, the update's partials, the results)
     SCRATCH_COUNT
 };
 

@@ -724,6 +724,162 @@ extern "C" int dinov2_hip_op_bank_bench(const float* q_dev, int32_t nq, const fl
     return rc;
 }
 
+// ---- dinov2_hip_kmeans_tokens' kernels (csrc/kmeans.hip) on host data ----
+namespace {
+bool kmeans_shape_ok(int n, int K, int H) { return n >= 1 && n <= KMEANS_N_MAX && K >= 1 && K <= KMEANS_K_MAX && H >= 8 && H <= 4096; }
+// The buffers of one run, each an allocation of its own that starts as 0xff bytes; the four results between guard bands.
+struct KmeansOpBufs {
+    OpBuf x16, xt, c16, cvec, labels, sim, part, cpart, counts, chpart, changed;
+    KmeansBufs b{};
+    hipError_t alloc(int K, int H, const KmeansPlan& p) {
+        const struct { OpBuf* buf; size_t n, esz, guard; } all[] = {
+            {&x16, (size_t)p.npad * p.hpad, 2, 0}, {&xt, (size_t)p.hpad128 * p.npad, 2, 0}, {&c16, (size_t)p.kpad * p.hpad, 2, 0},
+            {&cvec, (size_t)K * H, 4, (size_t)H}, {&labels, (size_t)p.npad, 4, 1}, {&sim, (size_t)p.npad, 4, 1},
+            {&part, p.part_bytes / 4, 4, 0}, {&cpart, (size_t)p.nsplit * p.kpad, 4, 0}, {&counts, (size_t)p.kpad, 4, 1},
+            {&chpart, (size_t)p.npad / 128, 4, 0}, {&changed, 1, 4, 0}};
+        for (const auto& a : all) {
+            const hipError_t e = a.buf->alloc(a.n, a.esz, OpBuf::nans(), a.guard);
+            if (e != hipSuccess) return e;
+        }
+        b.x16 = x16.as<_Float16>(); b.xt = xt.as<_Float16>(); b.c16 = c16.as<_Float16>(); b.cvec = cvec.as<float>();
+        b.labels = labels.as<int>(); b.sim = sim.as<float>(); b.part = part.as<float>(); b.cpart = cpart.as<int>();
+        b.counts = counts.as<int>(); b.chpart = chpart.as<int>(); b.changed = changed.as<int>();
+        return hipSuccess;
+    }
+    // the first `count` elements of a guarded buffer to `host` (nothing for a NULL host)
+    template <typename T>
+    static int head(const OpBuf& buf, T* host, size_t count) {
+        if (!host) return 0;
+        std::vector<T> all(buf.n);
+        const int rc = buf.fetch(all.data());
+        if (rc == 0) std::copy(all.begin(), all.begin() + count, host);
+        return rc;
+    }
+};
+}  // namespace
+
+extern "C" int dinov2_hip_op_kmeans_plan(int32_t n, int32_t K, int32_t H, int32_t nsplit, int64_t* out) {
+    if (!out || !kmeans_shape_ok(n, K, H) || nsplit < 0) return DINOV2_HIP_ERR_INVALID;
+    const KmeansPlan p = kmeans_plan(n, K, H, nsplit);
+    const int64_t v[8] = {p.npad, p.kpad, p.hpad, p.hpad128, p.chunk, p.nsplit, (int64_t)p.part_bytes, (int64_t)p.bytes};
+    std::copy(v, v + 8, out);
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_kmeans_assign(const float* rows, int32_t n, const float* centers, int32_t K, int32_t H, int32_t* labels, float* sim) {
+    if (!rows || !centers || !labels || !sim || !kmeans_shape_ok(n, K, H)) return DINOV2_HIP_ERR_INVALID;
+    const KmeansPlan plan = kmeans_plan(n, K, H, 0);
+    OpBuf dX, dC;
+    KmeansOpBufs w;
+    OP_TRY(dX.upload(rows, (size_t)n * H * 4));
+    OP_TRY(dC.upload(centers, (size_t)K * H * 4));
+    OP_TRY(w.alloc(K, H, plan));
+    OP_TRY(launch_match_normalise(dX.as<float>(), (size_t)H, w.b.x16, n, plan.npad, H, plan.hpad, nullptr));
+    OP_TRY(launch_match_normalise(dC.as<float>(), (size_t)H, w.b.c16, K, plan.kpad, H, plan.hpad, nullptr));
+    OP_TRY(launch_kmeans_assign(w.b, n, K, plan, true, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    OP_FETCH(KmeansOpBufs::head(w.labels, labels, (size_t)n));
+    return KmeansOpBufs::head(w.sim, sim, (size_t)n);
+}
+
+extern "C" int dinov2_hip_op_kmeans_update(const float* rows, int32_t n, const int32_t* labels_in, int32_t K, int32_t H, int32_t nsplit,
+                                           const float* prev_centers, float* centers_out, int32_t* counts, float* xhat_f16_as_f32) {
+    if (!rows || !labels_in || !prev_centers || !centers_out || !counts || !kmeans_shape_ok(n, K, H) || nsplit < 0) return DINOV2_HIP_ERR_INVALID;
+    for (int i = 0; i < n; ++i)
+        if (labels_in[i] < 0 || labels_in[i] >= K) return DINOV2_HIP_ERR_INVALID;
+    const KmeansPlan plan = kmeans_plan(n, K, H, nsplit);
+    OpBuf dX;
+    KmeansOpBufs w;
+    OP_TRY(dX.upload(rows, (size_t)n * H * 4));
+    OP_TRY(w.alloc(K, H, plan));
+    std::vector<int32_t> lab((size_t)plan.npad, -1);  // as the assignment leaves them
+    std::copy(labels_in, labels_in + n, lab.begin());
+    OP_TRY(hipMemcpy(w.b.labels, lab.data(), lab.size() * 4, hipMemcpyHostToDevice));
+    OP_TRY(hipMemcpy(w.b.cvec, prev_centers, (size_t)K * H * 4, hipMemcpyHostToDevice));
+    OP_TRY(launch_match_normalise(dX.as<float>(), (size_t)H, w.b.x16, n, plan.npad, H, plan.hpad, nullptr));
+    OP_TRY(launch_kmeans_transpose(w.b, plan, nullptr));
+    OP_TRY(launch_kmeans_update(w.b, K, H, plan, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    OP_FETCH(w.cvec.fetch(centers_out));
+    OP_FETCH(KmeansOpBufs::head(w.counts, counts, (size_t)K));
+    OP_FETCH(w.labels.fetch(lab.data()));  // (its guards)
+    if (xhat_f16_as_f32) {
+        std::vector<uint16_t> x16((size_t)plan.npad * plan.hpad);
+        OP_TRY(w.x16.read(x16.data(), 0, x16.size() * 2));
+        for (int i = 0; i < n; ++i) widen_to_f32(false, (const unsigned char*)(x16.data() + (size_t)i * plan.hpad), (size_t)H, xhat_f16_as_f32 + (size_t)i * H);
+    }
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_kmeans(const float* rows, int32_t n, int32_t K, int32_t H, int32_t max_iter, const float* init_centers,
+                                    const int32_t* init_rows, int32_t* labels, float* sim, float* centers, int32_t* counts, int32_t* iterations,
+                                    int32_t* converged) {
+    if (!rows || (!init_centers && !init_rows) || !kmeans_shape_ok(n, K, H) || max_iter < 0 || max_iter > KMEANS_ITER_MAX) return DINOV2_HIP_ERR_INVALID;
+    for (int j = 0; !init_centers && j < K; ++j)
+        if (init_rows[j] < 0 || init_rows[j] >= n) return DINOV2_HIP_ERR_INVALID;
+    const KmeansPlan plan = kmeans_plan(n, K, H, 0);
+    OpBuf dX, dI;
+    KmeansOpBufs w;
+    OP_TRY(dX.upload(rows, (size_t)n * H * 4));
+    OP_TRY(w.alloc(K, H, plan));
+    OP_TRY(launch_match_normalise(dX.as<float>(), (size_t)H, w.b.x16, n, plan.npad, H, plan.hpad, nullptr));
+    if (init_centers) {
+        OP_TRY(hipMemcpy(w.b.cvec, init_centers, (size_t)K * H * 4, hipMemcpyHostToDevice));
+    } else {
+        OP_TRY(dI.upload(init_rows, (size_t)K * 4));
+        OP_TRY(launch_kmeans_gather(dX.as<float>(), n, 0, (size_t)H, dI.as<int>(), K, H, w.b.cvec, nullptr));
+    }
+    int it = 0, conv = 0;
+    OP_TRY(kmeans_run(w.b, n, K, H, max_iter, plan, nullptr, &it, &conv));
+    OP_TRY(hipDeviceSynchronize());
+    OP_FETCH(KmeansOpBufs::head(w.labels, labels, (size_t)n));
+    OP_FETCH(KmeansOpBufs::head(w.sim, sim, (size_t)n));
+    if (centers) OP_FETCH(w.cvec.fetch(centers));
+    OP_FETCH(KmeansOpBufs::head(w.counts, counts, (size_t)K));
+    if (iterations) *iterations = it;
+    if (converged) *converged = conv;
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_kmeans_bench(const float* rows_dev, int32_t n, int32_t K, int32_t H, int32_t nsplit, int32_t max_iter, int32_t warmup,
+                                          int32_t iters, float* ms) {
+    if (!rows_dev || !ms || !kmeans_shape_ok(n, K, H) || K > n || nsplit < 0 || max_iter < 0 || max_iter > KMEANS_ITER_MAX || warmup < 0 || iters < 1)
+        return DINOV2_HIP_ERR_INVALID;
+    const KmeansPlan plan = kmeans_plan(n, K, H, nsplit);
+    OpBuf dW;
+    EventPair ev;
+    OP_TRY(dW.alloc(plan.bytes, 1, OpBuf::none()));
+    OP_TRY(ev.create());
+    const KmeansBufs b = kmeans_bufs(dW.as<char>(), plan);
+    auto seed = [&] { return hipMemcpyAsync(b.cvec, rows_dev, (size_t)K * H * 4, hipMemcpyDeviceToDevice, nullptr); };
+    auto whole = [&] {
+        hipError_t e = launch_match_normalise(rows_dev, (size_t)H, b.x16, n, plan.npad, H, plan.hpad, nullptr);
+        if (e == hipSuccess) e = seed();
+        int it, conv;
+        return e != hipSuccess ? e : kmeans_run(b, n, K, H, max_iter, plan, nullptr, &it, &conv);
+    };
+    OP_TRY(whole());  // leaves every buffer of the single steps in a real state
+    OP_TRY(launch_kmeans_transpose(b, plan, nullptr));
+    auto timed = [&](auto step, float* out) {
+        int rc = 0;
+        for (int i = 0; i < warmup + iters && rc == 0; ++i) {
+            if (i == warmup && hipEventRecord(ev.e0, nullptr) != hipSuccess) rc = -1;
+            if (step() != hipSuccess) rc = -1;
+        }
+        float t = 0.0f;
+        if (rc == 0 && (hipEventRecord(ev.e1, nullptr) != hipSuccess || hipEventSynchronize(ev.e1) != hipSuccess ||
+                        hipEventElapsedTime(&t, ev.e0, ev.e1) != hipSuccess))
+            rc = -1;
+        *out = t / (float)iters;
+        return rc;
+    };
+    int rc = timed([&] { return launch_kmeans_assign(b, n, K, plan, true, nullptr); }, ms + 0);
+    if (rc == 0) rc = timed([&] { return launch_kmeans_update(b, K, H, plan, nullptr); }, ms + 1);
+    if (rc == 0) rc = timed(whole, ms + 2);
+    (void)hipDeviceSynchronize();
+    return rc;
+}
+
 // ---- the device stages of dinov2_hip_pca3 (csrc/pca.cpp), each through the launch function the driver calls, on host data ----
 namespace {
 bool pca_shape_ok(int P, int H) { return P >= 4 && H >= 8 && H <= 4096; }  // the range dinov2_hip_pca3 accepts

@@ -1,5 +1,5 @@
 // resident.cpp -- what works on rows that stay on the device between calls: nearest rows of two sets (dinov2_hip_match_tokens), the bank of
-// normalised rows with its top-k search (dinov2_hip_bank_*), and the lifetime of a dense-prediction head (dinov2_hip_dense_head_*; its
+// normalised rows with its top-k search (dinov2_hip_bank_*), spherical k-means of rows (dinov2_hip_kmeans_tokens), and the lifetime of a dense-prediction head (dinov2_hip_dense_head_*; its
 // forward, dinov2_hip_predict_dense, is in model.cpp).
 #include <cstring>
 #include <memory>
@@ -136,20 +136,12 @@ extern "C" int dinov2_hip_bank_clear(dinov2_hip_bank* b) {
 }
 
 namespace {
-// Checks a dinov2_hip_rows against the session and the bank's H; on success *src / *ld are the device view of a resident source (nullptr
-// for DINOV2_HIP_ROWS_GIVEN).  Touches nothing.
-int check_rows(const char* who, const dinov2_hip_session* s, const dinov2_hip_bank* b, const dinov2_hip_rows* r, const float** src, size_t* ld,
-               char* err, size_t errlen) {
+// Checks a dinov2_hip_rows of row width H against the session; on success *src / *ld are the device view of a resident source (nullptr for
+// DINOV2_HIP_ROWS_GIVEN).  Touches nothing.
+int check_rows(const char* who, const dinov2_hip_session* s, int H, const dinov2_hip_rows* r, const float** src, size_t* ld, char* err,
+               size_t errlen) {
     *src = nullptr;
-    *ld = (size_t)b->H;
-    if (s->model->device != b->device) {
-        set_err(err, errlen, "%s: the session is on device %d, the bank on device %d", who, s->model->device, b->device);
-        return DINOV2_HIP_ERR_INVALID;
-    }
-    if (r->H != b->H) {
-        set_err(err, errlen, "%s: rows have H = %d, the bank %d", who, r->H, b->H);
-        return DINOV2_HIP_ERR_INVALID;
-    }
+    *ld = (size_t)H;
     if (r->n < 1 || r->n > (1 << 24)) {
         set_err(err, errlen, "%s: need 1 <= n <= %d", who, 1 << 24);
         return DINOV2_HIP_ERR_INVALID;
@@ -198,6 +190,21 @@ int check_rows(const char* who, const dinov2_hip_session* s, const dinov2_hip_ba
         *ld = (size_t)Hm;
     }
     return DINOV2_HIP_OK;
+}
+// The same against a bank: its device and its H first.
+int check_rows(const char* who, const dinov2_hip_session* s, const dinov2_hip_bank* b, const dinov2_hip_rows* r, const float** src, size_t* ld,
+               char* err, size_t errlen) {
+    *src = nullptr;
+    *ld = (size_t)b->H;
+    if (s->model->device != b->device) {
+        set_err(err, errlen, "%s: the session is on device %d, the bank on device %d", who, s->model->device, b->device);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (r->H != b->H) {
+        set_err(err, errlen, "%s: rows have H = %d, the bank %d", who, r->H, b->H);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    return check_rows(who, s, b->H, r, src, ld, err, errlen);
 }
 }  // namespace
 
@@ -281,6 +288,114 @@ extern "C" int dinov2_hip_bank_topk(dinov2_hip_session* s, const dinov2_hip_bank
     if (q->idx) HIP_TRY(hipMemcpyAsync(q->idx, buf + plan.idx, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
     if (q->sim) HIP_TRY(hipMemcpyAsync(q->sim, buf + plan.sim, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return DINOV2_HIP_OK;
+}
+
+// =============================================================================================================
+// spherical k-means of token rows (csrc/kmeans.hip; no reference counterpart)
+// =============================================================================================================
+extern "C" int dinov2_hip_kmeans_tokens(dinov2_hip_session* s, const dinov2_hip_kmeans* km, char* err, size_t errlen) {
+    if (!s || !km) {
+        set_err(err, errlen, "kmeans: null session / request");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    const int n = km->rows.n, H = km->rows.H, K = km->K;
+    if (n < 1 || n > KMEANS_N_MAX || H < 8 || H > 4096) {
+        set_err(err, errlen, "kmeans: need 1 <= n <= %d and 8 <= H <= 4096", KMEANS_N_MAX);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (K < 1 || K > KMEANS_K_MAX || km->max_iter < 0 || km->max_iter > KMEANS_ITER_MAX) {
+        set_err(err, errlen, "kmeans: need 1 <= K <= %d and 0 <= max_iter <= %d", KMEANS_K_MAX, KMEANS_ITER_MAX);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (km->init != DINOV2_HIP_KMEANS_INIT_GIVEN && km->init != DINOV2_HIP_KMEANS_INIT_ROWS) {
+        set_err(err, errlen, "kmeans: unknown init %d", (int)km->init);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (km->init == DINOV2_HIP_KMEANS_INIT_GIVEN ? !km->init_centers : !km->init_rows) {
+        set_err(err, errlen, "kmeans: init %d without its %s", (int)km->init, km->init == DINOV2_HIP_KMEANS_INIT_GIVEN ? "init_centers" : "init_rows");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    for (int j = 0; km->init == DINOV2_HIP_KMEANS_INIT_ROWS && j < K; ++j)
+        if (km->init_rows[j] < 0 || km->init_rows[j] >= n) {
+            set_err(err, errlen, "kmeans: init_rows[%d] = %d outside [0, %d)", j, (int)km->init_rows[j], n);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+    if (!km->labels && !km->sim && !km->centers && !km->counts && !km->iterations && !km->converged) {
+        set_err(err, errlen, "kmeans: no output requested");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    if (km->all_images != 0 && (km->all_images != 1 || km->rows.source != DINOV2_HIP_ROWS_LAST_PATCHES)) {
+        set_err(err, errlen, "kmeans: all_images is 0, or 1 with DINOV2_HIP_ROWS_LAST_PATCHES");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    // the view of the source: row r lives at src + (r / per) * outer + (r % per) * ld floats
+    const float* src;
+    size_t ld;
+    int per = n;
+    size_t outer = 0;
+    if (km->all_images) {
+        dinov2_hip_rows one = km->rows;  // image 0's patch rows stand for the checks of the resident source
+        one.image = 0;
+        const int P = s->last_b > 0 ? s->last_t - 1 - (int)s->model->hp.num_register_tokens : 0;
+        one.n = P > 0 ? P : 1;  // (no forward: the resident check below says so)
+        const int rc = check_rows("kmeans", s, H, &one, &src, &ld, err, errlen);
+        if (rc != DINOV2_HIP_OK) return rc;
+        if ((int64_t)n != (int64_t)s->last_b * P) {
+            set_err(err, errlen, "kmeans: all_images has the %d patch rows of each of the last %d images: n must be %d", P, s->last_b, s->last_b * P);
+            return DINOV2_HIP_ERR_INVALID;
+        }
+        per = P;
+        outer = (size_t)s->last_t * H;
+    } else {
+        const int rc = check_rows("kmeans", s, H, &km->rows, &src, &ld, err, errlen);
+        if (rc != DINOV2_HIP_OK) return rc;
+        if (km->rows.source == DINOV2_HIP_ROWS_LAST_CLS) {  // one row per image
+            per = 1;
+            outer = ld;
+        }
+    }
+    HIP_TRY(hipSetDevice(s->model->device));
+    hipStream_t st = s->stream;
+    const KmeansPlan plan = kmeans_plan(n, K, H, 0);
+    const bool stage = km->rows.source == DINOV2_HIP_ROWS_GIVEN && !km->rows.on_device;
+    const size_t n_x = (size_t)n * H * 4;
+    const int rs = reserve(s, s->scratch[SCRATCH_KMEANS], plan.bytes + align_up(stage ? n_x : 0, 256), "kmeans", err, errlen);
+    if (rs != DINOV2_HIP_OK) return rs;
+    char* const buf = s->scratch[SCRATCH_KMEANS].as<char>();
+    const KmeansBufs b = kmeans_bufs(buf, plan);
+    if (km->rows.source == DINOV2_HIP_ROWS_GIVEN) {
+        src = km->rows.data;
+        if (stage) {
+            HIP_TRY(hipMemcpyAsync(buf + plan.bytes, km->rows.data, n_x, hipMemcpyHostToDevice, st));
+            src = (const float*)(buf + plan.bytes);
+        }
+    }
+    if (km->all_images) {  // the images' patch rows are not contiguous in the token stream: one launch per image, consecutive row blocks
+        for (int i = 0; i < s->last_b; ++i) {
+            const bool last = i == s->last_b - 1;
+            HIP_TRY(launch_match_normalise(src + (size_t)i * outer, ld, b.x16 + (size_t)i * per * plan.hpad, per,
+                                           last ? plan.npad - i * per : per, H, plan.hpad, st));
+        }
+    } else {
+        HIP_TRY(launch_match_normalise(src, ld, b.x16, n, plan.npad, H, plan.hpad, st));
+    }
+    if (km->init == DINOV2_HIP_KMEANS_INIT_GIVEN) {
+        HIP_TRY(hipMemcpyAsync(b.cvec, km->init_centers, (size_t)K * H * 4, hipMemcpyHostToDevice, st));
+    } else {
+        int* const idx = (int*)(buf + plan.init);
+        HIP_TRY(hipMemcpyAsync(idx, km->init_rows, (size_t)K * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(launch_kmeans_gather(src, per, outer, ld, idx, K, H, b.cvec, st));
+    }
+    int iterations = 0, converged = 0;
+    HIP_TRY(kmeans_run(b, n, K, H, km->max_iter, plan, st, &iterations, &converged));
+    if (km->labels) HIP_TRY(hipMemcpyAsync(km->labels, b.labels, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (km->sim) HIP_TRY(hipMemcpyAsync(km->sim, b.sim, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (km->centers) HIP_TRY(hipMemcpyAsync(km->centers, b.cvec, (size_t)K * H * 4, hipMemcpyDeviceToHost, st));
+    if (km->counts) HIP_TRY(hipMemcpyAsync(km->counts, b.counts, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (km->iterations) *km->iterations = iterations;
+    if (km->converged) *km->converged = converged;
     return DINOV2_HIP_OK;
 }
 

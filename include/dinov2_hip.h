@@ -461,6 +461,62 @@ typedef struct dinov2_hip_topk {
  * count and k.  An allocation the device refuses returns DINOV2_HIP_ERR_HIP. */
 int  dinov2_hip_bank_topk(dinov2_hip_session *s, const dinov2_hip_bank *bank, const dinov2_hip_topk *q, char *err, size_t errlen);
 
+/* -- spherical k-means of token rows (no reference counterpart: k-means over the patch tokens of one image for unsupervised part or object
+ *    segments, over the patches of a whole batch for co-segmentation, and a fixed vocabulary of centres applied to new frames -- visual
+ *    words, labels that stay consistent from frame to frame in the realtime loop).  The rows are a caller's matrix or resident tokens of
+ *    the session's last un-split forward; only [n] labels and [K, H] centres cross PCIe.  On the device (csrc/kmeans.hip): the rows are
+ *    normalised and transposed once; every iteration assigns each row to its most similar centre on the matrix cores (dinov2_hip_match's
+ *    tile and K loop, the similarity matrix never written) and sums the members of every cluster with a second GEMM, X^T times the one-hot
+ *    matrix of the labels, which is built in LDS and never exists in memory.
+ *    Contract:
+ *    1. Operands.  Rows and centre vectors go through contract 1 of dinov2_hip_match, the same kernel: f16 unit rows, a zero row stays zero.
+ *       Inputs must be finite: the update multiplies rows by a one-hot operand on the matrix cores, so 0 x NaN makes one non-finite row
+ *       poison every centre.
+ *    2. Assignment.  label[i] = argmax_c sim(i, c) over the K real centres; sim is contract 2 of dinov2_hip_match (the same MFMA shape and
+ *       operand roles, k-steps of 32 ascending, an order that depends on H alone); ties go to the LOWEST c, -0 equals +0.  Hence labels and
+ *       sim equal idx_ab and sim_ab of dinov2_hip_match_tokens(rows, centre vectors) bit for bit, and a row's label does not depend on the
+ *       rows that travel with it.
+ *    3. Update.  For every cluster with at least one member, S_c[h] = sum over label[i] == c of x^_ih: the f16 values are exact in f32; the
+ *       accumulation is f32 in an order fixed by a pure planner from (n, K, H) alone -- ascending rows within a chunk of rows, then the
+ *       chunks ascending.  No atomics: the result is bit-reproducible run to run.  counts are exact integers.
+ *    4. Centres.  The vector of centre c is S_c of the last update in which c had members, otherwise the vector it had before -- initially
+ *       the init vector, verbatim in f32: an EMPTY cluster keeps its vector.  The f16 centre used for assignment is always
+ *       normalise(vector).  `centers` returns these f32 vectors: they point in the right direction but are not unit length.  Passing them
+ *       back as DINOV2_HIP_KMEANS_INIT_GIVEN with max_iter = 0 therefore reproduces labels and sim bit for bit.
+ *    5. Loop.  c^0 = the init vectors.  Iteration t: labels^t = assign(c^(t-1)); changed = the labels that differ from labels^(t-1) (n at
+ *       t = 1).  changed == 0: stop, converged, iterations = t - 1.  Otherwise update, giving c^t.  After max_iter updates one more
+ *       assignment runs against c^max_iter (converged if it changes nothing).  The returned labels, sim and counts are always the assignment
+ *       against the returned centers.  The host reads one 4-byte `changed` per iteration.
+ *    Out of scope: Euclidean k-means; k-means++ or maximin seeding (the Python Session.kmeans offers a seeded sample of rows through
+ *    DINOV2_HIP_KMEANS_INIT_ROWS); re-seeding empty clusters; K > 1024; bf16 operands; the device group; device-side outputs; the rows of a
+ *    list forward; dinov2_compat.hpp and the example programs.
+ *    Times: profiles/kmeans.md. */
+enum dinov2_hip_kmeans_init { DINOV2_HIP_KMEANS_INIT_GIVEN = 0, DINOV2_HIP_KMEANS_INIT_ROWS = 1 };
+typedef struct dinov2_hip_kmeans {
+    dinov2_hip_rows rows;     /* GIVEN (host / device), LAST_CLS, LAST_PATCHES of `rows.image`; 1 <= n <= 1 048 576, 8 <= H <= 4096 */
+    int32_t all_images;       /* 1 with LAST_PATCHES: the patch rows of EVERY image of the last un-split forward, image-major;
+                                 rows.image is ignored and rows.n must be last_b * P.  Must be 0 for the other sources. */
+    int32_t K;                /* 1 .. 1024 */
+    int32_t max_iter;         /* 0 .. 1000; 0 = assign only (a stored vocabulary applied to new rows) */
+    int32_t init;             /* GIVEN: init_centers [K, H] f32 HOST.  ROWS: init_rows [K] HOST indices in [0, n): centre j starts as row init_rows[j] */
+    const float   *init_centers;
+    const int32_t *init_rows;
+    int32_t *labels;          /* [n] HOST; any output may be NULL, not all */
+    float   *sim;             /* [n] cosine of each row to its centre */
+    float   *centers;         /* [K, H] f32, see contract 4 */
+    int32_t *counts;          /* [K] */
+    int32_t *iterations;      /* updates performed */
+    int32_t *converged;       /* 1 if the loop ended because no label changed */
+    int32_t reserved[4];
+} dinov2_hip_kmeans;
+/* Synchronous: returns after the copy-out, like dinov2_hip_match_tokens.  Argument errors (NULL session or request; n, H, K or max_iter out
+ * of range; an unknown init or its pointer NULL; an init_rows entry outside [0, n); all_images with a source other than LAST_PATCHES; all
+ * outputs NULL; the resident-source errors of dinov2_hip_bank_add; a misaligned device pointer) return DINOV2_HIP_ERR_INVALID before anything
+ * is launched, allocated or copied, with the outputs untouched.  The scratch (host rows' staging copy, X^ and X^T in f16, the centres, at
+ * most 32 MiB of partial sums, the results) is a session-owned buffer grown on demand; an allocation the device refuses returns
+ * DINOV2_HIP_ERR_HIP.  The session's last forward stays what it was. */
+int dinov2_hip_kmeans_tokens(dinov2_hip_session *s, const dinov2_hip_kmeans *km, char *err, size_t errlen);
+
 /* -- linear dense-prediction heads (no reference counterpart: semantic segmentation and depth estimation with a linear head on frozen
  *    patch features, two of the evaluation protocols of the DINOv2 paper; upstream: BNHead of
  *    dinov2/eval/segmentation/models/decode_heads/linear_head.py and of dinov2/eval/depth/models/decode_heads/linear_head.py).  A resident head

@@ -6,7 +6,7 @@
  * kernel against the oracle in isolation -- the per-op granularity the reference gets from ggml's own op tests and
  * that /root/reference itself never had (it holds no tests at all).  All return 0 on success, -1 on a HIP error
  * (the entry points with guard bands -- attention_ex, layer_tap, attn_rows, pca_prepare / pca_cov / pca_power / pca_project, dense_reduce,
- * dense_pack -- also DINOV2_HIP_OP_GUARD_CHANGED).  Each family has its cases in tests/*_cases.py, CPU probes of those cases and a GPU file; for the
+ * dense_pack, kmeans_assign / _update / kmeans -- also DINOV2_HIP_OP_GUARD_CHANGED).  Each family has its cases in tests/*_cases.py, CPU probes of those cases and a GPU file; for the
  * pca_* entry points: tests/pca_cases.py, tests/test_pca_probes.py, tests/test_gpu_pca_kernels.py.
  */
 #ifndef DINOV2_HIP_OPS_H
@@ -198,6 +198,31 @@ int dinov2_hip_op_bank_plan(int32_t nq, int32_t nb, int32_t H, int32_t k, int32_
  * in *ms.  floor_only = 1: the sweep with its selection epilogue compiled out (the kernel's own floor; its results mean nothing). */
 int dinov2_hip_op_bank_bench(const float *q_dev, int32_t nq, const float *b_dev, int32_t nb, int32_t H, int32_t k, int32_t chunk_tiles,
                              int32_t warmup, int32_t iters, int32_t floor_only, float *ms);
+
+/* the kernels behind dinov2_hip_kmeans_tokens (csrc/kmeans.hip) and the shared normaliser, without a model or session; cases, the numpy
+ * restatement and the bounds: tests/kmeans_cases.py.  1 <= n <= 2^20, 1 <= K <= 1024, 8 <= H <= 4096, else DINOV2_HIP_ERR_INVALID.  Every
+ * device buffer starts as 0xff bytes, so anything the kernels read without having written it shows up as NaN / -1; labels, sim, centres and
+ * counts sit between guard bands: a changed one returns DINOV2_HIP_OP_GUARD_CHANGED.
+ * kmeans_assign: host rows [n, H] against host centers [K, H] (vectors of any length) -> labels [n], sim [n] (both required): one
+ *                kmeans_assign_kernel launch, contract 2.
+ * kmeans_update: transpose, update and finish for GIVEN labels_in [n] in [0, K): centers_out [K, H] = prev_centers with the vector of every
+ *                cluster that has members replaced by its sum S_c (contract 3 / 4), counts [K]; xhat_f16_as_f32 [n, H] (may be NULL) = the f32
+ *                values of the f16 rows that were summed.  nsplit: chunks of rows, 0 = the planner's choice.
+ * kmeans_plan (no device): out[0 .. 7] = npad, kpad, hpad, hpad128, chunk rows, nsplit, bytes of the partials, bytes of the workspace.
+ * kmeans:        the whole loop of dinov2_hip_kmeans_tokens on host rows; init_centers [K, H] or (when it is NULL) init_rows [K]; any output
+ *                may be NULL.
+ * kmeans_bench (tools/kmeans_bench.py): DEVICE f32 rows_dev [n, H], centres = the first K rows: ms[0] = one assignment, ms[1] = one update
+ *                (sweep, fold, normalise), ms[2] = the whole call (normalise, transpose, `max_iter` iterations with their 4-byte reads), each
+ *                the mean of `iters` timed runs after `warmup`, by HIP events on the null stream. */
+int dinov2_hip_op_kmeans_assign(const float *rows, int32_t n, const float *centers, int32_t K, int32_t H, int32_t *labels, float *sim);
+int dinov2_hip_op_kmeans_update(const float *rows, int32_t n, const int32_t *labels_in, int32_t K, int32_t H, int32_t nsplit,
+                                const float *prev_centers, float *centers_out, int32_t *counts, float *xhat_f16_as_f32);
+int dinov2_hip_op_kmeans_plan(int32_t n, int32_t K, int32_t H, int32_t nsplit, int64_t *out);
+int dinov2_hip_op_kmeans(const float *rows, int32_t n, int32_t K, int32_t H, int32_t max_iter, const float *init_centers,
+                         const int32_t *init_rows, int32_t *labels, float *sim, float *centers, int32_t *counts, int32_t *iterations,
+                         int32_t *converged);
+int dinov2_hip_op_kmeans_bench(const float *rows_dev, int32_t n, int32_t K, int32_t H, int32_t nsplit, int32_t max_iter, int32_t warmup,
+                               int32_t iters, float *ms);
 
 /* the two kernels of csrc/dense.hip (behind dinov2_hip_predict_dense) without a model or session; cases and the numpy restatement:
  * tests/dense_cases.py.
