@@ -76,7 +76,7 @@ static hipError_t pack_dispatch(const float* x, const float* w, const float* b, 
 
 hipError_t launch_dense_pack(const float* x, const float* w, const float* b, float eps, int B, int T, int R, int H, bool norm, bool concat_cls,
                              _Float16* A, size_t lda, int col0, hipStream_t st) {
-    if (H % 8 != 0 || H <= 0 || H > 64 * 4 * 8 || B <= 0 || R < 0 || T < 2 + R) return hipErrorInvalidValue;  // ln_dispatch's widths; P >= 1
+    if (H % 8 != 0 || H <= 0 || H > LN_MAX_WIDTH || B <= 0 || R < 0 || T < 2 + R) return hipErrorInvalidValue;  // ln_dispatch's widths; P >= 1
     if (!x || !A || (norm && (!w || !b))) return hipErrorInvalidValue;
     if (lda % 8 != 0 || col0 < 0 || col0 % 8 != 0 || ((size_t)A & 15) != 0 || (size_t)col0 + (size_t)H * (concat_cls ? 2 : 1) > lda)
         return hipErrorInvalidValue;

@@ -41,6 +41,29 @@ constexpr int LN_GROUP = 64;      // columns per partial-sum group of EPI_RESID_
 constexpr int LN_MAX_GROUPS = 24; // hidden sizes up to 1 536 (ViT-g); larger models keep the LayerNorm launches
 inline int ln_stat_slots(int hidden) { return hidden / LN_GROUP <= 12 ? 12 : 24; }  // slots per row of the statistics buffer (device_types.h, ln_row_load)
 
+// ---- the geometry limits of the row kernels, stated once: the launchers below refuse what is outside them, and dinov2_hip_model_load refuses
+// a model that would reach such a launch (include/dinov2_hip.h, "Supported geometry") ----
+// LayerNorm, layer tap, ln_prepare and dense_pack keep one token row in the registers of one wave: at most 8 float4 per lane of 64.
+constexpr int LN_MAX_WIDTH = 64 * 4 * 8;
+// im2col lays IM2COL_CHUNK patches of Kpad two-byte elements out in LDS (64 KiB per workgroup), divides a pixel column by 3 through a
+// multiplication that is exact below 32 768, and by the patch size through one that must be exact for every column of the chunk.
+constexpr int IM2COL_CHUNK = 10;
+inline bool im2col_patch_ok(int patch, int Kpad) {
+    if (patch <= 0 || 3LL * IM2COL_CHUNK * patch >= 32768) return false;  // (first: the loader hands over any 32-bit patch_size)
+    if (Kpad % 8 != 0 || (long long)Kpad < 3LL * patch * patch) return false;
+    if ((size_t)IM2COL_CHUNK * Kpad * 2 > 64 * 1024) return false;
+    for (unsigned x = 0, mg = 65536u / (unsigned)patch + 1u; x < (unsigned)(IM2COL_CHUNK * patch); ++x)
+        if (((x * mg) >> 16) != x / (unsigned)patch) return false;
+    return true;
+}
+// the largest patch size whose K = 3 p^2, padded to a multiple of 64 as the loader pads it, im2col takes (32: Kpad = 3 072, 60 KiB of LDS;
+// 33 needs Kpad = 3 328, 65 KiB)
+inline int im2col_max_patch() {
+    int p = 0;
+    while (im2col_patch_ok(p + 1, (3 * (p + 1) * (p + 1) + 63) / 64 * 64)) ++p;
+    return p;
+}
+
 struct GemmArgs {
     const void* A;      // [M, K]  T, row-major, K % 64 == 0
     const void* W;      // [N, K]  T, row-major (ggml ne = [K, N])

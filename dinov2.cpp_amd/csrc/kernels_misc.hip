@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 template <typename OutT>
 static hipError_t ln_dispatch(const float* x, const float* w, const float* b, OutT* y, int rows, int H, float eps,
                               hipStream_t st) {
-    if (H % 4 != 0 || H > 64 * 4 * 8) return hipErrorInvalidValue;
+    if (H % 4 != 0 || H > LN_MAX_WIDTH) return hipErrorInvalidValue;
     const dim3 grid((rows + 3) / 4), block(256);
     const int nv = (H / 4 + 63) / 64;
     if (nv <= 2) hipLaunchKernelGGL((layernorm_kernel<OutT, 2>), grid, block, 0, st, x, w, b, y, rows, H, eps);
@@ -212,7 +212,7 @@ static hipError_t tap_dispatch(const float* x, const float* w, const float* b, c
 
 hipError_t launch_layer_tap(const float* x, const float* w, const float* b, float eps, int B, int T, int R, int H, bool norm, bool chw,
                             float* patch_out, float* cls_out, float* reg_out, hipStream_t st) {
-    if (H % 4 != 0 || H <= 0 || H > 64 * 4 * 8 || B <= 0 || R < 0 || T < 2 + R) return hipErrorInvalidValue;  // ln_dispatch's widths; P >= 1
+    if (H % 4 != 0 || H <= 0 || H > LN_MAX_WIDTH || B <= 0 || R < 0 || T < 2 + R) return hipErrorInvalidValue;  // ln_dispatch's widths; P >= 1
     if (reg_out && R == 0) return hipErrorInvalidValue;
     if (norm && (!w || !b)) return hipErrorInvalidValue;
     if (!patch_out && !cls_out && !reg_out) return hipSuccess;
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) void ln_prepare_kernel(const float* __restrict
 }
 
 hipError_t launch_ln_prepare(DType dt, const float* x, const float* gamma, void* xg, float* stats, int gs, int rows, int H, hipStream_t st) {
-    if (H % 64 != 0 || H > 64 * 4 * 8) return hipErrorInvalidValue;
+    if (H % 64 != 0 || H > LN_MAX_WIDTH) return hipErrorInvalidValue;
     const dim3 grid((rows + 3) / 4), block(256);
     const int nv = (H / 4 + 63) / 64;
 #define DINO_LNP(TT, MV) hipLaunchKernelGGL((ln_prepare_kernel<TT, MV>), grid, block, 0, st, x, gamma, (TT*)xg, stats, gs, rows, H)
@@ -317,7 +317,6 @@ hipError_t launch_ln_fold_vectors(DType dt, const void* W, const float* bias, co
 // One workgroup per (image, patch row, chunk of <= IM2COL_CHUNK patches): the 3 x ps image rows of the chunk are read as contiguous runs
 // (coalesced; the first version gathered 8 pixels per thread from 8 addresses and ran at 1.7 TB/s), converted, laid out as the chunk's
 // [patches][Kpad] block in LDS, and leave as whole 16-byte pieces of whole rows.  Same values as ever: one (T) rounding of the f32 pixel.
-constexpr int IM2COL_CHUNK = 10;
 template <typename T>
 __global__ __launch_bounds__(1024) void im2col_kernel(const float* __restrict__ img, T* __restrict__ col, int B, int Hh,
                                                      int Ww, int ps, int Kpad, int layout, int nchunk) {
@@ -373,14 +372,12 @@ __global__ __launch_bounds__(1024) void im2col_kernel(const float* __restrict__ 
 
 hipError_t launch_im2col(DType dt, const float* img, void* col, int B, int Hh, int Ww, int patch, int Kpad, int layout,
                          hipStream_t st) {
-    if (patch <= 0 || Kpad % 8 != 0 || Kpad < 3 * patch * patch) return hipErrorInvalidValue;
+    // (kernels.h: the LDS tile of a chunk and the kernel's two divisions by multiplication; with the loader's Kpad, patch sizes up to 32)
+    if (!im2col_patch_ok(patch, Kpad)) return hipErrorInvalidValue;
     const int w0 = Ww / patch, h0 = Hh / patch;
     if (w0 <= 0 || h0 <= 0 || B <= 0) return hipErrorInvalidValue;
     const int nchunk = (w0 + IM2COL_CHUNK - 1) / IM2COL_CHUNK;
     const size_t lds = (size_t)IM2COL_CHUNK * Kpad * 2;
-    if (lds > 64 * 1024 || 3 * IM2COL_CHUNK * patch >= 32768) return hipErrorInvalidValue;  // (Kpad <= 1 638: patch sizes up to 23)
-    for (unsigned x = 0, mg = 65536u / (unsigned)patch + 1u; x < (unsigned)(IM2COL_CHUNK * patch); ++x)
-        if (((x * mg) >> 16) != x / (unsigned)patch) return hipErrorInvalidValue;  // (never for patch <= 23; the kernel divides by multiplication)
     // few workgroups (batch 1: 148): 16 waves each, so that a wave's chain of runs is three deep (10 us; 15 with four waves); many (batch 32:
     // 4 736): four waves, more workgroups per CU overlap better (51 us against 69; the gather this replaces took 92 / 10 us)
     const size_t nwg = (size_t)B * h0 * nchunk;

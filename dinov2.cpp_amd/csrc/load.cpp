@@ -208,6 +208,16 @@ extern "C" int dinov2_hip_model_load(const char* path, const dinov2_hip_load_opt
         set_err(err, errlen, "hidden_size %d is not a multiple of 64", H);
         return DINOV2_HIP_ERR_UNSUPPORTED;
     }
+    // what the kernels behind the forward take (kernels.h): refused here, by name, rather than by a launch of the first forward
+    if (H > LN_MAX_WIDTH) {
+        set_err(err, errlen, "unsupported hidden_size %d: the LayerNorm kernels take rows of up to %d (num_attention_heads <= %d)", H,
+                LN_MAX_WIDTH, LN_MAX_WIDTH / 64);
+        return DINOV2_HIP_ERR_UNSUPPORTED;
+    }
+    if (!im2col_patch_ok(ps, (int)align_up((size_t)3 * ps * ps, 64))) {
+        set_err(err, errlen, "unsupported patch_size %d: the patch-embedding im2col takes patch sizes up to %d", ps, im2col_max_patch());
+        return DINOV2_HIP_ERR_UNSUPPORTED;
+    }
     const int Mgrid = (int)(hp.img_size / hp.patch_size);
 
     auto need = [&](const std::string& name, const GgufTensor** t) -> bool {

@@ -112,6 +112,17 @@ typedef struct dinov2_hip_output {
 
 /* -- load (replaces dino_model_load, dinov2.h:98-99 / dinov2.cpp:239-352) ---------------------------- */
 void dinov2_hip_default_load_opts(dinov2_hip_load_opts *opts);
+/* Supported geometry.  A model is either refused here with DINOV2_HIP_ERR_UNSUPPORTED and a message that names the hparam, its value and
+ * the limit, or every forward entry point runs it (tests/geometry_cases.py sweeps both sides of each limit):
+ *   hidden_size = 64 * num_attention_heads (head dim 64), at most 2 048 (32 heads): the LayerNorm kernels keep a row in one wave;
+ *   FFN width a multiple of 64 (GELU: any such width; SwiGLU: the width of weights_out, its x1 | x2 rows interleaved in blocks of 32);
+ *   patch_size 1 .. 32 (the im2col tile of ten patches of 3 p^2 elements, padded to a multiple of 64, must fit 64 KiB of LDS);
+ *   img_size >= patch_size; any number of layers, register tokens and classes; 2-D weights F32 / F16 / BF16 / Q4_0 / Q4_1 / Q5_0 /
+ *   Q5_1 / Q8_0 (the patch-embedding kernel F32 / F16 / BF16), every other tensor F32.
+ * ln_fold applies where hidden_size % 128 == 0 and hidden_size <= 1 536; elsewhere the model runs with separate LayerNorm launches.
+ * What has been RUN off the four published geometries: widths 64 .. 2 048, patch sizes 8, 14, 16 and 32, through dinov2_hip_predict,
+ * _predict_layers, _predict_attention and _predict_dense.  Patch sizes 1 .. 7 and the other entry points (predict_list, kmeans, match,
+ * bank) at such geometries are inside the limits above by the kernels' index arithmetic, not by a test. */
 int dinov2_hip_model_load(const char *gguf_path, const dinov2_hip_load_opts *opts, dinov2_hip_model **out,
                           char *err, size_t errlen);
 /* replaces the caller-side frees of inference.cpp:70-73 */

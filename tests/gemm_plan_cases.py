@@ -12,13 +12,25 @@ SIDES = (224, 518)
 REGISTERS = (0, 4)
 
 
-def model_gemms(name, batch, side, registers):
-    """(epilogue, M, N, K) of every GEMM launch of one forward (csrc/model.cpp forward())."""
-    H, F, swiglu = MODELS[name]
-    P = (side // 14) ** 2
+def _geometry(model):
+    """(hidden, ffn, swiglu, patch) of a family name (MODELS) or of a synth config dict (tests/geometry_cases.py: any width, FFN and patch)."""
+    if isinstance(model, str):
+        return MODELS[model] + (14,)
+    return model["hidden"], model["ffn"], bool(model["swiglu"]), model["patch"]
+
+
+def _patches(side, patch):
+    h, w = (side, side) if isinstance(side, int) else side
+    return (h // patch) * (w // patch)
+
+
+def model_gemms(model, batch, side, registers):
+    """(epilogue, M, N, K) of every GEMM launch of one forward (csrc/model.cpp forward()); `side`: pixels, or (height, width)."""
+    H, F, swiglu, patch = _geometry(model)
+    P = _patches(side, patch)
     T = P + 1 + registers
     M = batch * T
-    out = [(EPI_PATCH, batch * P, H, 640), (EPI_QKV, M, 3 * H, H), (EPI_RESID, M, H, H), (EPI_RESID, M, H, F)]
+    out = [(EPI_PATCH, batch * P, H, (3 * patch * patch + 63) // 64 * 64), (EPI_QKV, M, 3 * H, H), (EPI_RESID, M, H, H), (EPI_RESID, M, H, F)]
     out.append((EPI_SWIGLU, M, 2 * F, H) if swiglu else (EPI_GELU, M, F, H))
     return out
 
@@ -158,9 +170,14 @@ COVERAGE_CASES = [
 EPI_RESID_LN, EPI_QKV_LN, EPI_GELU_LN, EPI_SWIGLU_LN = 6, 7, 8, 9
 
 
-def model_gemms_ln(name, batch, side, registers):
-    H, F, swiglu = MODELS[name]
-    T = (side // 14) ** 2 + 1 + registers
+def ln_fold_applies(hidden):
+    """csrc/load.cpp: the fold is taken where hidden % 128 == 0 and hidden / 64 <= LN_MAX_GROUPS = 24; elsewhere the LayerNorm launches stay."""
+    return hidden % 128 == 0 and hidden // 64 <= 24
+
+
+def model_gemms_ln(model, batch, side, registers):
+    H, F, swiglu, patch = _geometry(model)
+    T = _patches(side, patch) + 1 + registers
     M = batch * T
     return [(EPI_QKV_LN, M, 3 * H, H), (EPI_RESID_LN, M, H, H), (EPI_RESID_LN, M, H, F), (EPI_SWIGLU_LN, M, 2 * F, H) if swiglu else (EPI_GELU_LN, M, F, H)]
 
@@ -272,6 +289,78 @@ def cases_leaves(api, cases):
     return got
 
 
+# ---- the off-family geometries of tests/geometry_cases.py (any width = 64 * heads up to 2 048, any FFN width, patch sizes 8 .. 32) ----
+def geometry_problems(ln=False):
+    """(epilogue, M, N, K) of every GEMM the geometry sweep launches (tests/test_gpu_geometry.py): every "runs" row at its own batch and at
+    batch 1 (the image run alone); `ln`: the launches with ln_fold = 1, for the rows whose width takes the fold."""
+    from geometry_cases import RUNNING
+    out = set()
+    for g in RUNNING:
+        if ln and not ln_fold_applies(g["cfg"]["hidden"]):
+            continue
+        for batch in (g["batch"], 1):
+            out.update((model_gemms_ln if ln else model_gemms)(g["cfg"], batch, g["size"], g["registers"]))
+    return sorted(out)
+
+
+def geometry_reachable(api, ln=False, dtypes=(F16, BF16)):
+    """{(leaf, epilogue, dtype): (M, N, K) of the smallest problem of the sweep that reaches it}"""
+    found = {}
+    for epi, M, N, K in geometry_problems(ln):
+        for dt in dtypes:
+            for leaf in api.gemm_plan(dt, epi, M, N, K).split(";"):
+                key = (leaf, epi, dt)
+                if key not in found or M * N * K < found[key][0] * found[key][1] * found[key][2]:
+                    found[key] = (M, N, K)
+    return found
+
+
+def greedy_cases(api, need, have=()):
+    """One case per key of `need` that `have` lacks, smallest problems first (a split plan covers several leaves)."""
+    chosen, have = [], set(have)
+    for key, (M, N, K) in sorted(need.items(), key=lambda kv: (kv[1][0] * kv[1][1] * kv[1][2], kv[0])):
+        if key in have:
+            continue
+        case = (key[2], key[1], M, N, K)
+        chosen.append(case)
+        have |= cases_leaves(api, [case])
+    return chosen
+
+
+# One problem per (leaf, epilogue, dtype) that the geometry sweep reaches and COVERAGE_CASES / LN_COVERAGE_CASES do not launch, generated like
+# them (`python tests/gemm_plan_cases.py`); tests/test_geometry_probes.py holds the two lists complete and free of stale entries on the CPU,
+# tests/test_gpu_geometry.py runs them through the bit-equality bodies of test_gemm_plan_coverage_case_bits / test_ln_plan_coverage_case_bits.
+# What those bodies can show HERE is less than for the family's lists: an odd K / 64 or K < 256 sends the forced small-tile launch and the
+# 100-row launch to the same small<64x128,w4x2,st3,ks1> configuration, so for the cases under 100 rows they establish that a row's bits do not
+# depend on M, not that two kernels agree (only the 36 751-row GELU case compares two configurations).  The configuration's epilogues are
+# therefore also held to float64 (tests/test_gpu_geometry.py::test_ks1_configuration_against_float64).
+GEOMETRY_COVERAGE_CASES = [
+    (0, 2, 17, 64, 64),  # small<64x128,w4x2,st3,ks1>
+    (1, 2, 17, 64, 64),  # small<64x128,w4x2,st3,ks1>
+    (0, 3, 17, 64, 64),  # small<64x128,w4x2,st3,ks1>
+    (1, 3, 17, 64, 64),  # small<64x128,w4x2,st3,ks1>
+    (0, 1, 17, 192, 64),  # small<64x128,w4x2,st3,ks1>
+    (1, 1, 17, 192, 64),  # small<64x128,w4x2,st3,ks1>
+    (0, 0, 63, 320, 192),  # small<64x128,w4x2,st3,ks1>
+    (1, 0, 63, 320, 192),  # small<64x128,w4x2,st3,ks1>
+    (0, 4, 67, 1664, 320),  # small<64x128,w4x2,st3,ks1>
+    (1, 4, 67, 1664, 320),  # small<64x128,w4x2,st3,ks1>
+    (0, 3, 36751, 1280, 320),  # small<128x128,w2x2,st2,ks1>
+    (1, 3, 36751, 1280, 320),  # small<128x128,w2x2,st2,ks1>
+]
+
+GEOMETRY_LN_COVERAGE_CASES = [
+    (0, 6, 7, 128, 128),  # small<64x128,w4x2,st3,ks1>
+    (1, 6, 7, 128, 128),  # small<64x128,w4x2,st3,ks1>
+    (0, 8, 18, 64, 128),  # small<64x128,w4x2,st3,ks1>
+    (1, 8, 18, 64, 128),  # small<64x128,w4x2,st3,ks1>
+    (0, 7, 7, 384, 128),  # small<64x128,w4x2,st3,ks1>
+    (1, 7, 7, 384, 128),  # small<64x128,w4x2,st3,ks1>
+    (0, 6, 2827, 1280, 1280),  # gemm4_short<64>
+    (1, 6, 2827, 1280, 1280),  # gemm4_short<64>
+]
+
+
 if __name__ == "__main__":
     import os
     import sys
@@ -303,3 +392,8 @@ if __name__ == "__main__":
         have |= cases_leaves(api, [case])
     for c in chosen:
         print(f"    {c},  # {api.gemm_plan(*c)}")
+    for title, ln, base in (("GEOMETRY_COVERAGE_CASES", False, COVERAGE_CASES), ("GEOMETRY_LN_COVERAGE_CASES", True, LN_COVERAGE_CASES)):
+        need = geometry_reachable(api, ln)
+        print(f"# {title}: {len(need)} (leaf, epilogue, dtype) combinations reached by the geometry sweep")
+        for c in greedy_cases(api, need, cases_leaves(api, base)):
+            print(f"    {c},  # {api.gemm_plan(*c)}")

@@ -710,6 +710,13 @@ def test_gemm_plan_coverage_case_bits(api, case):
     BIT (a) over the whole output with the same problem forced onto the plain 128 x 128 / 64 x 128 small-tile kernel
     (dinov2_hip_op_set_tuning("gemm_tile", 128)), and (b) -- the rows repeat every 100 -- with a 100-row launch of the same rows (few-tile
     plans: 32 x 64 tiles), so that a token's bits depend neither on the plan nor on the batch it travels in."""
+    gemm_plan_case_bits(api, case)
+
+
+def gemm_plan_case_bits(api, case):
+    """The body of test_gemm_plan_coverage_case_bits, shared with tests/test_gpu_geometry.py (GEOMETRY_COVERAGE_CASES).  A problem of fewer than
+    100 rows (the off-family sweep has them) is the head of the 100-row launch instead: its rows must carry that launch's bits (where both
+    launches get the same configuration, as those cases do, this shows that a row's bits do not depend on M, nothing more)."""
     dt, epi, M, N, K = case
     rng = np.random.default_rng(M + 3 * N + 7 * K + 11 * epi + dt)
     Nout = N // 2 if epi == EPI_SWIGLU else N
@@ -727,8 +734,8 @@ def test_gemm_plan_coverage_case_bits(api, case):
         kw.update(P=P, T=T, R=R)
         auxv, ldo = pos, N
     else:
-        x0 = rng.standard_normal((100, Nout)).astype(np.float32) if epi == EPI_RESID else np.zeros((100, Nout), np.float32)
-        x0 = np.ascontiguousarray(np.tile(x0, ((M + 99) // 100, 1))[:M])
+        x100 = rng.standard_normal((100, Nout)).astype(np.float32) if epi == EPI_RESID else np.zeros((100, Nout), np.float32)
+        x0 = np.ascontiguousarray(np.tile(x100, ((M + 99) // 100, 1))[:M])
         auxv, ldo = (aux if epi == EPI_RESID else None), Nout
     plan = api.gemm_plan(dt, epi, M, N, K)
     out = x0.copy()
@@ -749,6 +756,14 @@ def test_gemm_plan_coverage_case_bits(api, case):
         assert np.array_equal(small, out[:100]), (plan, "rows 0..99")
         last = M - 100 - M % 100
         assert np.array_equal(small, out[last:last + 100]), (plan, "last whole copy of the rows")
+    elif epi != EPI_PATCH and M < 100:
+        whole = x100.copy()
+        _gemm(api, dt, epi, X, W, bias, auxv, whole, 100, N, K, ldo, **kw)
+        assert np.array_equal(whole[:M], out), (plan, api.gemm_plan(dt, epi, 100, N, K), "the rows inside a 100-row launch")
+    elif epi == EPI_PATCH and M < 100:  # the same image eight times over (another tile grid): every copy's token rows carry the single launch's bits
+        x8 = np.ascontiguousarray(np.tile(x0, (8, 1)))
+        _gemm(api, dt, epi, np.ascontiguousarray(np.tile(A, (8, 1))), W, bias, auxv, x8, 8 * M, N, K, ldo, **kw)
+        assert np.array_equal(x8, np.tile(out, (8, 1))), (plan, api.gemm_plan(dt, epi, 8 * M, N, K), "the image inside a batch of eight")
 
 
 @pytest.mark.parametrize("dt", [F16, BF16])
