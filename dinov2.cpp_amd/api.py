@@ -622,6 +622,7 @@ def lib():
     L.dinov2_hip_op_get_tuning.argtypes = [cp]
     L.dinov2_hip_op_gemm_plan.argtypes = [i32, i32, i32, i32, i32, C.c_char_p, i32]
     L.dinov2_hip_op_gemm_plan_parts.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64), i32]
+    L.dinov2_hip_op_stream_delay.argtypes = [vp, i32]
     _lib = L
     return L
 
@@ -845,6 +846,11 @@ class DeviceArray:
             cls._hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
             cls._hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
             cls._hip.hipSetDevice.argtypes = [C.c_int]
+            cls._hip.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
+            cls._hip.hipStreamDestroy.argtypes = [C.c_void_p]
+            cls._hip.hipStreamQuery.argtypes = [C.c_void_p]
+            cls._hip.hipStreamSynchronize.argtypes = [C.c_void_p]
+            cls._hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         return cls._hip
 
     def _select(self):
@@ -886,6 +892,68 @@ class DeviceArray:
     def __del__(self):
         try:
             self.free()
+        except Exception:
+            pass
+
+
+def stream_delay(stream, ms):
+    """Testing aid (dinov2_hip_op_stream_delay): one kernel on `stream` (a Stream or a raw hipStream_t) that keeps it busy for `ms`
+    milliseconds, 1 .. 100 -- a bounded wait, never a hang; returns at once.  ValueError for the null stream or ms out of range."""
+    h = int(getattr(stream, "handle", stream) or 0)
+    ms = int(ms)
+    rc = lib().dinov2_hip_op_stream_delay(C.c_void_p(h) if h else None, ms if -2**31 <= ms < 2**31 else 0)
+    if rc == 4:
+        raise ValueError(f"stream_delay: stream = {h:#x}, ms = {ms}: needs a stream of its own and 1 <= ms <= 100")
+    if rc != 0:
+        raise RuntimeError(f"dinov2_hip_op_stream_delay failed ({rc})")
+
+
+class Stream:
+    """A non-blocking HIP stream of the caller's, for hosts that have no torch in the process (Session(model, stream=s.handle)): created,
+    queried, synchronised and destroyed through the runtime handle DeviceArray holds, on HIP device `device`."""
+    NOT_READY = 600  # hipErrorNotReady
+
+    def __init__(self, device: int = 0, handle: int | None = None):
+        """handle: an existing hipStream_t to look at (Session.stream) instead of a new stream; it stays its owner's to destroy."""
+        self.device, self.handle, self.owned = int(device), int(handle or 0), handle is None
+        if not self.owned:
+            return
+        rt = DeviceArray._rt()
+        h = C.c_void_p()
+        if rt.hipSetDevice(self.device) != 0 or rt.hipStreamCreateWithFlags(C.byref(h), 1) != 0:  # hipStreamNonBlocking
+            raise RuntimeError("hipStreamCreateWithFlags failed")
+        self.handle = int(h.value)
+
+    def copy(self, dst, src, nbytes: int | None = None):
+        """Device-to-device copy on this stream; dst / src: DeviceArrays or raw device pointers (then `nbytes` is needed)."""
+        n = int(nbytes if nbytes is not None else min(getattr(dst, "nbytes", 1 << 62), getattr(src, "nbytes", 1 << 62)))
+        if DeviceArray._rt().hipMemcpyAsync(int(getattr(dst, "ptr", dst)), int(getattr(src, "ptr", src)), n, 3, self.handle) != 0:
+            raise RuntimeError("hipMemcpyAsync (device to device) failed")
+
+    def query(self) -> bool:
+        """True when everything queued on the stream has finished.  A "not ready" answer is cleared from the runtime's last-error slot,
+        so that the library's next launch check does not report it."""
+        rt = DeviceArray._rt()
+        rc = rt.hipStreamQuery(self.handle)
+        if rc == self.NOT_READY:
+            rt.hipGetLastError()
+            return False
+        if rc != 0:
+            raise RuntimeError(f"hipStreamQuery failed ({rc})")
+        return True
+
+    def synchronize(self):
+        if DeviceArray._rt().hipStreamSynchronize(self.handle) != 0:
+            raise RuntimeError("hipStreamSynchronize failed")
+
+    def destroy(self):
+        if self.handle and self.owned:
+            DeviceArray._rt().hipStreamDestroy(self.handle)
+        self.handle = 0
+
+    def __del__(self):
+        try:
+            self.destroy()
         except Exception:
             pass
 

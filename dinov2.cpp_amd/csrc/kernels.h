@@ -580,6 +580,10 @@ hipError_t gemm_clock_probe_read(unsigned long long* out);
 hipError_t gemm4_clock_probe_read(unsigned long long* out);
 hipError_t attention_clock_probe_read(unsigned long long* out);
 
+// testing aid (dinov2_hip_op_stream_delay): one wave that keeps `stream` busy for `milliseconds` of the 100 MHz wall clock, or for a fixed
+// number of polls if that comes first; touches no memory
+hipError_t launch_stream_delay(int milliseconds, hipStream_t stream);
+
 // debugging aid: what ds_read_b64_tr_b16 returns per lane for addr = lane*8 over an LDS image holding its own
 // element index (out: [64][4] int16)
 hipError_t launch_probe_tr16(int16_t* out, hipStream_t stream);

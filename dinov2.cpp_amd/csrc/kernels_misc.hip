@@ -813,4 +813,21 @@ hipError_t launch_pca_project(const float* tok, const float* mean, const float* 
     return hipGetLastError();
 }
 
+// A bounded stall of one stream, for the ordering tests (tests/stream_cases.py): one wave polls the 100 MHz wall clock, sleeping between
+// polls (s_sleep 127: 8 128 shader cycles, 3.4 us at 2.4 GHz), until `ticks` have passed or STREAM_DELAY_POLLS polls are done, whichever
+// comes first -- a stopped clock cannot keep it alive (65 536 polls: 0.22 s at 2.4 GHz, 0.5 s at 1 GHz).  Reads and writes no memory.
+constexpr int STREAM_DELAY_POLLS = 1 << 16;
+__global__ __launch_bounds__(64) void stream_delay_kernel(unsigned long long ticks) {
+    const unsigned long long t0 = wall_clock64();
+    for (int i = 0; i < STREAM_DELAY_POLLS; ++i) {
+        if (wall_clock64() - t0 >= ticks) break;
+        __builtin_amdgcn_s_sleep(127);
+    }
+}
+
+hipError_t launch_stream_delay(int milliseconds, hipStream_t st) {
+    hipLaunchKernelGGL(stream_delay_kernel, dim3(1), dim3(64), 0, st, (unsigned long long)milliseconds * 100000ull);
+    return hipGetLastError();
+}
+
 }  // namespace dinov2

@@ -951,6 +951,12 @@ extern "C" int dinov2_hip_op_pca_chol_rinv(const double* gram, double* rinv) {
     return DINOV2_HIP_OK;
 }
 
+// ---- a bounded stall of a caller's stream (tests/stream_cases.py): refusals first, before any HIP call ----
+extern "C" int dinov2_hip_op_stream_delay(void* stream, int32_t milliseconds) {
+    if (!stream || milliseconds < 1 || milliseconds > 100) return DINOV2_HIP_ERR_INVALID;
+    return launch_stream_delay(milliseconds, (hipStream_t)stream) == hipSuccess ? DINOV2_HIP_OK : DINOV2_HIP_ERR_HIP;
+}
+
 // ---- the kernels of csrc/dense.hip (dinov2_hip_predict_dense) on host data ----
 extern "C" int dinov2_hip_op_dense_reduce_plan(int32_t h0, int32_t w0, int32_t C, int32_t out_h, int32_t out_w, int64_t* out) {
     const DenseReducePlan p = dense_reduce_plan(h0, w0, C, out_h, out_w);

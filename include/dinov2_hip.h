@@ -94,7 +94,13 @@ typedef struct dinov2_hip_input {
                           its own non-blocking stream, which is not ordered after work the caller queued on another
                           stream (e.g. the kernel that produced the images) -- synchronise that stream first, or hand
                           the producer's stream to dinov2_hip_session_create.  Same for on_device outputs: read them
-                          after dinov2_hip_session_sync (or on the session's stream).                              */
+                          after dinov2_hip_session_sync (or on the session's stream).
+                          HOST inputs (on_device = 0) are read ON THE SESSION'S STREAM: when the call returns asynchronously
+                          -- out == NULL, or out->on_device = 1 -- the copy of `data` may still be in flight, and `data` must
+                          stay valid and unchanged until dinov2_hip_session_sync or until a later call on the session that
+                          returns host outputs.  That holds for pageable memory as well as for dinov2_hip_host_alloc
+                          buffers (the runtime usually has staged a pageable buffer by the time the call returns; nothing
+                          here promises it).  A call that returns host outputs has read its input when it returns.     */
 } dinov2_hip_input;
 
 /* Caller-allocated outputs; any pointer may be NULL.  Printing top-k stays in the caller. */
@@ -136,7 +142,18 @@ const char *dinov2_hip_model_label(const dinov2_hip_model *model, int32_t id);
 int dinov2_hip_model_arena(dinov2_hip_model *model, void **device_ptr, size_t *bytes);
 
 /* -- session (replaces ggml_gallocr_new / reuse across calls, inference.cpp:63, realtime.cpp:62) ---- */
-/* `stream`: a hipStream_t to run on, or NULL to let the session create its own. */
+/* `stream`: a hipStream_t to run on, or NULL to let the session create its own.
+ * Stream contract (held by tests/test_gpu_streams.py; every wait of the session code and what it protects: DESIGN.md section 10):
+ *   1. Everything a session launches or copies runs on its ONE stream, in call order: a caller's stream handed in here orders the session
+ *      behind the work queued on it before a call and ahead of the work queued after it; the stream stays the caller's, and usable, after
+ *      dinov2_hip_session_free.
+ *   2. A call whose outputs are all on the device (on_device = 1) or absent (out == NULL) is ASYNCHRONOUS in steady state: it returns once
+ *      its work is queued.  Steady state: the input shape, the list's sizes, the attention query list and the scratch sizes are those of
+ *      an earlier call; a call that sees one of them for the first time may wait for the stream (it restages or reallocates), and is right
+ *      either way.  Outputs of earlier asynchronous calls are never disturbed by later calls.
+ *   3. A call that returns HOST outputs returns after they are complete, whatever was queued on the stream before it.
+ *   4. Host INPUTS of a call that returns asynchronously: see dinov2_hip_input.on_device.
+ *   5. Sessions of one model on different streams share nothing mutable: neither waits for the other. */
 int dinov2_hip_session_create(dinov2_hip_model *model, void *stream, dinov2_hip_session **out, char *err,
                               size_t errlen);
 void dinov2_hip_session_free(dinov2_hip_session *session);
@@ -333,7 +350,9 @@ int dinov2_hip_group_wait(dinov2_hip_group *group, int64_t ticket, char *err, si
 
 /* Page-locked host memory for images / results handed to dinov2_hip_predict or dinov2_hip_group_predict: copies to and from
  * such buffers run at the full PCIe rate and truly asynchronously (pageable memory is staged through bounce buffers by the
- * runtime, at roughly half the rate).  Plain malloc'ed buffers remain valid inputs.  NULL on failure. */
+ * runtime, at roughly half the rate, and a copy into or out of it is usually finished when the copy call returns).  Plain malloc'ed
+ * buffers remain valid inputs.  With a page-locked INPUT an asynchronous call really returns while the copy is in flight: leave the buffer
+ * alone until dinov2_hip_session_sync (dinov2_hip_input.on_device).  NULL on failure. */
 void *dinov2_hip_host_alloc(size_t bytes);
 void dinov2_hip_host_free(void *ptr);
 

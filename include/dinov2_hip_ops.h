@@ -240,6 +240,13 @@ int dinov2_hip_op_dense_pack(const float *x, const float *ln_w, const float *ln_
                              int32_t norm, int32_t concat_cls, int32_t slot, int32_t nslots, float *out_f16_as_f32);
 int dinov2_hip_op_dense_reduce_plan(int32_t h0, int32_t w0, int32_t C, int32_t out_h, int32_t out_w, int64_t *out);
 
+/* A bounded stall for the stream-ordering tests (tests/stream_cases.py, DESIGN.md "Stream contract"): queues ONE kernel of one wave on
+ * `stream` (a hipStream_t) that polls the 100 MHz wall clock, sleeping between polls, and ends after `milliseconds` or after a fixed number
+ * of polls (65 536, a few hundred milliseconds), whichever comes first: a wait with an upper bound, never a hang.  It touches no memory.
+ * Work queued on the stream behind it starts when it ends; the call itself returns at once.  milliseconds outside 1 .. 100 and
+ * stream == NULL (the null stream would order every other stream behind the stall) return DINOV2_HIP_ERR_INVALID before any HIP call. */
+int dinov2_hip_op_stream_delay(void *stream, int32_t milliseconds);
+
 #ifdef __cplusplus
 }
 #endif
