@@ -41,7 +41,8 @@ class DinoError(RuntimeError):
 class LoadOpts(C.Structure):
     _fields_ = [("device", C.c_int32), ("compute_dtype", C.c_int32), ("classify", C.c_int32),
                 ("skip_tensor_data", C.c_int32), ("quirk_pool_const_divisor", C.c_int32),
-                ("quirk_pool_includes_registers", C.c_int32), ("batch_invariant", C.c_int32), ("ln_fold", C.c_int32), ("reserved", C.c_int32 * 8)]
+                ("quirk_pool_includes_registers", C.c_int32), ("batch_invariant", C.c_int32), ("ln_fold", C.c_int32), ("patch_stride", C.c_int32),
+                ("reserved", C.c_int32 * 7)]
 
 
 class HParams(C.Structure):
@@ -49,6 +50,7 @@ class HParams(C.Structure):
                                           "num_register_tokens", "patch_size", "img_size", "ftype")] + \
                [("eps", C.c_float)] + \
                [(n, C.c_uint32) for n in ("ffn_hidden", "swiglu", "has_classifier", "weight_type", "compute_dtype")]
+    patch_stride = 0  # not a field of the C struct: the stride the model was loaded with (Model and Group set it); 0 = patch_size
 
 
 class Input(C.Structure):
@@ -512,6 +514,8 @@ def lib():
     L.dinov2_hip_model_free.argtypes = [vp]
     L.dinov2_hip_model_free.restype = None
     L.dinov2_hip_model_hparams.argtypes = [vp, C.POINTER(HParams)]
+    L.dinov2_hip_model_patch_stride.argtypes = [vp]
+    L.dinov2_hip_model_grid.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), cp, sz]
     L.dinov2_hip_model_label.argtypes = [vp, i32]
     L.dinov2_hip_model_label.restype = cp
     L.dinov2_hip_model_arena.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
@@ -576,6 +580,7 @@ def lib():
     L.dinov2_hip_op_gemm_ln_consumer.argtypes = [i32, i32, fp, fp, fp, fp, fp, C.c_float, fp, i32, i32, i32, i32, i32, C.c_float]
     L.dinov2_hip_op_ln_prepare.argtypes = [i32, fp, fp, fp, fp, i32, i32]
     L.dinov2_hip_op_im2col.argtypes = [i32, fp, fp, i32, i32, i32, i32, i32, i32]
+    L.dinov2_hip_op_im2col_stride.argtypes = [i32, fp, fp, i32, i32, i32, i32, i32, i32, i32]
     L.dinov2_hip_op_ln_fold_vectors.argtypes = [i32, fp, fp, fp, fp, fp, fp, i32, i32]
     L.dinov2_hip_op_attention.argtypes = [i32, fp, fp, i32, i32, i32, i32]
     L.dinov2_hip_op_attention_ex.argtypes = [i32, fp, fp, i32, i32, i32, i32, i32]
@@ -694,8 +699,9 @@ class Model(_Handle):
 
     def __init__(self, path: str, *, device: int = 0, dtype: int = F16, classify: bool = True,
                  skip_tensor_data: bool = False, pool_const_divisor: bool = True, pool_includes_registers: bool = True,
-                 batch_invariant: bool = True, ln_fold: int = 0):
-        """ln_fold: 0 = the library's choice, 1 = LayerNorm folded into the neighbouring GEMMs, -1 = separate LayerNorm launches."""
+                 batch_invariant: bool = True, ln_fold: int = 0, patch_stride: int = 0):
+        """ln_fold: 0 = the library's choice, 1 = LayerNorm folded into the neighbouring GEMMs, -1 = separate LayerNorm launches.
+        patch_stride: pixels from one patch to the next, 0 = patch_size, else a divisor of it (overlapping patches: a denser token grid)."""
         L = lib()
         o = LoadOpts()
         L.dinov2_hip_default_load_opts(C.byref(o))
@@ -704,11 +710,13 @@ class Model(_Handle):
         o.quirk_pool_const_divisor, o.quirk_pool_includes_registers = int(pool_const_divisor), int(pool_includes_registers)
         o.batch_invariant = int(batch_invariant)
         o.ln_fold = int(ln_fold)
+        o.patch_stride = int(patch_stride)
         h = C.c_void_p()
         _call(L.dinov2_hip_model_load, path.encode(), C.byref(o), C.byref(h))
         self._h = h
         hp = HParams()
         L.dinov2_hip_model_hparams(h, C.byref(hp))
+        self.patch_stride = hp.patch_stride = int(L.dinov2_hip_model_patch_stride(h))  # resolved: never 0
         self.hparams = hp
         self.device = device
 
@@ -731,9 +739,15 @@ class Model(_Handle):
             raise DinoError(rc, "interpolate_pos_embed")
         return out
 
+    def grid(self, h, w) -> tuple[int, int]:
+        """(h0, w0): the patch grid of a NETWORK input size h x w (dinov2_hip_model_grid), or the refusal a predict of it would give."""
+        h0, w0 = C.c_int32(), C.c_int32()
+        _call(lib().dinov2_hip_model_grid, self._h, int(h), int(w), C.byref(h0), C.byref(w0))
+        return h0.value, w0.value
+
     def tokens(self, h, w):
-        p = self.hparams.patch_size
-        return 1 + self.hparams.num_register_tokens + (h // p) * (w // p)
+        h0, w0 = _grid_dims(self.hparams, h, w)
+        return 1 + self.hparams.num_register_tokens + h0 * w0
 
 
 def _images(images, layout, dtype=None):
@@ -749,10 +763,20 @@ def _images(images, layout, dtype=None):
     return img, img.shape[0], hh, ww
 
 
+def _grid_dims(hp, h, w):
+    """(h0, w0): the patch grid of a network input size h x w -- patches of hp.patch_size pixels every hp.patch_stride pixels (absent or 0:
+    the patch size).  THE definition on the Python side (csrc/kernels.h: grid_dim); nothing else here divides by the patch size for a grid
+    or a row count."""
+    p = hp.patch_size
+    s = getattr(hp, "patch_stride", 0) or p
+    return (0 if h < p else (h - p) // s + 1), (0 if w < p else (w - p) // s + 1)
+
+
 def _grid(hp, hh, ww, layout, classify):
     """(nh, nw, P): the network input size of an hh x ww image (raw 8-bit input: after the preprocessing) and its number of patches."""
     nh, nw = preprocess_size(1 if classify else 0, hh, ww, hp.patch_size) if layout == U8_BGR_HWC else (hh, ww)
-    return nh, nw, (nh // hp.patch_size) * (nw // hp.patch_size)
+    h0, w0 = _grid_dims(hp, nh, nw)
+    return nh, nw, h0 * w0
 
 
 def _device_output(cls_ptr, patch_ptr, logits_ptr, probs_ptr):
@@ -1049,11 +1073,12 @@ class Group(_Handle):
     _free = "dinov2_hip_group_free"
 
     def __init__(self, path: str, devices=None, *, dtype: int = F16, classify: bool = True, broadcast: bool = True,
-                 batch_invariant: bool = True, streams_per_device: int = 2):
+                 batch_invariant: bool = True, streams_per_device: int = 2, patch_stride: int = 0):
         L = lib()
         o = GroupOpts()
         L.dinov2_hip_default_group_opts(C.byref(o))
         o.load.compute_dtype, o.load.classify = dtype, int(classify)
+        o.load.patch_stride = int(patch_stride)
         o.load.batch_invariant = int(batch_invariant)
         o.broadcast = int(broadcast)
         o.streams_per_device = int(streams_per_device)
@@ -1066,6 +1091,7 @@ class Group(_Handle):
         self.size = int(L.dinov2_hip_group_size(h))
         self.hparams = HParams()
         L.dinov2_hip_model_hparams(L.dinov2_hip_group_model(h, 0), C.byref(self.hparams))
+        self.patch_stride = self.hparams.patch_stride = int(L.dinov2_hip_model_patch_stride(L.dinov2_hip_group_model(h, 0)))
         self.broadcast_ms = float(L.dinov2_hip_group_broadcast_ms(h))
         buf = C.create_string_buffer(8192)
         self.topology = buf.value.decode().splitlines() if L.dinov2_hip_group_describe(h, buf, len(buf)) == 0 else []
@@ -1181,9 +1207,9 @@ class Session(_Handle):
         hp = self.model.hparams
         out, o = _alloc_outputs(hp, B, hh, ww, layout, classify, topk, want)
         ids = self._layer_list(layers)
-        n, Hd, R, ps = len(ids), hp.hidden_size, hp.num_register_tokens, hp.patch_size
+        n, Hd, R = len(ids), hp.hidden_size, hp.num_register_tokens
         nh, nw, _ = _grid(hp, hh, ww, layout, classify)
-        h0, w0 = nh // ps, nw // ps
+        h0, w0 = _grid_dims(hp, nh, nw)
         arr = (C.c_int32 * max(n, 1))(*ids)
         patch = np.empty((n, B, Hd, h0, w0) if reshape else (n, B, h0 * w0, Hd), np.float32)
         cls = np.empty((n, B, Hd), np.float32) if return_class_token else None
@@ -1449,12 +1475,13 @@ class dino_model:  # dinov2.h:49-55
 
 
 def dino_model_load(img_size, fname: str, model: dino_model, params: dino_params, *, device: int = 0,
-                    dtype: int = F16) -> bool:
+                    dtype: int = F16, patch_stride: int = 0) -> bool:
     """dinov2.h:98-99.  `img_size` is unused, as in the reference (dinov2.cpp:309-324).  Returns False and prints to
-    stderr when the file cannot be opened (dinov2.cpp:269-272); other errors raise DinoError instead of asserting."""
+    stderr when the file cannot be opened (dinov2.cpp:269-272); other errors raise DinoError instead of asserting.
+    patch_stride (no field of the reference's dino_params): Model's option of that name."""
     import sys
     try:
-        model.handle = Model(fname, device=device, dtype=dtype, classify=params.classify)
+        model.handle = Model(fname, device=device, dtype=dtype, classify=params.classify, patch_stride=patch_stride)
     except DinoError as e:
         if e.status == 1:
             print(f"dino_model_load: failed to open '{fname}'", file=sys.stderr)

@@ -141,7 +141,7 @@ static int predict_tapped(dinov2_hip_session* s, const dinov2_hip_input* in, din
 
 extern "C" int dinov2_hip_predict_layers(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out,
                                          const dinov2_hip_layers* ly, uint32_t flags, char* err, size_t errlen) {
-    int rc = check_input(s, in, err, errlen);
+    int rc = check_input(s, in, flags, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
     rc = check_layers(s->model, ly, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
@@ -156,7 +156,7 @@ extern "C" int dinov2_hip_predict_layers(dinov2_hip_session* s, const dinov2_hip
 extern "C" int dinov2_hip_predict_attention(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out,
                                             const dinov2_hip_layers* taps, const dinov2_hip_attention* at, uint32_t flags, char* err,
                                             size_t errlen) {
-    int rc = check_input(s, in, err, errlen);
+    int rc = check_input(s, in, flags, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
     const dinov2_hip_model* m = s->model;
     const int L = (int)m->hp.num_hidden_layers;
@@ -213,7 +213,7 @@ extern "C" int dinov2_hip_predict_attention(dinov2_hip_session* s, const dinov2_
 extern "C" int dinov2_hip_predict_dense(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out,
                                         const dinov2_hip_dense_head* hd, const dinov2_hip_dense_out* o, uint32_t flags, char* err,
                                         size_t errlen) {
-    int rc = check_input(s, in, err, errlen);
+    int rc = check_input(s, in, flags, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
     const dinov2_hip_model* m = s->model;
     if (!hd || !o) {

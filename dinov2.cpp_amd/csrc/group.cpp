@@ -251,7 +251,9 @@ void run_job(dinov2_hip_group* g, int r, int l, int64_t k, const Job& job, int* 
     if (raw) dinov2_hip_preprocess_size(classify ? 1 : 0, in.height, in.width, (int32_t)hp.patch_size, &h, &w);
     const size_t in_stride = raw ? (size_t)in.height * in.width * 3 : (size_t)3 * h * w * sizeof(float);
     const size_t H = hp.hidden_size, C = hp.num_classes;
-    const size_t P = (size_t)(h / (int)hp.patch_size) * (w / (int)hp.patch_size);
+    int32_t gh = 0, gw = 0;  // (the submit has checked the input: the grid exists)
+    (void)dinov2_hip_model_grid(rk.model, h, w, &gh, &gw, nullptr, 0);
+    const size_t P = (size_t)gh * gw;
     const size_t tok_rows = P + (classify ? hp.num_register_tokens : 0);
     const size_t nbytes = (size_t)(hi - lo) * in_stride;
     const char* src = reinterpret_cast<const char*>(in.data) + (size_t)lo * in_stride;
@@ -575,7 +577,7 @@ static int group_submit_impl(dinov2_hip_group* g, const dinov2_hip_input* in, co
     {
         // layout / size checks BEFORE anything is queued: turnstile 0 sizes its host -> device copy from these fields, ahead of
         // dinov2_hip_predict's own checks
-        const int vrc = dinov2_check_input(g->ranks[0]->model, in, err, errlen);
+        const int vrc = dinov2_check_input_rows(g->ranks[0]->model, in, flags, err, errlen);
         if (vrc != DINOV2_HIP_OK) return vrc;
         if ((flags & DINOV2_HIP_CLASSIFY) && !g->ranks[0]->model->hp.has_classifier) {
             set_err(err, errlen, "classify requested but the model was loaded without a classifier head");

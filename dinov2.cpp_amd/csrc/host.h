@@ -31,12 +31,34 @@ struct Dims {
     int P, T, M;
 };
 
+// The patch grid of an image of network size h x w: THE definition on the host (kernels.h grid_dim: patches of patch_size pixels every
+// patch_stride pixels).  Nothing outside the kernels divides by the patch size for a grid or a row count.
+struct Grid {
+    int h0, w0;
+};
+inline Grid grid_of(const dinov2_hip_model* m, int h, int w) {
+    return Grid{grid_dim(h, (int)m->hp.patch_size, m->patch_stride), grid_dim(w, (int)m->hp.patch_size, m->patch_stride)};
+}
+
 inline Dims dims_of(const dinov2_hip_model* m, int B, int h, int w) {
     Dims d;
-    d.P = (h / (int)m->hp.patch_size) * (w / (int)m->hp.patch_size);
+    const Grid g = grid_of(m, h, w);
+    d.P = g.h0 * g.w0;
     d.T = 1 + (int)m->hp.num_register_tokens + d.P;
     d.M = B * d.T;
     return d;
+}
+
+// load.cpp: the widest activation row of a forward in elements (qkv, the FFN hidden layer or the im2col matrix), and one image of network
+// size h x w against the limit of a pass: token rows * widest_row * 2 bytes below 2^31 (model.h: dinov2_check_pass_rows words the refusal)
+size_t widest_row(const dinov2_hip_model* m);
+int check_rows_at(const dinov2_hip_model* m, int h, int w, char* err, size_t errlen);
+
+// The im2col of the patch embedding: the default stride keeps the launch it always had, a smaller one goes to the strided kernel
+inline hipError_t launch_patch_im2col(DType dt, const float* img, void* col, int B, int h, int w, int ps, int stride, int Kpad, int layout,
+                                      hipStream_t st) {
+    return stride == ps ? launch_im2col(dt, img, col, B, h, w, ps, Kpad, layout, st)
+                        : launch_im2col_stride(dt, img, col, B, h, w, ps, stride, Kpad, layout, st);
 }
 
 // Session scratch `buf`, at least `need` bytes: the one place that allocates it (model.cpp).  Returns at once when it is large enough; otherwise
@@ -63,9 +85,9 @@ void pca_ritz(const double* yprev, const double* ynext, const double* g_parts, i
 // interpolate_pos_embed of the reference (load.cpp).  pos: [1 + M*M, H]; out: [1 + h_new*w_new, H].
 void interpolate_pos_embed(const float* pos, int M, int H, int h_new, int w_new, float* out);
 
-// model.cpp, for extras.cpp: the argument checks of every predict (null session / dinov2_check_input; classify without a head, top-k on the
-// device), the network input size of `in` (raw 8-bit input: after the preprocessing), the passes themselves, and the copy-out of the last one.
-int check_input(const dinov2_hip_session* s, const dinov2_hip_input* in, char* err, size_t errlen);
+// model.cpp, for extras.cpp: the argument checks of every predict (null session / dinov2_check_input / dinov2_check_pass_rows; classify without
+// a head, top-k on the device), the network input size of `in` (raw 8-bit input: after the preprocessing), the passes themselves, and the copy-out of the last one.
+int check_input(const dinov2_hip_session* s, const dinov2_hip_input* in, uint32_t flags, char* err, size_t errlen);
 int check_predict_args(const dinov2_hip_model* m, const dinov2_hip_output* out, uint32_t flags, char* err, size_t errlen);
 void network_size(const dinov2_hip_model* m, const dinov2_hip_input* in, uint32_t flags, int* h, int* w);
 int predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out, uint32_t flags, const PassExtras& ex, char* err,

@@ -63,6 +63,36 @@ inline int im2col_max_patch() {
     while (im2col_patch_ok(p + 1, (3 * (p + 1) * (p + 1) + 63) / 64 * 64)) ++p;
     return p;
 }
+// ---- the patch grid of an image, stated once for the host and the kernels' launchers: patches of `patch` pixels every `stride` pixels
+// (dinov2_hip_load_opts.patch_stride; stride == patch: the reference's conv_2d_sk_p0).  The callers check px >= patch and
+// (px - patch) % stride == 0; with stride | patch every multiple of the patch size passes.
+inline int grid_dim(int px, int patch, int stride) { return px < patch ? 0 : (px - patch) / stride + 1; }
+// The strided im2col (launch_im2col_stride) stages the image strip under a run of patches of one grid row -- 3 patch image rows of
+// (np - 1) stride + patch pixels -- in LDS and gathers every col row from it.  A run is as many patches as a strip of IM2COL_CHUNK patch
+// widths covers (stride == patch: IM2COL_CHUNK patches; patch 14, stride 7: 19; stride 1: 127), so the strip, and the LDS it takes, do not
+// depend on the stride.
+inline int im2col_stride_run(int patch, int stride) { return (IM2COL_CHUNK - 1) * patch / stride + 1; }
+// elements from one strip row to the next in LDS: the strip's width up to an ODD number of dwords, so that the strip rows which the
+// consecutive 16-byte pieces of a col row walk (row k / patch, every `patch` elements a new one) start in different banks
+inline int im2col_stride_pitch(int patch, int stride) {
+    const int width = (im2col_stride_run(patch, stride) - 1) * stride + patch;
+    return (((width + 1) / 2) | 1) * 2;
+}
+// What the strided kernel takes: stride divides patch (the option's rule: the strip then starts on a stride boundary whatever the run, and
+// every multiple of the patch size is a valid input size); the strip fits the 64 KiB of LDS that need no attribute (the CU has 160 KiB; the
+// existing kernel stays under 64 as well); an interleaved strip row divides its element index by 3 through a multiplication that is exact
+// below 32 768; a col piece divides its first element index k < Kpad by the patch size through (k * magic) >> 20, which must be exact and
+// stay inside 32 bits.
+inline bool im2col_stride_ok(int patch, int stride, int Kpad) {
+    if (patch <= 0 || stride <= 0 || stride > patch || patch % stride != 0) return false;
+    if (3LL * IM2COL_CHUNK * patch >= 32768) return false;
+    if (Kpad % 8 != 0 || (long long)Kpad < 3LL * patch * patch || Kpad > (1 << 20)) return false;
+    if ((size_t)3 * patch * im2col_stride_pitch(patch, stride) * 2 > 64 * 1024) return false;
+    const unsigned long long mg = (1ull << 20) / (unsigned)patch + 1ull;
+    for (unsigned long long k = 0; k < (unsigned long long)Kpad; k += 8)
+        if (k * mg >= (1ull << 32) || ((k * mg) >> 20) != k / (unsigned)patch) return false;
+    return true;
+}
 
 struct GemmArgs {
     const void* A;      // [M, K]  T, row-major, K % 64 == 0
@@ -196,18 +226,18 @@ struct ListPlan {
     int64_t units;    // attention work items = sum ceil(T_i / 128) nh
     int32_t nruns;
 };
-// h[i], w[i]: NETWORK sizes in pixels (positive multiples of `patch`, the callers check).  items: [units], images: [n], runs: [<= n].
+// h[i], w[i]: NETWORK sizes in pixels (the callers check them against `patch` and `stride`: grid_dim).  items: [units], images: [n], runs: [<= n].
 // Table order: image-major, then head, then query block -- after xcd_remap over the table's length all query blocks of an (image, head) sit
 // on one XCD, except where the boundary between two XCD ranges falls inside one.  The images come in list order (LIST_ORDER_AS_GIVEN) or by
 // descending T, equal T in list order (LIST_ORDER_LONGEST_FIRST); the order changes no bit of any result.  The table holds row0 in 32 bits:
 // ask for it only where M < 2^31 (one pass is far below).
 enum ListOrder : int { LIST_ORDER_AS_GIVEN = 0, LIST_ORDER_LONGEST_FIRST = 1 };
-inline ListPlan list_plan(int n, const int32_t* h, const int32_t* w, int patch, int R, int nh, int order, ListImage* images, ListRun* runs,
-                          AttnItem* items) {
+inline ListPlan list_plan(int n, const int32_t* h, const int32_t* w, int patch, int stride, int R, int nh, int order, ListImage* images,
+                          ListRun* runs, AttnItem* items) {
     ListPlan p{};
     std::vector<std::pair<int32_t, int64_t>> seg(items ? (size_t)n : 0);  // (T, row0) per image, for the table
     for (int i = 0; i < n; ++i) {
-        const int h0 = h[i] / patch, w0 = w[i] / patch;
+        const int h0 = grid_dim(h[i], patch, stride), w0 = grid_dim(w[i], patch, stride);
         const int P = h0 * w0, T = 1 + R + P;
         if (images) images[i] = ListImage{p.M, T, P, h0, w0};
         if (items) seg[(size_t)i] = {T, p.M};
@@ -251,6 +281,10 @@ hipError_t launch_attn_rows_budget(DType dt, const void* qkv, int ld, float* out
 // patch vector order (c_rgb, ky, kx), zero padded to Kpad
 hipError_t launch_im2col(DType dt, const float* img, void* col, int B, int Hh, int Ww, int patch, int Kpad, int layout,
                          hipStream_t stream);
+// the same with patches every `stride` pixels (dinov2_hip_load_opts.patch_stride): col [B * h0 * w0, Kpad], h0 = grid_dim(Hh, patch, stride),
+// row = (b h0 + y) w0 + x, the same patch vector order, padding and single rounding.  im2col_stride_ok(patch, stride, Kpad), Hh, Ww >= patch.
+hipError_t launch_im2col_stride(DType dt, const float* img, void* col, int B, int Hh, int Ww, int patch, int stride, int Kpad, int layout,
+                                hipStream_t stream);
 // dino_preprocess / dino_classify_preprocess on the device: u8 BGR [B,h,w,3] -> normalised f32 BGR [B,oh,ow,3]
 // (bicubic to rh x rw, crop at (y0, x0))
 hipError_t launch_preprocess_u8(const uint8_t* src, float* dst, int B, int h, int w, int rh, int rw, int y0, int x0, int oh,

@@ -389,6 +389,97 @@ hipError_t launch_im2col(DType dt, const float* img, void* col, int B, int Hh, i
     return hipGetLastError();
 }
 
+// The same with patches every `stride` pixels, stride | ps (dinov2_hip_load_opts.patch_stride): neighbouring patches share ps - stride
+// columns and rows.  One workgroup per (image, grid row, run of <= im2col_stride_run patches).  It reads the ps image rows under its run
+// ONCE, as im2col_kernel reads them (one contiguous run per wave and step: coalesced), and keeps them in LDS as the converted strip
+// [3 ps strip rows (c_rgb, ky)][(np - 1) stride + ps pixels]; every col row is then gathered from the strip, so the horizontal overlap
+// costs LDS reads, not global ones.  What is read again: the <= ps - stride columns two neighbouring runs share, and the ps - stride image
+// rows a grid row shares with the next -- out of L2 (a 518 x 518 f32 image is 3.2 MB).
+// The output leaves as whole 16-byte pieces of whole col rows: a lane builds the piece k0 .. k0 + 7 of patch pl from eight two-byte LDS
+// reads at strip[(k / ps) pitch + pl stride + k % ps], consecutive lanes take consecutive pieces of one row.  Those walk the strip rows
+// (a new one every ps elements); `pitch` is an odd number of dwords (im2col_stride_pitch), so the rows that the 32 lanes of a group
+// touch start in different banks.  One division per piece, k0 / ps by multiplication (im2col_stride_ok checks its range).
+template <typename T>
+__global__ __launch_bounds__(1024) void im2col_stride_kernel(const float* __restrict__ img, T* __restrict__ col, int B, int Hh, int Ww, int ps,
+                                                            int stride, int Kpad, int layout, int nrunx, int runp, int pitch) {
+    extern __shared__ __attribute__((aligned(16))) char im2col_lds[];
+    T* const strip = (T*)im2col_lds;  // [3 ps][pitch]
+    const int w0 = (Ww - ps) / stride + 1, h0 = (Hh - ps) / stride + 1;
+    const int ck = blockIdx.x % nrunx, py = (blockIdx.x / nrunx) % h0, b = blockIdx.x / (nrunx * h0);
+    const int px0 = ck * runp, np = min(runp, w0 - px0);
+    const int Kreal = 3 * ps * ps, width = (np - 1) * stride + ps;
+    const int tid = threadIdx.x, nth = blockDim.x;
+    const int nrun = layout == 1 ? 3 * ps : ps, rlen = layout == 1 ? width : 3 * width;
+    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), nwv = nth >> 6;
+    constexpr int U = 5;
+    for (int rr = wv; rr < nrun; rr += nwv) {
+        const int c0 = layout == 1 ? rr / ps : 0, ky = layout == 1 ? rr - c0 * ps : rr;
+        const size_t y = (size_t)py * stride + ky, x = (size_t)px0 * stride;
+        const float* src = layout == 1 ? img + (((size_t)b * 3 + c0) * Hh + y) * Ww + x : img + (((size_t)b * Hh + y) * Ww + x) * 3;
+        T* const srow = strip + (c0 * ps + ky) * pitch;
+        for (int e0 = lane; e0 < rlen; e0 += 64 * U) {
+            float v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (e0 + 64 * u < rlen) v[u] = src[e0 + 64 * u];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int e = e0 + 64 * u;
+                if (e < rlen) {
+                    int xo = e, cc = 0;
+                    if (layout != 1) {
+                        xo = (int)(((unsigned)e * 21846u) >> 16);  // e / 3 (exact below 32 768)
+                        cc = (2 - (e - 3 * xo)) * ps * pitch;      // position 0 / 1 / 2 = B / G / R -> RGB index 2 / 1 / 0
+                    }
+                    srow[cc + xo] = (T)v[u];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int cpr = Kpad >> 3;  // 16-byte pieces per row
+    const unsigned magic = (1u << 20) / (unsigned)ps + 1u;
+    T* const dst = col + ((size_t)b * h0 * w0 + (size_t)py * w0 + px0) * Kpad;  // the run's rows are consecutive in col
+    for (int pl = wv; pl < np; pl += nwv) {
+        const T* const sp = strip + pl * stride;
+        for (int j = lane; j < cpr; j += 64) {
+            const int k0 = j << 3;
+            int r = (int)(((unsigned)k0 * magic) >> 20), kx = k0 - r * ps;
+            typedef T t8 __attribute__((ext_vector_type(8)));
+            t8 pk;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                pk[t] = k0 + t < Kreal ? sp[r * pitch + kx] : (T)0.f;
+                if (++kx == ps) {
+                    kx = 0;
+                    ++r;
+                }
+            }
+            *(t8*)(dst + (size_t)pl * Kpad + k0) = pk;
+        }
+    }
+}
+
+hipError_t launch_im2col_stride(DType dt, const float* img, void* col, int B, int Hh, int Ww, int patch, int stride, int Kpad, int layout,
+                                hipStream_t st) {
+    if (!im2col_stride_ok(patch, stride, Kpad)) return hipErrorInvalidValue;  // (kernels.h: the strip's LDS, the two divisions by multiplication)
+    if (Hh < patch || Ww < patch || B <= 0) return hipErrorInvalidValue;
+    const int w0 = grid_dim(Ww, patch, stride), h0 = grid_dim(Hh, patch, stride);
+    const int runp = im2col_stride_run(patch, stride), pitch = im2col_stride_pitch(patch, stride);
+    const int nrunx = (w0 + runp - 1) / runp;
+    const size_t lds = (size_t)3 * patch * pitch * 2;
+    const size_t nwg = (size_t)B * h0 * nrunx;
+    if (nwg > 0x7fffffffu) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)nwg), block(nwg >= 1024 ? 256 : 1024);  // as launch_im2col: few workgroups, many waves each
+    if (dt == DT_F16)
+        hipLaunchKernelGGL(im2col_stride_kernel<_Float16>, grid, block, lds, st, img, (_Float16*)col, B, Hh, Ww, patch, stride, Kpad, layout, nrunx,
+                           runp, pitch);
+    else
+        hipLaunchKernelGGL(im2col_stride_kernel<__bf16>, grid, block, lds, st, img, (__bf16*)col, B, Hh, Ww, patch, stride, Kpad, layout, nrunx, runp,
+                           pitch);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // dino_preprocess / dino_classify_preprocess on the device (/root/reference/dinov2.cpp:106-156), same arithmetic as
 // csrc/preprocess.cpp: u8 BGR [B,h,w,3] -> /255 -> bicubic (cv::INTER_CUBIC: A = -0.75, half-pixel centres, clamped

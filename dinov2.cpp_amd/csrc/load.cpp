@@ -123,6 +123,7 @@ extern "C" void dinov2_hip_default_load_opts(dinov2_hip_load_opts* o) {
     o->quirk_pool_includes_registers = 1;
     o->batch_invariant = 1;
     o->ln_fold = 0;
+    o->patch_stride = 0;
 }
 
 extern "C" int dinov2_hip_abi_version(void) { return DINOV2_HIP_ABI_VERSION; }
@@ -217,6 +218,20 @@ extern "C" int dinov2_hip_model_load(const char* path, const dinov2_hip_load_opt
     if (!im2col_patch_ok(ps, (int)align_up((size_t)3 * ps * ps, 64))) {
         set_err(err, errlen, "unsupported patch_size %d: the patch-embedding im2col takes patch sizes up to %d", ps, im2col_max_patch());
         return DINOV2_HIP_ERR_UNSUPPORTED;
+    }
+    {
+        // patch_stride: 0 = the patch size.  A divisor of it keeps every multiple of the patch size a valid network size (so the preprocessing
+        // needs no change) and lets the strided kernel think in stride x stride cells.
+        const int st = opts.patch_stride == 0 ? ps : opts.patch_stride;
+        if (st < 1 || st > ps || ps % st != 0) {
+            set_err(err, errlen, "unsupported patch_stride %d: it must divide patch_size %d (0 = the patch size)", opts.patch_stride, ps);
+            return DINOV2_HIP_ERR_UNSUPPORTED;
+        }
+        if (st != ps && !im2col_stride_ok(ps, st, (int)align_up((size_t)3 * ps * ps, 64))) {
+            set_err(err, errlen, "unsupported patch_size %d with patch_stride %d: outside the limits of the strided im2col (im2col_stride_ok)", ps, st);
+            return DINOV2_HIP_ERR_UNSUPPORTED;
+        }
+        m->patch_stride = st;
     }
     const int Mgrid = (int)(hp.img_size / hp.patch_size);
 
@@ -425,6 +440,52 @@ extern "C" void dinov2_hip_model_free(dinov2_hip_model* m) {
 extern "C" int dinov2_hip_model_hparams(const dinov2_hip_model* m, dinov2_hip_hparams* out) {
     if (!m || !out) return DINOV2_HIP_ERR_INVALID;
     *out = m->hp;
+    return DINOV2_HIP_OK;
+}
+
+// ---- what one pass of the forward takes of ONE image (model.h: dinov2_check_pass_rows) ----
+size_t dinov2::widest_row(const dinov2_hip_model* m) {
+    return std::max<size_t>({3 * (size_t)m->hp.hidden_size, (size_t)m->hp.ffn_hidden, (size_t)m->kpe_pad});
+}
+
+int dinov2::check_rows_at(const dinov2_hip_model* m, int h, int w, char* err, size_t errlen) {
+    const Grid g = grid_of(m, h, w);
+    const int64_t T = 1 + (int64_t)m->hp.num_register_tokens + (int64_t)g.h0 * g.w0, widest = (int64_t)widest_row(m);
+    if (T * widest * 2 >= ((int64_t)1 << 31)) {
+        set_err(err, errlen, "an image of %d x %d has too many token rows for one pass (%lld at patch_size %d, patch_stride %d; rows * %lld * 2 must "
+                "stay below 2^31, the 32-bit activation offsets of dinov2_hip_predict's passes).  An image is refused, not split",
+                h, w, (long long)T, (int)m->hp.patch_size, m->patch_stride, (long long)widest);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    return DINOV2_HIP_OK;
+}
+
+int dinov2_check_pass_rows(const dinov2_hip_model* m, const dinov2_hip_input* in, uint32_t flags, char* err, size_t errlen) {
+    int h, w;
+    network_size(m, in, flags, &h, &w);
+    return check_rows_at(m, h, w, err, errlen);
+}
+
+int dinov2_check_input_rows(const dinov2_hip_model* m, const dinov2_hip_input* in, uint32_t flags, char* err, size_t errlen) {
+    const int rc = dinov2_check_input(m, in, err, errlen);
+    return rc != DINOV2_HIP_OK ? rc : dinov2_check_pass_rows(m, in, flags, err, errlen);
+}
+
+extern "C" int dinov2_hip_model_patch_stride(const dinov2_hip_model* m) { return m ? m->patch_stride : 0; }
+
+extern "C" int dinov2_hip_model_grid(const dinov2_hip_model* m, int32_t h, int32_t w, int32_t* h0, int32_t* w0, char* err, size_t errlen) {
+    if (!m || !h0 || !w0) {
+        set_err(err, errlen, "null model / h0 / w0");
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    dinov2_hip_input in{};
+    in.data = reinterpret_cast<const float*>(m);  // (never dereferenced: the checks below read the sizes only)
+    in.batch = 1; in.height = h; in.width = w; in.layout = DINOV2_HIP_RGB_CHW;
+    const int rc = dinov2_check_input_rows(m, &in, 0, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    const Grid g = grid_of(m, h, w);
+    *h0 = g.h0;
+    *w0 = g.w0;
     return DINOV2_HIP_OK;
 }
 

@@ -23,7 +23,7 @@ int dinov2_check_input(const dinov2_hip_model* m, const dinov2_hip_input* in, ch
         set_err(err, errlen, "null session / input");
         return DINOV2_HIP_ERR_INVALID;
     }
-    const int ps = (int)m->hp.patch_size;
+    const int ps = (int)m->hp.patch_size, st = m->patch_stride;  // (st == ps: the sizes are the positive multiples of the patch size)
     if (in->layout == DINOV2_HIP_U8_BGR_HWC) {  // raw images: any size, preprocessed on the device
         if (in->batch <= 0 || in->height <= 0 || in->width <= 0) {
             set_err(err, errlen, "raw image input must have batch, height, width >= 1");
@@ -35,16 +35,16 @@ int dinov2_check_input(const dinov2_hip_model* m, const dinov2_hip_input* in, ch
         set_err(err, errlen, "unknown input layout %d", in->layout);
         return DINOV2_HIP_ERR_INVALID;
     }
-    if (in->batch <= 0 || in->height < ps || in->width < ps || in->height % ps || in->width % ps) {
-        set_err(err, errlen, "input must be batch >= 1 and height/width positive multiples of patch_size %d (got %d x %d x %d)",
-                ps, in->batch, in->height, in->width);
+    if (in->batch <= 0 || in->height < ps || in->width < ps || (in->height - ps) % st || (in->width - ps) % st) {
+        set_err(err, errlen, "input must be batch >= 1 and height/width = patch_size %d plus a multiple of patch_stride %d (got %d x %d x %d)",
+                ps, st, in->batch, in->height, in->width);
         return DINOV2_HIP_ERR_INVALID;
     }
     return DINOV2_HIP_OK;
 }
 
-int dinov2::check_input(const dinov2_hip_session* s, const dinov2_hip_input* in, char* err, size_t errlen) {
-    return dinov2_check_input(s ? s->model : nullptr, in, err, errlen);
+int dinov2::check_input(const dinov2_hip_session* s, const dinov2_hip_input* in, uint32_t flags, char* err, size_t errlen) {
+    return dinov2_check_input_rows(s ? s->model : nullptr, in, flags, err, errlen);
 }
 
 // dinov2_hip_predict's own argument checks; the calls that allocate or copy before they reach predict_impl make them first, too: nothing may run
@@ -192,11 +192,11 @@ int ensure_workspace_list(dinov2_hip_session* s, const ListPlan& lp, int n, char
 
 enum Kind : int {
     K_IM2COL = 0, K_INIT, K_PATCH_GEMM, K_LAYERNORM, K_QKV_GEMM, K_ATTENTION, K_OPROJ_GEMM, K_FC1_GEMM, K_FC2_GEMM,
-    K_FINAL_LN, K_HEAD, K_LAYER_TAP, K_COUNT
+    K_FINAL_LN, K_HEAD, K_LAYER_TAP, K_COUNT, K_IM2COL_STRIDE = K_COUNT, K_SLOTS  // (only the profile of a patch_stride model lists the last kind)
 };
-const char* const kKindNames[K_COUNT] = {"im2col", "init_tokens", "gemm_patch_embed", "layernorm", "gemm_qkv",
+const char* const kKindNames[K_SLOTS] = {"im2col", "init_tokens", "gemm_patch_embed", "layernorm", "gemm_qkv",
                                          "attention", "gemm_attn_out", "gemm_ffn_in", "gemm_ffn_out", "final_layernorm",
-                                         "head", "layer_tap"};
+                                         "head", "layer_tap", "im2col_stride"};
 
 struct Scope {  // optional per-launch event pair
     dinov2_hip_session* s;
@@ -227,8 +227,8 @@ struct Scope {  // optional per-launch event pair
 
 void drain_profile(dinov2_hip_session* s) {
     if (s->prof_ms.empty()) {
-        s->prof_ms.assign(K_COUNT, 0.0);
-        s->prof_n.assign(K_COUNT, 0);
+        s->prof_ms.assign(K_SLOTS, 0.0);
+        s->prof_n.assign(K_SLOTS, 0);
     }
     for (auto& r : s->records) {
         (void)hipEventSynchronize(r.b);
@@ -248,8 +248,8 @@ void drain_profile(dinov2_hip_session* s) {
 // synchronisation: must run BEFORE a stream capture, never inside one.
 int prepare_pos(dinov2_hip_session* s, int B, int h, int w, char* err, size_t errlen) {
     const dinov2_hip_model* m = s->model;
-    const int H = (int)m->hp.hidden_size, ps = (int)m->hp.patch_size;
-    const int h0 = h / ps, w0 = w / ps;
+    const int H = (int)m->hp.hidden_size;
+    const int h0 = grid_of(m, h, w).h0, w0 = grid_of(m, h, w).w0;
     if (s->pos_h == h0 && s->pos_w == w0) return DINOV2_HIP_OK;
     const Dims d = dims_of(m, B, h, w);
     hipStream_t st = s->stream;
@@ -290,8 +290,8 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
     }
 
     {
-        Scope sc(s, K_IM2COL);
-        HIP_TRY(launch_im2col(dt, img, s->col, B, h, w, ps, m->kpe_pad, layout, st));
+        Scope sc(s, m->patch_stride == ps ? K_IM2COL : K_IM2COL_STRIDE);
+        HIP_TRY(launch_patch_im2col(dt, img, s->col, B, h, w, ps, m->patch_stride, m->kpe_pad, layout, st));
     }
     {
         Scope sc(s, K_INIT);
@@ -505,8 +505,8 @@ int forward_list(dinov2_hip_session* s, const std::vector<const float*>& imgs, c
         char* const col = (char*)s->col + patch0 * (size_t)m->kpe_pad * 2;
         float* const x = s->x + (size_t)g.row0 * H;
         {
-            Scope sc(s, K_IM2COL);
-            HIP_TRY(launch_im2col(dt, imgs[r], col, B, hs[i0], ws[i0], ps, m->kpe_pad, layout, st));
+            Scope sc(s, m->patch_stride == ps ? K_IM2COL : K_IM2COL_STRIDE);
+            HIP_TRY(launch_patch_im2col(dt, imgs[r], col, B, hs[i0], ws[i0], ps, m->patch_stride, m->kpe_pad, layout, st));
         }
         {
             Scope sc(s, K_INIT);
@@ -757,7 +757,7 @@ extern "C" void dinov2_hip_session_free(dinov2_hip_session* s) {
 }
 
 extern "C" size_t dinov2_hip_workspace_bytes(const dinov2_hip_model* m, int32_t batch, int32_t height, int32_t width) {
-    if (!m || batch <= 0 || height <= 0 || width <= 0) return 0;
+    if (!m || batch <= 0 || height <= 0 || width <= 0 || check_rows_at(m, height, width, nullptr, 0) != DINOV2_HIP_OK) return 0;
     return carve_of(m, batch, height, width).total;
 }
 
@@ -774,8 +774,8 @@ extern "C" int dinov2_hip_session_profile(dinov2_hip_session* s, int32_t enable)
     drain_profile(s);
     s->profiling = enable != 0;
     if (enable) {
-        s->prof_ms.assign(K_COUNT, 0.0);
-        s->prof_n.assign(K_COUNT, 0);
+        s->prof_ms.assign(K_SLOTS, 0.0);
+        s->prof_n.assign(K_SLOTS, 0);
     }
     return DINOV2_HIP_OK;
 }
@@ -785,7 +785,7 @@ extern "C" int dinov2_hip_session_profile_read(dinov2_hip_session* s, int32_t ma
     if (!s) return 0;
     (void)hipStreamSynchronize(s->stream);
     drain_profile(s);
-    const int n = std::min<int>(max, K_COUNT);
+    const int n = std::min<int>(max, s->model->patch_stride == (int)s->model->hp.patch_size ? K_COUNT : K_SLOTS);
     for (int i = 0; i < n; ++i) {
         if (names) names[i] = kKindNames[i];
         if (total_ms) total_ms[i] = (float)s->prof_ms[(size_t)i];
@@ -798,8 +798,8 @@ size_t dinov2_max_pass_batch(const dinov2_hip_model* m, int h, int w) {
     // The kernels address activations with 32-bit offsets (staging cursors of the GEMMs and of the attention): the widest
     // activation buffer of one forward must stay below 2^31 bytes (ViT-L @518: 190 images per pass).
     const Dims d1 = dims_of(m, 1, h, w);
-    const size_t widest = std::max<size_t>({3 * (size_t)m->hp.hidden_size, (size_t)m->hp.ffn_hidden, (size_t)m->kpe_pad});
-    size_t bmax = std::max<size_t>(1, ((size_t)1 << 31) / ((size_t)d1.T * widest * 2));
+    // (an image whose own rows pass the limit is refused by every entry point before it gets here: dinov2_check_pass_rows)
+    size_t bmax = std::max<size_t>(1, ((size_t)1 << 31) / ((size_t)d1.T * widest_row(m) * 2));
     if (const char* e = getenv("DINOV2_HIP_MAX_CHUNK"))  // testing aid: force the split at small sizes
         if (atoi(e) > 0) bmax = std::min<size_t>(bmax, (size_t)atoi(e));
     return bmax;
@@ -814,7 +814,7 @@ static int dense_stage(dinov2_hip_session* s, const DenseRun& dr, int B, int h, 
     const dinov2_hip_model* m = s->model;
     const dinov2_hip_dense_head* hd = dr.head;
     const dinov2_hip_dense_out* o = dr.out;
-    const int ps = (int)m->hp.patch_size, h0 = h / ps, w0 = w / ps;
+    const int h0 = grid_of(m, h, w).h0, w0 = grid_of(m, h, w).w0;
     const size_t P = (size_t)h0 * w0, M = (size_t)B * P, K = (size_t)hd->K, C = (size_t)hd->C, cpad = (size_t)hd->cpad;
     hipStream_t st = s->stream;
     Scope sc(s, K_HEAD);
@@ -846,7 +846,7 @@ static int dense_stage(dinov2_hip_session* s, const DenseRun& dr, int B, int h, 
 // of dinov2_hip_predict_dense (extras.cpp builds them); empty for a plain predict
 int dinov2::predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out, uint32_t flags, const PassExtras& ex,
                          char* err, size_t errlen) {
-    int rc = check_input(s, in, err, errlen);
+    int rc = check_input(s, in, flags, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
     const dinov2_hip_model* m = s->model;
     rc = check_predict_args(m, out, flags, err, errlen);
@@ -972,7 +972,7 @@ int check_list(const dinov2_hip_model* m, const dinov2_hip_image_list* l, uint32
     hs.resize((size_t)l->n);
     ws.resize((size_t)l->n);
     // one pass, as dinov2_max_pass_batch has it for a uniform batch: the widest activation buffer stays below 2^31 bytes
-    const int64_t widest = (int64_t)std::max<size_t>({3 * (size_t)m->hp.hidden_size, (size_t)m->hp.ffn_hidden, (size_t)m->kpe_pad});
+    const int64_t widest = (int64_t)widest_row(m);
     int64_t M = 0;
     int first_over = -1;
     for (int i = 0; i < l->n; ++i) {
@@ -1041,10 +1041,10 @@ extern "C" int dinov2_hip_predict_list(dinov2_hip_session* s, const dinov2_hip_i
 
     std::vector<ListImage> im((size_t)n);
     std::vector<ListRun> runs((size_t)n);
-    ListPlan lp = list_plan(n, hs.data(), ws.data(), (int)m->hp.patch_size, R, nh, list_table_order(), im.data(), runs.data(), nullptr);
+    ListPlan lp = list_plan(n, hs.data(), ws.data(), (int)m->hp.patch_size, m->patch_stride, R, nh, list_table_order(), im.data(), runs.data(), nullptr);
     runs.resize((size_t)lp.nruns);
     std::vector<AttnItem> items((size_t)lp.units);
-    lp = list_plan(n, hs.data(), ws.data(), (int)m->hp.patch_size, R, nh, list_table_order(), nullptr, nullptr, items.data());
+    lp = list_plan(n, hs.data(), ws.data(), (int)m->hp.patch_size, m->patch_stride, R, nh, list_table_order(), nullptr, nullptr, items.data());
 
     rc = ensure_workspace_list(s, lp, n, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
@@ -1151,7 +1151,7 @@ extern "C" int dinov2_hip_fetch(dinov2_hip_session* s, dinov2_hip_output* out, c
 
 extern "C" int dinov2_hip_debug_hidden(dinov2_hip_session* s, const dinov2_hip_input* in, int32_t layer, float* out,
                                        char* err, size_t errlen) {
-    int rc = check_input(s, in, err, errlen);
+    int rc = check_input(s, in, 0, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
     const dinov2_hip_model* m = s->model;
     if (!out || layer < 0 || layer > (int)m->hp.num_hidden_layers) {

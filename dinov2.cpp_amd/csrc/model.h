@@ -122,6 +122,7 @@ struct dinov2_hip_model {
     bool quirk_const_div = true, quirk_pool_regs = true;
     bool ln_fold = false;      // LayerNorm 1 / 2 of every layer folded into the neighbouring GEMM epilogues (dinov2_hip_load_opts.ln_fold)
     int kpe = 0, kpe_pad = 0;  // patch-embed K (3*p*p) and its padding to a multiple of 64
+    int patch_stride = 0;      // pixels from one patch to the next (dinov2_hip_load_opts.patch_stride, resolved: a divisor of patch_size)
     char* arena = nullptr;     // ONE allocation, like model.buffer (dinov2.cpp:341)
     size_t arena_bytes = 0;
     std::vector<dinov2::LayerWeights> layers;
@@ -210,8 +211,13 @@ struct dinov2_hip_dense_head {
 };
 
 // Internal (not C-ABI) helpers shared by model.cpp and group.cpp (host.h has those of the other host files).
-// Argument checks of dinov2_hip_predict that need no session: layout, batch, height / width against the patch size.
+// Argument checks of dinov2_hip_predict that need no session: layout, batch, height / width against the patch size and stride.
 int dinov2_check_input(const dinov2_hip_model* m, const dinov2_hip_input* in, char* err, size_t errlen);
+// After it: ONE image of `in` (at its network size under `flags`) must fit a pass -- token rows * widest activation row * 2 bytes below 2^31,
+// the 32-bit staging cursors of the GEMMs and the attention.  dinov2_max_pass_batch only cuts a batch into images; an image is not cut.
+int dinov2_check_pass_rows(const dinov2_hip_model* m, const dinov2_hip_input* in, uint32_t flags, char* err, size_t errlen);
+// both, in that order: what every predict entry point checks of its input before anything is allocated or launched
+int dinov2_check_input_rows(const dinov2_hip_model* m, const dinov2_hip_input* in, uint32_t flags, char* err, size_t errlen);
 // Largest batch ONE pass of the forward takes at network input size h x w (32-bit activation offsets; DINOV2_HIP_MAX_CHUNK lowers it for
 // tests): dinov2_hip_predict cuts longer batches into passes and leaves nothing for dinov2_hip_fetch.
 size_t dinov2_max_pass_batch(const dinov2_hip_model* m, int h, int w);

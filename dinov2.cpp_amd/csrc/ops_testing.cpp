@@ -230,6 +230,19 @@ extern "C" int dinov2_hip_op_im2col(int32_t dtype, const float* img, float* col,
     return dC.fetch_as(dt, col);
 }
 
+extern "C" int dinov2_hip_op_im2col_stride(int32_t dtype, const float* img, float* col, int32_t B, int32_t Hh, int32_t Ww, int32_t patch,
+                                           int32_t stride, int32_t Kpad, int32_t layout) {
+    const DType dt = dtype_of(dtype);
+    if (B <= 0 || patch <= 0 || stride <= 0 || Hh < patch || Ww < patch || Kpad <= 0) return -1;
+    const size_t npix = (size_t)B * 3 * Hh * Ww, rows = (size_t)B * grid_dim(Hh, patch, stride) * grid_dim(Ww, patch, stride);
+    OpBuf dI, dC;
+    OP_TRY(dI.upload(img, sizeof(float) * npix));
+    OP_TRY(dC.alloc(rows * (size_t)Kpad, 2, OpBuf::nans()));  // every element must be written
+    OP_TRY(launch_im2col_stride(dt, dI.as<float>(), dC.p, B, Hh, Ww, patch, stride, Kpad, layout, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    return dC.fetch_as(dt, col);
+}
+
 extern "C" int dinov2_hip_op_ln_fold_vectors(int32_t dtype, const float* W, const float* bias, const float* gamma, const float* beta, float* s_out,
                                              float* c_out, int32_t N, int32_t K) {
     const DType dt = dtype_of(dtype);
@@ -272,7 +285,7 @@ extern "C" int dinov2_hip_op_list_plan(int32_t n, const int32_t* h, const int32_
         if (h[i] < 0 || w[i] < 0) return DINOV2_HIP_ERR_INVALID;
     std::vector<ListImage> im((size_t)n);
     std::vector<ListRun> rn((size_t)n);
-    const ListPlan p = list_plan(n, h, w, patch, R, nh, order, im.data(), rn.data(), nullptr);
+    const ListPlan p = list_plan(n, h, w, patch, patch, R, nh, order, im.data(), rn.data(), nullptr);
     totals[0] = p.M; totals[1] = p.P; totals[2] = p.pixels; totals[3] = p.units; totals[4] = p.nruns;
     if (p.M > (int64_t)INT32_MAX) return DINOV2_HIP_ERR_INVALID;  // (the table holds row0 in 32 bits)
     for (int i = 0; images && i < n; ++i) {
@@ -286,7 +299,7 @@ extern "C" int dinov2_hip_op_list_plan(int32_t n, const int32_t* h, const int32_
     if (items) {
         if (cap_items < p.units) return DINOV2_HIP_ERR_INVALID;
         static_assert(sizeof(AttnItem) == 4 * sizeof(int32_t), "an item is four int32: row0, T, head, query block");
-        (void)list_plan(n, h, w, patch, R, nh, order, nullptr, nullptr, reinterpret_cast<AttnItem*>(items));
+        (void)list_plan(n, h, w, patch, patch, R, nh, order, nullptr, nullptr, reinterpret_cast<AttnItem*>(items));
     }
     return DINOV2_HIP_OK;
 }
@@ -302,10 +315,10 @@ extern "C" int dinov2_hip_op_attention_list(int32_t dtype, const float* qkv, flo
         hh[(size_t)i] = T[i] - 1;
     }
     const int order = tune_get(TUNE_LIST_ORDER) == 1 ? LIST_ORDER_LONGEST_FIRST : LIST_ORDER_AS_GIVEN;
-    ListPlan p = list_plan(n, hh.data(), ww.data(), 1, 0, nh, order, nullptr, nullptr, nullptr);
+    ListPlan p = list_plan(n, hh.data(), ww.data(), 1, 1, 0, nh, order, nullptr, nullptr, nullptr);
     if (p.M > (int64_t)INT32_MAX) return -1;
     std::vector<AttnItem> items((size_t)p.units);
-    p = list_plan(n, hh.data(), ww.data(), 1, 0, nh, order, nullptr, nullptr, items.data());
+    p = list_plan(n, hh.data(), ww.data(), 1, 1, 0, nh, order, nullptr, nullptr, items.data());
     OpBuf dQ, dI, dO;
     OP_TRY(dQ.upload_as(dt, qkv, (size_t)p.M * 3 * H));
     OP_TRY(dI.upload(items.data(), items.size() * sizeof(AttnItem)));

@@ -84,14 +84,19 @@ def _usage(prog, p):
     print(f"  -t N, --threads         number of threads to use during computation (default: {p.n_threads})", file=e)
     print(f"  -c, --classify          whether to classify the image or get backbone PCA features (default: {int(p.classify)})", file=e)
     print(f"  -fa, --flash_attn          whether to enable flash_attn, less accurate (default: {int(p.enable_flash_attn)})", file=e)
+    print("  --patch-stride N        pixels from one patch to the next, a divisor of the patch size: overlapping patches, a denser", file=e)
+    print("                          PCA picture (default: 0 = the patch size)", file=e)
     print("", file=e)
 
 
 def dino_params_parse(argv, p: api.dino_params) -> bool:
     i = 1
+    p.patch_stride = 0  # (this program's own: the reference's dino_params has no such field)
     while i < len(argv):
         a = argv[i]
-        if a in ("-s", "--seed"):
+        if a == "--patch-stride":
+            i += 1; p.patch_stride = int(argv[i])
+        elif a in ("-s", "--seed"):
             i += 1; p.seed = int(argv[i])
         elif a in ("-m", "--model"):
             i += 1; p.model = argv[i]
@@ -132,7 +137,7 @@ def main(argv=None) -> int:
     img = np.ascontiguousarray(rgb[:, :, ::-1])  # cv::imread gives BGR
     print(f"main: loaded image '{p.fname_inp}' ({img.shape[0]} x {img.shape[1]})", file=sys.stderr)
     model = api.dino_model()
-    if not api.dino_model_load(img.shape[:2], p.model, model, p):
+    if not api.dino_model_load(img.shape[:2], p.model, model, p, patch_stride=p.patch_stride):
         print(f"main: failed to load model from '{p.model}'", file=sys.stderr)
         return 1
     hp = model.hparams
@@ -153,7 +158,7 @@ def main(argv=None) -> int:
             if i >= 0:
                 print(f" > {model.id2label.get(int(i), str(int(i)))} : {pr:.2f}")
         return 0
-    rows, cols = oh // hp.patch_size, ow // hp.patch_size
+    rows, cols = model.handle.grid(oh, ow)
     vis = pca_visual(hp.hidden_size, rows, cols, oh, ow, session=sess)
     try:
         Image.fromarray(np.ascontiguousarray(vis[:, :, ::-1])).save(p.image_out)  # stored BGR like the cv::Mat -> RGB file

@@ -68,7 +68,15 @@ typedef struct dinov2_hip_load_opts {
                         f16(LN(x)) exactly where ggml does.  On: the residual epilogues emit f16(gamma x) + row statistics and the QKV /
                         FFN-in epilogues apply mean, rstd and beta -- 2 of 7 launches per layer less; the activation is rounded BEFORE the
                         normalisation instead of after it (same 2^-11 relative rounding per element; parity numbers: profiles/r06_*).      */
-    int32_t reserved[8];
+    int32_t patch_stride; /* pixels from one patch to the next (took reserved[0]: size and ABI version unchanged).  0 = patch_size: the
+                        reference's non-overlapping patches, the same launches and bits as ever.  A smaller value s must DIVIDE patch_size
+                        (patch 14: 1, 2, 7) and gives overlapping patches, the dense grids of the "deep ViT features" line of work
+                        (stride 7 for patch 14): an image of h x w has h0 = (h - patch_size) / s + 1 rows of w0 = (w - patch_size) / s + 1
+                        patches, the position embedding is interpolated to (h0, w0), patch_tokens row = y * w0 + x; CLS, registers, head and
+                        the pooling quirks are untouched.  Inputs: h >= patch_size and (h - patch_size) % s == 0, likewise w -- every
+                        multiple of patch_size passes, so dinov2_hip_preprocess_size and raw 8-bit input work as they are.  The stride is the
+                        model's: one per load, not per call.  dinov2_hip_model_grid gives the grid of a size.          */
+    int32_t reserved[7];
 } dinov2_hip_load_opts;
 
 /* dino_hparams (dinov2.h:25-47) plus what the loader derives from the tensor list. */
@@ -86,7 +94,7 @@ typedef struct dinov2_hip_hparams {
 typedef struct dinov2_hip_input {
     const float *data; /* [batch] images, f32, already preprocessed (dino_preprocess output)               */
     int32_t batch;     /* the reference is batch 1 (dinov2.cpp:630); B images = B independent forwards     */
-    int32_t height;    /* multiples of patch_size, like img.size() in dinov2.cpp:908                       */
+    int32_t height;    /* multiples of patch_size, like img.size() in dinov2.cpp:908 (patch_stride: see there) */
     int32_t width;
     int32_t layout;    /* enum dinov2_hip_layout                                                           */
     int32_t on_device; /* 0: host memory (copied H2D each call); 1: device memory on the model's device.
@@ -123,6 +131,9 @@ void dinov2_hip_default_load_opts(dinov2_hip_load_opts *opts);
  *   hidden_size = 64 * num_attention_heads (head dim 64), at most 2 048 (32 heads): the LayerNorm kernels keep a row in one wave;
  *   FFN width a multiple of 64 (GELU: any such width; SwiGLU: the width of weights_out, its x1 | x2 rows interleaved in blocks of 32);
  *   patch_size 1 .. 32 (the im2col tile of ten patches of 3 p^2 elements, padded to a multiple of 64, must fit 64 KiB of LDS);
+ *   patch_stride 0 (= patch_size) or a divisor of patch_size; with a stride below the patch size the pair must also pass im2col_stride_ok
+ *   (csrc/kernels.h: the strided im2col keeps a strip of 3 p image rows of ten patch widths in at most 64 KiB of LDS) -- every divisor of
+ *   every patch size 1 .. 32 does;
  *   img_size >= patch_size; any number of layers, register tokens and classes; 2-D weights F32 / F16 / BF16 / Q4_0 / Q4_1 / Q5_0 /
  *   Q5_1 / Q8_0 (the patch-embedding kernel F32 / F16 / BF16), every other tensor F32.
  * ln_fold applies where hidden_size % 128 == 0 and hidden_size <= 1 536; elsewhere the model runs with separate LayerNorm launches.
@@ -135,6 +146,12 @@ int dinov2_hip_model_load(const char *gguf_path, const dinov2_hip_load_opts *opt
 void dinov2_hip_model_free(dinov2_hip_model *model);
 /* replaces reads of model.hparams (dinov2.cpp:276-299) */
 int dinov2_hip_model_hparams(const dinov2_hip_model *model, dinov2_hip_hparams *out);
+/* The resolved dinov2_hip_load_opts.patch_stride (never 0: patch_size where the option was 0). */
+int dinov2_hip_model_patch_stride(const dinov2_hip_model *model);
+/* The patch grid (h0 rows of w0 patches) of a NETWORK input size h x w, or the refusal a predict of such an image would give: a size that
+ * is not patch_size plus a multiple of the stride, or an image with too many token rows for one pass (rows * widest activation row * 2
+ * bytes must stay below 2^31; with stride 1 a 518 x 518 image has 255 030 rows, inside the limit for ViT-L, outside it for ViT-g). */
+int dinov2_hip_model_grid(const dinov2_hip_model *model, int32_t h, int32_t w, int32_t *h0, int32_t *w0, char *err, size_t errlen);
 /* replaces model.hparams.id2label.at(id) (dinov2.cpp:301-305, 972); NULL when out of range */
 const char *dinov2_hip_model_label(const dinov2_hip_model *model, int32_t id);
 /* The packed device weight arena (one allocation, like model.buffer of dinov2.cpp:341): lets a multi-GPU
@@ -157,7 +174,8 @@ int dinov2_hip_model_arena(dinov2_hip_model *model, void **device_ptr, size_t *b
 int dinov2_hip_session_create(dinov2_hip_model *model, void *stream, dinov2_hip_session **out, char *err,
                               size_t errlen);
 void dinov2_hip_session_free(dinov2_hip_session *session);
-/* Bytes of device workspace one predict of this shape needs (cf. ggml_gallocr_alloc_graph, dinov2.cpp:910). */
+/* Bytes of device workspace one predict of this shape needs (cf. ggml_gallocr_alloc_graph, dinov2.cpp:910); height / width: the NETWORK
+ * input size.  0 for an image with too many token rows for one pass, which every predict refuses (dinov2_hip_model_grid). */
 size_t dinov2_hip_workspace_bytes(const dinov2_hip_model *model, int32_t batch, int32_t height, int32_t width);
 /* Blocks until everything enqueued on the session's stream has finished (ggml_backend_synchronize,
  * inference.cpp:66). */

@@ -38,6 +38,10 @@ int dinov2_hip_op_gemm_ln_consumer(int32_t dtype, int32_t epilogue, const float 
 /* im2col of the patch embedding (ggml_conv_2d_sk_p0, /root/reference/dinov2.cpp:636): img f32, layout 1 = RGB planar [B,3,H,W], 0 = BGR interleaved
  * [B,H,W,3]; col [B * (H/patch) * (W/patch), Kpad] as f32 values of the compute type, k = c * patch^2 + ky * patch + kx, zero beyond 3 * patch^2 */
 int dinov2_hip_op_im2col(int32_t dtype, const float *img, float *col, int32_t B, int32_t Hh, int32_t Ww, int32_t patch, int32_t Kpad, int32_t layout);
+/* the same with patches every `stride` pixels (dinov2_hip_load_opts.patch_stride; csrc/kernels.h: im2col_stride_ok -- a pair outside it is refused):
+ * col [B * h0 * w0, Kpad], h0 = (H - patch) / stride + 1, w0 likewise, row = (b * h0 + y) * w0 + x */
+int dinov2_hip_op_im2col_stride(int32_t dtype, const float *img, float *col, int32_t B, int32_t Hh, int32_t Ww, int32_t patch, int32_t stride,
+                                int32_t Kpad, int32_t layout);
 int dinov2_hip_op_ln_prepare(int32_t dtype, const float *x, const float *gamma, float *xg, float *stats, int32_t rows, int32_t H);
 int dinov2_hip_op_ln_fold_vectors(int32_t dtype, const float *W, const float *bias, const float *gamma, const float *beta, float *s_out,
                                   float *c_out, int32_t N, int32_t K);
