@@ -126,6 +126,19 @@ class DenseOut(C.Structure):
                 ("on_device", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class Slide(C.Structure):
+    """dinov2_hip_slide (include/dinov2_hip.h)."""
+    _fields_ = [("crop_h", C.c_int32), ("crop_w", C.c_int32), ("stride_h", C.c_int32), ("stride_w", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+SLIDE_COVER_MAX = 16
+
+
+def _pair(v):
+    """(a, b) of a crop or stride given as one number or as (h, w)."""
+    return (int(v), int(v)) if isinstance(v, (int, np.integer)) else (int(v[0]), int(v[1]))
+
+
 DENSE_ARGMAX, DENSE_BINS = 0, 1
 _DENSE_REDUCE = {"argmax": DENSE_ARGMAX, "bins": DENSE_BINS}
 
@@ -406,6 +419,59 @@ def dense_reduce_plan(h0, w0, C_, out_h, out_w):
     return dict(zip(DENSE_PLAN_FIELDS, (int(v) for v in buf)))
 
 
+def _starts(y1, x1):
+    ys, xs = np.ascontiguousarray(y1, np.int32).ravel(), np.ascontiguousarray(x1, np.int32).ravel()
+    return ys, xs, ys.ctypes.data_as(C.POINTER(C.c_int32)), xs.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def op_slide_reduce(logits, h0, w0, crop, size, y1, x1, reduce="argmax", centers=None, eps=0.0, want=("labels", "value")):
+    """slide_reduce_kernel alone (dinov2_hip_op_slide_reduce): logits [len(y1) * len(x1), h0 * w0, C] of one image's windows (index order), crop
+    (crop_h, crop_w), size (h, w) -> dict of labels [h, w] uint8 (argmax only) and value [h, w] f32.  Raises on refused arguments, a HIP error
+    or a changed guard band."""
+    lg = _f32(logits)
+    ys, xs, yp, xp = _starts(y1, x1)
+    if lg.ndim != 3 or lg.shape[0] != len(ys) * len(xs) or lg.shape[1] != h0 * w0:
+        raise ValueError("op_slide_reduce: logits must be [ny * nx, h0 * w0, C]")
+    (ch, cw), (h, w) = _pair(crop), _pair(size)
+    red = _DENSE_REDUCE[reduce]
+    out = {}
+    if red == DENSE_ARGMAX and "labels" in want:
+        out["labels"] = np.empty((h, w), np.uint8)
+    if "value" in want:
+        out["value"] = np.empty((h, w), np.float32)
+    _op_rc(lib().dinov2_hip_op_slide_reduce(_ptr(lg), int(h0), int(w0), lg.shape[2], ch, cw, h, w, yp, len(ys), xp, len(xs), red,
+                                            _ptr(_f32(centers)), float(eps), _ptr(out.get("labels")), _ptr(out.get("value"))), "slide_reduce")
+    return out
+
+
+def op_slide_gather(image, crop, y1, x1, layout=RGB_CHW):
+    """slide_gather_kernel alone (dinov2_hip_op_slide_gather): image [3, h, w] (RGB_CHW) or [h, w, 3] f32 -> the window batch
+    [len(y1) * len(x1), 3, crop_h, crop_w] or [.., crop_h, crop_w, 3].  Raises on refused arguments, a HIP error or a changed guard band."""
+    img = _f32(image)
+    if img.ndim != 3 or (img.shape[0] if layout == RGB_CHW else img.shape[2]) != 3:
+        raise ValueError("op_slide_gather: image must be [3, h, w] (RGB_CHW) or [h, w, 3]")
+    h, w = (img.shape[1], img.shape[2]) if layout == RGB_CHW else (img.shape[0], img.shape[1])
+    ys, xs, yp, xp = _starts(y1, x1)
+    ch, cw = _pair(crop)
+    out = np.empty((len(ys) * len(xs),) + ((3, ch, cw) if layout == RGB_CHW else (ch, cw, 3)), np.float32)
+    _op_rc(lib().dinov2_hip_op_slide_gather(_ptr(img), int(layout), h, w, ch, cw, yp, len(ys), xp, len(xs), _ptr(out)), "slide_gather")
+    return out
+
+
+SLIDE_PLAN_FIELDS = ("tile_y", "tile_x", "slots_y", "slots_x", "span_y", "span_x", "chunk", "pitch", "lds_bytes", "cover")
+
+
+def op_slide_reduce_plan(h0, w0, C_, crop, size, y1, x1):
+    """slide_reduce_plan (csrc/kernels.h) as a dict; no device.  ValueError for refused arguments (sizes out of range, starts that do not
+    tile the image, a cover above SLIDE_COVER_MAX)."""
+    ys, xs, yp, xp = _starts(y1, x1)
+    (ch, cw), (h, w) = _pair(crop), _pair(size)
+    buf = (C.c_int64 * 10)()
+    if lib().dinov2_hip_op_slide_reduce_plan(int(h0), int(w0), int(C_), ch, cw, h, w, yp, len(ys), xp, len(xs), buf) != 0:
+        raise ValueError(f"slide_reduce_plan: {(h0, w0, C_, ch, cw, h, w)} with starts {ys.tolist()} x {xs.tolist()} refused")
+    return dict(zip(SLIDE_PLAN_FIELDS, (int(v) for v in buf)))
+
+
 def fold_batchnorm(weight, bias, gamma, beta, mean, var, eps=1e-5):
     """The BatchNorm in front of a linear head folded into it (float64 arithmetic, float32 results): s = gamma / sqrt(var + eps),
     W' = W diag(s), b' = b + W (beta - mean * s).  weight [C, K]; bias [C] or None; the four BatchNorm vectors [K]."""
@@ -614,6 +680,11 @@ def lib():
     L.dinov2_hip_op_dense_reduce.argtypes = [fp, i32, i32, i32, i32, i32, i32, fp, C.c_float, C.POINTER(C.c_uint8), fp]
     L.dinov2_hip_op_dense_pack.argtypes = [fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32, fp]
     L.dinov2_hip_op_dense_reduce_plan.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64)]
+    L.dinov2_hip_slide_windows.argtypes = [vp, i32, i32, C.POINTER(Slide), ip, ip, ip, ip, cp, sz]
+    L.dinov2_hip_predict_dense_slide.argtypes = [vp, C.POINTER(Input), vp, C.POINTER(Slide), C.POINTER(DenseOut), cp, sz]
+    L.dinov2_hip_op_slide_reduce.argtypes = [fp, i32, i32, i32, i32, i32, i32, i32, ip, i32, ip, i32, i32, fp, C.c_float, C.POINTER(C.c_uint8), fp]
+    L.dinov2_hip_op_slide_gather.argtypes = [fp, i32, i32, i32, i32, i32, ip, i32, ip, i32, fp]
+    L.dinov2_hip_op_slide_reduce_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, ip, i32, ip, i32, C.POINTER(C.c_int64)]
     L.dinov2_hip_op_bank_bench.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, fp]
     L.dinov2_hip_op_clock_probe.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.dinov2_hip_op_clock_slots.argtypes = [C.POINTER(C.c_uint64)]
@@ -744,6 +815,18 @@ class Model(_Handle):
         h0, w0 = C.c_int32(), C.c_int32()
         _call(lib().dinov2_hip_model_grid, self._h, int(h), int(w), C.byref(h0), C.byref(w0))
         return h0.value, w0.value
+
+    def slide_windows(self, h, w, crop, stride):
+        """(y1, x1): the window starts of sliding-window inference over an h x w image (dinov2_hip_slide_windows; no device), int32 arrays;
+        window k = iy * len(x1) + ix.  crop and stride: one number or (h, w).  Raises the refusal predict_dense_slide would give."""
+        (ch, cw), (sh, sw) = _pair(crop), _pair(stride)
+        sl = Slide(ch, cw, sh, sw)
+        ny, nx = C.c_int32(), C.c_int32()
+        y1, x1 = np.zeros(8192, np.int32), np.zeros(8192, np.int32)
+        ip = C.POINTER(C.c_int32)
+        _call(lib().dinov2_hip_slide_windows, self._h, int(h), int(w), C.byref(sl), C.byref(ny), C.byref(nx), y1.ctypes.data_as(ip),
+              x1.ctypes.data_as(ip))
+        return y1[:ny.value].copy(), x1[:nx.value].copy()
 
     def tokens(self, h, w):
         h0, w0 = _grid_dims(self.hparams, h, w)
@@ -1276,6 +1359,41 @@ class Session(_Handle):
         do = DenseOut(oh, ow, labels_ptr or None, value_ptr or None, logits_ptr or None, 1)
         i = Input(img_ptr, B, hh, ww, layout, 1)
         _call(lib().dinov2_hip_predict_dense, self._h, C.byref(i), None, head._h, C.byref(do), CLASSIFY if classify else 0)
+
+    def predict_dense_slide(self, images: np.ndarray, head: "DenseHead", crop, stride, want=("labels", "value", "logits"), *,
+                            layout: int = RGB_CHW) -> dict:
+        """Sliding-window inference with a linear dense head (dinov2_hip_predict_dense_slide) over images [B, 3, h, w] larger than the crop:
+        dict of "labels" [B, h, w] uint8 (argmax heads), "value" [B, h, w] f32 and "logits" [B, windows, P, C] f32 (the low-resolution
+        logits per window), whichever of `want` the head has.  crop and stride: one number or (h, w)."""
+        img, B, hh, ww = _images(images, layout)
+        (ch, cw), (sh, sw) = _pair(crop), _pair(stride)
+        y1, x1 = self.model.slide_windows(hh, ww, (ch, cw), (sh, sw))
+        h0, w0 = _grid_dims(self.model.hparams, ch, cw)
+        res = {}
+        if "labels" in want and head.reduce == "argmax":
+            res["labels"] = np.empty((B, hh, ww), np.uint8)
+        if "value" in want:
+            res["value"] = np.empty((B, hh, ww), np.float32)
+        if "logits" in want:
+            res["logits"] = np.empty((B, len(y1) * len(x1), h0 * w0, head.num_classes), np.float32)
+        ptr = lambda k: res[k].ctypes.data if k in res else None
+        do = DenseOut(0, 0, ptr("labels"), ptr("value"), ptr("logits"), 0)
+        i = Input(img.ctypes.data, B, hh, ww, layout, 0)
+        sl = Slide(ch, cw, sh, sw)
+        _call(lib().dinov2_hip_predict_dense_slide, self._h, C.byref(i), head._h, C.byref(sl), C.byref(do))
+        self._last_rows = {}  # the session holds windows afterwards: nothing resident for a Bank to name
+        return res
+
+    def predict_dense_slide_device(self, img_ptr: int, B: int, hh: int, ww: int, head: "DenseHead", crop, stride, *, labels_ptr: int = 0,
+                                   value_ptr: int = 0, logits_ptr: int = 0, layout: int = RGB_CHW):
+        """Asynchronous predict_dense_slide on device-resident input and outputs (raw device pointers, the outputs 16-byte aligned): labels
+        [B, h, w] uint8, value [B, h, w] f32, logits [B, windows, P, C] f32, any of them 0."""
+        (ch, cw), (sh, sw) = _pair(crop), _pair(stride)
+        do = DenseOut(0, 0, labels_ptr or None, value_ptr or None, logits_ptr or None, 1)
+        i = Input(img_ptr, B, hh, ww, layout, 1)
+        sl = Slide(ch, cw, sh, sw)
+        _call(lib().dinov2_hip_predict_dense_slide, self._h, C.byref(i), head._h, C.byref(sl), C.byref(do))
+        self._last_rows = {}
 
     def _attention_request(self, layers, queries, keys):
         """(layer ids, their C array, query ids, their C array or None, keys value) of a dinov2_hip_attention."""

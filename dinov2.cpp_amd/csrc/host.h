@@ -93,5 +93,14 @@ void network_size(const dinov2_hip_model* m, const dinov2_hip_input* in, uint32_
 int predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out, uint32_t flags, const PassExtras& ex, char* err,
                  size_t errlen);
 int fetch_outputs(dinov2_hip_session* s, dinov2_hip_output* out, char* err, size_t errlen);
+// model.cpp, for slide.cpp: while it lives, what the session's stream runs is booked under the kind `kind` ("im2col", "head", ...) of
+// dinov2_hip_session_profile, as the forward's own launches are; nothing while the session is not profiling
+struct ProfileMark {
+    ProfileMark(dinov2_hip_session* s, const char* kind);
+    ~ProfileMark();
+    ProfileMark(const ProfileMark&) = delete;
+    ProfileMark& operator=(const ProfileMark&) = delete;
+    void* scope = nullptr;
+};
 
 }  // namespace dinov2

@@ -608,6 +608,131 @@ hipError_t launch_dense_pack(const float* x, const float* w, const float* b, flo
 hipError_t launch_dense_reduce(const float* logits, int ldl, int B, int h0, int w0, int C, int out_h, int out_w, int reduce, const float* centers,
                                float eps, uint8_t* labels, float* value, const DenseReducePlan& plan, hipStream_t stream);
 
+// Sliding-window dense inference (csrc/slide.hip; contract in include/dinov2_hip.h, dinov2_hip_predict_dense_slide): slide_gather_kernel copies
+// the windows out of the resident images into one window batch, the ordinary forward and head give every window's low-resolution logits,
+// slide_reduce_kernel averages, per output pixel and class, the resampled logits of the windows that cover the pixel and reduces over the classes.
+constexpr int SLIDE_COVER_MAX = 16, SLIDE_WINDOWS_MAX = 65535;
+// Contract 1, one axis (mmsegmentation's slide_inference): the number of windows and where window i starts.
+inline int slide_count(int len, int crop, int stride) {
+    const int t = len - crop + stride - 1;
+    return (t > 0 ? t : 0) / stride + 1;
+}
+inline int slide_start(int i, int len, int crop, int stride) {
+    long long e = (long long)i * stride + crop;
+    e = (e < len ? e : len) - crop;
+    return e > 0 ? (int)e : 0;
+}
+// Window starts of one axis that the kernels accept: ascending, inside the image, and leaving no pixel uncovered.
+inline bool slide_axis_valid(const int* st, int n, int crop, int len) {
+    if (!st || n < 1 || crop < 1 || crop > len || st[0] != 0 || st[n - 1] + crop != len) return false;
+    for (int i = 1; i < n; ++i)
+        if (st[i] < st[i - 1] || st[i] > st[i - 1] + crop) return false;
+    return true;
+}
+// the largest number of windows over one coordinate (valid starts); a pixel's cover is the product of its two axes'
+inline int slide_axis_cover(const int* st, int n, int crop) {
+    int best = 0;
+    for (int i = 0, j = 0; i < n; ++i) {  // (the busiest coordinate is some window's first)
+        while (st[j] + crop <= st[i]) ++j;
+        best = i - j + 1 > best ? i - j + 1 : best;
+    }
+    return best;
+}
+// One axis cut into tiles of `tile` coordinates: per tile the first window that touches it and how many do (ranges[2 t], ranges[2 t + 1]; may
+// be nullptr); over all tiles the largest such number (slots) and the most low-resolution rows one window has to stage for one tile (span):
+// from the i0 of the tile's first coordinate inside the window to the i1 of its last.  The kernel computes the same rows by the same calls.
+inline void slide_axis_tiles(const int* st, int n, int crop, int len, int n_in, float scale, int tile, int* ranges, int& slots, int& span) {
+    slots = span = 0;
+    for (int t = 0, p0 = 0, lo = 0; p0 < len; ++t, p0 += tile) {
+        const int p1 = (p0 + tile < len ? p0 + tile : len) - 1;
+        while (st[lo] + crop <= p0) ++lo;
+        int hi = lo;
+        while (hi + 1 < n && st[hi + 1] <= p1) ++hi;
+        if (ranges) {
+            ranges[2 * t] = lo;
+            ranges[2 * t + 1] = hi - lo + 1;
+        }
+        slots = hi - lo + 1 > slots ? hi - lo + 1 : slots;
+        for (int i = lo; i <= hi; ++i) {
+            const int d0 = p0 > st[i] ? p0 - st[i] : 0, d1 = p1 - st[i] < crop - 1 ? p1 - st[i] : crop - 1;
+            int a, b, u;
+            float lam;
+            dense_axis(scale, d0, n_in, a, u, lam);
+            dense_axis(scale, d1, n_in, u, b, lam);
+            span = b - a + 1 > span ? b - a + 1 : span;
+        }
+    }
+}
+// The launch geometry and LDS layout of slide_reduce_kernel, decided without the device.  A workgroup owns tile_y x tile_x output pixels (at
+// most 256: one per thread) in IMAGE coordinates; up to slots_y x slots_x windows touch a tile, each stages up to span_y x span_x rows of
+// `chunk` classes (a multiple of 4, pitch = dense_pitch(chunk)).  The classes go through LDS chunk by chunk when the rows of all C do not fit:
+// a pixel's running argmax or sums stay in registers across the chunks, so the orders of contract 3 and 4 do not depend on the chunking.
+// The largest tile of the list that holds all classes, or at least 32 of them per chunk, within DENSE_LDS_BUDGET; a 1 x 1 tile has at most
+// SLIDE_COVER_MAX slots of 2 x 2 rows of 4 classes, 1 KiB: some tile always fits.
+struct SlideReducePlan {
+    int tile_y, tile_x;  // 0, 0: refused arguments
+    int slots_y, slots_x, span_y, span_x;
+    int chunk, pitch;
+    int grid_x, grid_y;
+    int cover;  // windows over the busiest pixel
+    float scale_y, scale_x;
+    size_t lds_bytes;
+};
+inline size_t slide_lds_bytes(int ty, int tx, int sy, int sx, int ny, int nx, int pitch, int C) {
+    return (size_t)sy * sx * ny * nx * pitch * 4 + (size_t)(C + 3) / 4 * 16 + ((size_t)ty * sy + (size_t)tx * sx + sy + sx) * 16 +
+           ((size_t)ty * tx + 15) / 16 * 16;
+}
+// (h0, w0): the crop's patch grid; y1 [ny], x1 [nx]: valid starts of windows of crop_h x crop_w in an image of h x w
+inline SlideReducePlan slide_reduce_plan(int h0, int w0, int C, int crop_h, int crop_w, int h, int w, const int* y1, int ny, const int* x1, int nx) {
+    SlideReducePlan p{};
+    if (h0 < 1 || w0 < 1 || C < 1 || C > DENSE_C_MAX || h > DENSE_OUT_MAX || w > DENSE_OUT_MAX) return p;
+    if (!slide_axis_valid(y1, ny, crop_h, h) || !slide_axis_valid(x1, nx, crop_w, w)) return p;
+    const int cover = slide_axis_cover(y1, ny, crop_h) * slide_axis_cover(x1, nx, crop_w);
+    if (cover > SLIDE_COVER_MAX) return p;
+    static const int tiles[5][2] = {{16, 16}, {8, 8}, {4, 4}, {2, 2}, {1, 1}};
+    p.scale_y = (float)h0 / (float)crop_h;
+    p.scale_x = (float)w0 / (float)crop_w;
+    p.cover = cover;
+    const int C4 = (C + 3) / 4;
+    for (const auto& t : tiles) {
+        int sy, sx, ry, rx;
+        slide_axis_tiles(y1, ny, crop_h, h, h0, p.scale_y, t[0], nullptr, sy, ry);
+        slide_axis_tiles(x1, nx, crop_w, w, w0, p.scale_x, t[1], nullptr, sx, rx);
+        int q = C4;  // classes per chunk in units of 4: the most whose pitch fits
+        while (q > 1 && slide_lds_bytes(t[0], t[1], sy, sx, ry, rx, dense_pitch(4 * q), C) > DENSE_LDS_BUDGET) --q;
+        if (slide_lds_bytes(t[0], t[1], sy, sx, ry, rx, dense_pitch(4 * q), C) > DENSE_LDS_BUDGET) continue;
+        if (q < C4 && q < 8 && t[0] > 1) continue;
+        p.tile_y = t[0]; p.tile_x = t[1]; p.slots_y = sy; p.slots_x = sx; p.span_y = ry; p.span_x = rx;
+        p.chunk = 4 * q;
+        p.pitch = dense_pitch(4 * q);
+        p.lds_bytes = slide_lds_bytes(t[0], t[1], sy, sx, ry, rx, p.pitch, C);
+        p.grid_y = (h + t[0] - 1) / t[0];
+        p.grid_x = (w + t[1] - 1) / t[1];
+        break;
+    }
+    return p;
+}
+// The window table both kernels read, in ints: y1 [ny] | x1 [nx] | per tile row (first window row, how many) [grid_y][2] | the same per tile
+// column [grid_x][2].  slide_table_fill writes slide_table_ints(plan, ny, nx) of them.
+inline size_t slide_table_ints(const SlideReducePlan& p, int ny, int nx) { return (size_t)ny + nx + 2 * ((size_t)p.grid_y + p.grid_x); }
+inline void slide_table_fill(const SlideReducePlan& p, int h0, int w0, int crop_h, int crop_w, int h, int w, const int* y1, int ny, const int* x1,
+                             int nx, int* tab) {
+    for (int i = 0; i < ny; ++i) tab[i] = y1[i];
+    for (int i = 0; i < nx; ++i) tab[ny + i] = x1[i];
+    int slots, span;
+    slide_axis_tiles(y1, ny, crop_h, h, h0, p.scale_y, p.tile_y, tab + ny + nx, slots, span);
+    slide_axis_tiles(x1, nx, crop_w, w, w0, p.scale_x, p.tile_x, tab + ny + nx + 2 * p.grid_y, slots, span);
+}
+// img [B, 3, h, w] (layout 1, RGB_CHW) or [B, h, w, 3] (0, BGR_HWC) f32 DEVICE -> win [B ny nx, ...] the same layout at crop_h x crop_w, window
+// (b, iy, ix) at index (b ny + iy) nx + ix: a copy, bit for bit.  tab: DEVICE, starts with y1 [ny] | x1 [nx].  B ny nx <= 65 535.
+hipError_t launch_slide_gather(const float* img, float* win, const int* tab, int B, int h, int w, int ny, int nx, int crop_h, int crop_w, int layout,
+                               hipStream_t stream);
+// logits [B ny nx, h0 w0, ldl] f32 DEVICE (ldl >= C, any alignment of the rows) -> labels [B, h, w] u8 (ARGMAX only) and / or value [B, h, w] f32;
+// tab: the DEVICE copy of slide_table_fill's table for `plan` = slide_reduce_plan of this problem; centers [C] DEVICE (BINS).
+hipError_t launch_slide_reduce(const float* logits, int ldl, int B, int h0, int w0, int C, int crop_h, int crop_w, int h, int w, int ny, int nx,
+                               const int* tab, int reduce, const float* centers, float eps, uint8_t* labels, float* value, const SlideReducePlan& plan,
+                               hipStream_t stream);
+
 // clock probe (device_types.h): per translation unit, [CLK_SLOTS][4] = running sums of shader cycles and 100 MHz ticks of workgroup 0 over
 // all launches of each kernel kind on the current device, the 100 MHz end stamp of the last one, the launch count
 hipError_t gemm_clock_probe_read(unsigned long long* out);

@@ -1179,3 +1179,12 @@ extern "C" int dinov2_hip_debug_hidden(dinov2_hip_session* s, const dinov2_hip_i
     HIP_TRY(hipStreamSynchronize(s->stream));
     return DINOV2_HIP_OK;
 }
+
+// For the entry points outside this file that launch kernels of their own (slide.cpp): an event pair around them, booked under the kind of
+// that name in dinov2_hip_session_profile.  Nothing happens while the session is not profiling.
+dinov2::ProfileMark::ProfileMark(dinov2_hip_session* s, const char* kind) {
+    int k = 0;
+    while (k < K_COUNT && strcmp(kKindNames[k], kind) != 0) ++k;
+    if (k < K_COUNT) scope = new Scope(s, k);
+}
+dinov2::ProfileMark::~ProfileMark() { delete static_cast<Scope*>(scope); }

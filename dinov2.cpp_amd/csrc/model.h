@@ -109,6 +109,7 @@ enum Scratch : int {
     SCRATCH_LIST_POS,    // dinov2_hip_predict_list: the interpolated position embeddings of up to LIST_POS_GRIDS patch grids (list_pos: what it holds)
     SCRATCH_LIST_ITEMS,  // dinov2_hip_predict_list: the attention work table of the last list (list_items_host: what it holds)
     SCRATCH_KMEANS,      // dinov2_hip_kmeans_tokens (staged host rows, the f16 operands, the update's partials, the results)
+    SCRATCH_SLIDE,       // dinov2_hip_predict_dense_slide (a host input's images, the window table, the window batch, every window's logits, host outputs' staging)
     SCRATCH_COUNT
 };
 
@@ -169,6 +170,7 @@ struct dinov2_hip_session {
     size_t list_pos_used = 0;                      // floats of scratch[SCRATCH_LIST_POS] taken by list_pos
     std::vector<float> list_pos_stage;             // host side of the uploads (never rewritten while a copy from it may be in flight)
     std::vector<dinov2::AttnItem> list_items_host;  // what scratch[SCRATCH_LIST_ITEMS] holds
+    std::vector<int> slide_tab_host;                // the window table at the front of scratch[SCRATCH_SLIDE] (dinov2_hip_predict_dense_slide)
     // hipGraph cache (the "allocr reuse" of the reference taken one step further): a forward that repeats with the same
     // shape, input pointer and workspace is captured once and replayed; 178 launches become one graph launch
     struct GraphEntry {

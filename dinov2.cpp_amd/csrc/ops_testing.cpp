@@ -1019,3 +1019,53 @@ extern "C" int dinov2_hip_op_dense_pack(const float* x, const float* ln_w, const
     OP_TRY(hipDeviceSynchronize());
     return dA.fetch_as(DT_F16, out);
 }
+
+// ---- the kernels of csrc/slide.hip (dinov2_hip_predict_dense_slide) on host data ----
+extern "C" int dinov2_hip_op_slide_reduce_plan(int32_t h0, int32_t w0, int32_t C, int32_t crop_h, int32_t crop_w, int32_t h, int32_t w,
+                                               const int32_t* y1, int32_t ny, const int32_t* x1, int32_t nx, int64_t* out) {
+    const SlideReducePlan p = slide_reduce_plan(h0, w0, C, crop_h, crop_w, h, w, y1, ny, x1, nx);
+    if (!out || p.tile_y == 0) return DINOV2_HIP_ERR_INVALID;
+    const int64_t v[10] = {p.tile_y, p.tile_x, p.slots_y, p.slots_x, p.span_y, p.span_x, p.chunk, p.pitch, (int64_t)p.lds_bytes, p.cover};
+    std::copy(v, v + 10, out);
+    return 0;
+}
+extern "C" int dinov2_hip_op_slide_reduce(const float* logits, int32_t h0, int32_t w0, int32_t C, int32_t crop_h, int32_t crop_w, int32_t h, int32_t w,
+                                          const int32_t* y1, int32_t ny, const int32_t* x1, int32_t nx, int32_t reduce, const float* centers,
+                                          float eps, uint8_t* labels, float* value) {
+    const SlideReducePlan plan = slide_reduce_plan(h0, w0, C, crop_h, crop_w, h, w, y1, ny, x1, nx);
+    if (!logits || plan.tile_y == 0 || (int64_t)ny * nx > SLIDE_WINDOWS_MAX || (reduce != DENSE_ARGMAX && reduce != DENSE_BINS))
+        return DINOV2_HIP_ERR_INVALID;
+    if (reduce == DENSE_BINS ? (!centers || !(eps > 0.0f) || labels || !value) : (!labels && !value)) return DINOV2_HIP_ERR_INVALID;
+    const size_t rows = (size_t)ny * nx * h0 * w0, npx = (size_t)h * w;
+    std::vector<int> tab(slide_table_ints(plan, ny, nx));
+    slide_table_fill(plan, h0, w0, crop_h, crop_w, h, w, y1, ny, x1, nx, tab.data());
+    OpBuf dL, dT, dC, dLab, dVal;
+    OP_TRY(dL.upload(logits, rows * (size_t)C * 4));  // (rows of C floats back to back: no more than a float's alignment, as in the session)
+    OP_TRY(dT.upload(tab.data(), tab.size() * sizeof(int)));
+    if (reduce == DENSE_BINS) OP_TRY(dC.upload(centers, (size_t)C * 4));
+    if (labels) OP_TRY(dLab.alloc(npx, 1, OpBuf::nans(), (size_t)w));
+    if (value) OP_TRY(dVal.alloc(npx, 4, OpBuf::nans(), (size_t)w));
+    OP_TRY(launch_slide_reduce(dL.as<float>(), C, 1, h0, w0, C, crop_h, crop_w, h, w, ny, nx, dT.as<int>(), reduce, dC.as<float>(), eps,
+                               dLab.as<uint8_t>(), dVal.as<float>(), plan, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    if (labels) OP_FETCH(dLab.fetch(labels));
+    if (value) OP_FETCH(dVal.fetch(value));
+    return 0;
+}
+extern "C" int dinov2_hip_op_slide_gather(const float* image, int32_t layout, int32_t h, int32_t w, int32_t crop_h, int32_t crop_w, const int32_t* y1,
+                                          int32_t ny, const int32_t* x1, int32_t nx, float* windows) {
+    if (!image || !windows || (layout != DINOV2_HIP_BGR_HWC && layout != DINOV2_HIP_RGB_CHW) || h > DENSE_OUT_MAX || w > DENSE_OUT_MAX)
+        return DINOV2_HIP_ERR_INVALID;
+    if (!slide_axis_valid(y1, ny, crop_h, h) || !slide_axis_valid(x1, nx, crop_w, w) || (int64_t)ny * nx > SLIDE_WINDOWS_MAX)
+        return DINOV2_HIP_ERR_INVALID;
+    std::vector<int> tab(y1, y1 + ny);
+    tab.insert(tab.end(), x1, x1 + nx);
+    OpBuf dI, dT, dW;
+    OP_TRY(dI.upload(image, (size_t)3 * h * w * 4));
+    OP_TRY(dT.upload(tab.data(), tab.size() * sizeof(int)));
+    OP_TRY(dW.alloc((size_t)ny * nx * 3 * crop_h * crop_w, 4, OpBuf::nans(), (size_t)crop_w * 3));
+    OP_TRY(launch_slide_gather(dI.as<float>(), dW.as<float>(), dT.as<int>(), 1, h, w, ny, nx, crop_h, crop_w, layout == DINOV2_HIP_RGB_CHW ? 1 : 0,
+                               nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    return dW.fetch(windows);
+}

@@ -603,8 +603,8 @@ int dinov2_hip_kmeans_tokens(dinov2_hip_session *s, const dinov2_hip_kmeans *km,
  *       that depends on C alone), uncontracted;  value = D / S with a correctly rounded division.
  *    6. Independence.  A pixel's result does not depend on launch geometry, on how out_h x out_w is tiled, or on the other images.
  *    Out of scope: the device group (dinov2_hip_group_*); dinov2_compat.hpp; C > 256; softmax probabilities; the final scalar resize of a
- *    depth map to the image size (upstream reduces over the bins at 4 h0 x 4 w0: pass that as out_h, out_w); multi-scale or sliding-window
- *    inference; reading head weights from GGUF or mmseg checkpoints; hidden sizes that are not a multiple of 64.
+ *    depth map to the image size (upstream reduces over the bins at 4 h0 x 4 w0: pass that as out_h, out_w); multi-scale
+ *    inference (sliding-window inference is dinov2_hip_predict_dense_slide, below); reading head weights from GGUF or mmseg checkpoints; hidden sizes that are not a multiple of 64.
  *    Times: profiles/dense_head.md. */
 enum dinov2_hip_dense_reduce { DINOV2_HIP_DENSE_ARGMAX = 0, DINOV2_HIP_DENSE_BINS = 1 };
 typedef struct dinov2_hip_dense_head dinov2_hip_dense_head;
@@ -652,6 +652,63 @@ typedef struct dinov2_hip_dense_out {
  * reduction under "head". */
 int dinov2_hip_predict_dense(dinov2_hip_session *session, const dinov2_hip_input *in, dinov2_hip_output *out /* may be NULL */,
                              const dinov2_hip_dense_head *head, const dinov2_hip_dense_out *dense, uint32_t flags, char *err, size_t errlen);
+
+/* -- sliding-window dense inference (no reference counterpart; mmsegmentation's slide_inference, test_cfg = dict(mode='slide', crop_size,
+ *    stride): how the published linear-head numbers are produced, and the way to label an image larger than the size the head was trained
+ *    at).  ONE call: the images are uploaded once, one kernel copies the windows into a window batch (csrc/slide.hip), the ordinary forward
+ *    and head give every window's low-resolution logits (split into passes as usual), and one kernel averages, per pixel and class, the
+ *    resampled logits of the windows that cover the pixel and reduces over the classes.  Neither the full-resolution logit planes nor the
+ *    windows' resamplings ever exist in memory.
+ *    Input: B f32 images of one size h x w, DINOV2_HIP_BGR_HWC or DINOV2_HIP_RGB_CHW, host or device; crop_h <= h <= 8192 and
+ *    crop_w <= w <= 8192; h and w need not be multiples of the patch size.  DINOV2_HIP_U8_BGR_HWC is refused (raw preprocessing resizes to a
+ *    network size, which is what sliding avoids).  Output: `dense` with out_h, out_w = 0, 0 (the image size); labels and value [B, h, w];
+ *    logits [B, ny nx, P, C], the low-resolution logits per window, image-major, windows in index order; any of the three may be NULL, not
+ *    all; on_device as for dinov2_hip_predict_dense.
+ *    Contract (continuing that of dinov2_hip_predict_dense, whose items 3 - 5 it refers to):
+ *    1. Windows.  Per axis (len = h or w, crop, stride):  n = max(len - crop + stride - 1, 0) / stride + 1  (integer division),
+ *       start_i = max(min(i * stride + crop, len) - crop, 0): the last window is pulled back to end at the image edge.  Window
+ *       k = iy * nx + ix covers rows [y1[iy], y1[iy] + crop_h) and columns [x1[ix], x1[ix] + crop_w).  dinov2_hip_slide_windows returns them.
+ *    2. Window logits.  Window k of image b has, bit for bit, the `logits` dinov2_hip_predict_dense returns for that crop alone (batch
+ *       invariance: the window batch goes through the ordinary forward, split into passes as usual).
+ *    3. Per pixel (Y, X) and class c, over the windows that cover the pixel in ascending k:  val_c^k = item 3 of dinov2_hip_predict_dense
+ *       with n_in = (h0, w0) of the crop's grid (dinov2_hip_model_grid), n_out = (crop_h, crop_w), dst = (Y - y1_k, X - x1_k);  acc_c starts as
+ *       the first covering window's val and adds the following ones one at a time in f32, in that order;  mean_c = acc_c / (float)n with n
+ *       the number of covering windows, a correctly rounded division.  Nothing is contracted into a fused multiply-add.
+ *    4. Reduction.  ARGMAX and BINS are applied to mean_c exactly as items 4 and 5 of dinov2_hip_predict_dense: ties go to the lowest
+ *       class, S and D are summed in ascending c.  The mean is taken BEFORE the argmax (upstream averages logits, then decides).
+ *    5. One window.  With h == crop_h and w == crop_w there is one window, n = 1, and labels and value have the bits of
+ *       dinov2_hip_predict_dense at out_h, out_w = 0, 0.
+ *    6. Independence.  A pixel's result does not depend on launch geometry, on the tiling or the staging of the classes, on the other images,
+ *       on the batch, or on how the windows were split into passes.
+ *    Out of scope: multi-scale and flip augmentation (they average softmax probabilities); a final resize of the map; images smaller than
+ *    the crop (dinov2_hip_predict_dense); raw 8-bit input; the classifier outputs of the window forwards; the device group;
+ *    dinov2_compat.hpp; lists of images of different sizes; graph capture.  Times: profiles/dense_slide.md. */
+#define DINOV2_HIP_SLIDE_COVER_MAX 16
+typedef struct dinov2_hip_slide {
+    int32_t crop_h, crop_w;      /* the window: a network input size of this model (dinov2_hip_model_grid accepts it) */
+    int32_t stride_h, stride_w;  /* 1 .. crop_h, 1 .. crop_w; any integer, no relation to the patch size needed    */
+    int32_t reserved[4];
+} dinov2_hip_slide;
+/* No device.  *ny, *nx and the window starts y1[ny], x1[nx] of contract 1 (either array may be NULL; 8192 entries always suffice); window
+ * k = iy * nx + ix.  Refuses (DINOV2_HIP_ERR_INVALID, naming the value): a NULL model, `sl`, ny or nx; a crop that dinov2_hip_model_grid
+ * refuses; a stride outside 1 .. crop; an image smaller than the crop or larger than 8192. */
+int dinov2_hip_slide_windows(const dinov2_hip_model *model, int32_t h, int32_t w, const dinov2_hip_slide *sl,
+                             int32_t *ny, int32_t *nx, int32_t *y1, int32_t *x1, char *err, size_t errlen);
+/* Argument errors (a NULL argument or input data; a batch below 1; raw 8-bit or unknown layout; the refusals of dinov2_hip_slide_windows;
+ * out_h, out_w other than 0, 0; `labels` from a BINS head; all outputs NULL; a device pointer that is not 16-byte aligned; the head / session
+ * mismatches of dinov2_hip_predict_dense; B ny nx > 65 535; a pixel covered by more than DINOV2_HIP_SLIDE_COVER_MAX windows -- per axis the
+ * cover is at most ceil(crop / stride) + 1, so stride >= crop / 3 always passes) return their status, naming the value, before anything is
+ * allocated, copied or launched, and leave the outputs untouched.  Afterwards the session has no last un-split forward, exactly as after
+ * dinov2_hip_predict_list: dinov2_hip_fetch, dinov2_hip_pca3(tokens = NULL), resident dinov2_hip_match_tokens and the bank's LAST_* sources
+ * are refused until the next dinov2_hip_predict, which gives the bits it gives in a fresh session.  Device input with device outputs is
+ * asynchronous on the session's stream in steady state; host outputs are complete on return (one stream wait at the end).  The call
+ * runs eagerly under DINOV2_HIP_GRAPHS=1.  The scratch (a host input's images, the window table, the window batch, the logits of all windows and
+ * host outputs' staging) is a session-owned buffer grown on demand, beside that of dinov2_hip_predict_dense for the window batch; an
+ * allocation the device refuses returns DINOV2_HIP_ERR_HIP.  In dinov2_hip_session_profile the window gather is booked under "im2col" (the
+ * kind of the input-side rearrangements; the raw 8-bit preprocessing launch is not booked at all) and the reduction under "head". */
+int dinov2_hip_predict_dense_slide(dinov2_hip_session *session, const dinov2_hip_input *in,
+                                   const dinov2_hip_dense_head *head, const dinov2_hip_slide *sl,
+                                   const dinov2_hip_dense_out *dense, char *err, size_t errlen);
 
 /* -- quantise a GGUF (replaces dino_model_quantize, dinov2.h:118 / dinov2.cpp:355-453).  Host only.
  *    itype: ggml type id 2 q4_0, 3 q4_1, 6 q5_0, 7 q5_1, 8 q8_0.  2-D tensors named `*weight` are re-encoded, the rest copied. */

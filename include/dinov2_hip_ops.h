@@ -6,7 +6,7 @@
  * kernel against the oracle in isolation -- the per-op granularity the reference gets from ggml's own op tests and
  * that /root/reference itself never had (it holds no tests at all).  All return 0 on success, -1 on a HIP error
  * (the entry points with guard bands -- attention_ex, layer_tap, attn_rows, pca_prepare / pca_cov / pca_power / pca_project, dense_reduce,
- * dense_pack, kmeans_assign / _update / kmeans -- also DINOV2_HIP_OP_GUARD_CHANGED).  Each family has its cases in tests/*_cases.py, CPU probes of those cases and a GPU file; for the
+ * dense_pack, slide_reduce, slide_gather, kmeans_assign / _update / kmeans -- also DINOV2_HIP_OP_GUARD_CHANGED).  Each family has its cases in tests/*_cases.py, CPU probes of those cases and a GPU file; for the
  * pca_* entry points: tests/pca_cases.py, tests/test_pca_probes.py, tests/test_gpu_pca_kernels.py.
  */
 #ifndef DINOV2_HIP_OPS_H
@@ -243,6 +243,25 @@ int dinov2_hip_op_dense_reduce(const float *logits, int32_t h0, int32_t w0, int3
 int dinov2_hip_op_dense_pack(const float *x, const float *ln_w, const float *ln_b, float eps, int32_t B, int32_t T, int32_t R, int32_t H,
                              int32_t norm, int32_t concat_cls, int32_t slot, int32_t nslots, float *out_f16_as_f32);
 int dinov2_hip_op_dense_reduce_plan(int32_t h0, int32_t w0, int32_t C, int32_t out_h, int32_t out_w, int64_t *out);
+
+/* the two kernels of csrc/slide.hip (behind dinov2_hip_predict_dense_slide) without a model or session; cases and the numpy restatement:
+ * tests/slide_cases.py.  y1 [ny], x1 [nx]: window starts -- ascending, inside the image, the first at 0, the last ending at the image edge, no
+ * gap between neighbours (what dinov2_hip_slide_windows gives); anything else is DINOV2_HIP_ERR_INVALID, as is a cover above 16.
+ * slide_reduce:  host logits [ny * nx, h0 * w0, C] f32 (one image's windows in index order, token-major) -> labels [h, w] u8 (ARGMAX only; NULL
+ *                otherwise) and / or value [h, w] f32, contracts 3 and 4 of dinov2_hip_predict_dense_slide.  reduce, centers, eps as for
+ *                dense_reduce.  Each device output is framed by guard bands of DINOV2_HIP_OP_GUARD_ROWS * w elements and starts as 0xff bytes; a
+ *                changed guard returns DINOV2_HIP_OP_GUARD_CHANGED.
+ * slide_gather:  host image [3, h, w] (layout DINOV2_HIP_RGB_CHW) or [h, w, 3] (DINOV2_HIP_BGR_HWC) f32 -> windows [ny * nx, ...] of crop_h x
+ *                crop_w in the same layout, framed and pre-filled the same way (guard row: crop_w * 3 elements).
+ * slide_reduce_plan (no device): out[0 .. 9] = tile_y, tile_x, slots_y, slots_x, span_y, span_x, classes per chunk, pitch, LDS bytes, cover of
+ *                slide_reduce_plan (csrc/kernels.h). */
+int dinov2_hip_op_slide_reduce(const float *logits, int32_t h0, int32_t w0, int32_t C, int32_t crop_h, int32_t crop_w, int32_t h, int32_t w,
+                               const int32_t *y1, int32_t ny, const int32_t *x1, int32_t nx, int32_t reduce, const float *centers, float eps,
+                               uint8_t *labels, float *value);
+int dinov2_hip_op_slide_gather(const float *image, int32_t layout, int32_t h, int32_t w, int32_t crop_h, int32_t crop_w, const int32_t *y1,
+                               int32_t ny, const int32_t *x1, int32_t nx, float *windows);
+int dinov2_hip_op_slide_reduce_plan(int32_t h0, int32_t w0, int32_t C, int32_t crop_h, int32_t crop_w, int32_t h, int32_t w, const int32_t *y1,
+                                    int32_t ny, const int32_t *x1, int32_t nx, int64_t *out);
 
 /* A bounded stall for the stream-ordering tests (tests/stream_cases.py, DESIGN.md "Stream contract"): queues ONE kernel of one wave on
  * `stream` (a hipStream_t) that polls the 100 MHz wall clock, sleeping between polls, and ends after `milliseconds` or after a fixed number
