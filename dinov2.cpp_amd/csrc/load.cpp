@@ -460,6 +460,22 @@ int dinov2::check_rows_at(const dinov2_hip_model* m, int h, int w, char* err, si
     return DINOV2_HIP_OK;
 }
 
+// dinov2_check_input, then raw 8-bit input against the grid at its network size: the classify preprocessing crops to 224 x 224 whatever the
+// patch size, and a size the model's grid does not hold is refused as the same size handed over as floats is
+int dinov2_check_input_grid(const dinov2_hip_model* m, const dinov2_hip_input* in, uint32_t flags, char* err, size_t errlen) {
+    const int rc = dinov2_check_input(m, in, err, errlen);
+    if (rc != DINOV2_HIP_OK || in->layout != DINOV2_HIP_U8_BGR_HWC) return rc;
+    const int ps = (int)m->hp.patch_size, st = m->patch_stride;
+    int h, w;
+    network_size(m, in, flags, &h, &w);
+    if (h < ps || w < ps || (h - ps) % st || (w - ps) % st) {
+        set_err(err, errlen, "raw image input is preprocessed to %d x %d, which is not patch_size %d plus a multiple of patch_stride %d (the classify "
+                "preprocessing crops to 224 x 224 whatever the patch size)", h, w, ps, st);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    return DINOV2_HIP_OK;
+}
+
 int dinov2_check_pass_rows(const dinov2_hip_model* m, const dinov2_hip_input* in, uint32_t flags, char* err, size_t errlen) {
     int h, w;
     network_size(m, in, flags, &h, &w);
@@ -467,7 +483,7 @@ int dinov2_check_pass_rows(const dinov2_hip_model* m, const dinov2_hip_input* in
 }
 
 int dinov2_check_input_rows(const dinov2_hip_model* m, const dinov2_hip_input* in, uint32_t flags, char* err, size_t errlen) {
-    const int rc = dinov2_check_input(m, in, err, errlen);
+    const int rc = dinov2_check_input_grid(m, in, flags, err, errlen);
     return rc != DINOV2_HIP_OK ? rc : dinov2_check_pass_rows(m, in, flags, err, errlen);
 }
 

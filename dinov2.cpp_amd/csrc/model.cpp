@@ -984,7 +984,7 @@ int check_list(const dinov2_hip_model* m, const dinov2_hip_image_list* l, uint32
         in.data = reinterpret_cast<const float*>(need_data ? l->data[i] : (const void*)l);  // (never dereferenced here)
         in.batch = 1; in.height = l->height[i]; in.width = l->width[i]; in.layout = l->layout; in.on_device = l->on_device;
         char why[256] = "";
-        const int rc = dinov2_check_input(m, &in, why, sizeof(why));
+        const int rc = dinov2_check_input_grid(m, &in, flags, why, sizeof(why));
         if (rc != DINOV2_HIP_OK) {
             set_err(err, errlen, "image %d: %s", i, why);
             return rc;

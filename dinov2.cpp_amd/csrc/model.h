@@ -215,10 +215,12 @@ struct dinov2_hip_dense_head {
 // Internal (not C-ABI) helpers shared by model.cpp and group.cpp (host.h has those of the other host files).
 // Argument checks of dinov2_hip_predict that need no session: layout, batch, height / width against the patch size and stride.
 int dinov2_check_input(const dinov2_hip_model* m, const dinov2_hip_input* in, char* err, size_t errlen);
+// ... and, for raw 8-bit input, its network size under `flags` against the grid (224 x 224 with DINOV2_HIP_CLASSIFY, whatever the patch size)
+int dinov2_check_input_grid(const dinov2_hip_model* m, const dinov2_hip_input* in, uint32_t flags, char* err, size_t errlen);
 // After it: ONE image of `in` (at its network size under `flags`) must fit a pass -- token rows * widest activation row * 2 bytes below 2^31,
 // the 32-bit staging cursors of the GEMMs and the attention.  dinov2_max_pass_batch only cuts a batch into images; an image is not cut.
 int dinov2_check_pass_rows(const dinov2_hip_model* m, const dinov2_hip_input* in, uint32_t flags, char* err, size_t errlen);
-// both, in that order: what every predict entry point checks of its input before anything is allocated or launched
+// dinov2_check_input_grid, then dinov2_check_pass_rows: what every predict entry point checks of its input before anything is allocated or launched
 int dinov2_check_input_rows(const dinov2_hip_model* m, const dinov2_hip_input* in, uint32_t flags, char* err, size_t errlen);
 // Largest batch ONE pass of the forward takes at network input size h x w (32-bit activation offsets; DINOV2_HIP_MAX_CHUNK lowers it for
 // tests): dinov2_hip_predict cuts longer batches into passes and leaves nothing for dinov2_hip_fetch.

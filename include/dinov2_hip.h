@@ -137,9 +137,17 @@ void dinov2_hip_default_load_opts(dinov2_hip_load_opts *opts);
  *   img_size >= patch_size; any number of layers, register tokens and classes; 2-D weights F32 / F16 / BF16 / Q4_0 / Q4_1 / Q5_0 /
  *   Q5_1 / Q8_0 (the patch-embedding kernel F32 / F16 / BF16), every other tensor F32.
  * ln_fold applies where hidden_size % 128 == 0 and hidden_size <= 1 536; elsewhere the model runs with separate LayerNorm launches.
- * What has been RUN off the four published geometries: widths 64 .. 2 048, patch sizes 8, 14, 16 and 32, through dinov2_hip_predict,
- * _predict_layers, _predict_attention and _predict_dense.  Patch sizes 1 .. 7 and the other entry points (predict_list, kmeans, match,
- * bank) at such geometries are inside the limits above by the kernels' index arithmetic, not by a test. */
+ * A call, not a model, is refused (DINOV2_HIP_ERR_INVALID, before anything is launched) where its network input size is off the model's
+ * grid: float input whose height or width is not patch_size plus a multiple of patch_stride, and raw 8-bit input with
+ * DINOV2_HIP_CLASSIFY on a model whose grid does not hold 224 x 224 -- the classify preprocessing crops to 224 x 224 whatever the patch
+ * size (patch 5: refused; every divisor of 224 and every patch_stride of the published patch 14: taken).
+ * What has been RUN off the four published geometries: widths 64 .. 2 048 and patch sizes 1 .. 8, 14, 16 and 32 through
+ * dinov2_hip_predict (with and without ln_fold); _predict_layers, _predict_attention and _predict_dense at widths 64, 320 and 2 048, the
+ * first two at patch 1 as well; dinov2_hip_predict_list / _list_rows, _match_tokens, the bank, _kmeans_tokens and _pca3 on resident rows
+ * at widths 64 .. 2 048 with 1, 2, 3, 5 and 32 heads, patch sizes 1, 3, 7, 8, 14, 16 and 32, 0 .. 4 registers, f16 and bf16;
+ * _predict_dense and _predict_dense_slide at patch sizes 1, 3, 8 and 16; patch_stride below patch sizes 2, 3, 4, 6, 7, 8, 16 and 32; raw
+ * 8-bit input at patch sizes 5 and 16; a one-device group at patch 16 (tests/test_gpu_geometry.py,
+ * tests/test_gpu_geometry_entry_points.py, tests/test_gpu_stride.py). */
 int dinov2_hip_model_load(const char *gguf_path, const dinov2_hip_load_opts *opts, dinov2_hip_model **out,
                           char *err, size_t errlen);
 /* replaces the caller-side frees of inference.cpp:70-73 */

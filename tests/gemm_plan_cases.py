@@ -289,7 +289,7 @@ def cases_leaves(api, cases):
     return got
 
 
-# ---- the off-family geometries of tests/geometry_cases.py (any width = 64 * heads up to 2 048, any FFN width, patch sizes 8 .. 32) ----
+# ---- the off-family geometries of tests/geometry_cases.py (any width = 64 * heads up to 2 048, any FFN width, patch sizes 1 .. 32) ----
 def geometry_problems(ln=False):
     """(epilogue, M, N, K) of every GEMM the geometry sweep launches (tests/test_gpu_geometry.py): every "runs" row at its own batch and at
     batch 1 (the image run alone); `ln`: the launches with ln_fold = 1, for the rows whose width takes the fold."""
@@ -339,10 +339,10 @@ GEOMETRY_COVERAGE_CASES = [
     (1, 2, 17, 64, 64),  # small<64x128,w4x2,st3,ks1>
     (0, 3, 17, 64, 64),  # small<64x128,w4x2,st3,ks1>
     (1, 3, 17, 64, 64),  # small<64x128,w4x2,st3,ks1>
+    (0, 0, 16, 128, 64),  # small<64x128,w4x2,st3,ks1>
+    (1, 0, 16, 128, 64),  # small<64x128,w4x2,st3,ks1>
     (0, 1, 17, 192, 64),  # small<64x128,w4x2,st3,ks1>
     (1, 1, 17, 192, 64),  # small<64x128,w4x2,st3,ks1>
-    (0, 0, 63, 320, 192),  # small<64x128,w4x2,st3,ks1>
-    (1, 0, 63, 320, 192),  # small<64x128,w4x2,st3,ks1>
     (0, 4, 67, 1664, 320),  # small<64x128,w4x2,st3,ks1>
     (1, 4, 67, 1664, 320),  # small<64x128,w4x2,st3,ks1>
     (0, 3, 36751, 1280, 320),  # small<128x128,w2x2,st2,ks1>

@@ -9,7 +9,8 @@ value of an axis that has a limit) or "first_refused" (the first value past it).
 112 pixels, except the large-M rows (one layer, 224 pixels: the smallest batch at which the GEMM planner leaves the small-tile kernel).
 
 Imported by tests/test_geometry_probes.py (CPU: the table is what it claims, the oracle runs every row, the planner plans every GEMM of it)
-and tests/test_gpu_geometry.py (the device).  Plain module, no fixtures."""
+and tests/test_gpu_geometry.py (the device); ENTRY_ROWS and what follows them by tests/test_gpu_geometry_entry_points.py (the entry points
+the sweep itself does not call).  Plain module, no fixtures."""
 F16, BF16 = 0, 1
 RUNS, REFUSED = "runs", "refused"
 
@@ -59,7 +60,7 @@ GEOMETRIES = [
     _g("w320_c1001", 320, 1280, grid=5, classes=1001, size=(84, 84), axes=[("width", "mid"), ("classes", "mid"), ("pos", "different")], seed=4),
     # SwiGLU with F = 64 * 13 (the loader interleaves x1 | x2 in 32-row blocks), patch 8 (K_pe = 192), three registers, bf16, 7 x 9 patches
     _g("w320_swiglu832_p8_bf16", 320, 832, swiglu=True, patch=8, grid=8, registers=3, classes=16, dtype=BF16, size=(56, 72),
-       axes=[("ffn", "swiglu_odd"), ("patch", "min"), ("registers", "mid"), ("types", "bf16"), ("pos", "nonsquare")], seed=5),
+       axes=[("ffn", "swiglu_odd"), ("patch", "mid"), ("registers", "mid"), ("types", "bf16"), ("pos", "nonsquare")], seed=5),
     # seven heads; GELU F = 64 * 17; eight registers; ONE class; 2 x 8 = 16 patches on a 4 x 4 table: the loader's identity path goes by the
     # patch COUNT (the reference compares counts, not shapes)
     _g("w448_f1088_r8_c1", 448, 1088, registers=8, classes=1, size=(28, 112), axes=[("width", "mid"), ("ffn", "gelu_odd"), ("registers", "mid"), ("classes", "min"), ("pos", "identity_by_count")], seed=6),
@@ -76,6 +77,21 @@ GEOMETRIES = [
     # ---- patch: the largest accepted on a narrow model as well, and the first refused ----
     _g("w128_p32", 128, 512, patch=MAX_PATCH, grid=2, size=(2 * MAX_PATCH, 3 * MAX_PATCH), axes=[("patch", "last")], seed=12),
     _g("w128_p33_refused", 128, 512, patch=MAX_PATCH + 1, grid=2, verdict=REFUSED, refusal=("patch_size", MAX_PATCH + 1, MAX_PATCH), axes=[("patch", "first_refused")], seed=13),
+    # ---- patch sizes 1 .. 7 (K_pe = 3 p^2 = 3 .. 147, padded to 64, 64, 64, 64, 128, 128, 192), each on a 4 x 4 position table ----
+    # patch 1: 3 of 64 K columns are real; a grid row of 23 patches takes three im2col chunks (10, 10, 3); 3 x 23 = 69 patches (resampled)
+    _g("w128_p1", 128, 512, patch=1, registers=2, classes=7, size=(3, 23), axes=[("patch", "min"), ("pos", "nonsquare")], seed=17),
+    # patch 2, bf16: w0 = 11, a second chunk holding one patch
+    _g("w128_p2_bf16", 128, 512, patch=2, dtype=BF16, size=(8, 22), axes=[("patch", "small"), ("types", "bf16"), ("pos", "nonsquare")], seed=18),
+    # patch 3 = the channel count (the two divisors of the interleaved im2col coincide); three heads; 3 x 5 patches
+    _g("w192_p3_r1", 192, 768, patch=3, registers=1, size=(9, 15), axes=[("patch", "small"), ("pos", "nonsquare")], seed=19),
+    # patch 4: the position table's identity path
+    _g("w128_p4", 128, 512, patch=4, size=(16, 16), axes=[("patch", "small"), ("pos", "identity")], seed=20),
+    # patch 5: K_pe = 75 of 128; 4 x 3 patches
+    _g("w128_p5", 128, 512, patch=5, size=(20, 15), axes=[("patch", "small"), ("pos", "nonsquare")], seed=21),
+    # patch 6: w0 = 10, one full chunk exactly
+    _g("w128_p6", 128, 512, patch=6, size=(18, 60), axes=[("patch", "small"), ("pos", "nonsquare")], seed=22),
+    # patch 7: K_pe = 147 of 192; four registers; 3 x 5 patches
+    _g("w128_p7_r4", 128, 512, patch=7, registers=4, size=(21, 35), axes=[("patch", "small"), ("pos", "nonsquare")], seed=23),
     # ---- FFN: q8_0 with two blocks per fc2 row; a width that is no multiple of 64 ----
     _g("w128_f64_q8_0", 128, 64, registers=1, wtype="q8_0", classes=32, axes=[("ffn", "min"), ("types", "q8_0")], seed=14),
     _g("w128_f96_refused", 128, 96, verdict=REFUSED, refusal=("FFN hidden size", 96, 64), axes=[("ffn", "first_refused")], seed=15),
@@ -96,6 +112,32 @@ RUNNING = [g for g in GEOMETRIES if g["verdict"] == RUNS]
 REFUSALS = [g for g in GEOMETRIES if g["verdict"] == REFUSED]
 LARGE_M = [g for g in RUNNING if any(a == "large_m" for a, _ in g["axes"])]
 SIDE_OUTPUTS = ("w64_f64", "w320_c1001", "w2048_p32")  # predict_layers / predict_attention / predict_dense at H = 64, 320, 2 048
+# predict_layers / predict_attention also at patch 1 (its 3 x 23 output is too small for predict_dense's float64-margin cap: the exact parts of
+# predict_dense run on it in tests/test_gpu_geometry_entry_points.py)
+SIDE_OUTPUTS_TAPS = SIDE_OUTPUTS + ("w128_p1",)
+
+# ---- the entry points the sweep above does not call (tests/test_gpu_geometry_entry_points.py): widths 64, 128, 192, 320 and 2 048; heads 1, 2,
+# 3, 5 and 32; patches 1, 3, 7, 8, 14, 16 and 32; f16 and bf16; registers 0 .. 4 ----
+ENTRY_ROWS = ("w64_f64", "w192_p16_r1", "w320_swiglu832_p8_bf16", "w2048_p32", "w128_p1", "w192_p3_r1", "w128_p7_r4")
+DENSE_ROWS = ("w192_p16_r1", "w320_swiglu832_p8_bf16", "w192_p3_r1", "w128_p1")  # predict_dense / predict_dense_slide, exact parts
+RAW_U8_ROWS = ("w192_p16_r1", "w128_p5")  # 224 (the classify preprocessing's crop) is a multiple of patch 16 and none of patch 5
+STRIDE_ROW, STRIDE = "w320_swiglu832_p8_bf16", 2
+
+
+def list_sizes(g):
+    """The images a row's predict_list gets: its own size, one single patch, its size transposed (a square one: two patches wider), and a
+    column of up to seven patches.  The last is there for the rows whose other grids a patch of 14 would also give (patch 16: 48 x 80 is
+    3 x 5 patches either way): seven patches, or as many as 112 pixels hold, are another number of 14s at every patch size but 14."""
+    p, (h, w) = g["cfg"]["patch"], g["size"]
+    return [(h, w), (p, p), (w, h) if h != w else (h, w + 2 * p), (min(7, 112 // p) * p, p)]
+
+
+def slide_case(g):
+    """(h, w, crop h, crop w, stride h, stride w) of a row's sliding windows: the row's size, a crop of 2 x 3 patches, one patch down per
+    window and -- where the patch is above 1 -- a horizontal stride that is no multiple of the patch."""
+    p, (h, w) = g["cfg"]["patch"], g["size"]
+    return (h, w, 2 * p, 3 * p, p, p + 1 if p > 1 else 1)
+
 
 # axes that have a limit: (axis, position) of the last accepted and of the first refused value
 BOUNDARIES = {"width": ("last", "first_refused"), "patch": ("last", "first_refused"), "ffn": ("min", "first_refused")}

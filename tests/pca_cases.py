@@ -619,3 +619,34 @@ def e2e_case(name):
 
 def e2e_tolerance(emulated):
     return max(E2E_MARGIN * emulated, E2E_FLOOR)
+
+
+def e2e_failures(x, comp, mean, proj, tied=None, emulated=None, what=""):
+    """The acceptance rule of tests/test_gpu_parity.py::test_pca3_within_16x_of_its_emulation for one result of the whole call on tokens x:
+    the kernel's mean bit for bit, unit components with a positive largest entry, the projection inside the projection kernel's bound on the
+    returned components, and both errors against the float64 SVD within e2e_tolerance of what the emulation shows on the same input
+    (`emulated` = its (cos error, projection error); computed here when absent).  Returns (failure messages, the figures as a string)."""
+    x = np.asarray(x, np.float32)
+    if emulated is None:
+        ecomp, _, eproj, _ = pca3_emulate(x)
+        emulated = e2e_errors(x, ecomp, eproj, tied)
+    emu_cos, emu_proj = emulated
+    fails = []
+    if not (np.isfinite(comp).all() and np.isfinite(proj).all()):
+        return [what + ": non-finite result"], ""
+    cos_err, proj_err = e2e_errors(x, comp, proj, tied)
+    figures = (f"{what}: 1 - |cos| {cos_err:.2e} (emulation {emu_cos:.2e}, allowed {e2e_tolerance(emu_cos):.2e}); projection {proj_err:.2e} "
+               f"(emulation {emu_proj:.2e}, allowed {e2e_tolerance(emu_proj):.2e})")
+    ok, msg = check_exact(mean, mean_emulate(x), what + " mean")
+    if not ok:
+        fails.append(msg)
+    if np.abs(np.linalg.norm(np.asarray(comp, np.float64), axis=1) - 1.0).max() > 2.0 ** -23:  # unit in double, each entry rounded once to f32
+        fails.append(what + ": components are not unit length")
+    if not all(comp[k][np.abs(comp[k]).argmax()] > 0 for k in range(3)):
+        fails.append(what + ": a component's largest entry is not positive")
+    fails += check_project(lambda *_: proj, x, mean, comp, what)
+    if cos_err > e2e_tolerance(emu_cos):
+        fails.append(f"{what}: 1 - |cos| {cos_err:.3e} > {e2e_tolerance(emu_cos):.3e}")
+    if proj_err > e2e_tolerance(emu_proj):
+        fails.append(f"{what}: projection error {proj_err:.3e} > {e2e_tolerance(emu_proj):.3e}")
+    return fails, figures

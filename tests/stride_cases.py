@@ -90,7 +90,25 @@ SIZES_14 = [(7, 14, 14), (7, 28, 42), (7, 70, 77), (7, 70, 84), (7, 28, 140), (7
 FORWARD_14 = [(7, 14, 14), (7, 28, 42), (7, 70, 77), (7, 70, 84), (7, 28, 140), (7, 28, 147), (7, 70, 154), (2, 28, 42), (2, 14, 142),
               (1, 14, 30), (1, 28, 28), (1, 14, 141)]
 # synthetic checkpoints (write_synthetic_gguf with a dict config): (patch, stride, img_size of the checkpoint, h, w)
-SYNTH = [(16, 4, 64, 32, 48), (16, 8, 64, 48, 64), (8, 1, 32, 16, 20)]
+SYNTH = [(16, 4, 64, 32, 48), (16, 8, 64, 48, 64), (8, 1, 32, 16, 20),
+         # patch sizes 2 .. 7 on a 4 x 4 table: grids 4 x 7, 4 x 5, 3 x 5, 3 x 4, 2 x 4, 4 x 6
+         (2, 1, 8, 5, 8), (3, 1, 12, 6, 7), (4, 2, 16, 8, 12), (6, 2, 24, 10, 12), (6, 3, 24, 9, 15), (7, 1, 28, 10, 12)]
+# (patch, stride) below patch 8 for the strided kernel alone: a 16-byte output piece (8 elements) spans four strip rows at patch 2, crosses a
+# channel boundary inside one piece at patch 3 (k = 8 | 9), and 3 p^2 = 12 .. 147 real columns sit in Kpad = 64, 64, 64, 128, 128, 192
+SMALL_PS = [(2, 1), (3, 1), (4, 1), (4, 2), (5, 1), (6, 1), (6, 2), (6, 3), (7, 1)]
+
+
+def small_kernel_cases():
+    """(p, s, h, w) for SMALL_PS, three grid rows each: a grid row that is exactly one workgroup's run, and one of a run plus two patches."""
+    out = []
+    for p, s in SMALL_PS:
+        h = 2 * s + p
+        for w0 in (run(p, s), run(p, s) + 2):
+            out.append((p, s, h, (w0 - 1) * s + p))
+    return out
+
+
+SMALL_KERNEL = small_kernel_cases()
 
 
 def synth_config(patch, img_size):

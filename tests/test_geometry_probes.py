@@ -42,7 +42,7 @@ def _table(g):
 
 # ------------------------------------------------------------------------------------------------------------ the table
 def test_the_table_holds_every_axis_and_its_boundary_pairs():
-    assert 20 <= len(gc.GEOMETRIES) <= 24 and len({g["name"] for g in gc.GEOMETRIES}) == len(gc.GEOMETRIES)
+    assert 26 <= len(gc.GEOMETRIES) <= 30 and len({g["name"] for g in gc.GEOMETRIES}) == len(gc.GEOMETRIES)
     for g in gc.GEOMETRIES:
         large = g in gc.LARGE_M
         assert g["cfg"]["layers"] <= (1 if large else 2), g["name"]
@@ -69,9 +69,12 @@ def test_the_table_holds_every_axis_and_its_boundary_pairs():
     assert all(g["cfg"]["ffn"] == g["cfg"]["hidden"] for g in _rows("ffn", "equals_hidden")) and runs(_rows("ffn", "equals_hidden"))
     for pos, swiglu in (("gelu_odd", False), ("swiglu_odd", True)):
         assert all(g["cfg"]["swiglu"] == swiglu and g["cfg"]["ffn"] % 64 == 0 and (g["cfg"]["ffn"] // 64) % 2 == 1 for g in _rows("ffn", pos)) and runs(_rows("ffn", pos))
-    # patch: 8 (K_pe = 192), 16 (768), the last accepted and the first refused
-    assert all(g["cfg"]["patch"] == 8 for g in _rows("patch", "min")) and all(g["cfg"]["patch"] == 16 for g in _rows("patch", "mid"))
-    assert (gc.kpe_pad(8), gc.kpe_pad(16)) == (192, 768) and runs(_rows("patch", "min") + _rows("patch", "mid"))
+    # patch: 1 (K_pe = 3 of 64), every size 2 .. 7, 8 (K_pe = 192) and 16 (768), the last accepted and the first refused
+    assert all(g["cfg"]["patch"] == 1 for g in _rows("patch", "min"))
+    assert {g["cfg"]["patch"] for g in _rows("patch", "small")} == {2, 3, 4, 5, 6, 7} and {g["cfg"]["patch"] for g in _rows("patch", "mid")} == {8, 16}
+    assert [gc.kpe_pad(p) for p in range(1, 8)] == [64, 64, 64, 64, 128, 128, 192] and [3 * p * p for p in range(1, 8)] == [3, 12, 27, 48, 75, 108, 147]
+    assert (gc.kpe_pad(8), gc.kpe_pad(16)) == (192, 768) and runs(_rows("patch", "min") + _rows("patch", "small") + _rows("patch", "mid"))
+    assert all(g["cfg"]["img_size"] == 4 * g["cfg"]["patch"] and g["cfg"]["hidden"] in (128, 192) for g in _rows("patch", "min") + _rows("patch", "small"))
     assert all(g["cfg"]["patch"] == gc.MAX_PATCH for g in _rows("patch", "last")) and runs(_rows("patch", "last"))
     assert all(g["cfg"]["patch"] == gc.MAX_PATCH + 1 for g in _rows("patch", "first_refused")) and refused(_rows("patch", "first_refused"))
     # registers: 1, 3, 8, and 16 on a 1 x 1 and a 2 x 2 patch grid
@@ -100,6 +103,50 @@ def test_the_table_holds_every_axis_and_its_boundary_pairs():
     for axis, (last, first) in gc.BOUNDARIES.items():
         assert runs(_rows(axis, last)) and refused(_rows(axis, first)), axis
     assert set(gc.SIDE_OUTPUTS) <= set(run) and [run[n]["cfg"]["hidden"] for n in gc.SIDE_OUTPUTS] == [64, 320, 2048]
+
+
+def test_the_entry_point_rows_cover_what_they_claim():
+    """ENTRY_ROWS and what goes with them (tests/test_gpu_geometry_entry_points.py): running rows with a classifier; widths 64 .. 2 048, heads
+    1, 2, 3, 5 and 32, patches 1, 3, 7, 8, 14, 16 and 32, both compute types, registers 0 .. 4; four different list sizes per row, none above
+    112 pixels; enough patches for k = 5 neighbours and pca3; window grids with more than one window each way and a cover far below the 48 the
+    reduction takes."""
+    import slide_cases as sl
+    rows = [gc.BY_NAME[n] for n in gc.ENTRY_ROWS]
+    assert all(g in gc.RUNNING and g["num_classes"] > 0 and g not in gc.LARGE_M for g in rows)
+    assert {g["cfg"]["hidden"] for g in rows} == {64, 128, 192, 320, 2048} and {g["cfg"]["heads"] for g in rows} == {1, 2, 3, 5, 32}
+    assert {g["cfg"]["patch"] for g in rows} == {1, 3, 7, 8, 14, 16, 32} and {g["dtype"] for g in rows} == {F16, BF16}
+    assert {g["registers"] for g in rows} == {0, 1, 2, 3, 4}
+    for g in rows:
+        p, sizes = g["cfg"]["patch"], gc.list_sizes(g)
+        assert len(set(sizes)) == 4 and all(h % p == 0 and w % p == 0 and p <= max(h, w) <= 112 for h, w in sizes), g["name"]
+        assert _grid(g)[0] * _grid(g)[1] >= 5 and g["cfg"]["hidden"] >= 8, g["name"]
+    assert set(gc.DENSE_ROWS) <= set(gc.ENTRY_ROWS) and {gc.BY_NAME[n]["cfg"]["patch"] for n in gc.DENSE_ROWS} == {1, 3, 8, 16}
+    for n in gc.DENSE_ROWS:
+        h, w, ch, cw, sh, sw = gc.slide_case(gc.BY_NAME[n])
+        ys, xs = sl.starts(h, ch, sh), sl.starts(w, cw, sw)
+        assert h > ch and w > cw and len(ys) >= 2 and len(xs) >= 3 and sl.cover_map(ys, xs, ch, cw, h, w).max() <= 8, n
+        assert 2 * len(ys) * len(xs) <= 84  # windows of a batch of two
+    assert [gc.BY_NAME[n]["cfg"]["patch"] for n in gc.RAW_U8_ROWS] == [16, 5] and 224 % 16 == 0 and 224 % 5 != 0
+    g = gc.BY_NAME[gc.STRIDE_ROW]
+    assert g["cfg"]["patch"] % gc.STRIDE == 0 and g["dtype"] == BF16 and g["cfg"]["swiglu"]
+
+
+def test_the_list_plan_of_every_entry_point_row(api):
+    """The library's list_plan (no device) on each row's list sizes, with the row's patch, registers and heads: the restatement of
+    tests/list_cases.py, the token rows of the grids, one attention item per (image, head, query block) -- and, for every row whose patch is
+    not 14, another plan than a patch of 14 would give (so a family constant in its place cannot pass the bit-equality of
+    tests/test_gpu_geometry_entry_points.py: the forward would attend over other rows than predict alone does)."""
+    import list_cases as lc
+    for name in gc.ENTRY_ROWS:
+        g = gc.BY_NAME[name]
+        p, R, nh, sizes = g["cfg"]["patch"], g["registers"], g["cfg"]["heads"], gc.list_sizes(g)
+        got, exp = api.list_plan(sizes, p, R, nh), lc.plan(sizes, p, R, nh)
+        for k in ("images", "runs", "items"):
+            assert np.array_equal(got[k], exp[k]), (name, k)
+        assert [int(t) for t in got["images"][:, 1]] == [1 + R + (h // p) * (w // p) for h, w in sizes] and got["M"] == int(got["images"][:, 1].sum())
+        assert {int(h) for h in got["items"][:, 2]} == set(range(nh)) and len(got["items"]) == got["units"]
+        if p != 14:
+            assert api.list_plan(sizes, 14, R, nh)["M"] != got["M"], name
 
 
 def test_the_limits_follow_from_the_kernels_conditions():

@@ -130,9 +130,10 @@ def test_incremental_adds_clear_and_refill(api, golden):
     assert bc.scenario_failures(lambda H, cap: _SessionBank(api, model, sess, H, cap)) == []
 
 
-@pytest.mark.parametrize("classify", [False, True], ids=["features", "classify"])
-def test_resident_rows_equal_the_fetched_tokens(api, golden, classify):
-    model, img = golden
+def check_resident_bank(api, model, img, classify):
+    """The body of test_resident_rows_equal_the_fetched_tokens for any model and batch of two images with at least five patches each (also
+    run off the family by tests/test_gpu_geometry_entry_points.py): k = 5 neighbours.  Returns the top-3 of the CLS rows (on a model whose two
+    CLS rows are equal after the f16 normalisation both find row 0: that each finds itself is asserted where the images make them differ)."""
     sess = api.Session(model)
     R = int(model.hparams.num_register_tokens)
     out = sess.predict(img, classify=classify, want=("cls", "patch_tokens"))
@@ -154,7 +155,6 @@ def test_resident_rows_equal_the_fetched_tokens(api, golden, classify):
     assert ok, msg
     rc = bank.topk(sess, k=3, source="last_cls")
     _same(rc, api.op_bank_topk(cls, rows, 3), "LAST_CLS queries")
-    assert np.array_equal(rc["idx"][:, 0], [0, 1])  # every CLS row finds itself
     # a bank filled from host rows holds the same bits
     host = api.Bank(model, H, 2 + P)
     assert host.add(sess, rows) == 0
@@ -166,6 +166,14 @@ def test_resident_rows_equal_the_fetched_tokens(api, golden, classify):
     assert np.array_equal(big["idx"][:P, :5], resident["idx"])
     bank.free()
     host.free()
+    return rc
+
+
+@pytest.mark.parametrize("classify", [False, True], ids=["features", "classify"])
+def test_resident_rows_equal_the_fetched_tokens(api, golden, classify):
+    model, img = golden
+    rc = check_resident_bank(api, model, img, classify)
+    assert np.array_equal(rc["idx"][:, 0], [0, 1])  # every CLS row finds itself
 
 
 def _add(api, sess_h, bank_h, **kw):

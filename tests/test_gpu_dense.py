@@ -77,10 +77,12 @@ def _operands(taps, concat_cls):
     return np.concatenate(blocks, axis=1).astype(np.float16)
 
 
-def _check_dense(api, sess, model, imgs, layers, C_, norm, concat_cls, out_size, what):
+def _check_dense(api, sess, model, imgs, layers, C_, norm, concat_cls, out_size, what, margin=True):
+    """`margin`: also the float64 pipeline outside its top-2 margin, with the cap on the pixels inside it (stated for outputs of 56 pixels
+    and more: the off-family entry-point tests run the exact parts alone on their small outputs)."""
     hp = model.hparams
     B, (hh, ww) = imgs.shape[0], imgs.shape[2:]
-    h0, w0 = hh // hp.patch_size, ww // hp.patch_size
+    h0, w0 = model.grid(hh, ww)
     P, K = h0 * w0, len(layers) * hp.hidden_size * (1 + concat_cls)
     oh, ow = (hh, ww) if out_size is None else out_size
     cen = dc.bin_centers(C_)
@@ -106,6 +108,8 @@ def _check_dense(api, sess, model, imgs, layers, C_, norm, concat_cls, out_size,
         fails = dc.compare({"labels": rs["labels"][b], "value": rs["value"][b]}, dc.emulate(Lb, h0, w0, oh, ow), "%s image %d argmax" % (what, b))
         fails += dc.compare({"value": rd["value"][b]}, dc.emulate(Lb, h0, w0, oh, ow, dc.BINS, cen, 0.1), "%s image %d bins" % (what, b))
         assert not fails, "\n".join(fails)
+        if not margin:
+            continue
         r64, b64 = ref[b * P:(b + 1) * P], bound[b * P:(b + 1) * P]
         f64 = dc.reference(r64, h0, w0, oh, ow)
         vb = dc.val_bound(b64, np.abs(r64), h0, w0, oh, ow).max(axis=2)
@@ -116,6 +120,8 @@ def _check_dense(api, sess, model, imgs, layers, C_, norm, concat_cls, out_size,
         d64 = dc.reference(r64, h0, w0, oh, ow, dc.BINS, cen, 0.1)["value"]
         tol = dc.bins_bound(b64, r64, h0, w0, oh, ow, cen, 0.1)
         assert (np.abs(rd["value"][b] - d64) <= tol).all(), "%s image %d: bins outside the bound" % (what, b)
+    if not margin:
+        return
     print("%s: %d of %d pixels inside the margin" % (what, excluded, total))
     assert excluded <= 0.02 * total, "%s: %d of %d pixels excluded by the margin" % (what, excluded, total)
 

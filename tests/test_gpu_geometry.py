@@ -279,13 +279,13 @@ def test_geometry_ln_plan_coverage_case_bits(api, case):
     ln_plan_case_bits(api, case)
 
 
-# ---- side outputs at H = 64, 320 and 2 048 ----
+# ---- side outputs at H = 64, 320 and 2 048, and at patch 1 (H = 128, 3 x 23 patches, two registers) ----
 def _final_ln(path):
     t = GGUFFile(path).tensors
     return t["layernorm.weight"].to_f32().reshape(-1).astype(np.float32), t["layernorm.bias"].to_f32().reshape(-1).astype(np.float32)
 
 
-@pytest.mark.parametrize("name", gc.SIDE_OUTPUTS)
+@pytest.mark.parametrize("name", gc.SIDE_OUTPUTS_TAPS)
 def test_layer_taps_tokens_and_chw_against_float64_of_the_oracle(api, pkg, files, name):
     """predict_layers with norm = True, every layer, both layouts: ln_reference (float64) of the oracle's hidden states under the token bound
     5e-3 * max(1, max|ref|) (tests/test_gpu_layers.py::test_normalised_taps_against_float64_of_the_oracle); CHW is TOKENS transposed, bit for
@@ -321,7 +321,7 @@ def test_layer_taps_tokens_and_chw_against_float64_of_the_oracle(api, pkg, files
     _record(name + "_layer_taps", worst_error_over_bound=worst)
 
 
-@pytest.mark.parametrize("name", gc.SIDE_OUTPUTS)
+@pytest.mark.parametrize("name", gc.SIDE_OUTPUTS_TAPS)
 def test_cls_attention_row_of_the_last_block_against_float64(api, pkg, files, name):
     """predict_attention, the CLS query of the last block, all heads (1, 5 and 32 of them): the float64 softmax and the derived bound of
     tests/test_gpu_attention_maps.py::test_float64_reference (separate LayerNorm launches: the GEMM's operand is the LayerNorm kernel's output)."""

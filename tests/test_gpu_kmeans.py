@@ -153,30 +153,47 @@ def golden(api, golden_dir):
     return model, img
 
 
-@pytest.mark.parametrize("classify", [False, True], ids=["features", "classify"])
-def test_resident_rows_equal_the_fetched_tokens(api, golden, classify):
-    model, img = golden
-    sess = api.Session(model)
-    R = int(model.hparams.num_register_tokens)
+def check_resident_kmeans(api, sess, img, classify, max_iter, init, max_iter_all, init_all):
+    """The resident-row part of test_resident_rows_equal_the_fetched_tokens for any session and batch (also run off the family by
+    tests/test_gpu_geometry_entry_points.py): the patch rows of image 1, and of every image, against the testing op, host rows and a
+    DeviceArray, bit for bit, and inside the assign tolerance of the float64 cosine against the returned centres.  Returns (tok, cls, the
+    image-1 result)."""
+    R = int(sess.model.hparams.num_register_tokens)
     out = sess.predict(img, classify=classify, want=("cls", "patch_tokens"))
     tok, cls = out["patch_tokens"], out["cls"]
     if classify:
         tok = tok[:, R:]
     B, P, H = tok.shape
-    init = np.array([1, 5, P - 1], np.int32)
-    resident = sess.kmeans(K=3, max_iter=4, init=init, source="last_patches", image=1)
-    _same_run(resident, api.op_kmeans(tok[1], 3, 4, init), "resident patches x testing op")
-    _same_run(resident, sess.kmeans(tok[1], K=3, max_iter=4, init=init), "resident patches x host rows")
+    K = len(init)
+    resident = sess.kmeans(K=K, max_iter=max_iter, init=init, source="last_patches", image=1)
+    _same_run(resident, api.op_kmeans(tok[1], K, max_iter, init), "resident patches x testing op")
+    _same_run(resident, sess.kmeans(tok[1], K=K, max_iter=max_iter, init=init), "resident patches x host rows")
     d = api.DeviceArray.from_host(tok[1])
-    _same_run(resident, sess.kmeans(d, K=3, max_iter=4, init=init), "resident patches x DeviceArray")
+    _same_run(resident, sess.kmeans(d, K=K, max_iter=max_iter, init=init), "resident patches x DeviceArray")
     d.free()
     assert resident["labels"].shape == (P,) and resident["counts"].sum() == P
-    # every image's patches, image-major; the init rows reach into the second and third image
+    ok, msg = kc.check_assign(resident, tok[1], resident["centers"], "resident patches")
+    assert ok, msg
+    # every image's patches, image-major; the init rows reach into the later images
     flat = tok.reshape(B * P, H)
-    init_all = np.array([0, P + 3, 2 * P + 7, B * P - 1], np.int32)
-    every = sess.kmeans(K=4, max_iter=3, init=init_all, source="last_patches", all_images=True)
-    _same_run(every, api.op_kmeans(flat, 4, 3, init_all), "all_images x testing op")
-    _same_run(every, sess.kmeans(flat, K=4, max_iter=3, init=init_all), "all_images x host rows")
+    Ka = len(init_all)
+    every = sess.kmeans(K=Ka, max_iter=max_iter_all, init=init_all, source="last_patches", all_images=True)
+    _same_run(every, api.op_kmeans(flat, Ka, max_iter_all, init_all), "all_images x testing op")
+    _same_run(every, sess.kmeans(flat, K=Ka, max_iter=max_iter_all, init=init_all), "all_images x host rows")
+    ok, msg = kc.check_assign(every, flat, every["centers"], "all_images")
+    assert ok, msg
+    return tok, cls, resident
+
+
+@pytest.mark.parametrize("classify", [False, True], ids=["features", "classify"])
+def test_resident_rows_equal_the_fetched_tokens(api, golden, classify):
+    model, img = golden
+    sess = api.Session(model)
+    R = int(model.hparams.num_register_tokens)
+    P = int(np.prod(model.grid(*img.shape[2:])))
+    init = np.array([1, 5, P - 1], np.int32)
+    tok, cls, resident = check_resident_kmeans(api, sess, img, classify, 4, init, 3, np.array([0, P + 3, 2 * P + 7, 3 * P - 1], np.int32))
+    B, P, H = tok.shape
     # CLS rows: one per image, strided through the token stream
     rc = sess.kmeans(K=2, max_iter=2, init=np.array([0, 2], np.int32), source="last_cls")
     _same_run(rc, api.op_kmeans(cls, 2, 2, np.array([0, 2], np.int32)), "LAST_CLS x testing op")

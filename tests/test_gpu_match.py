@@ -102,14 +102,11 @@ def _same(x, y, what):
     assert np.array_equal(x["mutual"], y["mutual"]), what
 
 
-@pytest.mark.parametrize("classify", [False, True], ids=["features", "classify"])
-def test_resident_sides_equal_the_fetched_patch_tokens(api, golden, classify):
-    """match(None, None) on what the last predict left on the device == match(tok[0], tok[1]) on the fetched patch tokens, bit for bit;
-    under DINOV2_HIP_CLASSIFY too, where the rows predict hands out start with the registers and the resident view must not."""
-    model, img = golden
+def check_resident_match(api, model, img, classify):
+    """The body of test_resident_sides_equal_the_fetched_patch_tokens for any model and batch of two images (also run off the family by
+    tests/test_gpu_geometry_entry_points.py)."""
     sess = api.Session(model)
     R = int(model.hparams.num_register_tokens)
-    assert R == 4
     tok = sess.predict(img, classify=classify, want=("patch_tokens",))["patch_tokens"]
     if classify:
         tok = tok[:, R:]
@@ -125,6 +122,15 @@ def test_resident_sides_equal_the_fetched_patch_tokens(api, golden, classify):
     ok, msg = mc.check_against_reference(host, mc.reference(tok[0], tok[1]), H, "golden tokens")
     assert ok, msg
     _same(host, api.op_match(tok[0], tok[1]) | {"mutual": host["mutual"]}, "session call x testing op")
+
+
+@pytest.mark.parametrize("classify", [False, True], ids=["features", "classify"])
+def test_resident_sides_equal_the_fetched_patch_tokens(api, golden, classify):
+    """match(None, None) on what the last predict left on the device == match(tok[0], tok[1]) on the fetched patch tokens, bit for bit;
+    under DINOV2_HIP_CLASSIFY too, where the rows predict hands out start with the registers and the resident view must not."""
+    model, img = golden
+    assert int(model.hparams.num_register_tokens) == 4
+    check_resident_match(api, model, img, classify)
 
 
 def test_device_inputs(api, golden):

@@ -768,11 +768,15 @@ def gemm_plan_case_bits(api, case):
 
 @pytest.mark.parametrize("dt", [F16, BF16])
 @pytest.mark.parametrize("layout", [1, 0])
-@pytest.mark.parametrize("B,Hh,Ww,ps", [(2, 518, 518, 14), (1, 224, 224, 14), (3, 70, 98, 14), (1, 490, 868, 14), (2, 64, 83, 16), (1, 14, 14, 14)])
+@pytest.mark.parametrize("B,Hh,Ww,ps", [(2, 518, 518, 14), (1, 224, 224, 14), (3, 70, 98, 14), (1, 490, 868, 14), (2, 64, 83, 16), (1, 14, 14, 14),
+                                        (1, 1, 1, 1), (2, 3, 23, 1), (1, 4, 22, 2), (2, 9, 33, 3), (1, 7, 31, 3), (1, 8, 44, 4), (1, 10, 55, 5),
+                                        (1, 12, 60, 6), (3, 14, 147, 7)])
 def test_im2col_bit_exact(api, dt, layout, B, Hh, Ww, ps):
     """im2col of ggml_conv_2d_sk_p0 (/root/reference/dinov2.cpp:636; BGR-interleaved input: the repack of :914-931 folded in): every element
     of [B * P, Kpad] equals the compute-type rounding of its pixel, k = c * ps^2 + ky * ps + kx with c the RGB index, zero in the K padding --
-    square, non-square, several chunks per patch row (868 wide: 62 patches), widths that are no multiple of the patch size, one patch."""
+    square, non-square, several chunks per patch row (868 wide: 62 patches), widths that are no multiple of the patch size, one patch; and
+    every patch size 1 .. 7 (3 p^2 = 3 .. 147 real columns of Kpad 64, 64, 64, 64, 128, 128, 192: one pixel, chunks of 10 + 10 + 3, 10 + 1 and
+    exactly 10 patches, patch 3 = the channel count, a width that is no multiple of patch 3)."""
     rng = np.random.default_rng(B * 1000 + Ww)
     Kpad = (3 * ps * ps + 63) // 64 * 64
     rgb = (rng.standard_normal((B, 3, Hh, Ww)) * 1.5).astype(np.float32)

@@ -101,12 +101,18 @@ def _operands(taps, concat_cls):
     return np.concatenate(blocks, axis=1).astype(np.float16)
 
 
-def _check_slide(api, model, C_, layers, concat_cls, what):
+def _check_slide(api, model, C_, layers, concat_cls, what, case=sl.MODEL_CASE, margin=True):
+    """`case` = (h, w, crop h, crop w, stride h, stride w) of the images and windows; `margin`: also the float64 pipeline outside its top-2
+    margin, with the cap on the pixels inside it (the off-family entry-point tests run the exact parts alone on their small outputs)."""
+    h, w, ch, cw, sh, sw = case
+    ys, xs = sl.starts(h, ch, sh), sl.starts(w, cw, sw)
+    y1, x1 = model.slide_windows(h, w, (ch, cw), (sh, sw))
+    assert list(y1) == list(ys) and list(x1) == list(xs), (what, list(y1), list(x1))
     sess = api.Session(model)
-    h0, w0 = model.grid(CH, CW)
-    P, nwin = h0 * w0, len(YS) * len(XS)
-    imgs = _images(2, (H, W), C_)
-    crops = _crops(imgs, YS, XS, CH, CW)
+    h0, w0 = model.grid(ch, cw)
+    P, nwin = h0 * w0, len(ys) * len(xs)
+    imgs = _images(2, (h, w), C_)
+    crops = _crops(imgs, ys, xs, ch, cw)
     taps = sess.predict_layers(crops, list(layers), norm=True, return_class_token=True)
     A16 = _operands(taps, concat_cls)
     rms = float(np.sqrt((A16.astype(np.float64) ** 2).mean()))
@@ -115,10 +121,10 @@ def _check_slide(api, model, C_, layers, concat_cls, what):
     cen = dc.bin_centers(C_)
     seg = api.DenseHead(model, list(layers), Wt, bias, norm=True, concat_cls=bool(concat_cls))
     dep = api.DenseHead(model, list(layers), Wt, bias, norm=True, concat_cls=bool(concat_cls), reduce="bins", bin_centers=cen, bins_eps=0.1)
-    rs = sess.predict_dense_slide(imgs, seg, (CH, CW), (SH, SW))
-    rd = sess.predict_dense_slide(imgs, dep, (CH, CW), (SH, SW))
+    rs = sess.predict_dense_slide(imgs, seg, (ch, cw), (sh, sw))
+    rd = sess.predict_dense_slide(imgs, dep, (ch, cw), (sh, sw))
     assert set(rs) == {"labels", "value", "logits"} and set(rd) == {"value", "logits"}
-    assert rs["logits"].shape == (2, nwin, P, C_) and rs["labels"].shape == (2, H, W) and rs["value"].shape == (2, H, W)
+    assert rs["logits"].shape == (2, nwin, P, C_) and rs["labels"].shape == (2, h, w) and rs["value"].shape == (2, h, w)
     direct = api.Session(model).predict_dense(crops, seg, want=("logits",))["logits"]  # contract 2: the crop alone, through predict_dense
     ok, msg = mc.check_exact(rs["logits"].reshape(2 * nwin, P, C_), direct, what + ": window logits against predict_dense of the crops")
     assert ok, msg
@@ -129,10 +135,12 @@ def _check_slide(api, model, C_, layers, concat_cls, what):
     excluded = total = 0
     for b in range(2):
         Lb = rs["logits"][b]
-        fails = sl.compare({"labels": rs["labels"][b], "value": rs["value"][b]}, sl.emulate(Lb, YS, XS, h0, w0, CH, CW, H, W), "%s image %d argmax" % (what, b))
-        fails += sl.compare({"value": rd["value"][b]}, sl.emulate(Lb, YS, XS, h0, w0, CH, CW, H, W, dc.BINS, cen, 0.1), "%s image %d bins" % (what, b))
+        fails = sl.compare({"labels": rs["labels"][b], "value": rs["value"][b]}, sl.emulate(Lb, ys, xs, h0, w0, ch, cw, h, w), "%s image %d argmax" % (what, b))
+        fails += sl.compare({"value": rd["value"][b]}, sl.emulate(Lb, ys, xs, h0, w0, ch, cw, h, w, dc.BINS, cen, 0.1), "%s image %d bins" % (what, b))
         assert not fails, "\n".join(fails)
-        f64 = sl.reference(ref[b], YS, XS, h0, w0, CH, CW, H, W)
+        if not margin:
+            continue
+        f64 = sl.reference(ref[b], ys, xs, h0, w0, ch, cw, h, w)
         # the logits' own error passes through convex combinations and a mean unamplified; the float32 mean adds slide_cases.mean_bound
         lb = float(bound[b].max())
         tol = lb + sl.mean_bound(f64["n"], np.abs(ref[b]).max() + lb)
@@ -140,6 +148,8 @@ def _check_slide(api, model, C_, layers, concat_cls, what):
         assert (rs["labels"][b][sure] == f64["labels"][sure]).all(), "%s image %d: labels differ from float64 outside the margin" % (what, b)
         excluded += int((~sure).sum())
         total += sure.size
+    if not margin:
+        return
     print("%s: %d of %d pixels inside the margin" % (what, excluded, total))
     assert excluded <= 0.02 * total, "%s: %d of %d pixels excluded by the margin" % (what, excluded, total)
 

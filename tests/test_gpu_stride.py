@@ -123,7 +123,7 @@ def test_explicit_patch_size_is_the_default(api, golden_dir):
 
 @pytest.mark.parametrize("p,s,img_size,h,w", sc.SYNTH)
 def test_synthetic_checkpoints(api, pkg, tmp_path, p, s, img_size, h, w):
-    """Other patch sizes: 16 at strides 4 and 8, 8 at stride 1."""
+    """Other patch sizes: 16 at strides 4 and 8, 8 at stride 1; 2, 3 and 7 at stride 1, 4 at stride 2, 6 at strides 2 and 3."""
     path = str(tmp_path / "synth.gguf")
     pkg.synth.write_synthetic_gguf(path, sc.synth_config(p, img_size), registers=2, num_classes=5)
     ms, md = api.Model(path, patch_stride=s), api.Model(path)
@@ -166,7 +166,7 @@ def _op(api, dt, rgb, p, s, layout, Kpad=None):
 
 
 KERNEL_CASES = [(P14, s, h, w) for s, h, w in sc.SIZES_14] + [(32, 16, 64, 400), (32, 1, 34, 321), (16, 4, 32, 48), (8, 1, 16, 20),
-                                                              (33, 11, 55, 66), (14, 7, 518, 518)]
+                                                              (33, 11, 55, 66), (14, 7, 518, 518)] + sc.SMALL_KERNEL
 
 
 @pytest.mark.parametrize("dt", [F16, BF16])
@@ -175,7 +175,8 @@ KERNEL_CASES = [(P14, s, h, w) for s, h, w in sc.SIZES_14] + [(32, 16, 64, 400),
 def test_im2col_stride_bit_exact(api, dt, layout, p, s, h, w):
     """Every element of col equals the compute-type rounding of its pixel (one rounding), the K padding is exactly zero, every element is
     written (the op pre-fills NaN): both layouts, runs of one and of several workgroups, patch 32 at strides 16 and 1, and patch 33 at
-    stride 11 -- the largest patch im2col_stride_ok admits."""
+    stride 11 -- the largest patch im2col_stride_ok admits; every (patch, stride) below patch 8 (stride_cases.SMALL_PS), a grid row of
+    exactly one run and of a run plus two patches each."""
     assert sc.stride_ok(p, s, sc.kpad(p))
     rgb = (_img(h, w, seed=p + s, B=2) * 1.5).astype(np.float32)
     rc, col = _op(api, dt, rgb, p, s, layout)
@@ -194,12 +195,14 @@ def test_im2col_stride_refuses_what_is_outside_its_limits(api):
 
 
 @pytest.mark.parametrize("dt,layout", [(F16, 1), (BF16, 0)])
-@pytest.mark.parametrize("s,h,w", [(7, 42, 154), (2, 16, 142), (1, 16, 141)])
-def test_im2col_stride_nan_tracer(api, dt, layout, s, h, w):
+@pytest.mark.parametrize("p,s,h,w", [(P14, 7, 42, 154), (P14, 2, 16, 142), (P14, 1, 16, 141), (3, 1, 7, 33), (2, 1, 5, 24)],
+                         ids=["7-42-154", "2-16-142", "1-16-141", "p3-1-7-33", "p2-1-5-24"])  # (the patch-14 cases keep their names)
+def test_im2col_stride_nan_tracer(api, dt, layout, p, s, h, w):
     """One NaN in one pixel channel: exactly the col elements of the patches that cover the pixel turn NaN, each at its own (c, ky, kx);
     everything else keeps the bits of the clean launch.  Pixels: a corner (one patch), an interior pixel (the full (p / s)^2), the last
-    column that only the first workgroup's run reads and the first that only the next one's does, and the columns the two runs share."""
-    p = P14
+    column that only the first workgroup's run reads and the first that only the next one's does, the columns the two runs share, and one
+    interior pixel in each of its three channels in turn (patch 3 = the channel count: only the (c, ky, kx) that turns NaN tells the
+    channel index from the column inside the patch)."""
     rgb = _img(h, w, seed=11, B=2)
     rc, clean = _op(api, dt, rgb, p, s, layout)
     assert rc == 0 and not np.isnan(clean).any()
@@ -209,7 +212,7 @@ def test_im2col_stride_nan_tracer(api, dt, layout, s, h, w):
     last_of_first = r * s - 1            # column r s - 1: under patches <= r - 1 only
     first_of_next = (r - 1) * s + p      # the first column patch r - 1 no longer covers
     pixels = [(0, 0, 0, 0), (1, 2, h - 1, w - 1), (0, 1, min(p - 1, h - 1), p - 1 + s), (1, 0, 0, last_of_first), (0, 2, h - 1, first_of_next),
-              (1, 1, 1, r * s)]
+              (1, 1, 1, r * s)] + [(0, c, min(p, h - 1), r * s + 1) for c in range(3)]
     for b, c, y, x in pixels:
         hit = sc.footprint(b, c, y, x, h, w, p, s)
         bad = rgb.copy()

@@ -368,14 +368,20 @@ def test_head(api, pool_regs, const_div, dt):
 # ------------------------------------------------------------------------------------------------------------------- im2col, convert_weight
 @pytest.mark.parametrize("dt", [tc.F16, tc.BF16], ids=["f16", "bf16"])
 @pytest.mark.parametrize("layout", [1, 0], ids=["rgb_chw", "bgr_hwc"])
-@pytest.mark.parametrize("B,Hh,Ww,ps", [(2, 70, 98, 14), (2, 64, 83, 16)])
+@pytest.mark.parametrize("B,Hh,Ww,ps", [(2, 70, 98, 14), (2, 64, 83, 16), (2, 11, 38, 3)])
 def test_im2col(api, dt, layout, B, Hh, Ww, ps):
-    """One pixel gives exactly one element of col (none when the patch grid crops it); the pad columns K .. Kpad are written, as zeros."""
+    """One pixel gives exactly one element of col (none when the patch grid crops it); the pad columns K .. Kpad are written, as zeros.
+    Patch 3 (the patch size equals the channel count, 27 of 64 columns are real, 12 patches per grid row): also the pixel columns either side
+    of the chunk boundary (patch 9 | 10).  Every case then plants one pixel in each of its three channels IN TURN: which (c, ky, kx) turns NaN
+    is the only thing that tells a division by 3 (channels) from a division by the patch size when the two agree on the patch index."""
     rng = np.random.default_rng(Hh + Ww)
     K, Kpad = 3 * ps * ps, (3 * ps * ps + 63) // 64 * 64
     h0, w0 = Hh // ps, Ww // ps
     rgb = (rng.standard_normal((B, 3, Hh, Ww)) * 1.5).astype(np.float32)
     pixels = [(0, 0, 0, 0), (1, 2, h0 * ps - 1, w0 * ps - 1), (0, 1, ps, ps - 1), (1, 0, ps - 1, ps), (1, 1, Hh - 1, Ww - 1), (0, 2, 2 * ps + 3, Ww - 1)]
+    chunk = 10 * ps  # IM2COL_CHUNK patches
+    if w0 > 10:
+        pixels += [(0, 0, 1, chunk - 1), (1, 2, 1, chunk), (0, 1, ps + 1, chunk + 1)]
 
     def run(a):
         img = a if layout == 1 else np.ascontiguousarray(a[:, ::-1].transpose(0, 2, 3, 1))  # BGR interleaved
@@ -384,7 +390,7 @@ def test_im2col(api, dt, layout, B, Hh, Ww, ps):
         return col
 
     clean = run(rgb)
-    assert (Kpad > K) == (ps == 14) and not clean[:, K:].any()  # (patch 16: 768 columns, no pad)
+    assert (Kpad > K) == (ps != 16) and not clean[:, K:].any()  # (patch 16: 768 columns, no pad)
     mask = np.zeros(clean.shape, bool)
     hit = [tc.im2col_element(*px, Hh, Ww, ps) for px in pixels]
     assert (None in hit) == (Ww % ps != 0 or Hh % ps != 0)
@@ -392,6 +398,12 @@ def test_im2col(api, dt, layout, B, Hh, Ww, ps):
         if at is not None:
             mask[at] = True
     _ok(tc.check_footprint(run(tc.plant(rgb, pixels)), clean, mask, "pixels %r" % (pixels,)))
+    y, x = ps + 1, min(chunk, (w0 - 1) * ps) + 1  # an interior pixel: second patch row, the first patch of the second chunk where there is one
+    for c in range(3):
+        one = np.zeros(clean.shape, bool)
+        one[tc.im2col_element(1, c, y, x, Hh, Ww, ps)] = True
+        assert one.sum() == 1 and one[B * h0 * w0 // 2 + w0 + x // ps, c * ps * ps + ps + x % ps]
+        _ok(tc.check_footprint(run(tc.plant(rgb, [(1, c, y, x)])), clean, one, "pixel %r" % ((1, c, y, x),)))
 
 
 @pytest.mark.parametrize("dt", [mc.F16, mc.BF16], ids=["to_f16", "to_bf16"])

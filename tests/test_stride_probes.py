@@ -14,7 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_footprint_against_brute_force():
     """Every pixel of small images, several (patch, stride) pairs: the closed form lists exactly the col elements a brute-force gather of a
     one-hot image lights up, never more than (p / s)^2 of them, one when the pixel is a corner."""
-    for p, s, h, w in [(14, 7, 28, 42), (14, 2, 16, 20), (14, 1, 16, 17), (4, 2, 8, 10), (4, 4, 8, 12), (6, 3, 6, 6)]:
+    for p, s, h, w in [(14, 7, 28, 42), (14, 2, 16, 20), (14, 1, 16, 17), (4, 2, 8, 10), (4, 4, 8, 12), (6, 3, 6, 6),
+                       (2, 1, 4, 24), (3, 1, 5, 33), (5, 1, 7, 9), (6, 2, 10, 12), (7, 1, 9, 11)]:
         Kpad = (3 * p * p + 7) // 8 * 8
         for b, c, y, x in [(b, c, y, x) for b in range(2) for c in range(3) for y in range(h) for x in range(w)][::7]:
             rgb = np.zeros((2, 3, h, w), np.float32)
@@ -31,7 +32,8 @@ def test_footprint_against_brute_force():
 def test_expansion_identity():
     """The default im2col of the expanded image is the strided im2col of the image, grid included: the identity every GPU test rests on."""
     rng = np.random.default_rng(0)
-    for p, s, h, w in [(14, 7, 28, 42), (14, 2, 16, 20), (14, 1, 16, 17), (16, 4, 32, 48), (8, 1, 16, 20), (14, 14, 28, 42)]:
+    for p, s, h, w in [(14, 7, 28, 42), (14, 2, 16, 20), (14, 1, 16, 17), (16, 4, 32, 48), (8, 1, 16, 20), (14, 14, 28, 42)] + \
+            sc.SMALL_KERNEL + [(p, s, h, w) for p, s, _, h, w in sc.SYNTH]:
         rgb = rng.standard_normal((2, 3, h, w)).astype(np.float32)
         E = sc.expand(rgb, p, s)
         h0, w0 = sc.grid(h, w, p, s)
@@ -64,6 +66,24 @@ def test_limits_restated_from_the_kernel():
     assert not any(sc.stride_ok(34, s, sc.kpad(34)) for s in (1, 2, 17, 34))
     assert not sc.stride_ok(14, 7, 588) and not sc.stride_ok(14, 7, 584)  # Kpad: a multiple of 8 that holds 3 p^2
     assert sc.run(14, 14) == 10 and sc.run(14, 7) == 19 and sc.run(14, 2) == 64 and sc.run(14, 1) == 127
+
+
+def test_small_patch_cases_sit_where_the_comments_say():
+    """Every (patch, stride) of SMALL_PS is inside the kernel's limits, with one grid row of exactly one run and one of more; the synthetic
+    checkpoints' sizes are on their strides and give the grids the comment names."""
+    assert sc.SMALL_PS == [(p, s) for p in range(2, 8) for s in range(1, p) if p % s == 0]  # every proper divisor of every patch 2 .. 7
+    assert {p for p, _ in sc.SMALL_PS} == {2, 3, 4, 5, 6, 7} and len(sc.SMALL_KERNEL) == 2 * len(sc.SMALL_PS)
+    assert [sc.run(p, s) for p, s in sc.SMALL_PS] == [19, 28, 37, 19, 46, 55, 28, 19, 64]
+    for p, s, h, w in sc.SMALL_KERNEL:
+        assert sc.stride_ok(p, s, sc.kpad(p)) and (h - p) % s == 0 and (w - p) % s == 0
+        h0, w0 = sc.grid(h, w, p, s)
+        assert h0 == 3 and w0 in (sc.run(p, s), sc.run(p, s) + 2)
+    for p, s in sc.SMALL_PS:
+        assert sorted(sc.grid(h, w, p, s)[1] > sc.run(p, s) for q, t, h, w in sc.SMALL_KERNEL if (q, t) == (p, s)) == [False, True]
+    small = [c for c in sc.SYNTH if c[0] < 8]
+    assert [(p, s) for p, s, _, _, _ in small] == [(2, 1), (3, 1), (4, 2), (6, 2), (6, 3), (7, 1)]
+    assert [sc.grid(h, w, p, s) for p, s, _, h, w in small] == [(4, 7), (4, 5), (3, 5), (3, 4), (2, 4), (4, 6)]
+    assert all(img == 4 * p and (h - p) % s == 0 and (w - p) % s == 0 for p, s, img, h, w in small)
 
 
 def test_sizes_sit_where_the_comments_say():

@@ -302,7 +302,7 @@ def test_head_placements_and_pool_mutants(pool_regs):
 
 def test_im2col_and_patch_token_closed_forms():
     """The closed forms against the reshape restatement of tests/test_gpu_ops.py::test_im2col_bit_exact."""
-    for B, Hh, Ww, ps in ((2, 70, 98, 14), (2, 64, 83, 16)):
+    for B, Hh, Ww, ps in ((2, 70, 98, 14), (2, 64, 83, 16), (2, 11, 38, 3)):
         h0, w0 = Hh // ps, Ww // ps
         for b, c, y, x in ((0, 0, 0, 0), (1, 2, h0 * ps - 1, w0 * ps - 1), (1, 1, ps, ps - 1), (0, 1, Hh - 1, Ww - 1)):
             rgb = np.zeros((B, 3, Hh, Ww), np.float32)
@@ -312,3 +312,50 @@ def test_im2col_and_patch_token_closed_forms():
             assert [tuple(i) for i in np.argwhere(np.isnan(col))] == ([at] if at else [])
             if at:
                 assert tc.patch_token(y, x, ps, w0, 4) == 1 + 4 + at[0] - b * h0 * w0
+
+
+IM2COL_TRACER_CASES = ((2, 70, 98, 14), (2, 64, 83, 16), (2, 11, 38, 3))  # tests/test_gpu_tracers.py::test_im2col
+
+
+def _im2col_pixels(Hh, Ww, ps):
+    """The placements of tests/test_gpu_tracers.py::test_im2col: the joint one, then one pixel in each of its three channels in turn."""
+    h0, w0 = Hh // ps, Ww // ps
+    joint = [(0, 0, 0, 0), (1, 2, h0 * ps - 1, w0 * ps - 1), (0, 1, ps, ps - 1), (1, 0, ps - 1, ps), (1, 1, Hh - 1, Ww - 1), (0, 2, 2 * ps + 3, Ww - 1)]
+    chunk = tc.IM2COL_CHUNK * ps
+    if w0 > tc.IM2COL_CHUNK:
+        joint += [(0, 0, 1, chunk - 1), (1, 2, 1, chunk), (0, 1, ps + 1, chunk + 1)]
+    y, x = ps + 1, min(chunk, (w0 - 1) * ps) + 1
+    return [joint] + [[(1, c, y, x)] for c in range(3)]
+
+
+def test_im2col_restatement_and_the_swapped_divisions():
+    """The kernel's index arithmetic restated in numpy equals the reshape definition at every small patch size and at the tracer's cases, with
+    no write outside the tile.  With the two divisions by multiplication of the interleaved path exchanged, the tracer's placements fail at
+    patch 14 and 16 (and most writes leave the LDS tile, which is why that mutant is tried here and not on a device); at patch 3 the exchange
+    is the identity -- both multipliers are 21 846 -- so there is nothing for any test to see."""
+    shapes = IM2COL_TRACER_CASES + ((1, 1, 1, 1), (2, 3, 23, 1), (1, 4, 22, 2), (1, 7, 31, 3), (1, 8, 44, 4), (1, 10, 55, 5), (1, 12, 60, 6), (1, 14, 77, 7))
+    for B, Hh, Ww, ps in shapes:
+        rgb = np.random.default_rng(Hh + Ww).standard_normal((B, 3, Hh, Ww)).astype(np.float32)
+        h0, w0 = Hh // ps, Ww // ps
+        K = 3 * ps * ps
+        ref = np.zeros((B * h0 * w0, (K + 63) // 64 * 64), np.float32)
+        ref[:, :K] = rgb[:, :, :h0 * ps, :w0 * ps].reshape(B, 3, h0, ps, w0, ps).transpose(0, 2, 4, 1, 3, 5).reshape(B * h0 * w0, K)
+        for layout in (1, 0):
+            col, outside = tc.im2col_emulate(rgb, ps, layout)
+            assert outside == 0 and np.array_equal(col, ref), (B, Hh, Ww, ps, layout)
+    assert 65536 // 3 + 1 == 21846
+    for B, Hh, Ww, ps in IM2COL_TRACER_CASES:
+        rgb = np.random.default_rng(Hh + Ww).standard_normal((B, 3, Hh, Ww)).astype(np.float32)
+        clean = tc.im2col_emulate(rgb, ps, 0)[0]
+        caught = []
+        for pixels in _im2col_pixels(Hh, Ww, ps):
+            mask = np.zeros(clean.shape, bool)
+            for px in pixels:
+                at = tc.im2col_element(*px, Hh, Ww, ps)
+                if at is not None:
+                    mask[at] = True
+            _ok(tc.check_footprint(tc.im2col_emulate(tc.plant(rgb, pixels), ps, 0)[0], clean, mask, "unmutated"))
+            got, outside = tc.im2col_emulate(tc.plant(rgb, pixels), ps, 0, mutant="div3_divps_swapped")
+            caught.append(not tc.check_footprint(got, clean, mask, "swapped")[0])
+            assert (outside > 0) == (ps != 3)
+        assert all(caught) if ps != 3 else not any(caught), (ps, caught)

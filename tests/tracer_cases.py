@@ -384,6 +384,53 @@ def im2col_element(b, c_rgb, y, x, Hh, Ww, ps):
     return (b * h0 * w0 + (y // ps) * w0 + x // ps, c_rgb * ps * ps + (y % ps) * ps + x % ps)
 
 
+IM2COL_CHUNK = 10  # csrc/kernels.h
+
+
+def im2col_emulate(rgb, ps, layout, mutant=None):
+    """im2col_kernel's index arithmetic restated (csrc/kernels_misc.hip), values in float32: per (image, patch row, chunk of ten patches) the
+    LDS tile [np][Kpad] is zero in the K padding and filled from contiguous image runs -- planar: element e of the run of (channel c0, row
+    ky) goes to patch pl = e / ps (by multiplication, magic = 65536 / ps + 1) at k = c0 ps^2 + ky ps + e % ps; BGR-interleaved: element e of
+    the run of row ky is pixel e / 3 (by multiplication with 21 846), channel 2 - e % 3.  Returns (col [B h0 w0, Kpad], the number of writes
+    that fell outside the tile: they are dropped here).
+    mutant "div3_divps_swapped": the two multipliers of the interleaved path exchanged.  At patch 3 it is NOT a mutant -- 65536 / 3 + 1 is
+    21 846, the same number --; at every other patch size the channel term leaves 0 .. 2 and most writes leave the tile."""
+    B, _, Hh, Ww = rgb.shape
+    img = rgb if layout == 1 else np.ascontiguousarray(rgb[:, ::-1].transpose(0, 2, 3, 1))
+    Kreal, pp2 = 3 * ps * ps, ps * ps
+    Kpad = (Kreal + 63) // 64 * 64
+    h0, w0 = Hh // ps, Ww // ps
+    magic, third = 65536 // ps + 1, 21846
+    if mutant == "div3_divps_swapped":
+        magic, third = third, magic
+    col = np.full((B * h0 * w0, Kpad), NAN, np.float32)  # (as the testing op pre-fills it)
+    outside = 0
+    for b in range(B):
+        for py in range(h0):
+            for px0 in range(0, w0, IM2COL_CHUNK):
+                np_ = min(IM2COL_CHUNK, w0 - px0)
+                run = np_ * ps
+                tile = np.full(np_ * Kpad, NAN, np.float32)
+                tile.reshape(np_, Kpad)[:, Kreal:] = 0.0
+                for rr in range(3 * ps if layout == 1 else ps):
+                    c0, ky = (rr // ps, rr % ps) if layout == 1 else (0, rr)
+                    y = py * ps + ky
+                    src = img[b, c0, y, px0 * ps:px0 * ps + run] if layout == 1 else img[b, y, px0 * ps:px0 * ps + run].reshape(-1)
+                    e = np.arange(len(src), dtype=np.int64)
+                    xo, cc = e, np.zeros_like(e)
+                    if layout != 1:
+                        xo = (e * third) >> 16
+                        cc = (2 - (e - 3 * xo)) * pp2
+                    pl = (xo * magic) >> 16
+                    at = pl * Kpad + cc + (xo - pl * ps) + c0 * pp2 + ky * ps
+                    ok = (at >= 0) & (at < tile.size)
+                    outside += int((~ok).sum())
+                    tile[at[ok]] = src[ok]
+                row0 = b * h0 * w0 + py * w0 + px0
+                col[row0:row0 + np_] = tile.reshape(np_, Kpad)
+    return col, outside
+
+
 def patch_token(y, x, ps, w0, R):
     """Token row of the patch that pixel (y, x) of an image belongs to: 1 + R + (y // ps) * w0 + x // ps."""
     return 1 + R + (y // ps) * w0 + x // ps
