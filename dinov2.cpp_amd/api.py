@@ -177,12 +177,15 @@ def build_id() -> str:
     return lib().dinov2_hip_build_id().decode()
 
 
-def gemm_plan(dtype, epilogue, M, N, K):
-    """The kernel plan launch_gemm picks for a shape (text; no device needed)."""
+def gemm_plan(dtype, epilogue, M, N, K, lda=0, ldw=0):
+    """The kernel plan launch_gemm picks for a shape (text; no device needed).  lda, ldw: row strides of A and W in elements, 0 = K."""
     buf = C.create_string_buffer(256)
-    rc = lib().dinov2_hip_op_gemm_plan(int(dtype), int(epilogue), int(M), int(N), int(K), buf, 256)
+    if lda or ldw:
+        rc = lib().dinov2_hip_op_gemm_plan_strided(int(dtype), int(epilogue), int(M), int(N), int(K), int(lda), int(ldw), buf, 256)
+    else:
+        rc = lib().dinov2_hip_op_gemm_plan(int(dtype), int(epilogue), int(M), int(N), int(K), buf, 256)
     if rc != 0:
-        raise ValueError(f"launch_gemm refuses dtype={dtype} epilogue={epilogue} M={M} N={N} K={K}")
+        raise ValueError(f"launch_gemm refuses dtype={dtype} epilogue={epilogue} M={M} N={N} K={K} lda={lda} ldw={ldw}")
     return buf.value.decode()
 
 
@@ -215,6 +218,55 @@ def _ptr(a):
 
 def _f32(a):
     return None if a is None else np.ascontiguousarray(a, np.float32)
+
+
+OP_NO_MEMORY = -3  # DINOV2_HIP_OP_NO_MEMORY: a far op's allocation was refused
+
+
+class DeviceMemoryRefused(RuntimeError):
+    """A far-operand op could not allocate its buffers (it reports that apart from a HIP error)."""
+
+
+def device_memory():
+    """(free, total) bytes of the current device (hipMemGetInfo)."""
+    free, total = C.c_int64(0), C.c_int64(0)
+    _op_rc(lib().dinov2_hip_op_device_memory(C.byref(free), C.byref(total)), "device_memory")
+    return free.value, total.value
+
+
+def _far_rc(rc, name):
+    if rc == OP_NO_MEMORY:
+        raise DeviceMemoryRefused(f"dinov2_hip_op_{name}: a device allocation was refused")
+    if rc == 4:
+        raise ValueError(f"dinov2_hip_op_{name} refuses these arguments")
+    _op_rc(rc, name)
+
+
+def op_gemm_far(dtype, epilogue, M, N, K, W, bias, aux, rows, *, lda=0, ldw=0, ldo=0, seed_a=1, seed_out=2, qcols=0, qscale=1.0):
+    """launch_gemm once on a device-made A [M, K] at row stride lda (dinov2_hip_op_gemm_far): W [N, K], bias [N], aux [N] host f32.  Returns
+    (the output rows `rows` as f32 [len(rows), width], the number of payload elements the launch left untouched).  Raises ValueError for a
+    shape the launcher refuses, DeviceMemoryRefused, AssertionError for a changed guard band."""
+    W = _f32(W)
+    assert W.shape == (N, K), W.shape
+    width = N // 2 if epilogue == 4 else N
+    r = np.ascontiguousarray(rows, np.int64)
+    out = np.full((len(r), width), np.nan, np.float32)
+    untouched = C.c_int64(-1)
+    _far_rc(lib().dinov2_hip_op_gemm_far(int(dtype), int(epilogue), int(M), int(N), int(K), int(lda or K), int(ldw or K), int(ldo or width),
+                                         int(seed_a), int(seed_out), _ptr(W), _ptr(_f32(bias)), _ptr(_f32(aux)), int(qcols), float(qscale),
+                                         _ptr(r), len(r), _ptr(out), C.byref(untouched)), "gemm_far")
+    return out, untouched.value
+
+
+def op_attention_far(dtype, B, T, nh, rows, *, seed=1, log2_scores=True):
+    """launch_attention once on a device-made qkv [B*T, 3*64*nh] (dinov2_hip_op_attention_far).  Returns (rows `rows` of the output as f32
+    [len(rows), 64*nh], the untouched count); raises as op_gemm_far."""
+    r = np.ascontiguousarray(rows, np.int64)
+    out = np.full((len(r), 64 * nh), np.nan, np.float32)
+    untouched = C.c_int64(-1)
+    _far_rc(lib().dinov2_hip_op_attention_far(int(dtype), int(B), int(T), int(nh), int(seed), int(log2_scores), _ptr(r), len(r), _ptr(out),
+                                              C.byref(untouched)), "attention_far")
+    return out, untouched.value
 
 
 def op_layer_tap(x, w, b, eps, R, h0, w0, *, norm, chw, want=("patch", "cls", "reg")):
@@ -697,8 +749,14 @@ def lib():
     L.dinov2_hip_op_set_tuning.argtypes = [cp, i32]
     L.dinov2_hip_op_get_tuning.argtypes = [cp]
     L.dinov2_hip_op_gemm_plan.argtypes = [i32, i32, i32, i32, i32, C.c_char_p, i32]
-    L.dinov2_hip_op_gemm_plan_parts.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64), i32]
+    L.dinov2_hip_op_gemm_plan_strided.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.c_char_p, i32]
+    L.dinov2_hip_op_gemm_plan_parts.argtypes =[i32, i32, i32, i32, i32, C.POINTER(C.c_int64), i32]
     L.dinov2_hip_op_stream_delay.argtypes = [vp, i32]
+    i64p = C.POINTER(C.c_int64)
+    L.dinov2_hip_op_device_memory.argtypes = [i64p, i64p]
+    L.dinov2_hip_op_gemm_far.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint64, fp, fp, fp, i32, C.c_float, i64p, i32, fp,
+                                         i64p]
+    L.dinov2_hip_op_attention_far.argtypes = [i32, i32, i32, i32, C.c_uint64, i32, i64p, i32, fp, i64p]
     _lib = L
     return L
 

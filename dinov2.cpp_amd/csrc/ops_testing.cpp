@@ -13,6 +13,7 @@
 #include "../../include/dinov2_hip.h"
 #include "../../include/dinov2_hip_ops.h"
 #include "device_types.h"
+#include "far_pattern.h"
 #include "host.h"
 #include "ops_frame.h"
 
@@ -446,6 +447,186 @@ extern "C" int dinov2_hip_op_probe_tr16(int16_t* out256) {
     return d.fetch(out256);
 }
 
+// ---- far operands: ONE launch of a GEMM or of attention whose operands end just below the launchers' 32-bit byte-offset limits.  Host
+// operands of that size would take gigabytes and tens of seconds to round, so A / qkv (and a residual's initial contents) are written on the
+// device from far_value (csrc/far_pattern.h); the caller gets the output rows it lists, the number of payload elements that still hold their
+// initial bits, and DINOV2_HIP_OP_GUARD_CHANGED if a guard band changed -- all three found on the device. ----
+namespace {
+
+enum FarKind : int { FAR_F16 = 0, FAR_BF16 = 1, FAR_F32 = 2 };
+constexpr int FAR_BLOCKS = 4096, FAR_THREADS = 256;
+
+// p[r * ld + c] = far_value(seed, r, c) as `kind`, r < rows, c < cols; the gap cols .. ld of a row is left as it is
+__global__ void far_fill_kernel(void* p, size_t rows, int cols, size_t ld, int kind, uint64_t seed) {
+    const size_t n = rows * (size_t)cols, step = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        const size_t r = i / (size_t)cols;
+        const int c = (int)(i - r * (size_t)cols);
+        const float v = far_value(seed, r, (uint32_t)c);
+        const size_t at = r * ld + (size_t)c;
+        if (kind == FAR_F32) {
+            ((float*)p)[at] = v;
+        } else if (kind == FAR_F16) {
+            ((_Float16*)p)[at] = (_Float16)v;
+        } else {
+            ((uint16_t*)p)[at] = (uint16_t)(__float_as_uint(v) >> 16);  // exact: 7 significant bits
+        }
+    }
+}
+
+// *count += the payload elements (r < rows, c < cols at row stride ld) that still hold their initial bits: all-ones elements of esz bytes
+// (pattern = 0), or the f32 pattern value of `seed` (pattern = 1, esz = 4)
+__global__ void far_count_kernel(const void* p, size_t rows, int cols, size_t ld, int esz, int pattern, uint64_t seed, unsigned long long* count) {
+    const size_t n = rows * (size_t)cols, step = (size_t)gridDim.x * blockDim.x;
+    unsigned long long mine = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
+        const size_t r = i / (size_t)cols;
+        const int c = (int)(i - r * (size_t)cols);
+        const size_t at = r * ld + (size_t)c;
+        if (esz == 2) mine += ((const uint16_t*)p)[at] == 0xffffu;
+        else if (!pattern) mine += ((const uint32_t*)p)[at] == 0xffffffffu;
+        else mine += ((const uint32_t*)p)[at] == __float_as_uint(far_value(seed, r, (uint32_t)c));
+    }
+    if (mine) atomicAdd(count, mine);
+}
+
+// *count += the 32-bit words of [p, p + words) that are not all ones
+__global__ void far_band_kernel(const uint32_t* p, size_t words, unsigned long long* count) {
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    unsigned long long mine = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += step) mine += p[i] != 0xffffffffu;
+    if (mine) atomicAdd(count, mine);
+}
+
+// dst[i][0 .. units) = the first `units` two-byte units of row rows[i] of src (row stride ld_units two-byte units); one block per listed row
+__global__ void far_gather_kernel(const uint16_t* src, size_t ld_units, const int64_t* rows, int units, uint16_t* dst) {
+    const uint16_t* s = src + (size_t)rows[blockIdx.x] * ld_units;
+    uint16_t* d = dst + (size_t)blockIdx.x * (size_t)units;
+    for (int k = threadIdx.x; k < units; k += blockDim.x) d[k] = s[k];
+}
+
+// a refused allocation is an answer of its own (the caller asked hipMemGetInfo first and may skip on it), any other failure a HIP error
+#define FAR_ALLOC(x)                                                          \
+    do {                                                                      \
+        const hipError_t e__ = (x);                                           \
+        if (e__ == hipErrorOutOfMemory) {                                     \
+            (void)hipGetLastError();                                          \
+            return DINOV2_HIP_OP_NO_MEMORY;                                   \
+        }                                                                     \
+        if (e__ != hipSuccess) return -1;                                     \
+    } while (0)
+
+hipError_t far_fill(const OpBuf& b, size_t rows, int cols, size_t ld, int kind, uint64_t seed) {
+    far_fill_kernel<<<FAR_BLOCKS, FAR_THREADS>>>(b.as<void>(), rows, cols, ld, kind, seed);
+    return hipGetLastError();
+}
+
+// What both far ops end with.  out: [rows_all, ld] elements of esz bytes between guard bands, `width` payload columns.  0, -1,
+// DINOV2_HIP_OP_GUARD_CHANGED; *untouched and the listed rows (widened to f32 when esz == 2) are written on 0 only.
+int far_collect(const OpBuf& out, DType dt, size_t rows_all, int width, size_t ld, int pattern, uint64_t seed_o, const int64_t* rows, int nrows,
+                float* out_rows, int64_t* untouched) {
+    OpBuf dCnt, dRows, dG;
+    OP_TRY(dCnt.alloc(2, 8, OpBuf::zeros()));
+    unsigned long long* cnt = dCnt.as<unsigned long long>();
+    const size_t band_words = out.ng * out.esz / 4;
+    if (band_words) {
+        far_band_kernel<<<FAR_BLOCKS, FAR_THREADS>>>((const uint32_t*)out.p, band_words, cnt);
+        far_band_kernel<<<FAR_BLOCKS, FAR_THREADS>>>((const uint32_t*)(out.as<char>() + out.n * out.esz), band_words, cnt);
+    }
+    far_count_kernel<<<FAR_BLOCKS, FAR_THREADS>>>(out.as<void>(), rows_all, width, ld, (int)out.esz, pattern, seed_o, cnt + 1);
+    OP_TRY(hipGetLastError());
+    const int units = width * (int)out.esz / 2;
+    OP_TRY(dRows.upload(rows, sizeof(int64_t) * (size_t)nrows));
+    OP_TRY(dG.alloc((size_t)nrows * units, 2, OpBuf::nans()));
+    far_gather_kernel<<<nrows, FAR_THREADS>>>(out.as<uint16_t>(), ld * out.esz / 2, dRows.as<int64_t>(), units, dG.as<uint16_t>());
+    OP_TRY(hipGetLastError());
+    OP_TRY(hipDeviceSynchronize());
+    unsigned long long c[2] = {0, 0};
+    OP_TRY(dCnt.read(c, 0, sizeof(c)));
+    if (c[0]) return DINOV2_HIP_OP_GUARD_CHANGED;
+    *untouched = (int64_t)c[1];
+    if (out.esz == 4) return dG.fetch(out_rows);
+    std::vector<uint16_t> raw((size_t)nrows * units);
+    OP_FETCH(dG.fetch(raw.data()));
+    widen_to_f32(dt == DT_BF16, raw.data(), raw.size(), out_rows);
+    return 0;
+}
+
+bool far_rows_ok(const int64_t* rows, int nrows, int64_t limit) {
+    if (!rows || nrows <= 0 || nrows > (1 << 20)) return false;
+    for (int i = 0; i < nrows; ++i)
+        if (rows[i] < 0 || rows[i] >= limit) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int dinov2_hip_op_device_memory(int64_t* free_bytes, int64_t* total_bytes) {
+    size_t f = 0, t = 0;
+    OP_TRY(hipMemGetInfo(&f, &t));
+    if (free_bytes) *free_bytes = (int64_t)f;
+    if (total_bytes) *total_bytes = (int64_t)t;
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_gemm_far(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t ldo,
+                                      uint64_t seed_a, uint64_t seed_out, const float* W, const float* bias, const float* aux, int32_t qcols,
+                                      float qscale, const int64_t* rows, int32_t nrows, float* out_rows, int64_t* untouched) {
+    const DType dt = dtype_of(dtype);
+    if (epilogue < EPI_QKV || epilogue > EPI_PLAIN_F32 || M <= 0 || N <= 0 || K <= 0 || lda < K || ldw < K || !W || !out_rows || !untouched ||
+        !far_rows_ok(rows, nrows, M))
+        return DINOV2_HIP_ERR_INVALID;
+    const int width = epilogue == EPI_SWIGLU ? N / 2 : N;
+    if (ldo < width || (epilogue == EPI_RESID && !aux)) return DINOV2_HIP_ERR_INVALID;
+    {  // the planner's own refusal (the strides included), before anything is allocated
+        GemmArgs q{};
+        q.M = M; q.N = N; q.K = K; q.lda = lda; q.ldw = ldw; q.ldo = ldo; q.P = 1; q.T = 2; q.qcols = qcols;
+        GemmPlan plan;
+        if (gemm_plan(dt, (Epilogue)epilogue, q, false, &plan) != hipSuccess) return DINOV2_HIP_ERR_INVALID;
+    }
+    if (gemm_init() != hipSuccess) return -1;
+    const bool f32out = epilogue == EPI_RESID || epilogue == EPI_PLAIN_F32;
+    OpBuf dA, dW, dB, dX, dO;
+    FAR_ALLOC(dA.alloc((size_t)M * lda, 2, OpBuf::nans()));  // the gap K .. lda of every row stays NaN
+    OP_TRY(far_fill(dA, (size_t)M, K, (size_t)lda, dt == DT_BF16 ? FAR_BF16 : FAR_F16, seed_a));
+    if (ldw == K) {
+        FAR_ALLOC(dW.upload_as(dt, W, (size_t)N * K));
+    } else {
+        std::vector<uint16_t> w((size_t)N * K);
+        for (size_t i = 0; i < w.size(); ++i) w[i] = OpBuf::round_to(dt, W[i]);
+        FAR_ALLOC(dW.alloc((size_t)N * ldw, 2, OpBuf::nans()));
+        OP_TRY(hipMemcpy2D(dW.p, (size_t)ldw * 2, w.data(), (size_t)K * 2, (size_t)K * 2, (size_t)N, hipMemcpyHostToDevice));
+    }
+    if (bias) OP_TRY(dB.upload(bias, sizeof(float) * N));
+    if (aux) OP_TRY(dX.upload(aux, sizeof(float) * N));
+    FAR_ALLOC(dO.alloc((size_t)M * ldo, f32out ? 4 : 2, OpBuf::nans(), (size_t)ldo));
+    if (epilogue == EPI_RESID) OP_TRY(far_fill(dO, (size_t)M, width, (size_t)ldo, FAR_F32, seed_out));
+    GemmArgs a{};
+    a.A = dA.p; a.W = dW.p; a.bias = dB.as<float>(); a.out = dO.as<void>(); a.aux = dX.as<float>();
+    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldo = ldo; a.P = 1; a.T = 2; a.qcols = qcols; a.qscale = qscale;
+    OP_TRY(launch_gemm(dt, (Epilogue)epilogue, a, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    return far_collect(dO, dt, (size_t)M, width, (size_t)ldo, epilogue == EPI_RESID, seed_out, rows, nrows, out_rows, untouched);
+}
+
+extern "C" int dinov2_hip_op_attention_far(int32_t dtype, int32_t B, int32_t T, int32_t nh, uint64_t seed, int32_t log2_scores, const int64_t* rows,
+                                           int32_t nrows, float* out_rows, int64_t* untouched) {
+    const DType dt = dtype_of(dtype);
+    if (B <= 0 || T <= 0 || nh <= 0 || nh > 64 || !out_rows || !untouched || (int64_t)B * T > (int64_t)INT32_MAX ||
+        !far_rows_ok(rows, nrows, (int64_t)B * T))
+        return DINOV2_HIP_ERR_INVALID;
+    const int H = 64 * nh;
+    if ((size_t)B * T * 3 * H * 2 >= ((size_t)1 << 32)) return DINOV2_HIP_ERR_INVALID;  // launch_attention's own refusal, before anything is allocated
+    const size_t M = (size_t)B * T;
+    OpBuf dQ, dO;
+    FAR_ALLOC(dQ.alloc(M * 3 * H, 2, OpBuf::nans()));
+    OP_TRY(far_fill(dQ, M, 3 * H, (size_t)3 * H, dt == DT_BF16 ? FAR_BF16 : FAR_F16, seed));
+    FAR_ALLOC(dO.alloc(M * H, 2, OpBuf::nans(), (size_t)H));
+    OP_TRY(launch_attention(dt, dQ.p, dO.as<void>(), B, T, H, nh, log2_scores != 0, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    return far_collect(dO, dt, M, H, (size_t)H, 0, 0, rows, nrows, out_rows, untouched);
+}
+
 // ---- micro-benchmarks: device-resident random operands, HIP-event timing around `iters` launches ----
 namespace {
 // the two events a timed loop sits between, destroyed on return
@@ -565,6 +746,14 @@ static GemmArgs plan_query_args(int32_t epilogue, int32_t M, int32_t N, int32_t 
 extern "C" int dinov2_hip_op_gemm_plan(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, char* out, int32_t cap) {
     if (!out || cap <= 0 || epilogue < 0 || epilogue > EPI_SWIGLU_LN) return DINOV2_HIP_ERR_INVALID;
     const GemmArgs a = plan_query_args(epilogue, M, N, K);
+    return gemm_plan_describe(dtype_of(dtype), (Epilogue)epilogue, a, out, (size_t)cap) == hipSuccess ? DINOV2_HIP_OK : DINOV2_HIP_ERR_INVALID;
+}
+// ... with row strides of A and W (0 = K): what stamp_args refuses of them is refused here
+extern "C" int dinov2_hip_op_gemm_plan_strided(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, char* out,
+                                               int32_t cap) {
+    if (!out || cap <= 0 || epilogue < 0 || epilogue > EPI_SWIGLU_LN) return DINOV2_HIP_ERR_INVALID;
+    GemmArgs a = plan_query_args(epilogue, M, N, K);
+    a.lda = lda; a.ldw = ldw;
     return gemm_plan_describe(dtype_of(dtype), (Epilogue)epilogue, a, out, (size_t)cap) == hipSuccess ? DINOV2_HIP_OK : DINOV2_HIP_ERR_INVALID;
 }
 // The same plan as data.  Every pointer of the query is a distinct made-up address (never dereferenced), so that what a part's arguments add

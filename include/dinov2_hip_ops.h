@@ -58,6 +58,28 @@ int dinov2_hip_op_attention(int32_t dtype, const float *qkv, float *out, int32_t
 int dinov2_hip_op_attention_ex(int32_t dtype, const float *qkv, float *out, int32_t B, int32_t T, int32_t H, int32_t nh,
                                int32_t log2_scores);
 
+/* Far operands: ONE launch of launch_gemm / launch_attention whose operands end just below the launchers' 32-bit byte-offset limits
+ * (M * lda * 2, N * ldw * 2 and B * T * 3H * 2 < 2^32).  Cases, the numpy restatement of the pattern and the sampled rows: tests/far_cases.py;
+ * tests/test_far_probes.py (CPU), tests/test_gpu_far.py.  The large operands are written ON THE DEVICE from far_value (csrc/far_pattern.h: a
+ * multiple of 1/64 in [-1, 1), a pure function of (seed, row, col)); every device buffer starts as 0xff bytes, so the gap between a row's last
+ * column and its stride reads as NaN; the output sits between guard bands of DINOV2_HIP_OP_GUARD_ROWS rows.  Everything is freed on return.
+ * Returns 0, -1 (HIP error), DINOV2_HIP_OP_GUARD_CHANGED, DINOV2_HIP_OP_NO_MEMORY (an allocation was refused) or DINOV2_HIP_ERR_INVALID (bad
+ * arguments, or a shape the launcher refuses: nothing is allocated or launched then).
+ *   device_memory: hipMemGetInfo of the current device.
+ *   gemm_far: A [M, K] at row stride lda = far_value(seed_a, m, k); W [N, K] (host f32, rounded as dinov2_hip_op_gemm rounds it; placed at row
+ *             stride ldw when ldw > K), bias [N] and aux [N] from the host; epilogue 1 .. 5.  The output [M, ldo] starts as NaN, or, for
+ *             epilogue 2, as the f32 values far_value(seed_out, m, n).  out_rows [nrows, N (N / 2 for epilogue 4)] = the output rows rows[i]
+ *             as f32; *untouched = the payload elements that still hold their initial bits.
+ *   attention_far: qkv [B * T, 3 * 64 * nh] = far_value(seed, row, col) (q counts as already scaled) -> out_rows [nrows, 64 * nh] = the rows
+ *             rows[i] of out [B * T, 64 * nh]; the kernel follows "attn_v" / "attn_nwv" as in dinov2_hip_op_attention_ex. */
+#define DINOV2_HIP_OP_NO_MEMORY (-3)
+int dinov2_hip_op_device_memory(int64_t *free_bytes, int64_t *total_bytes);
+int dinov2_hip_op_gemm_far(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t ldo,
+                           uint64_t seed_a, uint64_t seed_out, const float *W, const float *bias, const float *aux, int32_t qcols, float qscale,
+                           const int64_t *rows, int32_t nrows, float *out_rows, int64_t *untouched);
+int dinov2_hip_op_attention_far(int32_t dtype, int32_t B, int32_t T, int32_t nh, uint64_t seed, int32_t log2_scores, const int64_t *rows,
+                                int32_t nrows, float *out_rows, int64_t *untouched);
+
 /* dinov2_hip_predict_list (include/dinov2_hip.h).  Cases, the numpy restatement of the plan and the per-segment emulation: tests/list_cases.py;
  * tests/test_list_probes.py (CPU), tests/test_gpu_attention_list.py, tests/test_gpu_predict_list.py.
  * list_plan (no device; list_plan of csrc/kernels.h): n images of NETWORK size h[i] x w[i] pixels, `patch` pixels per patch side, R register
@@ -146,6 +168,10 @@ int dinov2_hip_op_get_tuning(const char *key); /* -1: unknown key */
 /* Which kernel plan the GEMM planner (csrc/gemm.hip gemm_plan; launch_gemm launches it) picks for a shape, as text: ';'-separated leaves such as "gemm4_mixed<256+192>", "gemm2<128>",
  * "gemm4<256>;small<64x128,w2x2,st3,ks1>".  Needs no device (nothing is launched).  0 on success. */
 int dinov2_hip_op_gemm_plan(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, char *out, int32_t cap);
+/* The same for A and W at row strides lda and ldw (elements; 0 = K).  The plan of a strided call is the plan of (M, N, K); the strides enter the
+ * refusals only (a multiple of 8, at least K, M * lda * 2 and N * ldw * 2 below 2^32). */
+int dinov2_hip_op_gemm_plan_strided(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, char *out,
+                                    int32_t cap);
 /* The same plan as data: one record of DINOV2_HIP_PLAN_PART_FIELDS int64 per argument block a kernel of the plan is launched with (a step of
  * a two-height kernel has two, the first possibly empty), in launch order:
  *   0 step (index into the text's leaves)  1 part within the step  2 row0  3 rows  4 col0  5 cols: the rectangle of the output it covers

@@ -122,16 +122,47 @@ def error_bound(o, A, S, M, qkv, B, T, nh, dt, log2):
       * f32 PV accumulation, the l sum, 1/l and the rescales (alpha scales O and l alike): eps_acc A_d, eps_acc = (4 n_tiles + 64) 2^-24
       * one final rounding to T: u |o| (f16: + 2^-25 for a subnormal result)
     """
-    u = U[dt]
-    ntiles = (T + KT - 1) // KT
     vmax = np.abs(split_heads(qkv, B, T, nh)[2]).max(2)  # [B, nh, 64]
     vmax = np.repeat(vmax.reshape(B, 1, nh * 64), T, 1).reshape(B * T, nh * 64)
+    return _bound(o, A, S, M, vmax, T, dt, log2)
+
+
+def _bound(o, A, S, M, vmax, T, dt, log2):
+    """error_bound's formula: o, A, vmax [rows, 64 * heads]; S, M [rows, heads]; T keys."""
+    u = U[dt]
+    ntiles = (T + KT - 1) // KT
     ds = 72 * 2.0 ** -24 * (S + np.abs(M))
     eps_p = np.repeat(ds * (LN2 if log2 else 1.0) + 2.0 ** -22, 64, axis=1)
     eps_acc = (4 * ntiles + 64) * 2.0 ** -24
     sub = T * (2.0 ** -25 if dt == F16 else 2.0 ** -126) * vmax
     inner = u * A + sub + 2 * eps_p * A + eps_acc * A
     return inner + u * (np.abs(o) + inner) + (2.0 ** -25 if dt == F16 else 0.0)
+
+
+def reference_rows(q, k, v, log2, chunk=64):
+    """reference() for SOME queries of ONE (image, head): q [nq, 64], k, v [T, 64] -> o, A [nq, 64], S, M [nq].  The same float64 arithmetic, a
+    chunk of queries at a time, for sequences whose full score matrix no host holds (tests/far_cases.py)."""
+    q, k, v = (np.asarray(x, np.float64) for x in (q, k, v))
+    nq = len(q)
+    o, A, S, M = np.empty((nq, 64)), np.empty((nq, 64)), np.empty(nq), np.empty(nq)
+    ka, va = np.abs(k), np.abs(v)
+    for i in range(0, nq, chunk):
+        j = slice(i, min(nq, i + chunk))
+        s = q[j] @ k.T
+        M[j] = s.max(-1)
+        S[j] = (np.abs(q[j]) @ ka.T).max(-1)
+        p = np.exp((s - M[j][:, None]) * (LN2 if log2 else 1.0))
+        l = p.sum(-1, keepdims=True)
+        o[j] = (p @ v) / l
+        A[j] = (p @ va) / l
+    return o, A, S, M
+
+
+def error_bound_rows(o, A, S, M, v, dt, log2):
+    """error_bound for the rows of reference_rows: the same formula, with the head's own max_j |v_jd| and key count."""
+    v = np.asarray(v, np.float64)
+    vmax = np.repeat(np.abs(v).max(0)[None, :], len(o), 0)
+    return _bound(o, A, S[:, None], M[:, None], vmax, len(v), dt, log2)
 
 
 def check_against_reference(out, ref, bound):

@@ -307,7 +307,7 @@ def test_largest_patch_loads_at_its_strides(api, pkg, tmp_path):
 
 def test_single_image_limit_of_a_pass(api, pkg, tmp_path):
     """An image whose own token rows times the widest activation row times 2 bytes reach 2^31 is refused by every predict entry point
-    before anything is allocated or launched; just below the limit the checks pass (that forward is not run here)."""
+    before anything is allocated or launched; just below the limit the checks pass (attention over one image of that size is run by case A2 of tests/test_gpu_far.py)."""
     path = str(tmp_path / "small1.gguf")
     pkg.synth.write_synthetic_gguf(path, "small", registers=4, num_classes=10, layers=1)
     model = api.Model(path, patch_stride=1)
