@@ -49,6 +49,22 @@ inline Dims dims_of(const dinov2_hip_model* m, int B, int h, int w) {
     return d;
 }
 
+// The runs of a pass (model.h), no device needed.  A uniform batch is one run that starts at row, patch and image 0 ...
+inline PassRun uniform_run(const dinov2_hip_model* m, const float* img, int B, int h, int w, const float* pos) {
+    const Dims d = dims_of(m, B, h, w);
+    return PassRun{img, B, h, w, pos, 0, 0, 0, d.P, d.T};
+}
+// ... and a list has list_plan's runs, each behind the rows and patches of the runs before it (hs / ws: network sizes per image; the caller
+// fills in img and pos)
+inline void list_runs(const ListImage* im, const ListRun* lr, int nruns, const int32_t* hs, const int32_t* ws, PassRun* out) {
+    int64_t patch0 = 0;
+    for (int r = 0; r < nruns; ++r) {
+        const int i0 = lr[r].first;
+        out[r] = PassRun{nullptr, lr[r].count, hs[i0], ws[i0], nullptr, im[i0].row0, patch0, i0, im[i0].P, im[i0].T};
+        patch0 += (int64_t)lr[r].count * im[i0].P;
+    }
+}
+
 // load.cpp: the widest activation row of a forward in elements (qkv, the FFN hidden layer or the im2col matrix), and one image of network
 // size h x w against the limit of a pass: token rows * widest_row * 2 bytes below 2^31 (model.h: dinov2_check_pass_rows words the refusal)
 size_t widest_row(const dinov2_hip_model* m);

@@ -4,7 +4,8 @@
 //   build_graph + dino_predict  /root/reference/dinov2.cpp:823-838, :900-999  -> forward() + dinov2_hip_predict
 // There is no graph builder / allocator / backend scheduler here: the forward is a fixed sequence of ~8 fused
 // kernel launches per layer on one HIP stream over a pre-carved workspace.
-// dinov2_hip_predict_list (no reference counterpart) is here too: forward_list() is forward() over images of different sizes.
+// dinov2_hip_predict_list (no reference counterpart) is here too: forward() takes a pass of runs (model.h), a uniform batch is one run and a
+// list of images of different sizes one run per stretch of equal sizes; copy_out() hands out the results of either.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -245,7 +246,7 @@ void drain_profile(dinov2_hip_session* s) {
 
 // The forward pass: forward_features (dinov2.cpp:616-790) [+ forward_head :792-821], `nlayers` <= L layers.
 // pos-embed for this grid, cached per (h0, w0): the reference recomputes it on every call (dinov2.cpp:937).  Host work +
-// synchronisation: must run BEFORE a stream capture, never inside one.
+// synchronisation: the callers of forward() run it first, BEFORE a stream capture, never inside one.
 int prepare_pos(dinov2_hip_session* s, int B, int h, int w, char* err, size_t errlen) {
     const dinov2_hip_model* m = s->model;
     const int H = (int)m->hp.hidden_size;
@@ -270,39 +271,47 @@ struct LayerCursor {
     int take(int layer) { return next < n && layers[next] == layer ? next++ : -1; }
 };
 
-// `img` is a DEVICE pointer.  Leaves final-LN tokens in s->fin, logits/probs in s->logits/s->probs.
+// One pass over `p.runs` (model.h): the residual stream holds the runs' token rows one after the other.  The embedding and the head run once
+// per run with B = its length and its own position embedding and pooling divisor; every layer launch works per row and takes M = all rows;
+// attention goes over runs[0] or over the list's work table.  The position embeddings (prepare_pos / prepare_pos_list) and the table
+// (prepare_items_list) are there before the call: nothing here synchronises or allocates, so a pass can be captured into a graph.
+// Leaves final-LN tokens in s->fin, logits / probs [images, C] in s->logits / s->probs.
 // ex.taps (dinov2_hip_predict_layers): one layer_tap launch per requested layer, on x as it stands after that many layers.  ex.attn
 // (dinov2_hip_predict_attention): one attn_rows launch per requested block, on that block's qkv right after its QKV GEMM (the next block
 // overwrites qkv; attention only reads it).  ex.dense (dinov2_hip_predict_dense): one dense_pack launch per requested layer, beside the tap.
 // Without any of them, the launches are those of a plain forward.
-int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int layout, bool classify, int nlayers, bool finalize,
-            const PassExtras& ex, char* err, size_t errlen) {
+int forward(dinov2_hip_session* s, const Pass& p, char* err, size_t errlen) {
     const dinov2_hip_model* m = s->model;
     const int H = (int)m->hp.hidden_size, F = (int)m->hp.ffn_hidden, R = (int)m->hp.num_register_tokens;
     const int nh = (int)m->hp.num_attention_heads, ps = (int)m->hp.patch_size;
-    const Dims d = dims_of(m, B, h, w);
+    const int M = p.M, nlayers = p.nlayers;
+    const PassExtras& ex = p.ex;
     hipStream_t st = s->stream;
     const DType dt = m->dt;
+    if (p.nruns < 1 || (p.nruns > 1 && (!p.items || ex.any()))) {
+        set_err(err, errlen, "forward: a pass of %d runs needs an attention work table and takes no taps, attention rows or dense pack", p.nruns);
+        return DINOV2_HIP_ERR_INVALID;
+    }
+    const int B = p.runs[0].B, T = p.runs[0].T;  // what the extras and the uniform attention go by
 
-    {
-        const int rcp = prepare_pos(s, B, h, w, err, errlen);  // no-op when predict already did it (graph capture relies on that)
-        if (rcp != DINOV2_HIP_OK) return rcp;
-    }
-
-    {
-        Scope sc(s, m->patch_stride == ps ? K_IM2COL : K_IM2COL_STRIDE);
-        HIP_TRY(launch_patch_im2col(dt, img, s->col, B, h, w, ps, m->patch_stride, m->kpe_pad, layout, st));
-    }
-    {
-        Scope sc(s, K_INIT);
-        HIP_TRY(launch_init_tokens(s->x, m->cls, s->pos, m->reg, B, d.T, R, H, st));
-    }
-    {
-        Scope sc(s, K_PATCH_GEMM);
-        GemmArgs a{};
-        a.A = s->col; a.W = m->patch_w; a.bias = m->patch_b; a.out = s->x; a.aux = s->pos;
-        a.M = B * d.P; a.N = H; a.K = m->kpe_pad; a.ldo = H; a.P = d.P; a.T = d.T; a.R = R;
-        HIP_TRY(launch_gemm(dt, EPI_PATCH, a, st));
+    for (const PassRun* r = p.runs; r != p.runs + p.nruns; ++r) {
+        char* const col = (char*)s->col + (size_t)r->patch0 * (size_t)m->kpe_pad * 2;
+        float* const x = s->x + (size_t)r->row0 * H;
+        {
+            Scope sc(s, m->patch_stride == ps ? K_IM2COL : K_IM2COL_STRIDE);
+            HIP_TRY(launch_patch_im2col(dt, r->img, col, r->B, r->h, r->w, ps, m->patch_stride, m->kpe_pad, p.layout, st));
+        }
+        {
+            Scope sc(s, K_INIT);
+            HIP_TRY(launch_init_tokens(x, m->cls, r->pos, m->reg, r->B, r->T, R, H, st));
+        }
+        {
+            Scope sc(s, K_PATCH_GEMM);
+            GemmArgs a{};
+            a.A = col; a.W = m->patch_w; a.bias = m->patch_b; a.out = x; a.aux = r->pos;
+            a.M = r->B * r->P; a.N = H; a.K = m->kpe_pad; a.ldo = H; a.P = r->P; a.T = r->T; a.R = R;
+            HIP_TRY(launch_gemm(dt, EPI_PATCH, a, st));
+        }
     }
     const float eps = m->hp.eps;
     LayerCursor tap_at{ex.taps.layers, ex.taps.n}, pack_at{ex.dense.layers, ex.dense.n}, attn_at{ex.attn.layers, ex.attn.n};
@@ -312,7 +321,7 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
         const TapRun& t = ex.taps;
         const size_t k = (size_t)slot;
         Scope sc(s, K_LAYER_TAP);
-        return launch_layer_tap(s->x, m->ln_w, m->ln_b, eps, B, d.T, R, H, t.norm, t.chw, t.patch ? t.patch + k * t.patch_stride : nullptr,
+        return launch_layer_tap(s->x, m->ln_w, m->ln_b, eps, B, T, R, H, t.norm, t.chw, t.patch ? t.patch + k * t.patch_stride : nullptr,
                                 t.cls ? t.cls + k * t.cls_stride : nullptr, t.reg ? t.reg + k * t.reg_stride : nullptr, st);
     };
     HIP_TRY(tap(0));
@@ -321,7 +330,7 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
         if (slot < 0) return hipSuccess;
         const dinov2_hip_dense_head* hd = ex.dense.head;
         Scope sc(s, K_LAYER_TAP);
-        return launch_dense_pack(s->x, m->ln_w, m->ln_b, eps, B, d.T, R, H, hd->norm, hd->concat_cls, ex.dense.A, (size_t)hd->K,
+        return launch_dense_pack(s->x, m->ln_w, m->ln_b, eps, B, T, R, H, hd->norm, hd->concat_cls, ex.dense.A, (size_t)hd->K,
                                  slot * hd->H * (hd->concat_cls ? 2 : 1), st);
     };
     HIP_TRY(pack(0));
@@ -332,20 +341,20 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
     const int gs = ln_stat_slots(H);
     if (fold && nlayers > 0) {
         Scope sc(s, K_LAYERNORM);
-        HIP_TRY(launch_ln_prepare(dt, s->x, m->layers[0].norm1_w, s->ln, s->stats, gs, d.M, H, st));
+        HIP_TRY(launch_ln_prepare(dt, s->x, m->layers[0].norm1_w, s->ln, s->stats, gs, M, H, st));
     }
     for (int il = 0; il < nlayers; ++il) {
         const LayerWeights& ly = m->layers[(size_t)il];
         if (!fold) {
             Scope sc(s, K_LAYERNORM);
-            HIP_TRY(launch_layernorm(dt, s->x, ly.norm1_w, ly.norm1_b, s->ln, d.M, H, eps, st));
+            HIP_TRY(launch_layernorm(dt, s->x, ly.norm1_w, ly.norm1_b, s->ln, M, H, eps, st));
         }
         int ldq = 3 * H;
         {
             Scope sc(s, K_QKV_GEMM);
             GemmArgs a{};
             a.A = s->ln; a.W = ly.qkv_w; a.bias = ly.qkv_b; a.out = s->qkv;
-            a.M = d.M; a.N = 3 * H; a.K = H; a.ldo = 3 * H; a.qcols = H;
+            a.M = M; a.N = 3 * H; a.K = H; a.ldo = 3 * H; a.qcols = H;
 #if defined(DINO_PREC) && (DINO_PREC & 25)
             a.ldo = 6 * H;
 #endif
@@ -359,17 +368,18 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
         if (const int slot = attn_at.take(il + 1); slot >= 0) {  // booked as a tap: a tap of the attention
             const AttnRun& at = ex.attn;
             Scope sc(s, K_LAYER_TAP);
-            HIP_TRY(launch_attn_rows(dt, s->qkv, ldq, at.probs + (size_t)slot * at.stride, B, d.T, H, nh, at.queries, at.nq, at.key0, at.nkeys, st));
+            HIP_TRY(launch_attn_rows(dt, s->qkv, ldq, at.probs + (size_t)slot * at.stride, B, T, H, nh, at.queries, at.nq, at.key0, at.nkeys, st));
         }
         {
-            Scope sc(s, K_ATTENTION);
-            HIP_TRY(launch_attention(dt, s->qkv, s->att, B, d.T, H, nh, true, st));
+            Scope sc(s, K_ATTENTION);  // (the two launchers give the same bits; the uniform one is the faster where it applies)
+            HIP_TRY(p.items ? launch_attention_list(dt, s->qkv, s->att, p.items, p.n_items, p.n_items, H, nh, true, st)
+                            : launch_attention(dt, s->qkv, s->att, B, T, H, nh, true, st));
         }
         {
             Scope sc(s, K_OPROJ_GEMM);
             GemmArgs a{};
             a.A = s->att; a.W = ly.o_w; a.bias = ly.o_b; a.out = s->x; a.aux = ly.ls1;
-            a.M = d.M; a.N = H; a.K = H; a.ldo = H;
+            a.M = M; a.N = H; a.K = H; a.ldo = H;
             if (fold) {
                 a.ln_gamma = ly.norm2_w; a.xg = s->ln; a.stats = s->stats; a.ln_gs = gs;
             }
@@ -377,13 +387,13 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
         }
         if (!fold) {
             Scope sc(s, K_LAYERNORM);
-            HIP_TRY(launch_layernorm(dt, s->x, ly.norm2_w, ly.norm2_b, s->ln, d.M, H, eps, st));
+            HIP_TRY(launch_layernorm(dt, s->x, ly.norm2_w, ly.norm2_b, s->ln, M, H, eps, st));
         }
         {
             Scope sc(s, K_FC1_GEMM);
             GemmArgs a{};
             a.A = s->ln; a.W = ly.fc1_w; a.bias = ly.fc1_b; a.out = s->hid;
-            a.M = d.M; a.N = m->hp.swiglu ? 2 * F : F; a.K = H; a.ldo = F;
+            a.M = M; a.N = m->hp.swiglu ? 2 * F : F; a.K = H; a.ldo = F;
             if (fold) {
                 a.stats = s->stats; a.ln_gs = gs; a.ln_s = ly.fc1_s; a.ln_c = ly.fc1_c; a.ln_eps = eps;
             }
@@ -393,7 +403,7 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
             Scope sc(s, K_FC2_GEMM);
             GemmArgs a{};
             a.A = s->hid; a.W = ly.fc2_w; a.bias = ly.fc2_b; a.out = s->x; a.aux = ly.ls2;
-            a.M = d.M; a.N = H; a.K = F; a.ldo = H;
+            a.M = M; a.N = H; a.K = F; a.ldo = H;
             const bool feeds_ln1 = fold && il + 1 < nlayers;  // (the last layer's x goes to the final LayerNorm kernel)
             if (feeds_ln1) {
                 a.ln_gamma = m->layers[(size_t)il + 1].norm1_w; a.xg = s->ln; a.stats = s->stats; a.ln_gs = gs;
@@ -403,18 +413,21 @@ int forward(dinov2_hip_session* s, const float* img, int B, int h, int w, int la
         HIP_TRY(tap(il + 1));
         HIP_TRY(pack(il + 1));
     }
-    if (!finalize) return DINOV2_HIP_OK;
+    if (!p.finalize) return DINOV2_HIP_OK;
     {
         Scope sc(s, K_FINAL_LN);
-        HIP_TRY(launch_layernorm_f32(s->x, m->ln_w, m->ln_b, s->fin, d.M, H, eps, st));
+        HIP_TRY(launch_layernorm_f32(s->x, m->ln_w, m->ln_b, s->fin, M, H, eps, st));
     }
-    if (classify) {
+    if (!p.classify) return DINOV2_HIP_OK;
+    const int first = m->quirk_pool_regs ? 1 : 1 + R;
+    const int Mg = (int)(m->hp.img_size / m->hp.patch_size);
+    const size_t C = m->hp.num_classes;
+    for (const PassRun* r = p.runs; r != p.runs + p.nruns; ++r) {  // the pooling divisor is the run's own
+        const float div = m->quirk_const_div ? (float)(Mg * Mg) : (float)(r->T - first);
+        const size_t i0 = (size_t)r->image0;
         Scope sc(s, K_HEAD);
-        const int first = m->quirk_pool_regs ? 1 : 1 + R;
-        const int Mg = (int)(m->hp.img_size / m->hp.patch_size);
-        const float div = m->quirk_const_div ? (float)(Mg * Mg) : (float)(d.T - first);
-        HIP_TRY(launch_head(dt, s->fin, m->head_w, m->head_b, s->feat, s->logits, s->probs, B, d.T, H,
-                            (int)m->hp.num_classes, first, 1.0f / div, st));
+        HIP_TRY(launch_head(dt, s->fin + (size_t)r->row0 * H, m->head_w, m->head_b, s->feat + i0 * 2 * H, s->logits + i0 * C, s->probs + i0 * C,
+                            r->B, r->T, H, (int)C, first, 1.0f / div, st));
     }
     return DINOV2_HIP_OK;
 }
@@ -486,149 +499,31 @@ int prepare_items_list(dinov2_hip_session* s, const std::vector<AttnItem>& items
     return DINOV2_HIP_OK;
 }
 
-// forward() over a list: the residual stream holds the images' rows one after the other (image i at rows [row0, row0 + T_i)).  The embedding
-// and the head run once per run of equal size with B = run length, every layer launch is forward()'s with M = sum T_i, and attention goes
-// over the work table.  `imgs[r]`: DEVICE images of run r, contiguous.  Leaves final-LN tokens in s->fin, logits / probs [n, C] in s->logits / s->probs.
-int forward_list(dinov2_hip_session* s, const std::vector<const float*>& imgs, const std::vector<ListImage>& im, const std::vector<ListRun>& runs,
-                 const std::vector<const float*>& pos_of, const int32_t* hs, const int32_t* ws, int n_items, int layout, bool classify, char* err,
-                 size_t errlen) {
-    const dinov2_hip_model* m = s->model;
-    const int H = (int)m->hp.hidden_size, F = (int)m->hp.ffn_hidden, R = (int)m->hp.num_register_tokens;
-    const int nh = (int)m->hp.num_attention_heads, ps = (int)m->hp.patch_size, nlayers = (int)m->hp.num_hidden_layers;
-    const int M = (int)(im.back().row0 + im.back().T);
-    hipStream_t st = s->stream;
-    const DType dt = m->dt;
-    size_t patch0 = 0;  // patches before this run: its rows of `col`
-    for (size_t r = 0; r < runs.size(); ++r) {
-        const ListImage& g = im[(size_t)runs[r].first];
-        const int B = runs[r].count, i0 = runs[r].first;
-        char* const col = (char*)s->col + patch0 * (size_t)m->kpe_pad * 2;
-        float* const x = s->x + (size_t)g.row0 * H;
-        {
-            Scope sc(s, m->patch_stride == ps ? K_IM2COL : K_IM2COL_STRIDE);
-            HIP_TRY(launch_patch_im2col(dt, imgs[r], col, B, hs[i0], ws[i0], ps, m->patch_stride, m->kpe_pad, layout, st));
-        }
-        {
-            Scope sc(s, K_INIT);
-            HIP_TRY(launch_init_tokens(x, m->cls, pos_of[(size_t)i0], m->reg, B, g.T, R, H, st));
-        }
-        {
-            Scope sc(s, K_PATCH_GEMM);
-            GemmArgs a{};
-            a.A = col; a.W = m->patch_w; a.bias = m->patch_b; a.out = x; a.aux = pos_of[(size_t)i0];
-            a.M = B * g.P; a.N = H; a.K = m->kpe_pad; a.ldo = H; a.P = g.P; a.T = g.T; a.R = R;
-            HIP_TRY(launch_gemm(dt, EPI_PATCH, a, st));
-        }
-        patch0 += (size_t)B * g.P;
-    }
-    const float eps = m->hp.eps;
-    const bool fold = m->ln_fold;
-    const int gs = ln_stat_slots(H);
-    if (fold && nlayers > 0) {
-        Scope sc(s, K_LAYERNORM);
-        HIP_TRY(launch_ln_prepare(dt, s->x, m->layers[0].norm1_w, s->ln, s->stats, gs, M, H, st));
-    }
-    for (int il = 0; il < nlayers; ++il) {  // forward()'s layer, launch for launch, but for the attention
-        const LayerWeights& ly = m->layers[(size_t)il];
-        if (!fold) {
-            Scope sc(s, K_LAYERNORM);
-            HIP_TRY(launch_layernorm(dt, s->x, ly.norm1_w, ly.norm1_b, s->ln, M, H, eps, st));
-        }
-        {
-            Scope sc(s, K_QKV_GEMM);
-            GemmArgs a{};
-            a.A = s->ln; a.W = ly.qkv_w; a.bias = ly.qkv_b; a.out = s->qkv;
-            a.M = M; a.N = 3 * H; a.K = H; a.ldo = 3 * H; a.qcols = H;
-            a.qscale = 0.125f * 1.44269504088896340736f;
-            if (fold) {
-                a.stats = s->stats; a.ln_gs = gs; a.ln_s = ly.qkv_s; a.ln_c = ly.qkv_c; a.ln_eps = eps;
-            }
-            HIP_TRY(launch_gemm(dt, fold ? EPI_QKV_LN : EPI_QKV, a, st));
-        }
-        {
-            Scope sc(s, K_ATTENTION);
-            HIP_TRY(launch_attention_list(dt, s->qkv, s->att, s->scratch[SCRATCH_LIST_ITEMS].as<AttnItem>(), n_items, n_items, H, nh, true, st));
-        }
-        {
-            Scope sc(s, K_OPROJ_GEMM);
-            GemmArgs a{};
-            a.A = s->att; a.W = ly.o_w; a.bias = ly.o_b; a.out = s->x; a.aux = ly.ls1;
-            a.M = M; a.N = H; a.K = H; a.ldo = H;
-            if (fold) {
-                a.ln_gamma = ly.norm2_w; a.xg = s->ln; a.stats = s->stats; a.ln_gs = gs;
-            }
-            HIP_TRY(launch_gemm(dt, fold ? EPI_RESID_LN : EPI_RESID, a, st));
-        }
-        if (!fold) {
-            Scope sc(s, K_LAYERNORM);
-            HIP_TRY(launch_layernorm(dt, s->x, ly.norm2_w, ly.norm2_b, s->ln, M, H, eps, st));
-        }
-        {
-            Scope sc(s, K_FC1_GEMM);
-            GemmArgs a{};
-            a.A = s->ln; a.W = ly.fc1_w; a.bias = ly.fc1_b; a.out = s->hid;
-            a.M = M; a.N = m->hp.swiglu ? 2 * F : F; a.K = H; a.ldo = F;
-            if (fold) {
-                a.stats = s->stats; a.ln_gs = gs; a.ln_s = ly.fc1_s; a.ln_c = ly.fc1_c; a.ln_eps = eps;
-            }
-            HIP_TRY(launch_gemm(dt, m->hp.swiglu ? (fold ? EPI_SWIGLU_LN : EPI_SWIGLU) : (fold ? EPI_GELU_LN : EPI_GELU), a, st));
-        }
-        {
-            Scope sc(s, K_FC2_GEMM);
-            GemmArgs a{};
-            a.A = s->hid; a.W = ly.fc2_w; a.bias = ly.fc2_b; a.out = s->x; a.aux = ly.ls2;
-            a.M = M; a.N = H; a.K = F; a.ldo = H;
-            const bool feeds_ln1 = fold && il + 1 < nlayers;
-            if (feeds_ln1) {
-                a.ln_gamma = m->layers[(size_t)il + 1].norm1_w; a.xg = s->ln; a.stats = s->stats; a.ln_gs = gs;
-            }
-            HIP_TRY(launch_gemm(dt, feeds_ln1 ? EPI_RESID_LN : EPI_RESID, a, st));
-        }
-    }
-    {
-        Scope sc(s, K_FINAL_LN);
-        HIP_TRY(launch_layernorm_f32(s->x, m->ln_w, m->ln_b, s->fin, M, H, eps, st));
-    }
-    if (classify) {
-        const int first = m->quirk_pool_regs ? 1 : 1 + R;
-        const int Mg = (int)(m->hp.img_size / m->hp.patch_size);
-        const size_t C = m->hp.num_classes;
-        for (const ListRun& run : runs) {  // the pooling divisor is the run's own
-            const ListImage& g = im[(size_t)run.first];
-            const float div = m->quirk_const_div ? (float)(Mg * Mg) : (float)(g.T - first);
-            Scope sc(s, K_HEAD);
-            HIP_TRY(launch_head(dt, s->fin + (size_t)g.row0 * H, m->head_w, m->head_b, s->feat + (size_t)run.first * 2 * H,
-                                s->logits + (size_t)run.first * C, s->probs + (size_t)run.first * C, run.count, g.T, H, (int)C, first, 1.0f / div, st));
-        }
-    }
-    return DINOV2_HIP_OK;
-}
-
 // Opt-in (DINOV2_HIP_GRAPHS=1): second and later forwards with the same (workspace, input pointer, shape, flags) replay a
 // captured hipGraph; the first occurrence runs eagerly (one-off shapes never pay for a capture), the second is captured.
 // Off by default because it buys nothing on an idle host: the forward is kernel-bound (178 launches, mean gap 1.0 us in the
 // rocprofv3 trace at batch 1), measured p50 3.07 ms with graphs vs 3.06 ms without.  It is there for hosts whose launch
 // thread is contended.
-int forward_maybe_graph(dinov2_hip_session* s, const float* img, int B, int h, int w, int layout, bool classify, char* err,
-                        size_t errlen) {
+int forward_maybe_graph(dinov2_hip_session* s, const Pass& p, char* err, size_t errlen) {
     static const bool enabled = [] {
         const char* e = getenv("DINOV2_HIP_GRAPHS");
         return e && atoi(e) != 0;
     }();
-    const int nl = (int)s->model->hp.num_hidden_layers;
-    const PassExtras none;
-    if (!enabled || s->profiling) return forward(s, img, B, h, w, layout, classify, nl, true, none, err, errlen);
+    auto eager = [&] { return forward(s, p, err, errlen); };
+    if (!enabled || s->profiling) return eager();
+    const PassRun& r = p.runs[0];  // (a uniform batch: its one run is the key)
     hipStream_t st = s->stream;
     dinov2_hip_session::GraphEntry* hit = nullptr;
     for (auto& g : s->graphs)
-        if (g.ws == s->scratch[SCRATCH_WS].ptr && g.img == img && g.b == B && g.h == h && g.w == w && g.layout == layout && g.classify == (int)classify)
+        if (g.ws == s->scratch[SCRATCH_WS].ptr && g.img == r.img && g.b == r.B && g.h == r.h && g.w == r.w && g.layout == p.layout &&
+            g.classify == (int)p.classify)
             hit = &g;
     if (hit && hit->exec) {
         ++hit->uses;
         HIP_TRY(hipGraphLaunch(hit->exec, st));
         return DINOV2_HIP_OK;
     }
-    if (hit && hit->uses < 0) return forward(s, img, B, h, w, layout, classify, nl, true, none, err, errlen);  // capture failed before
+    if (hit && hit->uses < 0) return eager();  // capture failed before
     if (!hit) {  // first sighting: remember it, run eagerly
         if (s->graphs.size() >= 8) {  // evict the least used entry
             size_t v = 0;
@@ -637,15 +532,15 @@ int forward_maybe_graph(dinov2_hip_session* s, const float* img, int B, int h, i
             if (s->graphs[v].exec) (void)hipGraphExecDestroy(s->graphs[v].exec);
             s->graphs.erase(s->graphs.begin() + (long)v);
         }
-        s->graphs.push_back({s->scratch[SCRATCH_WS].ptr, img, B, h, w, layout, (int)classify, 0, nullptr});
-        return forward(s, img, B, h, w, layout, classify, nl, true, none, err, errlen);
+        s->graphs.push_back({s->scratch[SCRATCH_WS].ptr, r.img, r.B, r.h, r.w, p.layout, (int)p.classify, 0, nullptr});
+        return eager();
     }
-    // second sighting: capture.  Nothing in forward() synchronises or allocates once prepare_pos has run.
+    // second sighting: capture.  Nothing in forward() synchronises or allocates.
     if (hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed) != hipSuccess) {
         (void)hipGetLastError();
-        return forward(s, img, B, h, w, layout, classify, nl, true, none, err, errlen);
+        return eager();
     }
-    const int rc = forward(s, img, B, h, w, layout, classify, nl, true, none, err, errlen);
+    const int rc = eager();
     hipGraph_t graph = nullptr;
     const hipError_t ec = hipStreamEndCapture(st, &graph);
     if (rc != DINOV2_HIP_OK || ec != hipSuccess || !graph) {
@@ -653,7 +548,7 @@ int forward_maybe_graph(dinov2_hip_session* s, const float* img, int B, int h, i
         (void)hipGetLastError();
         hit->uses = -1000000;  // do not try again for this key
         if (rc != DINOV2_HIP_OK) return rc;
-        return forward(s, img, B, h, w, layout, classify, nl, true, none, err, errlen);
+        return eager();
     }
     hipGraphExec_t exec = nullptr;
     const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
@@ -661,7 +556,7 @@ int forward_maybe_graph(dinov2_hip_session* s, const float* img, int B, int h, i
     if (ei != hipSuccess || !exec) {
         (void)hipGetLastError();
         hit->uses = -1000000;
-        return forward(s, img, B, h, w, layout, classify, nl, true, none, err, errlen);
+        return eager();
     }
     hit->exec = exec;
     hit->uses = 1;
@@ -687,39 +582,47 @@ static void topk_rows(const float* probs_host, int B, size_t C, dinov2_hip_outpu
     }
 }
 
-// Copy-out of the session's last forward (shape in s->last_*): the tail of dino_predict (dinov2.cpp:950-999).
-int dinov2::fetch_outputs(dinov2_hip_session* s, dinov2_hip_output* out, char* err, size_t errlen) {
+// Copy-out of a finished pass, run by run: the tail of dino_predict (dinov2.cpp:950-999).  cls [n, H]; the patch rows packed, one image after
+// the other (a list's image i at rows [offsets[i], offsets[i + 1]) of dinov2_hip_list_rows); logits / probs [n, C].  Device outputs are only
+// enqueued; host outputs are complete on return, after ONE wait.
+static int copy_out(dinov2_hip_session* s, const PassRun* runs, int nruns, bool classify, dinov2_hip_output* out, char* err, size_t errlen) {
     const dinov2_hip_model* m = s->model;
-    const int B = s->last_b, h = s->last_h, w = s->last_w;
-    const bool classify = s->last_classify;
     hipStream_t st = s->stream;
-    const Dims d = dims_of(m, B, h, w);
     const size_t H = m->hp.hidden_size, C = m->hp.num_classes;
-    const int R = (int)m->hp.num_register_tokens;
+    const int n = runs[nruns - 1].image0 + runs[nruns - 1].B;
+    const int first = classify ? 1 : 1 + (int)m->hp.num_register_tokens;  // rows [1+R, T) for features, [1, T) when classifying (dinov2.cpp:770-789)
     const hipMemcpyKind kind = out->on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const size_t pitch = sizeof(float) * (size_t)d.T * H;
-    if (out->cls)  // "cls_token" = final-LN row 0 (dinov2.cpp:764-768)
-        HIP_TRY(hipMemcpy2DAsync(out->cls, sizeof(float) * H, s->fin, pitch, sizeof(float) * H, (size_t)B, kind, st));
-    if (out->patch_tokens) {  // rows [1+R, T) for features, [1, T) when classifying (dinov2.cpp:770-789)
-        const int first = classify ? 1 : 1 + R;
-        const size_t wbytes = sizeof(float) * (size_t)(d.T - first) * H;
-        HIP_TRY(hipMemcpy2DAsync(out->patch_tokens, wbytes, s->fin + (size_t)first * H, pitch, wbytes, (size_t)B, kind, st));
+    size_t orow = 0;
+    for (const PassRun* r = runs; r != runs + nruns; ++r) {
+        const float* fin = s->fin + (size_t)r->row0 * H;
+        const size_t pitch = sizeof(float) * (size_t)r->T * H, wbytes = sizeof(float) * (size_t)(r->T - first) * H;
+        if (out->cls)  // "cls_token" = final-LN row 0 (dinov2.cpp:764-768)
+            HIP_TRY(hipMemcpy2DAsync(out->cls + (size_t)r->image0 * H, sizeof(float) * H, fin, pitch, sizeof(float) * H, (size_t)r->B, kind, st));
+        if (out->patch_tokens)
+            HIP_TRY(hipMemcpy2DAsync(out->patch_tokens + orow * H, wbytes, fin + (size_t)first * H, pitch, wbytes, (size_t)r->B, kind, st));
+        orow += (size_t)r->B * (size_t)(r->T - first);
     }
     if (classify) {
-        if (out->logits) HIP_TRY(hipMemcpyAsync(out->logits, s->logits, sizeof(float) * B * C, kind, st));
-        if (out->probs) HIP_TRY(hipMemcpyAsync(out->probs, s->probs, sizeof(float) * B * C, kind, st));
+        if (out->logits) HIP_TRY(hipMemcpyAsync(out->logits, s->logits, sizeof(float) * n * C, kind, st));
+        if (out->probs) HIP_TRY(hipMemcpyAsync(out->probs, s->probs, sizeof(float) * n * C, kind, st));
     }
     if (out->on_device) return DINOV2_HIP_OK;
 
     std::vector<float> probs_host;
     const bool want_topk = classify && out->topk > 0 && (out->topk_ids || out->topk_probs);
     if (want_topk) {
-        probs_host.resize((size_t)B * C);
-        HIP_TRY(hipMemcpyAsync(probs_host.data(), s->probs, sizeof(float) * B * C, hipMemcpyDeviceToHost, st));
+        probs_host.resize((size_t)n * C);
+        HIP_TRY(hipMemcpyAsync(probs_host.data(), s->probs, sizeof(float) * n * C, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
-    if (want_topk) topk_rows(probs_host.data(), B, C, out);
+    if (want_topk) topk_rows(probs_host.data(), n, C, out);
     return DINOV2_HIP_OK;
+}
+
+// ... of the session's last un-split forward (shape in s->last_*): one run
+int dinov2::fetch_outputs(dinov2_hip_session* s, dinov2_hip_output* out, char* err, size_t errlen) {
+    const PassRun run = uniform_run(s->model, nullptr, s->last_b, s->last_h, s->last_w, nullptr);
+    return copy_out(s, &run, 1, s->last_classify, out, err, errlen);
 }
 
 extern "C" int dinov2_hip_session_create(dinov2_hip_model* m, void* stream, dinov2_hip_session** out, char* err,
@@ -842,6 +745,15 @@ static int dense_stage(dinov2_hip_session* s, const DenseRun& dr, int B, int h, 
     return DINOV2_HIP_OK;
 }
 
+// The preprocessed f32 images of `in` on the device: where the caller has them, or host ones copied into the workspace (carved for them)
+static int images_f32(dinov2_hip_session* s, const dinov2_hip_input* in, const float** img, char* err, size_t errlen) {
+    *img = in->data;
+    if (in->on_device) return DINOV2_HIP_OK;
+    HIP_TRY(hipMemcpyAsync(s->img, in->data, sizeof(float) * 3 * (size_t)in->batch * in->height * in->width, hipMemcpyHostToDevice, s->stream));
+    *img = s->img;
+    return DINOV2_HIP_OK;
+}
+
 // `ex`: the layer taps of dinov2_hip_predict_layers, the attention rows of dinov2_hip_predict_attention (device pointers), the head and outputs
 // of dinov2_hip_predict_dense (extras.cpp builds them); empty for a plain predict
 int dinov2::predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dinov2_hip_output* out, uint32_t flags, const PassExtras& ex,
@@ -911,26 +823,25 @@ int dinov2::predict_impl(dinov2_hip_session* s, const dinov2_hip_input* in, dino
         const int rh = classify ? 256 : h, rw = classify ? 256 : w;
         HIP_TRY(launch_preprocess_u8(src, s->img, B, in->height, in->width, rh, rw, (rh - h) / 2, (rw - w) / 2, h, w, st));
         img = s->img;
-    } else if (!in->on_device) {
-        HIP_TRY(hipMemcpyAsync(s->img, in->data, sizeof(float) * 3 * (size_t)B * h * w, hipMemcpyHostToDevice, st));
-        img = s->img;
+    } else {
+        rc = images_f32(s, in, &img, err, errlen);
+        if (rc != DINOV2_HIP_OK) return rc;
     }
     rc = prepare_pos(s, B, h, w, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
+    const PassRun run = uniform_run(m, img, B, h, w, s->pos);
+    const Pass pass{&run, 1, B * run.T, nullptr, 0, layout, classify, (int)m->hp.num_hidden_layers, true, ex};
     // (a tapped forward runs eagerly, past the graph cache: its key knows nothing of the caller's tap pointers)
-    rc = ex.any() ? forward(s, img, B, h, w, layout, classify, (int)m->hp.num_hidden_layers, true, ex, err, errlen)
-                  : forward_maybe_graph(s, img, B, h, w, layout, classify, err, errlen);
+    rc = ex.any() ? forward(s, pass, err, errlen) : forward_maybe_graph(s, pass, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
     if (ex.dense.n) {
         rc = dense_stage(s, ex.dense, B, h, w, err, errlen);
         if (rc != DINOV2_HIP_OK) return rc;
     }
-    {  // what dinov2_hip_pca3(tokens = NULL) works on: the patch rows of image 0 in `fin`
-        const Dims dd = dims_of(m, B, h, w);
-        s->last_first = classify ? 1 : 1 + (int)m->hp.num_register_tokens;
-        s->last_patches = dd.T - s->last_first;
-        s->last_t = dd.T;
-    }
+    // what dinov2_hip_pca3(tokens = NULL) works on: the patch rows of image 0 in `fin`
+    s->last_first = classify ? 1 : 1 + (int)m->hp.num_register_tokens;
+    s->last_patches = run.T - s->last_first;
+    s->last_t = run.T;
     s->last_b = B;
     s->last_h = h;
     s->last_w = w;
@@ -1032,7 +943,6 @@ extern "C" int dinov2_hip_predict_list(dinov2_hip_session* s, const dinov2_hip_i
     if (rc != DINOV2_HIP_OK) return rc;
     const bool classify = (flags & DINOV2_HIP_CLASSIFY) != 0;
     const int n = list->n, R = (int)m->hp.num_register_tokens, nh = (int)m->hp.num_attention_heads;
-    const size_t H = m->hp.hidden_size, C = m->hp.num_classes;
     HIP_TRY(hipSetDevice(m->device));
     // a list forward leaves no "last un-split forward": nothing for dinov2_hip_fetch, pca3(tokens = NULL), match / bank on resident tokens
     s->last_b = 0;
@@ -1040,9 +950,10 @@ extern "C" int dinov2_hip_predict_list(dinov2_hip_session* s, const dinov2_hip_i
     s->last_t = 0;
 
     std::vector<ListImage> im((size_t)n);
-    std::vector<ListRun> runs((size_t)n);
-    ListPlan lp = list_plan(n, hs.data(), ws.data(), (int)m->hp.patch_size, m->patch_stride, R, nh, list_table_order(), im.data(), runs.data(), nullptr);
-    runs.resize((size_t)lp.nruns);
+    std::vector<ListRun> lruns((size_t)n);
+    ListPlan lp = list_plan(n, hs.data(), ws.data(), (int)m->hp.patch_size, m->patch_stride, R, nh, list_table_order(), im.data(), lruns.data(), nullptr);
+    std::vector<PassRun> runs((size_t)lp.nruns);
+    list_runs(im.data(), lruns.data(), lp.nruns, hs.data(), ws.data(), runs.data());
     std::vector<AttnItem> items((size_t)lp.units);
     lp = list_plan(n, hs.data(), ws.data(), (int)m->hp.patch_size, m->patch_stride, R, nh, list_table_order(), nullptr, nullptr, items.data());
 
@@ -1055,7 +966,6 @@ extern "C" int dinov2_hip_predict_list(dinov2_hip_session* s, const dinov2_hip_i
     const int layout = raw_u8 ? DINOV2_HIP_BGR_HWC : list->layout;
     std::vector<size_t> pix((size_t)n + 1, 0);  // pixels before image i (network size): its place in s->img
     for (int i = 0; i < n; ++i) pix[(size_t)i + 1] = pix[(size_t)i] + (size_t)hs[(size_t)i] * ws[(size_t)i];
-    std::vector<const float*> imgs(runs.size());
     if (raw_u8) {
         std::vector<const uint8_t*> src((size_t)n);
         for (int i = 0; i < n; ++i) src[(size_t)i] = static_cast<const uint8_t*>(list->data[i]);
@@ -1077,61 +987,35 @@ extern "C" int dinov2_hip_predict_list(dinov2_hip_session* s, const dinov2_hip_i
             HIP_TRY(launch_preprocess_u8(src[(size_t)i], s->img + 3 * pix[(size_t)i], 1, list->height[i], list->width[i], rh, rw, (rh - h) / 2,
                                          (rw - w) / 2, h, w, st));
         }
-        for (size_t r = 0; r < runs.size(); ++r) imgs[r] = s->img + 3 * pix[(size_t)runs[r].first];
+        for (PassRun& r : runs) r.img = s->img + 3 * pix[(size_t)r.image0];
     } else {
-        for (size_t r = 0; r < runs.size(); ++r) {
-            const int i0 = runs[r].first, i1 = i0 + runs[r].count;
-            const size_t fl = 3 * (size_t)hs[(size_t)i0] * ws[(size_t)i0];  // floats of one image of the run
+        for (PassRun& r : runs) {
+            const int i0 = r.image0, i1 = i0 + r.B;
+            const size_t fl = 3 * (size_t)r.h * r.w;  // floats of one image of the run
             bool in_place = list->on_device != 0;
             for (int i = i0 + 1; i < i1 && in_place; ++i)
                 in_place = static_cast<const float*>(list->data[i]) == static_cast<const float*>(list->data[i - 1]) + fl;
             if (in_place) {
-                imgs[r] = static_cast<const float*>(list->data[i0]);
+                r.img = static_cast<const float*>(list->data[i0]);
                 continue;
             }
             for (int i = i0; i < i1; ++i)
                 HIP_TRY(hipMemcpyAsync(s->img + 3 * pix[(size_t)i], list->data[i], sizeof(float) * fl,
                                        list->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-            imgs[r] = s->img + 3 * pix[(size_t)i0];
+            r.img = s->img + 3 * pix[(size_t)i0];
         }
     }
     std::vector<const float*> pos_of;
     rc = prepare_pos_list(s, im, pos_of, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
+    for (PassRun& r : runs) r.pos = pos_of[(size_t)r.image0];
     rc = prepare_items_list(s, items, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
-    rc = forward_list(s, imgs, im, runs, pos_of, hs.data(), ws.data(), (int)items.size(), layout, classify, err, errlen);
-    if (rc != DINOV2_HIP_OK) return rc;
-    if (!out) return DINOV2_HIP_OK;
-
-    // copy-out, run by run: cls [n, H]; the patch rows packed, image i at rows [offsets[i], offsets[i + 1]) of dinov2_hip_list_rows
-    const hipMemcpyKind kind = out->on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const int skip = classify ? 1 : 1 + R;
-    size_t orow = 0;
-    for (const ListRun& run : runs) {
-        const ListImage& g = im[(size_t)run.first];
-        const float* fin = s->fin + (size_t)g.row0 * H;
-        const size_t pitch = sizeof(float) * (size_t)g.T * H, wbytes = sizeof(float) * (size_t)(g.T - skip) * H;
-        if (out->cls)
-            HIP_TRY(hipMemcpy2DAsync(out->cls + (size_t)run.first * H, sizeof(float) * H, fin, pitch, sizeof(float) * H, (size_t)run.count, kind, st));
-        if (out->patch_tokens)
-            HIP_TRY(hipMemcpy2DAsync(out->patch_tokens + orow * H, wbytes, fin + (size_t)skip * H, pitch, wbytes, (size_t)run.count, kind, st));
-        orow += (size_t)run.count * (size_t)(g.T - skip);
-    }
-    if (classify) {
-        if (out->logits) HIP_TRY(hipMemcpyAsync(out->logits, s->logits, sizeof(float) * n * C, kind, st));
-        if (out->probs) HIP_TRY(hipMemcpyAsync(out->probs, s->probs, sizeof(float) * n * C, kind, st));
-    }
-    if (out->on_device) return DINOV2_HIP_OK;
-    std::vector<float> probs_host;
-    const bool want_topk = classify && out->topk > 0 && (out->topk_ids || out->topk_probs);
-    if (want_topk) {
-        probs_host.resize((size_t)n * C);
-        HIP_TRY(hipMemcpyAsync(probs_host.data(), s->probs, sizeof(float) * n * C, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    if (want_topk) topk_rows(probs_host.data(), n, C, out);
-    return DINOV2_HIP_OK;
+    const Pass pass{runs.data(), lp.nruns, (int)lp.M, s->scratch[SCRATCH_LIST_ITEMS].as<AttnItem>(), (int)items.size(), layout, classify,
+                    (int)m->hp.num_hidden_layers, true, PassExtras{}};
+    rc = forward(s, pass, err, errlen);
+    if (rc != DINOV2_HIP_OK || !out) return rc;
+    return copy_out(s, runs.data(), lp.nruns, classify, out, err, errlen);
 }
 
 extern "C" int dinov2_hip_fetch(dinov2_hip_session* s, dinov2_hip_output* out, char* err, size_t errlen) {
@@ -1167,15 +1051,16 @@ extern "C" int dinov2_hip_debug_hidden(dinov2_hip_session* s, const dinov2_hip_i
     const int B = in->batch, h = in->height, w = in->width;
     rc = ensure_workspace(s, B, h, w, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
-    const float* img = in->data;
-    if (!in->on_device) {
-        HIP_TRY(hipMemcpyAsync(s->img, in->data, sizeof(float) * 3 * (size_t)B * h * w, hipMemcpyHostToDevice, s->stream));
-        img = s->img;
-    }
-    rc = forward(s, img, B, h, w, in->layout, false, layer, false, PassExtras{}, err, errlen);
+    const float* img = nullptr;
+    rc = images_f32(s, in, &img, err, errlen);
     if (rc != DINOV2_HIP_OK) return rc;
-    const Dims d = dims_of(m, B, h, w);
-    HIP_TRY(hipMemcpyAsync(out, s->x, sizeof(float) * (size_t)d.M * m->hp.hidden_size, hipMemcpyDeviceToHost, s->stream));
+    rc = prepare_pos(s, B, h, w, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    const PassRun run = uniform_run(m, img, B, h, w, s->pos);
+    const Pass pass{&run, 1, B * run.T, nullptr, 0, in->layout, false, layer, false, PassExtras{}};
+    rc = forward(s, pass, err, errlen);
+    if (rc != DINOV2_HIP_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, s->x, sizeof(float) * (size_t)pass.M * m->hp.hidden_size, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return DINOV2_HIP_OK;
 }

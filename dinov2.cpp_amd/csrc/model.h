@@ -95,6 +95,34 @@ struct PassExtras {
     }
 };
 
+// One run of a pass: B consecutive images of ONE network size h x w, embedded and pooled by one launch each.  A uniform batch is one run;
+// a list (dinov2_hip_predict_list) has one per stretch of equal-sized images (list_plan).  The run owns rows [row0, row0 + B T) of the
+// residual stream and of `fin`, rows [patch0, patch0 + B P) of `col`, and the slices of feat / logits / probs from image `image0` on.
+struct PassRun {
+    const float* img = nullptr;  // DEVICE: the run's images, contiguous
+    int B = 0, h = 0, w = 0;
+    const float* pos = nullptr;  // DEVICE: the position embedding [1 + P, H] of the run's patch grid
+    int64_t row0 = 0, patch0 = 0;
+    int image0 = 0;
+    int P = 0, T = 0;  // patches and tokens (1 + R + P) of one image
+};
+
+// One pass of the forward: the runs, and what is the same for all of them.  Attention is the one launch that is not per row: without a work
+// table it is launch_attention over runs[0] (a uniform batch), with one launch_attention_list over the table.  The extras are a uniform
+// batch's only: forward() refuses a pass of several runs that carries any.
+struct Pass {
+    const PassRun* runs = nullptr;
+    int nruns = 0;
+    int M = 0;                        // token rows of all runs
+    const AttnItem* items = nullptr;  // DEVICE: the list's attention work table (null: uniform over runs[0])
+    int n_items = 0;
+    int layout = 0;
+    bool classify = false;
+    int nlayers = 0;
+    bool finalize = true;  // final LayerNorm (and the head with `classify`) after the layers
+    PassExtras ex;
+};
+
 // The scratch buffers of a session, one DevBuf each in dinov2_hip_session::scratch: dinov2_hip_session_free frees them all.
 enum Scratch : int {
     SCRATCH_WS = 0,  // the forward's workspace, carved into the views below

@@ -114,13 +114,13 @@ def segment_input(T, nh, dt, log2, seed):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the host path's bookkeeping
-# What forward_list hands the per-run launches, restated from the plan: for image i the position embedding it is embedded with (by patch
+# What forward() is handed for the per-run launches of a list, restated from the plan: for image i the position embedding it is embedded with (by patch
 # grid) and the pooling divisor of the head (quirk off: T_i - first).  The truth is what predict would use for that image alone.
 HOST_MUTANTS = ("pos_embed_of_wrong_size", "pool_divisor_of_first_image")
 
 
 def host_bookkeeping(sizes, patch, R, first, mutant=None):
-    """[(h0, w0) of the position embedding, pooling divisor] per image, as forward_list derives them run by run."""
+    """[(h0, w0) of the position embedding, pooling divisor] per image, as the forward derives them run by run."""
     p = plan(sizes, patch, R, 1)
     out = []
     for first_img, count in p["runs"]:

@@ -39,13 +39,13 @@ CSRC = os.path.join(ROOT, "dinov2.cpp_amd", "csrc")
 # The waits of the session code a step can run into: name -> (file under csrc/, line, what it keeps safe).  tests/test_stream_cases.py
 # checks that each line holds a wait and that DESIGN.md's table has a row for it.
 WAIT_SITES = {
-    "reserve":        ("model.cpp", 77, "a scratch buffer is freed and reallocated: work in flight may still use the old one"),
-    "apply_carve":    ("model.cpp", 140, "the workspace grows: captured graphs and work in flight point into the old one"),
-    "prepare_pos":    ("model.cpp", 260, "pos_stage (host) is rewritten by the next shape; the call returns after the copy has landed"),
-    "list_pos":       ("model.cpp", 466, "list_pos_stage (host) is rewritten by the next list with a new grid"),
-    "list_items":     ("model.cpp", 485, "list_items_host is rewritten by the next list with another work table"),
-    "fetch_outputs":  ("model.cpp", 720, "host outputs of predict / fetch are complete on return"),
-    "list_outputs":   ("model.cpp", 1132, "host outputs of predict_list are complete on return"),
+    "reserve":        ("model.cpp", 78, "a scratch buffer is freed and reallocated: work in flight may still use the old one"),
+    "apply_carve":    ("model.cpp", 141, "the workspace grows: captured graphs and work in flight point into the old one"),
+    "prepare_pos":    ("model.cpp", 261, "pos_stage (host) is rewritten by the next shape; the call returns after the copy has landed"),
+    "list_pos":       ("model.cpp", 479, "list_pos_stage (host) is rewritten by the next list with a new grid"),
+    "list_items":     ("model.cpp", 498, "list_items_host is rewritten by the next list with another work table"),
+    "fetch_outputs":  ("model.cpp", 617, "host outputs of predict / fetch are complete on return"),
+    "list_outputs":   ("model.cpp", 617, "host outputs of predict_list are complete on return (the same copy-out, one run per image size)"),
     "attn_queries":   ("extras.cpp", 107, "the device query list is replaced: an attention kernel in flight may still read the old one"),
     "tapped_outputs": ("extras.cpp", 138, "host taps / attention rows (staged in session scratch) are complete on return"),
     "dense_outputs":  ("extras.cpp", 271, "host label / value / logit maps are complete on return"),

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times dinov2_hip_predict_list (csrc/model.cpp forward_list, csrc/attention.hip launch_attention_list) with device-resident inputs and no
+"""Times dinov2_hip_predict_list (csrc/model.cpp forward() over a list's runs, csrc/attention.hip launch_attention_list) with device-resident inputs and no
 outputs on a synthetic ViT-L/14 with 4 registers, f16.  HIP events on the session's stream around every call; the calls that are compared
 alternate; median, minimum and p90 of `--calls` calls after `--warmup`.
   (a) 32 images, all 518 x 518: the list call against the uniform dinov2_hip_predict at batch 32 (the difference is the attention table
