@@ -3,156 +3,91 @@
 // No reference counterpart: k-means over the patch tokens of one image or of a batch (unsupervised part segments, co-segmentation), a fixed
 // vocabulary of centres applied to new frames (visual words).  Rows and centre vectors are normalised by match.hip's kernel
 // (launch_match_normalise); the kernels here:
-//   kmeans_assign_kernel     one workgroup per 128-row tile of X^ walks the centre tiles with match_kernel's staging, LDS image, K loop and
-//                            operand swap, keeps the best (value, lowest centre) per row across the tiles and writes label, sim and the
-//                            workgroup's count of rows whose label changed
+//   kmeans_assign_kernel     one workgroup per 128-row tile of X^ walks the centre tiles, each a tile of sim_tile.h, keeps the best (value,
+//                            lowest centre) per row across the tiles and writes label, sim and the workgroup's count of rows whose label
+//                            changed
 //   kmeans_fold_kernel       the changed-count partials -> one int
 //   kmeans_transpose_kernel  X^ [npad, hpad] -> X^T [hpad128, npad], once per call (padding rows of H written as zeros)
-//   kmeans_update_kernel     D[h, c] = sum_i X^T[h, i] * (label[i] == c) on the matrix cores over one chunk of rows: the one-hot operand is
-//                            built straight into the swizzled LDS image from 64 labels per K-tile; f32 partials [chunk][c][h], exact counts
+//   kmeans_update_kernel     D[h, c] = sum_i X^T[h, i] * (label[i] == c) on the matrix cores over one chunk of rows, as a tile of sim_tile.h
+//                            whose one-hot operand is built straight into the LDS image from 64 labels per K-tile; f32 partials
+//                            [chunk][c][h], exact counts
 //   kmeans_finish_kernel     folds the partials in ascending chunk order over the centre vectors of the clusters that have members
 //   kmeans_count_kernel      members per cluster of the labels as they stand (the exits on which no update follows the last assignment)
 //   kmeans_gather_kernel     centre j = row init[j] of the source, verbatim
-// The similarity of a pair is match_kernel's, instruction for instruction in the K loop: k steps of 32 in ascending order, an order that
-// depends on hpad alone.  "Best" is match.hip's total order -- the larger f32 value, among equal values (-0 == +0) the lower index -- so the
-// label does not depend on which lane, wave or centre tile met a centre first.  No atomics anywhere: every sum has one fixed order.
-#include <climits>
-
-#include "device_types.h"
-#include "kernels.h"
+// The similarity of a pair and the total order of "best" are sim_tile.h's, so the label does not depend on which lane, wave or centre tile
+// met a centre first.  No atomics anywhere: every sum has one fixed order.
+#include "sim_tile.h"
 
 namespace dinov2 {
 
 namespace {
 
-struct Best {
-    float v;
-    int i;
-};
-// match.hip's order: larger value first, then lower index (an empty slot is (-inf, INT_MAX))
-__device__ __forceinline__ bool better(float v, int i, const Best& b) { return v > b.v || (v == b.v && i < b.i); }
-__device__ __forceinline__ void fold(Best& b, float v, int i) {
-    if (better(v, i, b)) {
-        b.v = v;
-        b.i = i;
+// kmeans_update_kernel's B operand for sim_tile: the image [128 c][64 i] = (label[i] == n0 + c) as 1.0 / 0.0 in f16, from the K-tile's 64
+// labels.  A thread's four staging slots share the chunk index tid & 7, so its 8 labels serve all four; cnt[j] counts the ones it wrote
+// for the centre of slot j.
+struct OneHotRows {
+    const int* lsrc;  // the 8 labels of this thread's chunk of K-tile 0
+    int crow;         // the centre of its slot j = 0; slot j is 32 j further
+    u32x4 l0, l1;     // (compared as unsigned: the -1 of a padding row equals no centre)
+    int cnt[4];
+    __device__ __forceinline__ void fetch(int kt) {
+        l0 = *(const u32x4*)(lsrc + kt * 64);
+        l1 = *(const u32x4*)(lsrc + kt * 64 + 4);
     }
-}
-template <int OFF>
-__device__ __forceinline__ void fold_lane(Best& b) {
-    const float v = __shfl_xor(b.v, OFF);
-    const int i = __shfl_xor(b.i, OFF);
-    fold(b, v, i);
-}
-
-constexpr int TILE = 128, ROWB = 128;  // match_kernel's tile; bytes of one LDS row (64 k of f16)
+    __device__ __forceinline__ void store(const SimPlace& p, char* s) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned c = (unsigned)(crow + 32 * j);
+            const unsigned lab[8] = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+            u32x4 oh;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned lo = lab[2 * e] == c, hi = lab[2 * e + 1] == c;
+                oh[e] = lo * 0x3c00u | hi * 0x3c000000u;  // 1.0 in f16
+                cnt[j] += (int)(lo + hi);
+            }
+            *(u32x4*)(s + p.sdst[j]) = oh;
+        }
+    }
+};
 
 }  // namespace
 
-// X [npad, hpad], Cn [kpad, hpad]: the normalised operands, padded to whole tiles (padding rows zero).  Workgroup x owns rows [128 x, +128);
-// four waves, 2 x 2, each 64 x 64 = 4 x 4 accumulator blocks of 16 x 16, as in match_kernel.  label [npad] is read (the previous labels) and
-// written in place: rows >= n get -1.  sim [n].  chpart[x] = rows of this tile whose label changed (`first`: every real row counts).
+// X [npad, hpad], Cn [kpad, hpad]: the normalised operands, padded to whole tiles (padding rows zero).  Workgroup x owns rows [128 x, +128)
+// and walks the centre tiles.  label [npad] is read (the previous labels) and written in place: rows >= n get -1.  sim [n].  chpart[x] =
+// rows of this tile whose label changed (`first`: every real row counts).
 __global__ __launch_bounds__(256) void kmeans_assign_kernel(const _Float16* __restrict__ X, const _Float16* __restrict__ Cn, int hpad, int n, int K,
                                                             int kpad, int* __restrict__ label, float* __restrict__ sim, int* __restrict__ chpart,
                                                             int first) {
-    using E = Elem<_Float16>;
-    __shared__ __attribute__((aligned(16))) char sA[TILE * ROWB];
-    __shared__ __attribute__((aligned(16))) char sB[TILE * ROWB];
-    __shared__ float red_rv[2][TILE];
-    __shared__ int red_ri[2][TILE];
+    __shared__ __attribute__((aligned(16))) char sA[SIM_TILE * SIM_ROWB];
+    __shared__ __attribute__((aligned(16))) char sB[SIM_TILE * SIM_ROWB];
+    __shared__ float red_rv[2][SIM_TILE];
+    __shared__ int red_ri[2][SIM_TILE];
     __shared__ int red_ch[2];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = tid >> 6;
-    const int wm = wid >> 1, wn = wid & 1;
-    const int m0 = blockIdx.x * TILE;
-
-    // staging: 128 rows x 8 chunks of 16 bytes per operand = 4 chunks per thread; 8 neighbouring threads read one 128-byte row segment
-    const char* asrc[4];
-    size_t boff_g[4];
-    int sdst[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int q = j * 256 + tid, row = q >> 3, c = q & 7;
-        asrc[j] = (const char*)X + ((size_t)(m0 + row) * hpad) * 2 + c * 16;
-        boff_g[j] = ((size_t)row * hpad) * 2 + c * 16;
-        sdst[j] = row * ROWB + ((c ^ ((row >> 1) & 7)) << 4);
-    }
-    const int fr = lane & 15, fh = lane >> 4, sw = (fr >> 1) & 7;
-    const int aoff = (wm * 64 + fr) * ROWB, boff = (wn * 64 + fr) * ROWB;
-    const int nk = hpad / 64;
+    const SimPlace p;
+    const int m0 = blockIdx.x * SIM_TILE;
+    SimRows opa(p, X, m0, hpad);
 
     Best best[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) best[i] = Best{-INFINITY, INT_MAX};
 
-    for (int n0 = 0; n0 < kpad; n0 += TILE) {  // the centre tiles in ascending order
-        const char* const bbase = (const char*)Cn + ((size_t)n0 * hpad) * 2;
-        u32x4 ar[4], br[4];
-        auto fetch = [&](int kt) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ar[j] = *(const u32x4*)(asrc[j] + (size_t)kt * ROWB);
-                br[j] = *(const u32x4*)(bbase + boff_g[j] + (size_t)kt * ROWB);
-            }
-        };
+    for (int n0 = 0; n0 < kpad; n0 += SIM_TILE) {  // the centre tiles in ascending order
+        SimRows opb(p, Cn, n0, hpad);
         f32x4 acc[4][4];
+        sim_tile(p, sA, sB, hpad / 64, opa, opb, acc);
+        // acc[i][j][r] = sim(row, centre), row = m0 + 64 wm + 16 i + fr, centre = n0 + 64 wn + 16 j + 4 fh + r; centres >= K masked
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        fetch(0);
-        for (int kt = 0; kt < nk; ++kt) {
-            __syncthreads();  // every wave is done reading the previous tile
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                *(u32x4*)(sA + sdst[j]) = ar[j];
-                *(u32x4*)(sB + sdst[j]) = br[j];
-            }
-            __syncthreads();
-            if (kt + 1 < nk) fetch(kt + 1);  // in flight under the MFMAs below
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {  // k steps of 32 in ascending order
-                const int ch = ((ks * 4 + fh) ^ sw) << 4;
-                f16x8 af[4], bf[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) af[i] = *(const f16x8*)(sA + aoff + i * 16 * ROWB + ch);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) bf[j] = *(const f16x8*)(sB + boff + j * 16 * ROWB + ch);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[i][j] = E::mfma16(bf[j], af[i], acc[i][j]);  // operand swap: a lane owns one row, four columns
-            }
-        }
-        // acc[i][j][r] = sim(row, centre), row = m0 + 64 wm + 16 i + fr, centre = n0 + 64 wn + 16 j + 4 fh + r.  (+ 0.0f: a -0 becomes +0)
-        const int colb = n0 + wn * 64 + 4 * fh;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int col = colb + j * 16 + r;
-                    if (col < K) fold(best[i], acc[i][j][r] + 0.0f, col);  // a lane's columns ascending; columns >= K masked
-                }
+        for (int i = 0; i < 4; ++i) sim_row_fold(acc, i, n0 + p.wn * 64 + 4 * p.fh, K, best[i]);
     }
     // the four lanes that share a row, then the two waves side by side
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        Best b = best[i];
-        fold_lane<16>(b);
-        fold_lane<32>(b);
-        if (fh == 0) {
-            red_rv[wn][wm * 64 + i * 16 + fr] = b.v;
-            red_ri[wn][wm * 64 + i * 16 + fr] = b.i;
-        }
-    }
+    for (int i = 0; i < 4; ++i) sim_row_share(p, i, best[i], red_rv, red_ri);
     __syncthreads();
-    if (tid < TILE) {  // waves 0 and 1, whole
-        Best b{red_rv[0][tid], red_ri[0][tid]};
-        fold(b, red_rv[1][tid], red_ri[1][tid]);
-        const int row = m0 + tid;
+    if (p.tid < SIM_TILE) {  // waves 0 and 1, whole
+        const Best b = sim_fold_waves(red_rv, red_ri, p.tid);
+        const int row = m0 + p.tid;
         int changed = 0;
         if (row < n) {
             changed = first || label[row] != b.i;
@@ -162,10 +97,10 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const _Float16* __re
             label[row] = -1;
         }
         const unsigned long long m = __ballot(changed);
-        if (lane == 0) red_ch[wid] = __popcll(m);
+        if (p.lane == 0) red_ch[p.wid] = __popcll(m);
     }
     __syncthreads();
-    if (tid == 0) chpart[blockIdx.x] = red_ch[0] + red_ch[1];
+    if (p.tid == 0) chpart[blockIdx.x] = red_ch[0] + red_ch[1];
 }
 
 // out[0] = sum of part[0 .. count), in ascending order (integers: any order gives the same)
@@ -196,89 +131,26 @@ __global__ __launch_bounds__(256) void kmeans_transpose_kernel(const _Float16* _
 }
 
 // XT [hpad128, npad], label [npad] (-1 on padding rows).  Workgroup (x, y, z): rows h [128 x, +128) of XT, centres [128 y, +128), the rows i
-// of chunk z = [z chunk, min((z + 1) chunk, npad)) in K-tiles of 64.  The A operand is staged as in match_kernel; the B operand [128 c][64 i] =
-// (label[i] == 128 y + c) is written into the same swizzled image from the K-tile's 64 labels.  part [nsplit][kpad][hpad128]: every element
-// of the workgroup's tile is stored.  cpart [nsplit][kpad]: members of each centre in the chunk (workgroups x == 0).
+// of chunk z = [z chunk, min((z + 1) chunk, npad)) in K-tiles of 64, ascending.  part [nsplit][kpad][hpad128]: every element of the
+// workgroup's tile is stored.  cpart [nsplit][kpad]: members of each centre in the chunk (workgroups x == 0).
 __global__ __launch_bounds__(256) void kmeans_update_kernel(const _Float16* __restrict__ XT, const int* __restrict__ label, int npad, int chunk,
                                                             int kpad, int hpad128, float* __restrict__ part, int* __restrict__ cpart) {
-    using E = Elem<_Float16>;
-    __shared__ __attribute__((aligned(16))) char sA[TILE * ROWB];
-    __shared__ __attribute__((aligned(16))) char sB[TILE * ROWB];
+    __shared__ __attribute__((aligned(16))) char sA[SIM_TILE * SIM_ROWB];
+    __shared__ __attribute__((aligned(16))) char sB[SIM_TILE * SIM_ROWB];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = tid >> 6;
-    const int wm = wid >> 1, wn = wid & 1;
-    const int m0 = blockIdx.x * TILE, n0 = blockIdx.y * TILE;
+    const SimPlace p;
+    const int m0 = blockIdx.x * SIM_TILE, n0 = blockIdx.y * SIM_TILE;
     const int i0 = blockIdx.z * chunk;
     const int i1 = i0 + chunk < npad ? i0 + chunk : npad;
-    const int nk = (i1 - i0) / 64;
 
-    const char* asrc[4];
-    int sdst[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int q = j * 256 + tid, row = q >> 3, c = q & 7;
-        asrc[j] = (const char*)XT + ((size_t)(m0 + row) * npad + i0) * 2 + c * 16;
-        sdst[j] = row * ROWB + ((c ^ ((row >> 1) & 7)) << 4);
-    }
-    // the 8 labels of this thread's chunk of every K-tile (the chunk index q & 7 = tid & 7 is the same for its four rows)
-    const int* const lsrc = label + i0 + (tid & 7) * 8;
-    const int crow = n0 + (tid >> 3);  // the centre of its row j = 0; row j is 32 j further
-    u32x4 ar[4];
-    u32x4 l0, l1;  // (compared as unsigned: the -1 of a padding row equals no centre)
-    auto fetch = [&](int kt) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ar[j] = *(const u32x4*)(asrc[j] + (size_t)kt * ROWB);
-        l0 = *(const u32x4*)(lsrc + kt * 64);
-        l1 = *(const u32x4*)(lsrc + kt * 64 + 4);
-    };
-
-    const int fr = lane & 15, fh = lane >> 4, sw = (fr >> 1) & 7;
-    const int aoff = (wm * 64 + fr) * ROWB, boff = (wn * 64 + fr) * ROWB;
+    SimRows opa(p, XT, m0, npad, i0);
+    OneHotRows opb{label + i0 + (p.tid & 7) * 8, n0 + (p.tid >> 3), {}, {}, {0, 0, 0, 0}};
     f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    int cnt[4] = {0, 0, 0, 0};
+    sim_tile(p, sA, sB, (i1 - i0) / 64, opa, opb, acc);
 
-    fetch(0);
-    for (int kt = 0; kt < nk; ++kt) {  // rows ascending
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            *(u32x4*)(sA + sdst[j]) = ar[j];
-            const unsigned c = (unsigned)(crow + 32 * j);
-            const unsigned lab[8] = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-            u32x4 oh;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const unsigned lo = lab[2 * e] == c, hi = lab[2 * e + 1] == c;
-                oh[e] = lo * 0x3c00u | hi * 0x3c000000u;  // 1.0 in f16
-                cnt[j] += (int)(lo + hi);
-            }
-            *(u32x4*)(sB + sdst[j]) = oh;
-        }
-        __syncthreads();
-        if (kt + 1 < nk) fetch(kt + 1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {  // k steps of 32 in ascending order
-            const int ch = ((ks * 4 + fh) ^ sw) << 4;
-            f16x8 af[4], bf[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = *(const f16x8*)(sA + aoff + i * 16 * ROWB + ch);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bf[j] = *(const f16x8*)(sB + boff + j * 16 * ROWB + ch);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = E::mfma16(bf[j], af[i], acc[i][j]);
-        }
-    }
     // acc[i][j][r] = D(h, c), h = m0 + 64 wm + 16 i + fr, c = n0 + 64 wn + 16 j + 4 fh + r
     float* const dst = part + ((size_t)blockIdx.z * kpad) * hpad128;
-    const int hb = m0 + wm * 64 + fr, cb = n0 + wn * 64 + 4 * fh;
+    const int hb = m0 + p.wm * 64 + p.fr, cb = n0 + p.wn * 64 + 4 * p.fh;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -288,11 +160,11 @@ __global__ __launch_bounds__(256) void kmeans_update_kernel(const _Float16* __re
     if (blockIdx.x == 0) {  // the eight threads that share a row of the one-hot image
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            int s = cnt[j];
+            int s = opb.cnt[j];
             s += __shfl_xor(s, 1);
             s += __shfl_xor(s, 2);
             s += __shfl_xor(s, 4);
-            if ((tid & 7) == 0) cpart[(size_t)blockIdx.z * kpad + crow + 32 * j] = s;
+            if ((p.tid & 7) == 0) cpart[(size_t)blockIdx.z * kpad + opb.crow + 32 * j] = s;
         }
     }
 }
@@ -349,7 +221,7 @@ KmeansBufs kmeans_bufs(char* ws, const KmeansPlan& p) {
 }
 
 hipError_t launch_kmeans_assign(const KmeansBufs& b, int n, int K, const KmeansPlan& p, bool first, hipStream_t st) {
-    const int tiles = p.npad / TILE;
+    const int tiles = p.npad / SIM_TILE;
     hipLaunchKernelGGL(kmeans_assign_kernel, dim3(tiles), dim3(256), 0, st, b.x16, b.c16, p.hpad, n, K, p.kpad, b.labels, b.sim, b.chpart,
                        first ? 1 : 0);
     hipLaunchKernelGGL(kmeans_fold_kernel, dim3(1), dim3(64), 0, st, b.chpart, tiles, b.changed);
@@ -362,7 +234,7 @@ hipError_t launch_kmeans_transpose(const KmeansBufs& b, const KmeansPlan& p, hip
 }
 
 hipError_t launch_kmeans_update(const KmeansBufs& b, int K, int H, const KmeansPlan& p, hipStream_t st) {
-    hipLaunchKernelGGL(kmeans_update_kernel, dim3(p.hpad128 / TILE, p.kpad / TILE, p.nsplit), dim3(256), 0, st, b.xt, b.labels, p.npad, p.chunk,
+    hipLaunchKernelGGL(kmeans_update_kernel, dim3(p.hpad128 / SIM_TILE, p.kpad / SIM_TILE, p.nsplit), dim3(256), 0, st, b.xt, b.labels, p.npad, p.chunk,
                        p.kpad, p.hpad128, b.part, b.cpart);
     hipLaunchKernelGGL(kmeans_finish_kernel, dim3((H + 255) / 256, K), dim3(256), 0, st, b.part, b.cpart, p.nsplit, p.kpad, p.hpad128, H, b.cvec,
                        b.counts);

@@ -8,38 +8,10 @@
 //                           (best value, lowest column) and per column (best value, lowest row) and stores one partial per (row, column
 //                           tile) and one per (column, row tile)
 //   match_reduce_kernel     folds the partials of a row (column) over the column (row) tiles
-// Both directions come from the same accumulators.  "Best" is one total order everywhere -- the larger f32 value, among equal values (-0 == +0)
-// the lower index -- so the result does not depend on which lane, wave, tile or pass met a pair first.  The K order of a pair depends on
-// hpad alone: k steps of 32 in ascending order, whatever tile the pair falls in.
-#include <climits>
-
-#include "device_types.h"
-#include "kernels.h"
+// Both directions come from the same accumulators.  The tile, the K order of a pair and the total order of "best" are sim_tile.h's.
+#include "sim_tile.h"
 
 namespace dinov2 {
-
-namespace {
-
-struct Best {
-    float v;
-    int i;
-};
-// the order of the whole file: larger value first, then lower index (an empty slot is (-inf, INT_MAX))
-__device__ __forceinline__ bool better(float v, int i, const Best& b) { return v > b.v || (v == b.v && i < b.i); }
-__device__ __forceinline__ void fold(Best& b, float v, int i) {
-    if (better(v, i, b)) {
-        b.v = v;
-        b.i = i;
-    }
-}
-template <int OFF>
-__device__ __forceinline__ void fold_lane(Best& b) {
-    const float v = __shfl_xor(b.v, OFF);
-    const int i = __shfl_xor(b.i, OFF);
-    fold(b, v, i);
-}
-
-}  // namespace
 
 // x: rows [n] of H floats, row stride ld.  out [nout, hpad] f16: row / sqrt(sum of squares), 0 for an all-zero row, for rows >= n and for
 // columns >= H; rows >= nout are not touched (the grid covers nout rounded up to 4).  Four rows per workgroup, one wave each; lane l owns the 4-float chunks l, l + 64, ... (16-byte loads when `vec`: H, ld
@@ -88,99 +60,31 @@ __global__ __launch_bounds__(256) void match_normalise_kernel(const float* __res
 }
 
 // A [na_pad, hpad], B [nb_pad, hpad]: the normalised operands.  Workgroup (x, y) owns rows [row0 + 128 y, +128) and columns
-// [col0 + 128 x, +128); four waves, 2 x 2, each 64 x 64 = 4 x 4 accumulator blocks of 16 x 16.  Operands are padded to whole tiles, so loads
-// need no guards; rows >= na and columns >= nb are masked in the epilogue.  LDS image as in gemm.hip: [row][64 k] f16, 128-byte rows, 16-byte
-// chunk c of row r at chunk c ^ ((r >> 1) & 7), which spreads every 16-lane ds_read_b128 group over 16 bank slots.
+// [col0 + 128 x, +128): one tile of sim_tile.h.  Rows >= na and columns >= nb are masked in the epilogue.
 // prow_*[x * prow_ld + 128 y + r]: best column of row r among this tile's columns; pcol_*[y * pcol_ld + 128 x + c]: best row of column c.
 __global__ __launch_bounds__(256) void match_kernel(const _Float16* __restrict__ A, const _Float16* __restrict__ B, int hpad, int na, int nb,
                                                     int row0, int col0, float* __restrict__ prow_v, int* __restrict__ prow_i, size_t prow_ld,
                                                     float* __restrict__ pcol_v, int* __restrict__ pcol_i, size_t pcol_ld) {
-    using E = Elem<_Float16>;
-    constexpr int BM = MATCH_TM, BN = MATCH_TN, ROWB = 128;
-    __shared__ __attribute__((aligned(16))) char sA[BM * ROWB];
-    __shared__ __attribute__((aligned(16))) char sB[BN * ROWB];
+    constexpr int BM = MATCH_TM, BN = MATCH_TN;
+    __shared__ __attribute__((aligned(16))) char sA[BM * SIM_ROWB];
+    __shared__ __attribute__((aligned(16))) char sB[BN * SIM_ROWB];
     __shared__ float red_rv[2][BM], red_cv[2][BN];
     __shared__ int red_ri[2][BM], red_ci[2][BN];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = tid >> 6;
-    const int wm = wid >> 1, wn = wid & 1;
+    const SimPlace p;
     const int m0 = row0 + blockIdx.y * BM, n0 = col0 + blockIdx.x * BN;
-
-    // staging: 128 rows x 8 chunks of 16 bytes per operand = 4 chunks per thread; 8 neighbouring threads read one 128-byte row segment
-    const char* asrc[4];
-    const char* bsrc[4];
-    int sdst[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int q = j * 256 + tid, row = q >> 3, c = q & 7;
-        asrc[j] = (const char*)A + ((size_t)(m0 + row) * hpad) * 2 + c * 16;
-        bsrc[j] = (const char*)B + ((size_t)(n0 + row) * hpad) * 2 + c * 16;
-        sdst[j] = row * ROWB + ((c ^ ((row >> 1) & 7)) << 4);
-    }
-    u32x4 ar[4], br[4];
-    auto fetch = [&](int kt) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            ar[j] = *(const u32x4*)(asrc[j] + (size_t)kt * ROWB);
-            br[j] = *(const u32x4*)(bsrc[j] + (size_t)kt * ROWB);
-        }
-    };
-
-    const int fr = lane & 15, fh = lane >> 4, sw = (fr >> 1) & 7;
-    const int aoff = (wm * 64 + fr) * ROWB, boff = (wn * 64 + fr) * ROWB;
+    SimRows opa(p, A, m0, hpad), opb(p, B, n0, hpad);
     f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int nk = hpad / 64;
-    fetch(0);
-    for (int kt = 0; kt < nk; ++kt) {
-        __syncthreads();  // every wave is done reading the previous tile
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            *(u32x4*)(sA + sdst[j]) = ar[j];
-            *(u32x4*)(sB + sdst[j]) = br[j];
-        }
-        __syncthreads();
-        if (kt + 1 < nk) fetch(kt + 1);  // in flight under the MFMAs below
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {  // k steps of 32 in ascending order
-            const int ch = ((ks * 4 + fh) ^ sw) << 4;
-            f16x8 af[4], bf[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = *(const f16x8*)(sA + aoff + i * 16 * ROWB + ch);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bf[j] = *(const f16x8*)(sB + boff + j * 16 * ROWB + ch);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = E::mfma16(bf[j], af[i], acc[i][j]);  // operand swap: a lane owns one row, four columns
-        }
-    }
+    sim_tile(p, sA, sB, hpad / 64, opa, opb, acc);
 
     // acc[i][j][r] = sim(row, col), row = m0 + 64 wm + 16 i + fr, col = n0 + 64 wn + 16 j + 4 fh + r.  (+ 0.0f: a -0 becomes +0)
-    const int rowb = m0 + wm * 64 + fr, colb = n0 + wn * 64 + 4 * fh;
+    const int rowb = m0 + p.wm * 64 + p.fr, colb = n0 + p.wn * 64 + 4 * p.fh;
     // per row over this wave's 64 columns: a lane's 16 in ascending order, then the four lanes that share the row
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         Best b{-INFINITY, INT_MAX};
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int col = colb + j * 16 + r;
-                if (col < nb) fold(b, acc[i][j][r] + 0.0f, col);
-            }
-        fold_lane<16>(b);
-        fold_lane<32>(b);
-        if (fh == 0) {
-            red_rv[wn][wm * 64 + i * 16 + fr] = b.v;
-            red_ri[wn][wm * 64 + i * 16 + fr] = b.i;
-        }
+        sim_row_fold(acc, i, colb, nb, b);
+        sim_row_share(p, i, b, red_rv, red_ri);
     }
     // per column over this wave's 64 rows: a lane's 4 in ascending order, then the sixteen lanes that share the column
 #pragma unroll
@@ -197,22 +101,20 @@ __global__ __launch_bounds__(256) void match_kernel(const _Float16* __restrict__
             fold_lane<2>(b);
             fold_lane<4>(b);
             fold_lane<8>(b);
-            if (fr == 0) {
-                red_cv[wm][wn * 64 + j * 16 + 4 * fh + r] = b.v;
-                red_ci[wm][wn * 64 + j * 16 + 4 * fh + r] = b.i;
+            if (p.fr == 0) {
+                red_cv[p.wm][p.wn * 64 + j * 16 + 4 * p.fh + r] = b.v;
+                red_ci[p.wm][p.wn * 64 + j * 16 + 4 * p.fh + r] = b.i;
             }
         }
     __syncthreads();
-    if (tid < BM) {  // the two waves side by side
-        Best b{red_rv[0][tid], red_ri[0][tid]};
-        fold(b, red_rv[1][tid], red_ri[1][tid]);
-        const size_t o = (size_t)blockIdx.x * prow_ld + (size_t)blockIdx.y * BM + tid;
+    if (p.tid < BM) {  // the two waves side by side
+        const Best b = sim_fold_waves(red_rv, red_ri, p.tid);
+        const size_t o = (size_t)blockIdx.x * prow_ld + (size_t)blockIdx.y * BM + p.tid;
         prow_v[o] = b.v;
         prow_i[o] = b.i;
     } else {  // the two waves above each other
-        const int c = tid - BM;
-        Best b{red_cv[0][c], red_ci[0][c]};
-        fold(b, red_cv[1][c], red_ci[1][c]);
+        const int c = p.tid - BM;
+        const Best b = sim_fold_waves(red_cv, red_ci, c);
         const size_t o = (size_t)blockIdx.y * pcol_ld + (size_t)blockIdx.x * BN + c;
         pcol_v[o] = b.v;
         pcol_i[o] = b.i;

@@ -198,3 +198,21 @@ def test_gemm_epilogue_arithmetic_has_a_single_source():
     assert "gemm_epilogue.h" not in text["attention.hip"]
     for needle in ("#define DINO2_ST16", "#define DINO4_ST16"):
         assert not [f for f, t in text.items() if needle in t], needle
+
+
+# ------------------------------------------------------------------------------------------------------------------ sim_tile.h
+def test_similarity_tile_and_its_order_have_a_single_source():
+    """match, bank top-k and k-means must give a pair the same similarity bits and choose by the same total order, so the 128 x 128 tile
+    (staging addresses, swizzled LDS image, K loop, MFMAs) and the order are written once, in csrc/sim_tile.h, which match.hip, bank.hip and
+    kmeans.hip include.  The tile's fingerprints -- the swizzle of the LDS destination, the chunk expression of the fragment reads, the
+    MFMA call -- and a definition of the pair type or of a comparison may not reappear in those three files."""
+    csrc = os.path.join(ROOT, "dinov2.cpp_amd", "csrc")
+    assert os.path.isfile(os.path.join(csrc, "sim_tile.h"))
+    header = open(os.path.join(csrc, "sim_tile.h")).read()
+    for needle in ("(row >> 1) & 7)) << 4", "^ p.sw) << 4", "mfma16(", "bool before("):
+        assert needle in header, needle
+    for f in ("match.hip", "bank.hip", "kmeans.hip"):
+        text = open(os.path.join(csrc, f)).read()
+        assert re.search(r'^#include "sim_tile\.h"', text, re.M), f
+        for needle in ("(row >> 1) & 7)) << 4", "^ sw) << 4", "^ p.sw) << 4", "mfma16(", "struct Best", "bool better(", "bool before("):
+            assert needle not in text, (f, needle)

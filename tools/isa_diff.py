@@ -7,7 +7,8 @@ Each named file (relative to <tree>/dinov2.cpp_amd) is cross-compiled from both 
 `-S --cuda-device-only`, and the assembly is normalised the way tests/test_kernel_build_checks.py::misc_instruction_streams does it:
 comments and directives dropped, branch labels numbered per function.  Per file: functions and instructions on either side, and the names
 of the functions whose streams differ (with the size of a unified diff of the two).  Exit status 1 if anything differs.  A refactor that is
-meant to leave the kernels alone proves it with `git worktree add /tmp/parent HEAD~1 && tools/isa_diff.py /tmp/parent .`."""
+meant to leave the kernels alone proves it with `git worktree add /tmp/parent HEAD~1 && tools/isa_diff.py /tmp/parent .`; one that moves
+the similarity tile of csrc/sim_tile.h names its users: `... /tmp/parent . csrc/match.hip csrc/bank.hip csrc/kmeans.hip`."""
 import argparse
 import concurrent.futures
 import difflib
