@@ -269,6 +269,24 @@ def op_attention_far(dtype, B, T, nh, rows, *, seed=1, log2_scores=True):
     return out, untouched.value
 
 
+def op_rows_fill(dst, row0, n, dictionary, d_common, seed, plants=(), *, ld=None):
+    """Rows [row0, row0 + n) of a far operand into the first n rows of the DeviceArray dst [>= n, H] (dinov2_hip_op_rows_fill): row r is
+    dictionary[entry(r)], entry = a hash of r onto [0, d_common) unless r is planted.  dictionary: host [D, H]; plants: (row, entry) pairs.
+    ld: the row stride in floats (default: dst's row length).  A testing aid: nothing of the product path calls it."""
+    dic = _f32(dictionary)
+    D, H = dic.shape
+    ld = int(dst.shape[1] if ld is None else ld)
+    if len(dst.shape) != 2 or n < 1 or ld < H or (int(n) - 1) * ld + H > dst.shape[0] * dst.shape[1]:
+        raise ValueError(f"rows_fill: {n} rows of {H} floats at stride {ld} do not fit a buffer of shape {dst.shape}")
+    pl = sorted((int(r), int(e)) for r, e in plants)
+    pr, pe = np.array([r for r, _ in pl], np.int64), np.array([e for _, e in pl], np.int32)
+    rc = lib().dinov2_hip_op_rows_fill(C.c_void_p(dst.ptr), ld, int(row0), int(n), H, _ptr(dic), D, int(d_common), int(seed),
+                                       _ptr(pr) if len(pl) else None, _ptr(pe) if len(pl) else None, len(pl))
+    if rc == 4:
+        raise ValueError("dinov2_hip_op_rows_fill refuses these arguments")
+    _op_rc(rc, "rows_fill")
+
+
 def op_layer_tap(x, w, b, eps, R, h0, w0, *, norm, chw, want=("patch", "cls", "reg")):
     """layer_tap_kernel alone (dinov2_hip_op_layer_tap): x [B, T, H] f32 -> dict of the destinations in `want`.  Raises on a HIP error or a
     changed guard band."""
@@ -757,6 +775,7 @@ def lib():
     L.dinov2_hip_op_gemm_far.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint64, fp, fp, fp, i32, C.c_float, i64p, i32, fp,
                                          i64p]
     L.dinov2_hip_op_attention_far.argtypes = [i32, i32, i32, i32, C.c_uint64, i32, i64p, i32, fp, i64p]
+    L.dinov2_hip_op_rows_fill.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, i32, fp, i32, i32, C.c_uint64, i64p, C.POINTER(i32), i32]
     _lib = L
     return L
 

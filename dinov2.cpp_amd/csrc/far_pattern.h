@@ -31,4 +31,25 @@ FAR_PATTERN_HD inline int far_value_q(uint64_t seed, uint64_t row, uint32_t col)
 // exact in f32, in any order.
 FAR_PATTERN_HD inline float far_value(uint64_t seed, uint64_t row, uint32_t col) { return (float)far_value_q(seed, row, col) * 0.015625f; }
 
+// Far ROWS (dinov2_hip_op_rows_fill; tests/rows_far_cases.py restates both functions in numpy): row `row` of an operand is one entry of a small
+// dictionary of rows.  The common entries [0, d_common) are drawn by a hash of the full 64-bit row index -- two far_value_q calls give 14 bits,
+// reduced modulo d_common (1 .. 16384) -- so, like far_value, the choice has no period in `row`.
+FAR_PATTERN_HD inline int far_rows_sel(uint64_t seed, uint64_t row, int d_common) {
+    const int hi = far_value_q(seed, row, 0u) + 64, lo = far_value_q(seed, row, 1u) + 64;
+    return (hi * 128 + lo) % d_common;
+}
+
+// The entry of a row: a short list of planted rows (plant_rows strictly ascending; plant_entries beside it) overrides the hash.
+FAR_PATTERN_HD inline int far_rows_entry(uint64_t seed, uint64_t row, int d_common, const int64_t* plant_rows, const int32_t* plant_entries,
+                                         int nplants) {
+    int lo = 0, hi = nplants;  // the first plant whose row is >= row
+    while (lo < hi) {
+        const int mid = (lo + hi) / 2;
+        if ((uint64_t)plant_rows[mid] < row) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo < nplants && (uint64_t)plant_rows[lo] == row) return plant_entries[lo];
+    return far_rows_sel(seed, row, d_common);
+}
+
 }  // namespace dinov2

@@ -627,6 +627,51 @@ extern "C" int dinov2_hip_op_attention_far(int32_t dtype, int32_t B, int32_t T, 
     return far_collect(dO, dt, M, H, (size_t)H, 0, 0, rows, nrows, out_rows, untouched);
 }
 
+// ---- far rows: rows [row0, row0 + n) of an operand whose row r is dictionary entry far_rows_entry(seed, r, ...) (csrc/far_pattern.h), written
+// into the CALLER's device buffer, for the resident-rows entry points (match, bank, k-means) at the far end of their row offsets ----
+namespace {
+
+// dst[r * ld + c] = dict[entry(row0 + r) * H + c], r < n, c < H; one wave per row, four rows per workgroup
+__global__ __launch_bounds__(256) void rows_fill_kernel(float* __restrict__ dst, size_t ld, uint64_t row0, size_t n, int H,
+                                                        const float* __restrict__ dict, int d_common, uint64_t seed,
+                                                        const int64_t* __restrict__ plant_rows, const int32_t* __restrict__ plant_entries,
+                                                        int nplants) {
+    const int lane = threadIdx.x & 63;
+    const size_t step = (size_t)gridDim.x * 4;
+    for (size_t r = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += step) {
+        const int e = far_rows_entry(seed, row0 + r, d_common, plant_rows, plant_entries, nplants);
+        const float* const src = dict + (size_t)e * (size_t)H;
+        float* const out = dst + r * ld;
+        for (int c = lane; c < H; c += 64) out[c] = src[c];
+    }
+}
+
+}  // namespace
+
+extern "C" int dinov2_hip_op_rows_fill(float* dst_dev, int64_t ld, int64_t row0, int64_t n, int32_t H, const float* dict, int32_t D,
+                                       int32_t d_common, uint64_t seed, const int64_t* plant_rows, const int32_t* plant_entries,
+                                       int32_t nplants) {
+    if (!dst_dev || ((size_t)dst_dev & 3) != 0 || !dict || H < 1 || H > 4096 || ld < H || row0 < 0 || n < 1 || n > ((int64_t)1 << 32) ||
+        D < 1 || D > 16384 || d_common < 1 || d_common > D || nplants < 0 || nplants > 256 || (nplants > 0 && (!plant_rows || !plant_entries)))
+        return DINOV2_HIP_ERR_INVALID;
+    for (int i = 0; i < nplants; ++i)
+        if (plant_rows[i] < 0 || (i > 0 && plant_rows[i] <= plant_rows[i - 1]) || plant_entries[i] < 0 || plant_entries[i] >= D)
+            return DINOV2_HIP_ERR_INVALID;
+    OpBuf dD, dR, dE;
+    OP_TRY(dD.upload(dict, sizeof(float) * (size_t)D * H));
+    if (nplants > 0) {
+        OP_TRY(dR.upload(plant_rows, sizeof(int64_t) * nplants));
+        OP_TRY(dE.upload(plant_entries, sizeof(int32_t) * nplants));
+    }
+    const size_t groups = ((size_t)n + 3) / 4;
+    const unsigned blocks = (unsigned)(groups < ((size_t)1 << 20) ? groups : ((size_t)1 << 20));
+    rows_fill_kernel<<<blocks, 256>>>(dst_dev, (size_t)ld, (uint64_t)row0, (size_t)n, H, dD.as<float>(), d_common, seed, dR.as<int64_t>(),
+                                      dE.as<int32_t>(), nplants);
+    OP_TRY(hipGetLastError());
+    OP_TRY(hipDeviceSynchronize());
+    return 0;
+}
+
 // ---- micro-benchmarks: device-resident random operands, HIP-event timing around `iters` launches ----
 namespace {
 // the two events a timed loop sits between, destroyed on return

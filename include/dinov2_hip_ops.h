@@ -80,6 +80,19 @@ int dinov2_hip_op_gemm_far(int32_t dtype, int32_t epilogue, int32_t M, int32_t N
 int dinov2_hip_op_attention_far(int32_t dtype, int32_t B, int32_t T, int32_t nh, uint64_t seed, int32_t log2_scores, const int64_t *rows,
                                 int32_t nrows, float *out_rows, int64_t *untouched);
 
+/* Far rows: the operands of the resident-rows entry points (dinov2_hip_match_tokens, dinov2_hip_bank_add / _topk, dinov2_hip_kmeans_tokens) at
+ * the far end of their row offsets.  Cases, the numpy restatement of the selection rule and the exact expectations: tests/rows_far_cases.py;
+ * tests/test_rows_far_probes.py (CPU), tests/test_gpu_rows_far.py.
+ *   rows_fill: writes rows [row0, row0 + n) of a far operand into the CALLER's device buffer dst_dev as f32 [n, H] at row stride ld (floats,
+ *             >= H; the gap H .. ld of a row is left as it is).  Row r of the operand is row far_rows_entry(seed, r, d_common, plants)
+ *             (csrc/far_pattern.h) of the host dictionary dict [D, H]: a hash of the full 64-bit row index onto the common entries
+ *             [0, d_common), overridden for the at most 256 planted rows (plant_rows strictly ascending, plant_entries[i] in [0, D)).  The caller
+ *             owns dst_dev and answers for its size ((n - 1) * ld + H floats); the call touches nothing else, synchronises the device before it
+ *             returns and frees what it staged.  A testing aid only: no entry point of include/dinov2_hip.h reaches it.
+ *             Returns 0, -1 (HIP error) or DINOV2_HIP_ERR_INVALID (nothing is launched then). */
+int dinov2_hip_op_rows_fill(float *dst_dev, int64_t ld, int64_t row0, int64_t n, int32_t H, const float *dict, int32_t D, int32_t d_common,
+                            uint64_t seed, const int64_t *plant_rows, const int32_t *plant_entries, int32_t nplants);
+
 /* dinov2_hip_predict_list (include/dinov2_hip.h).  Cases, the numpy restatement of the plan and the per-segment emulation: tests/list_cases.py;
  * tests/test_list_probes.py (CPU), tests/test_gpu_attention_list.py, tests/test_gpu_predict_list.py.
  * list_plan (no device; list_plan of csrc/kernels.h): n images of NETWORK size h[i] x w[i] pixels, `patch` pixels per patch side, R register
