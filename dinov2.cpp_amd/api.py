@@ -113,6 +113,16 @@ class KMeans(C.Structure):
 KMEANS_INIT_GIVEN, KMEANS_INIT_ROWS = 0, 1
 
 
+class Vlad(C.Structure):
+    """dinov2_hip_vlad (include/dinov2_hip.h)."""
+    _fields_ = [("rows", Rows), ("all_images", C.c_int32), ("offsets", C.c_void_p), ("n_seg", C.c_int32), ("K", C.c_int32),
+                ("centers", C.c_void_p), ("flags", C.c_uint32), ("vlad", C.c_void_p), ("counts", C.c_void_p), ("labels", C.c_void_p),
+                ("sim", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+VLAD_INTRA_NORM, VLAD_L2_NORM = 1, 2
+
+
 class DenseDesc(C.Structure):
     """dinov2_hip_dense_desc (include/dinov2_hip.h)."""
     _fields_ = [("layers", C.POINTER(C.c_int32)), ("n_layers", C.c_int32), ("norm", C.c_int32), ("concat_cls", C.c_int32),
@@ -449,6 +459,50 @@ def op_kmeans(rows, K, max_iter=20, init=None, seed=0):
     return out
 
 
+VLAD_PLAN_FIELDS = ("kpad", "hpad", "hpad128", "chunk", "cap", "npad", "ntiles", "nchunks", "npass", "partial_bytes", "bytes")
+
+
+def _vlad_offsets(offsets, n):
+    """[n_seg + 1] int32 offsets; None = one segment of n rows."""
+    return np.asarray([0, n], np.int32) if offsets is None else np.ascontiguousarray(offsets, np.int32)
+
+
+def op_vlad_plan(offsets, K, H):
+    """vlad_plan (csrc/kernels.h) as a dict: its numbers, segs [n_seg, 4] (first padded row, length, first chunk, chunks) and chunks
+    [nchunks, 3] (segment, first padded row, K-tiles); no device needed."""
+    off = _vlad_offsets(offsets, 0)
+    n_seg = len(off) - 1
+    buf = (C.c_int64 * 12)()
+    segs = np.full((max(n_seg, 0), 4), -7, np.int32)
+    if lib().dinov2_hip_op_vlad_plan(_ptr(off), n_seg, int(K), int(H), buf, _ptr(segs), None, 0) != 0:
+        raise ValueError(f"vlad refuses offsets={list(off[:8])}.. K={K} H={H}")
+    out = dict(zip(VLAD_PLAN_FIELDS, [int(v) for v in buf]))
+    chunks = np.full((out["nchunks"], 3), -7, np.int32)
+    if lib().dinov2_hip_op_vlad_plan(_ptr(off), n_seg, int(K), int(H), buf, _ptr(segs), _ptr(chunks), out["nchunks"]) != 0:
+        raise ValueError("vlad_plan refuses its own chunk count")
+    out.update(segs=segs, chunks=chunks)
+    return out
+
+
+def op_vlad(rows, centers, offsets=None, flags=VLAD_INTRA_NORM | VLAD_L2_NORM):
+    """The device work of dinov2_hip_vlad_tokens on host rows without a model or session (dinov2_hip_op_vlad): dict of labels [n], sim [n],
+    counts [n_seg, K], vlad [n_seg, K, H], and xhat [n, H] / chat [K, H], the f32 values of the f16 operands.  Raises on a HIP error or a
+    changed guard band."""
+    x, c = _f32(rows), _f32(centers)
+    assert x.ndim == 2 and c.ndim == 2 and x.shape[1] == c.shape[1], (x.shape, c.shape)
+    n, H = x.shape
+    K = c.shape[0]
+    off = _vlad_offsets(offsets, n)
+    n_seg = len(off) - 1
+    assert n_seg >= 1 and int(off[-1]) == n, (off, n)
+    out = {"labels": np.full(n, -7, np.int32), "sim": np.full(n, np.nan, np.float32), "counts": np.full((n_seg, K), -7, np.int32),
+           "vlad": np.full((n_seg, K, H), np.nan, np.float32), "xhat": np.full((n, H), np.nan, np.float32),
+           "chat": np.full((K, H), np.nan, np.float32)}
+    _op_rc(lib().dinov2_hip_op_vlad(_ptr(x), _ptr(off), n_seg, _ptr(c), K, H, int(flags), _ptr(out["labels"]), _ptr(out["sim"]),
+                                    _ptr(out["counts"]), _ptr(out["vlad"]), _ptr(out["xhat"]), _ptr(out["chat"])), "vlad")
+    return out
+
+
 def op_dense_reduce(logits, h0, w0, out_h, out_w, reduce="argmax", centers=None, eps=0.0, want=("labels", "value")):
     """dense_reduce_kernel alone (dinov2_hip_op_dense_reduce): logits [h0 * w0, C] of one image -> dict of labels [out_h, out_w] uint8 (argmax
     only) and value [out_h, out_w] f32.  Raises on a HIP error or a changed guard band."""
@@ -696,6 +750,7 @@ def lib():
     L.dinov2_hip_pca3.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, cp, sz]
     L.dinov2_hip_match_tokens.argtypes = [vp, C.POINTER(Match), cp, sz]
     L.dinov2_hip_kmeans_tokens.argtypes = [vp, C.POINTER(KMeans), cp, sz]
+    L.dinov2_hip_vlad_tokens.argtypes = [vp, C.POINTER(Vlad), cp, sz]
     L.dinov2_hip_bank_create.argtypes = [vp, i32, i32, C.POINTER(vp), cp, sz]
     L.dinov2_hip_bank_free.argtypes = [vp]
     L.dinov2_hip_bank_free.restype = None
@@ -746,6 +801,9 @@ def lib():
     L.dinov2_hip_op_kmeans_plan.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int64)]
     L.dinov2_hip_op_kmeans.argtypes = [fp, i32, i32, i32, i32, fp, ip, ip, fp, fp, ip, ip, ip]
     L.dinov2_hip_op_kmeans_bench.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, fp]
+    L.dinov2_hip_op_vlad_plan.argtypes = [ip, i32, i32, i32, C.POINTER(C.c_int64), ip, ip, i32]
+    L.dinov2_hip_op_vlad.argtypes = [fp, ip, i32, fp, i32, i32, u32, ip, fp, ip, fp, fp, fp]
+    L.dinov2_hip_op_vlad_bench.argtypes = [vp, ip, i32, vp, i32, i32, u32, i32, i32, fp]
     L.dinov2_hip_op_bank_plan.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64)]
     L.dinov2_hip_op_dense_reduce.argtypes = [fp, i32, i32, i32, i32, i32, i32, fp, C.c_float, C.POINTER(C.c_uint8), fp]
     L.dinov2_hip_op_dense_pack.argtypes = [fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32, fp]
@@ -1616,6 +1674,63 @@ class Session(_Handle):
                     out["counts"].ctypes.data, C.addressof(it), C.addressof(conv))
         _call(lib().dinov2_hip_kmeans_tokens, self._h, C.byref(km))
         out.update(iterations=int(it.value), converged=bool(conv.value))
+        return out
+
+    def vlad(self, rows=None, centers=None, *, source=None, image: int = 0, all_images: bool = False, offsets=None, intra_norm: bool = True,
+             l2_norm: bool = True, want=("vlad", "counts"), n: int | None = None, H: int | None = None):
+        """VLAD descriptors on the device (dinov2_hip_vlad_tokens).  rows: [n, H] host array or DeviceArray, cut into segments by offsets
+        [n_seg + 1] (None: one segment); or rows=None with source="last_patches": the patch rows of image `image` of the last un-split
+        predict, or one segment per image with all_images=True.  `n` and `H` (as in Session.kmeans) override the row count and width that
+        are otherwise taken from the session's last predict(): needed only after a predict of another kind.
+        centers: [K, H] vectors of any length, e.g. Session.kmeans(...)["centers"].  want: which of "vlad" [n_seg, K, H], "counts"
+        [n_seg, K], "labels" [n], "sim" [n] to fetch.  Returns a dict of those."""
+        if source is None:
+            source = "given" if rows is not None else None
+        if source not in _ROWS_SOURCE or (source == "given") != (rows is not None):
+            raise ValueError("vlad: give rows, or source = 'last_patches' without rows")
+        if centers is None:
+            raise ValueError("vlad: centers are required")
+        cen = np.ascontiguousarray(centers, dtype=np.float32)
+        if cen.ndim != 2:
+            raise ValueError("vlad: centers must be [K, H]")
+        n_seg, off = 1, None
+        if source != "given":
+            last = getattr(self, "_last_rows", {})
+            if all_images:
+                n_seg = max(int(last.get("last_cls", 0)), 1)
+            if n is None:
+                n = last.get(source, 0) * (last.get("last_cls", 0) if all_images else 1)
+            r = Rows(_ROWS_SOURCE[source], None, int(n), int(H if H is not None else self.model.hparams.hidden_size), int(image), 0)
+            keep = None
+            if offsets is not None:
+                off = np.ascontiguousarray(offsets, np.int32)  # (the library refuses it)
+        else:
+            if isinstance(rows, DeviceArray):
+                if len(rows.shape) != 2:
+                    raise ValueError("vlad: rows must be [n, H]")
+                r, keep = Rows(ROWS_GIVEN, rows.ptr, rows.shape[0], rows.shape[1], 0, 1), rows
+            else:
+                keep = np.ascontiguousarray(rows, dtype=np.float32)
+                if keep.ndim != 2:
+                    raise ValueError("vlad: rows must be [n, H]")
+                r = Rows(ROWS_GIVEN, keep.ctypes.data, keep.shape[0], keep.shape[1], 0, 0)
+            if offsets is not None:
+                off = np.ascontiguousarray(offsets, np.int32)
+                if off.ndim != 1 or len(off) < 2:
+                    raise ValueError("vlad: offsets must be [n_seg + 1]")
+                n_seg = len(off) - 1
+        nn, HH, K = max(int(r.n), 0), int(r.H), int(cen.shape[0])
+        if cen.shape[1] != HH:
+            raise ValueError(f"vlad: centers are [K, {cen.shape[1]}], the rows have H = {HH}")
+        unknown = set(want) - {"vlad", "counts", "labels", "sim"}
+        if unknown:
+            raise ValueError(f"vlad: unknown outputs {sorted(unknown)}")
+        shapes = {"vlad": ((n_seg, K, HH), np.float32), "counts": ((n_seg, K), np.int32), "labels": ((nn,), np.int32), "sim": ((nn,), np.float32)}
+        out = {k: np.full(shapes[k][0], -7 if shapes[k][1] is np.int32 else np.nan, shapes[k][1]) for k in shapes if k in want}
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        v = Vlad(r, int(bool(all_images)), None if off is None else off.ctypes.data, n_seg, K, cen.ctypes.data,
+                 (VLAD_INTRA_NORM if intra_norm else 0) | (VLAD_L2_NORM if l2_norm else 0), ptr("vlad"), ptr("counts"), ptr("labels"), ptr("sim"))
+        _call(lib().dinov2_hip_vlad_tokens, self._h, C.byref(v))
         return out
 
     def sync(self):

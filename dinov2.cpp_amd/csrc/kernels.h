@@ -534,6 +534,127 @@ hipError_t launch_kmeans_gather(const float* src, int per, size_t outer, size_t 
 hipError_t kmeans_run(const KmeansBufs& b, int n, int K, int H, int max_iter, const KmeansPlan& plan, hipStream_t stream, int* iterations,
                       int* converged);
 
+// VLAD descriptors of row segments (csrc/vlad.hip; contract in include/dinov2_hip.h, dinov2_hip_vlad).  Every segment has a block of its own
+// in the f16 operand, padded to whole 128-row tiles, so that an assignment tile belongs to one segment and the K-tiles of the cluster sums
+// start at the segment's first row: what a segment's sums are made of, and in which order, never depends on its neighbours or its offset.
+// The sums are k-means' one-hot GEMM over chunks of vlad_chunk_rows(K, H) rows of ONE segment; the chunks of all segments in ascending order
+// are walked in passes of at most `cap` chunks, whose f32 partials [cap][kpad][hpad128] never exceed VLAD_PARTIAL_MAX.
+constexpr int VLAD_SEG_MAX = 4096, VLAD_N_MAX = 1 << 20;
+constexpr size_t VLAD_OUT_MAX = (size_t)1 << 28, VLAD_PARTIAL_MAX = (size_t)32 << 20;
+enum VladFlags : unsigned { VLAD_INTRA_NORM = 1u, VLAD_L2_NORM = 2u };
+struct VladSeg {  // one segment: rows [row0, row0 + pad) of the padded layout hold its `len` rows and zeros; chunks [chunk0, chunk0 + nchunks)
+    int row0, len, chunk0, nchunks;
+};
+struct VladChunk {  // one workgroup layer of the sums: `ktiles` K-tiles of 64 rows from padded row `row0` on, all of segment `seg`
+    int seg, row0, ktiles;
+};
+struct VladTile {  // one assignment tile: its first `valid` rows are real, and they are rows out0 .. of the caller's rows
+    int valid, out0;
+};
+// rows of a segment's block: its length to whole 128-row tiles
+inline int vlad_seg_pad(int len) { return (len + 127) / 128 * 128; }
+// Rows per chunk: a multiple of 64 from (K, H) alone -- as many K-tiles as the sums have output tiles, between 4 and 32: few output tiles
+// need many chunks to fill the device, many output tiles amortise their stores over a longer chunk.
+inline int vlad_chunk_rows(int K, int H) {
+    const int tiles = ((H + 127) / 128) * ((K + 127) / 128);
+    return 64 * (tiles < 4 ? 4 : tiles > 32 ? 32 : tiles);
+}
+struct VladPlan {
+    int kpad, hpad, hpad128;        // as KmeansPlan
+    int chunk, cap;                 // rows per chunk; chunks per pass
+    int npad, ntiles;               // rows of the padded layout (the sum of the segments' pads), its 128-row tiles
+    int nchunks, npass;             // pass p = chunks [p cap, min((p + 1) cap, nchunks))
+    size_t x16, xt, c16;            // f16: X^ [npad, hpad], X^T [hpad128, npad], unit centres [kpad, hpad]
+    size_t cvec;                    // the caller's centre vectors [K, H] f32
+    size_t labels;                  // int32 [npad], padded layout (-1 on padding rows)
+    size_t labels_out, sim_out;     // int32 / f32 [n], the caller's order
+    size_t part, cpart;             // f32 [cap'][kpad][hpad128], int32 [cap'][kpad], cap' = min(cap, nchunks)
+    size_t vlad, counts, rowss;     // f32 [n_seg, K, H], int32 [n_seg, K], f32 [n_seg, K] (sum of squares of each written row)
+    size_t segs, chunks, tiles;     // VladSeg [n_seg], VladChunk [nchunks], VladTile [ntiles]
+    size_t part_bytes, bytes;
+};
+// offsets [n_seg + 1] strictly ascending from 0.  Pure: a segment's chunks follow from (its length, K, H) alone; the pass boundaries depend
+// on the segments before it, and the fold of vlad_finish_kernel is the same left-to-right chain wherever a pass ends.  segs / chunks / tiles
+// (any may be NULL) receive the three tables.
+inline VladPlan vlad_plan(const int32_t* offsets, int n_seg, int K, int H, std::vector<VladSeg>* segs, std::vector<VladChunk>* chunks,
+                          std::vector<VladTile>* tiles) {
+    VladPlan p{};
+    p.kpad = (K + 127) / 128 * 128;
+    p.hpad = (H + 63) / 64 * 64;
+    p.hpad128 = (H + 127) / 128 * 128;
+    p.chunk = vlad_chunk_rows(K, H);
+    const size_t per_chunk = (size_t)p.kpad * p.hpad128 * 4;  // <= 16 MiB
+    p.cap = (int)(VLAD_PARTIAL_MAX / per_chunk);
+    if (segs) segs->clear();
+    if (chunks) chunks->clear();
+    if (tiles) tiles->clear();
+    for (int s = 0; s < n_seg; ++s) {
+        const int len = offsets[s + 1] - offsets[s], pad = vlad_seg_pad(len), nch = (pad + p.chunk - 1) / p.chunk;
+        if (segs) segs->push_back(VladSeg{p.npad, len, p.nchunks, nch});
+        for (int j = 0; chunks && j < nch; ++j) {
+            const int r0 = j * p.chunk, r1 = r0 + p.chunk < pad ? r0 + p.chunk : pad;
+            chunks->push_back(VladChunk{s, p.npad + r0, (r1 - r0) / 64});
+        }
+        for (int t = 0; tiles && t < pad / 128; ++t) {
+            const int left = len - t * 128;
+            tiles->push_back(VladTile{left < 128 ? left : 128, offsets[s] + t * 128});
+        }
+        p.npad += pad;
+        p.nchunks += nch;
+    }
+    p.ntiles = p.npad / 128;
+    p.npass = (p.nchunks + p.cap - 1) / p.cap;
+    const int n = offsets[n_seg], held = p.nchunks < p.cap ? p.nchunks : p.cap;
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t off = need; need += (bytes + 255) / 256 * 256; return off; };
+    p.x16 = take((size_t)p.npad * p.hpad * 2);
+    p.xt = take((size_t)p.hpad128 * p.npad * 2);
+    p.c16 = take((size_t)p.kpad * p.hpad * 2);
+    p.cvec = take((size_t)K * H * 4);
+    p.labels = take((size_t)p.npad * 4);
+    p.labels_out = take((size_t)n * 4);
+    p.sim_out = take((size_t)n * 4);
+    p.part_bytes = per_chunk * held;
+    p.part = take(p.part_bytes);
+    p.cpart = take((size_t)held * p.kpad * 4);
+    p.vlad = take((size_t)n_seg * K * H * 4);
+    p.counts = take((size_t)n_seg * K * 4);
+    p.rowss = take((size_t)n_seg * K * 4);
+    p.segs = take((size_t)n_seg * sizeof(VladSeg));
+    p.chunks = take((size_t)p.nchunks * sizeof(VladChunk));
+    p.tiles = take((size_t)p.ntiles * sizeof(VladTile));
+    p.bytes = need;
+    return p;
+}
+struct VladBufs {  // the device arrays of one call: views of a workspace (vlad_bufs) or buffers of their own
+    _Float16 *x16, *xt, *c16;
+    float* cvec;
+    int *labels, *labels_out;
+    float *sim_out, *part;
+    int* cpart;
+    float* vlad;
+    int* counts;
+    float* rowss;
+    VladSeg* segs;
+    VladChunk* chunks;
+    VladTile* tiles;
+};
+VladBufs vlad_bufs(char* ws, const VladPlan& plan);
+// launch_match_normalise's rows, bit for bit (csrc/normalise_row.h), into a layout of `ntiles` 128-row tiles in ONE launch (VladPlan): row
+// r of tile t of out is source row g = tiles[t].out0 + r where r < tiles[t].valid, zeros otherwise; source row g lives at x + (g / per) * outer + (g % per) * ld floats (the
+// view of launch_kmeans_gather).  tiles: DEVICE.
+hipError_t launch_vlad_normalise(const float* x, int per, size_t outer, size_t ld, const VladTile* tiles, int ntiles, _Float16* out, int H,
+                                 int hpad, hipStream_t stream);
+// Everything after the operands: b.x16 (every segment normalised into its block by launch_vlad_normalise), b.cvec and
+// the three tables are in place; normalises the centres, assigns, transposes, then sums and finishes pass by pass (`chunks`: the host's copy
+// of that table) and takes the L2 step.  Afterwards labels_out, sim_out, counts and vlad hold the results.  No wait.
+hipError_t vlad_run(const VladBufs& b, int n_seg, int K, int H, unsigned flags, const VladPlan& plan, const VladChunk* chunks,
+                    hipStream_t stream);
+// the single steps, for the diagnostic ops' timings
+hipError_t launch_vlad_assign(const VladBufs& b, int K, const VladPlan& plan, hipStream_t stream);
+hipError_t launch_vlad_sums(const VladBufs& b, int n_seg, int K, int H, unsigned flags, const VladPlan& plan, const VladChunk* chunks,
+                            hipStream_t stream);
+
 // Dense linear heads (csrc/dense.hip; contract in include/dinov2_hip.h, dinov2_hip_predict_dense): dense_pack_kernel builds the f16 operand
 // A [B P, K] of the logits GEMM straight from the residual stream at each tapped layer, launch_gemm(DT_F16, EPI_PLAIN_F32) gives the
 // low-resolution logits [B P, Cpad] f32, dense_reduce_kernel resamples them to out_h x out_w and reduces over the classes per pixel.

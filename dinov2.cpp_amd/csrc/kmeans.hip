@@ -16,42 +16,10 @@
 //   kmeans_gather_kernel     centre j = row init[j] of the source, verbatim
 // The similarity of a pair and the total order of "best" are sim_tile.h's, so the label does not depend on which lane, wave or centre tile
 // met a centre first.  No atomics anywhere: every sum has one fixed order.
+#include "onehot_rows.h"
 #include "sim_tile.h"
 
 namespace dinov2 {
-
-namespace {
-
-// kmeans_update_kernel's B operand for sim_tile: the image [128 c][64 i] = (label[i] == n0 + c) as 1.0 / 0.0 in f16, from the K-tile's 64
-// labels.  A thread's four staging slots share the chunk index tid & 7, so its 8 labels serve all four; cnt[j] counts the ones it wrote
-// for the centre of slot j.
-struct OneHotRows {
-    const int* lsrc;  // the 8 labels of this thread's chunk of K-tile 0
-    int crow;         // the centre of its slot j = 0; slot j is 32 j further
-    u32x4 l0, l1;     // (compared as unsigned: the -1 of a padding row equals no centre)
-    int cnt[4];
-    __device__ __forceinline__ void fetch(int kt) {
-        l0 = *(const u32x4*)(lsrc + kt * 64);
-        l1 = *(const u32x4*)(lsrc + kt * 64 + 4);
-    }
-    __device__ __forceinline__ void store(const SimPlace& p, char* s) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const unsigned c = (unsigned)(crow + 32 * j);
-            const unsigned lab[8] = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-            u32x4 oh;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const unsigned lo = lab[2 * e] == c, hi = lab[2 * e + 1] == c;
-                oh[e] = lo * 0x3c00u | hi * 0x3c000000u;  // 1.0 in f16
-                cnt[j] += (int)(lo + hi);
-            }
-            *(u32x4*)(s + p.sdst[j]) = oh;
-        }
-    }
-};
-
-}  // namespace
 
 // X [npad, hpad], Cn [kpad, hpad]: the normalised operands, padded to whole tiles (padding rows zero).  Workgroup x owns rows [128 x, +128)
 // and walks the centre tiles.  label [npad] is read (the previous labels) and written in place: rows >= n get -1.  sim [n].  chpart[x] =
@@ -67,26 +35,8 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const _Float16* __re
 
     const SimPlace p;
     const int m0 = blockIdx.x * SIM_TILE;
-    SimRows opa(p, X, m0, hpad);
-
-    Best best[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) best[i] = Best{-INFINITY, INT_MAX};
-
-    for (int n0 = 0; n0 < kpad; n0 += SIM_TILE) {  // the centre tiles in ascending order
-        SimRows opb(p, Cn, n0, hpad);
-        f32x4 acc[4][4];
-        sim_tile(p, sA, sB, hpad / 64, opa, opb, acc);
-        // acc[i][j][r] = sim(row, centre), row = m0 + 64 wm + 16 i + fr, centre = n0 + 64 wn + 16 j + 4 fh + r; centres >= K masked
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sim_row_fold(acc, i, n0 + p.wn * 64 + 4 * p.fh, K, best[i]);
-    }
-    // the four lanes that share a row, then the two waves side by side
-#pragma unroll
-    for (int i = 0; i < 4; ++i) sim_row_share(p, i, best[i], red_rv, red_ri);
-    __syncthreads();
+    const Best b = sim_best_of_rows(p, sA, sB, red_rv, red_ri, X, m0, Cn, K, kpad, hpad);
     if (p.tid < SIM_TILE) {  // waves 0 and 1, whole
-        const Best b = sim_fold_waves(red_rv, red_ri, p.tid);
         const int row = m0 + p.tid;
         int changed = 0;
         if (row < n) {

@@ -9,54 +9,18 @@
 //                           tile) and one per (column, row tile)
 //   match_reduce_kernel     folds the partials of a row (column) over the column (row) tiles
 // Both directions come from the same accumulators.  The tile, the K order of a pair and the total order of "best" are sim_tile.h's.
+#include "normalise_row.h"
 #include "sim_tile.h"
 
 namespace dinov2 {
 
-// x: rows [n] of H floats, row stride ld.  out [nout, hpad] f16: row / sqrt(sum of squares), 0 for an all-zero row, for rows >= n and for
-// columns >= H; rows >= nout are not touched (the grid covers nout rounded up to 4).  Four rows per workgroup, one wave each; lane l owns the 4-float chunks l, l + 64, ... (16-byte loads when `vec`: H, ld
-// multiples of 4 and an aligned base; the summation order is the same either way, so it depends on H alone).
+// x: rows [n] of H floats, row stride ld.  out [nout, hpad] f16: match_normalise_row of every row, zeros for rows >= n; rows >= nout are
+// not touched (the grid covers nout rounded up to 4).  Four rows per workgroup, one wave each.
 __global__ __launch_bounds__(256) void match_normalise_kernel(const float* __restrict__ x, size_t ld, _Float16* __restrict__ out, int n,
                                                               int nout, int H, int hpad, int vec) {
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
     const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= (size_t)nout) return;
-    f16x4* const o = (f16x4*)(out + row * hpad);
-    const int nch = hpad / 4;
-    if (row >= (size_t)n) {
-        for (int c = lane; c < nch; c += 64) o[c] = f16x4{0, 0, 0, 0};
-        return;
-    }
-    const float* const src = x + row * ld;
-    auto chunk = [&](int c) {
-        float4 v;
-        if (vec && 4 * c + 4 <= H) {
-            v = *(const float4*)(src + 4 * c);
-        } else {
-            v.x = 4 * c + 0 < H ? src[4 * c + 0] : 0.0f;
-            v.y = 4 * c + 1 < H ? src[4 * c + 1] : 0.0f;
-            v.z = 4 * c + 2 < H ? src[4 * c + 2] : 0.0f;
-            v.w = 4 * c + 3 < H ? src[4 * c + 3] : 0.0f;
-        }
-        return v;
-    };
-    float ss = 0.0f;
-    for (int c = lane; c < nch; c += 64) {
-        const float4 v = chunk(c);
-        ss += v.x * v.x;
-        ss += v.y * v.y;
-        ss += v.z * v.z;
-        ss += v.w * v.w;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off);
-    // correctly rounded square root and division (the compiler's default for f32; no v_rsq_f32): once per row
-    const float r = ss > 0.0f ? 1.0f / sqrtf(ss) : 0.0f;
-    for (int c = lane; c < nch; c += 64) {
-        const float4 v = chunk(c);
-        o[c] = f16x4{(_Float16)(v.x * r), (_Float16)(v.y * r), (_Float16)(v.z * r), (_Float16)(v.w * r)};
-    }
+    match_normalise_row(row < (size_t)n ? x + row * ld : nullptr, (f16x4*)(out + row * hpad), threadIdx.x & 63, H, hpad, vec);
 }
 
 // A [na_pad, hpad], B [nb_pad, hpad]: the normalised operands.  Workgroup (x, y) owns rows [row0 + 128 y, +128) and columns

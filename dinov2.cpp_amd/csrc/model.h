@@ -138,6 +138,7 @@ enum Scratch : int {
     SCRATCH_LIST_ITEMS,  // dinov2_hip_predict_list: the attention work table of the last list (list_items_host: what it holds)
     SCRATCH_KMEANS,      // dinov2_hip_kmeans_tokens (staged host rows, the f16 operands, the update's partials, the results)
     SCRATCH_SLIDE,       // dinov2_hip_predict_dense_slide (a host input's images, the window table, the window batch, every window's logits, host outputs' staging)
+    SCRATCH_VLAD,        // dinov2_hip_vlad_tokens (staged host rows, the f16 operands, the tables, one pass's partials, the results)
     SCRATCH_COUNT
 };
 

@@ -1127,6 +1127,155 @@ extern "C" int dinov2_hip_op_kmeans_bench(const float* rows_dev, int32_t n, int3
     return rc;
 }
 
+// ---- dinov2_hip_vlad_tokens' kernels (csrc/vlad.hip) on host data ----
+namespace {
+bool vlad_shape_ok(const int32_t* offsets, int n_seg, int K, int H) {
+    if (!offsets || n_seg < 1 || n_seg > VLAD_SEG_MAX || K < 1 || K > KMEANS_K_MAX || H < 8 || H > 4096 || offsets[0] != 0) return false;
+    for (int i = 1; i <= n_seg; ++i)
+        if (offsets[i] <= offsets[i - 1] || offsets[i] > VLAD_N_MAX) return false;
+    return (uint64_t)n_seg * (uint64_t)K * (uint64_t)H <= VLAD_OUT_MAX;
+}
+// The buffers of one run, each an allocation of its own that starts as 0xff bytes; the four results between guard bands.
+struct VladOpBufs {
+    OpBuf x16, xt, c16, cvec, labels, labels_out, sim_out, part, cpart, vlad, counts, rowss, segs, chunks, tiles;
+    VladBufs b{};
+    hipError_t alloc(int n, int n_seg, int K, int H, const VladPlan& p) {
+        const size_t held = (size_t)(p.nchunks < p.cap ? p.nchunks : p.cap);
+        const struct { OpBuf* buf; size_t n, esz, guard; } all[] = {
+            {&x16, (size_t)p.npad * p.hpad, 2, 0}, {&xt, (size_t)p.hpad128 * p.npad, 2, 0}, {&c16, (size_t)p.kpad * p.hpad, 2, 0},
+            {&cvec, (size_t)K * H, 4, 0}, {&labels, (size_t)p.npad, 4, 1}, {&labels_out, (size_t)n, 4, 1}, {&sim_out, (size_t)n, 4, 1},
+            {&part, p.part_bytes / 4, 4, 0}, {&cpart, held * p.kpad, 4, 0}, {&vlad, (size_t)n_seg * K * H, 4, (size_t)H},
+            {&counts, (size_t)n_seg * K, 4, 1}, {&rowss, (size_t)n_seg * K, 4, 1}, {&segs, (size_t)n_seg * sizeof(VladSeg), 1, 0},
+            {&chunks, (size_t)p.nchunks * sizeof(VladChunk), 1, 0}, {&tiles, (size_t)p.ntiles * sizeof(VladTile), 1, 0}};
+        for (const auto& a : all) {
+            const hipError_t e = a.buf->alloc(a.n, a.esz, OpBuf::nans(), a.guard);
+            if (e != hipSuccess) return e;
+        }
+        b.x16 = x16.as<_Float16>(); b.xt = xt.as<_Float16>(); b.c16 = c16.as<_Float16>(); b.cvec = cvec.as<float>();
+        b.labels = labels.as<int>(); b.labels_out = labels_out.as<int>(); b.sim_out = sim_out.as<float>(); b.part = part.as<float>();
+        b.cpart = cpart.as<int>(); b.vlad = vlad.as<float>(); b.counts = counts.as<int>(); b.rowss = rowss.as<float>();
+        b.segs = segs.as<VladSeg>(); b.chunks = chunks.as<VladChunk>(); b.tiles = tiles.as<VladTile>();
+        return hipSuccess;
+    }
+};
+struct VladTables {
+    std::vector<VladSeg> segs;
+    std::vector<VladChunk> chunks;
+    std::vector<VladTile> tiles;
+    hipError_t upload(const VladBufs& b) const {
+        hipError_t e = hipMemcpy(b.segs, segs.data(), segs.size() * sizeof(VladSeg), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(b.chunks, chunks.data(), chunks.size() * sizeof(VladChunk), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(b.tiles, tiles.data(), tiles.size() * sizeof(VladTile), hipMemcpyHostToDevice);
+        return e;
+    }
+};
+// every segment of the device rows x [n, H] into its block of the padded layout (b.tiles uploaded)
+hipError_t vlad_normalise_segments(const float* x, int n, int H, const VladBufs& b, const VladPlan& p) {
+    return launch_vlad_normalise(x, n, 0, (size_t)H, b.tiles, p.ntiles, b.x16, H, p.hpad, nullptr);
+}
+}  // namespace
+
+extern "C" int dinov2_hip_op_vlad_plan(const int32_t* offsets, int32_t n_seg, int32_t K, int32_t H, int64_t* out, int32_t* segs, int32_t* chunks,
+                                       int32_t max_chunks) {
+    if (!out || !vlad_shape_ok(offsets, n_seg, K, H)) return DINOV2_HIP_ERR_INVALID;
+    VladTables t;
+    const VladPlan p = vlad_plan(offsets, n_seg, K, H, &t.segs, &t.chunks, nullptr);
+    if (chunks && max_chunks < p.nchunks) return DINOV2_HIP_ERR_INVALID;
+    const int64_t v[12] = {p.kpad, p.hpad, p.hpad128, p.chunk, p.cap, p.npad, p.ntiles, p.nchunks, p.npass, (int64_t)p.part_bytes, (int64_t)p.bytes, 0};
+    std::copy(v, v + 12, out);
+    for (int i = 0; segs && i < n_seg; ++i) {
+        const int32_t r[4] = {t.segs[i].row0, t.segs[i].len, t.segs[i].chunk0, t.segs[i].nchunks};
+        std::copy(r, r + 4, segs + 4 * i);
+    }
+    for (int i = 0; chunks && i < p.nchunks; ++i) {
+        const int32_t r[3] = {t.chunks[i].seg, t.chunks[i].row0, t.chunks[i].ktiles};
+        std::copy(r, r + 3, chunks + 3 * i);
+    }
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_vlad(const float* rows, const int32_t* offsets, int32_t n_seg, const float* centers, int32_t K, int32_t H, uint32_t flags,
+                                  int32_t* labels, float* sim, int32_t* counts, float* vlad, float* xhat_f16_as_f32, float* chat_f16_as_f32) {
+    if (!rows || !centers || !vlad_shape_ok(offsets, n_seg, K, H) || (flags & ~3u)) return DINOV2_HIP_ERR_INVALID;
+    const int n = offsets[n_seg];
+    VladTables t;
+    const VladPlan plan = vlad_plan(offsets, n_seg, K, H, &t.segs, &t.chunks, &t.tiles);
+    OpBuf dX;
+    VladOpBufs w;
+    OP_TRY(dX.upload(rows, (size_t)n * H * 4));
+    OP_TRY(w.alloc(n, n_seg, K, H, plan));
+    OP_TRY(t.upload(w.b));
+    OP_TRY(hipMemcpy(w.b.cvec, centers, (size_t)K * H * 4, hipMemcpyHostToDevice));
+    OP_TRY(vlad_normalise_segments(dX.as<float>(), n, H, w.b, plan));
+    OP_TRY(vlad_run(w.b, n_seg, K, H, flags, plan, t.chunks.data(), nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    std::vector<int32_t> li((size_t)n), ci((size_t)n_seg * K), lp((size_t)plan.npad);
+    std::vector<float> sf((size_t)n), rs((size_t)n_seg * K), vf((size_t)n_seg * K * H);
+    OP_FETCH(w.labels_out.fetch(li.data()));
+    OP_FETCH(w.sim_out.fetch(sf.data()));
+    OP_FETCH(w.counts.fetch(ci.data()));
+    OP_FETCH(w.vlad.fetch(vf.data()));
+    OP_FETCH(w.labels.fetch(lp.data()));  // (their guards)
+    OP_FETCH(w.rowss.fetch(rs.data()));
+    if (labels) std::copy(li.begin(), li.end(), labels);
+    if (sim) std::copy(sf.begin(), sf.end(), sim);
+    if (counts) std::copy(ci.begin(), ci.end(), counts);
+    if (vlad) std::copy(vf.begin(), vf.end(), vlad);
+    if (xhat_f16_as_f32) {
+        std::vector<uint16_t> x16((size_t)plan.npad * plan.hpad);
+        OP_TRY(w.x16.read(x16.data(), 0, x16.size() * 2));
+        for (int s = 0; s < n_seg; ++s)
+            for (int i = 0; i < t.segs[s].len; ++i)
+                widen_to_f32(false, (const unsigned char*)(x16.data() + (size_t)(t.segs[s].row0 + i) * plan.hpad), (size_t)H,
+                             xhat_f16_as_f32 + (size_t)(offsets[s] + i) * H);
+    }
+    if (chat_f16_as_f32) {
+        std::vector<uint16_t> c16((size_t)plan.kpad * plan.hpad);
+        OP_TRY(w.c16.read(c16.data(), 0, c16.size() * 2));
+        for (int c = 0; c < K; ++c)
+            widen_to_f32(false, (const unsigned char*)(c16.data() + (size_t)c * plan.hpad), (size_t)H, chat_f16_as_f32 + (size_t)c * H);
+    }
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_vlad_bench(const float* rows_dev, const int32_t* offsets, int32_t n_seg, const float* centers_dev, int32_t K, int32_t H,
+                                        uint32_t flags, int32_t warmup, int32_t iters, float* ms) {
+    if (!rows_dev || !centers_dev || !ms || !vlad_shape_ok(offsets, n_seg, K, H) || (flags & ~3u) || warmup < 0 || iters < 1)
+        return DINOV2_HIP_ERR_INVALID;
+    VladTables t;
+    const VladPlan plan = vlad_plan(offsets, n_seg, K, H, &t.segs, &t.chunks, &t.tiles);
+    OpBuf dW;
+    EventPair ev;
+    OP_TRY(dW.alloc(plan.bytes, 1, OpBuf::none()));
+    OP_TRY(ev.create());
+    const VladBufs b = vlad_bufs(dW.as<char>(), plan);
+    OP_TRY(t.upload(b));
+    auto whole = [&] {
+        hipError_t e = hipMemcpyAsync(b.cvec, centers_dev, (size_t)K * H * 4, hipMemcpyDeviceToDevice, nullptr);
+        if (e == hipSuccess) e = vlad_normalise_segments(rows_dev, offsets[n_seg], H, b, plan);
+        return e != hipSuccess ? e : vlad_run(b, n_seg, K, H, flags, plan, t.chunks.data(), nullptr);
+    };
+    OP_TRY(whole());  // leaves every buffer of the single steps in a real state
+    auto timed = [&](auto step, float* out) {
+        int rc = 0;
+        for (int i = 0; i < warmup + iters && rc == 0; ++i) {
+            if (i == warmup && hipEventRecord(ev.e0, nullptr) != hipSuccess) rc = -1;
+            if (step() != hipSuccess) rc = -1;
+        }
+        float tm = 0.0f;
+        if (rc == 0 && (hipEventRecord(ev.e1, nullptr) != hipSuccess || hipEventSynchronize(ev.e1) != hipSuccess ||
+                        hipEventElapsedTime(&tm, ev.e0, ev.e1) != hipSuccess))
+            rc = -1;
+        *out = tm / (float)iters;
+        return rc;
+    };
+    int rc = timed([&] { return launch_vlad_assign(b, K, plan, nullptr); }, ms + 0);
+    if (rc == 0) rc = timed([&] { return launch_vlad_sums(b, n_seg, K, H, flags, plan, t.chunks.data(), nullptr); }, ms + 1);
+    if (rc == 0) rc = timed(whole, ms + 2);
+    (void)hipDeviceSynchronize();
+    return rc;
+}
+
 // ---- the device stages of dinov2_hip_pca3 (csrc/pca.cpp), each through the launch function the driver calls, on host data ----
 namespace {
 bool pca_shape_ok(int P, int H) { return P >= 4 && H >= 8 && H <= 4096; }  // the range dinov2_hip_pca3 accepts

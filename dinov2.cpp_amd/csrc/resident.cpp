@@ -478,3 +478,11 @@ extern "C" void dinov2_hip_dense_head_free(dinov2_hip_dense_head* hd) {
     if (hd->dev) (void)hipFree(hd->dev);
     delete hd;
 }
+
+// =============================================================================================================
+// check_rows for the host files beside this one (host.h; vlad.cpp)
+// =============================================================================================================
+int dinov2::check_session_rows(const char* who, const dinov2_hip_session* s, int H, const dinov2_hip_rows* r, const float** src, size_t* ld,
+                               char* err, size_t errlen) {
+    return check_rows(who, s, H, r, src, ld, err, errlen);
+}

@@ -153,4 +153,30 @@ __device__ __forceinline__ Best sim_fold_waves(const float (&red_v)[2][SIM_TILE]
     return b;
 }
 
+// ---- the best column of every row of one 128-row tile of A over all of B's tiles (kmeans_assign_kernel, vlad_assign_kernel) ----------------
+// A [.., hpad], B [npad_b, hpad]: normalised operands padded to whole tiles.  The workgroup walks B's tiles in ascending order, each a
+// sim_tile, keeps the best (value, lowest column) per row across the tiles (columns >= nb masked) and folds lanes and waves.  Afterwards
+// thread tid < SIM_TILE holds the best of row m0 + tid; the other threads hold an empty slot.  The walk stands here once, so that k-means'
+// assignment and VLAD's cannot drift apart.  The caller declares the images and the two fold arrays.
+__device__ __forceinline__ Best sim_best_of_rows(const SimPlace& p, char* sA, char* sB, float (&red_v)[2][SIM_TILE], int (&red_i)[2][SIM_TILE],
+                                                 const _Float16* A, int m0, const _Float16* B, int nb, int npad_b, int hpad) {
+    SimRows opa(p, A, m0, hpad);
+    Best best[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) best[i] = Best{-INFINITY, INT_MAX};
+    for (int n0 = 0; n0 < npad_b; n0 += SIM_TILE) {  // B's tiles in ascending order
+        SimRows opb(p, B, n0, hpad);
+        f32x4 acc[4][4];
+        sim_tile(p, sA, sB, hpad / 64, opa, opb, acc);
+        // acc[i][j][r] = sim(row, column), row = m0 + 64 wm + 16 i + fr, column = n0 + 64 wn + 16 j + 4 fh + r; columns >= nb masked
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sim_row_fold(acc, i, n0 + p.wn * 64 + 4 * p.fh, nb, best[i]);
+    }
+    // the four lanes that share a row, then the two waves side by side
+#pragma unroll
+    for (int i = 0; i < 4; ++i) sim_row_share(p, i, best[i], red_v, red_i);
+    __syncthreads();
+    return p.tid < SIM_TILE ? sim_fold_waves(red_v, red_i, p.tid) : Best{-INFINITY, INT_MAX};
+}
+
 }  // namespace dinov2

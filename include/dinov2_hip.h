@@ -573,6 +573,60 @@ typedef struct dinov2_hip_kmeans {
  * DINOV2_HIP_ERR_HIP.  The session's last forward stays what it was. */
 int dinov2_hip_kmeans_tokens(dinov2_hip_session *s, const dinov2_hip_kmeans *km, char *err, size_t errlen);
 
+/* -- VLAD descriptors of row segments (no reference counterpart: one vector per image for place recognition and image retrieval from
+ *    frozen patch tokens -- every token is assigned to the nearest centre of a k-means vocabulary, the residuals are summed per centre,
+ *    each centre's sum is normalised, then the whole; the recipe of AnyLoc).  The last step of forward -> vocabulary
+ *    (dinov2_hip_kmeans_tokens) -> descriptor -> search.  The rows are a caller's matrix cut into segments by `offsets`, or resident patch
+ *    tokens of the session's last un-split forward, one segment per image; only [n_seg, K, H] descriptors cross PCIe, not the tokens.  On
+ *    the device (csrc/vlad.hip): every segment is normalised into a block of its own, padded to whole 128-row tiles; k-means' assignment
+ *    walk and its one-hot GEMM then run per segment, and one workgroup per (segment, centre) forms the residual and its norm.
+ *    Contract:
+ *    1. Operands.  Rows and centre vectors go through contract 1 of dinov2_hip_match, the same row code: x^, c^ (f16 unit rows; a zero
+ *       row stays zero).  Inputs must be finite.
+ *    2. Assignment.  Contract 2 of dinov2_hip_kmeans.  labels and sim equal those of dinov2_hip_kmeans_tokens(max_iter = 0) with the same
+ *       centres and idx_ab / sim_ab of dinov2_hip_match_tokens(rows, centers) bit for bit.
+ *    3. Sums.  For segment s and centre c, n_sc = the number of rows of s with label c (a zero row counts: the tie rule gives it centre
+ *       0), S_sc[h] = the f32 sum of the members' x^_ih.  The order is fixed by a pure planner from (len_s, K, H) alone -- ascending rows
+ *       within a chunk of rows of the segment, then the chunks ascending.  No atomics.  Hence a segment's descriptor, counts and labels
+ *       have the same bits whatever segments travel with it and at whatever position: alone, first or last of a list, and as
+ *       LAST_PATCHES of image i of a batch against GIVEN with the same rows.
+ *    4. Residual.  R_sc[h] = S_sc[h] - n_sc * c^_c[h] in f32 (the product rounded, then the difference); c^ is the f16 unit centre the
+ *       assignment used, not the caller's vector.  An empty cluster gives a zero row.
+ *    5. Norms.  DINOV2_HIP_VLAD_INTRA_NORM: R_sc <- R_sc / sqrt(ss) per (s, c), ss = the f32 sum of the f32 squares in an order that
+ *       depends on H alone; square root and division correctly rounded; ss == 0 stays zero.  DINOV2_HIP_VLAD_L2_NORM: the same over the
+ *       K H values of segment s as they stand after INTRA (if set), in an order that depends on (K, H) alone.  Nothing is normalised
+ *       across segments.  flags = 0 returns the raw R.
+ *    Out of scope: soft assignment; descriptors written into a bank (they are K H wide, the bank stops at 4096); device-side outputs; PCA
+ *    or whitening of descriptors; the device group; the rows of a list forward (GIVEN rows with `offsets` cover them); bf16 operands;
+ *    dinov2_compat.hpp and the example programs.
+ *    Times: profiles/vlad.md. */
+enum dinov2_hip_vlad_flags { DINOV2_HIP_VLAD_INTRA_NORM = 1, DINOV2_HIP_VLAD_L2_NORM = 2 };
+typedef struct dinov2_hip_vlad {
+    dinov2_hip_rows rows;     /* GIVEN (host / device) or LAST_PATCHES of `rows.image`; LAST_CLS is refused.  1 <= n <= 1 048 576, 8 <= H <= 4096 */
+    int32_t all_images;       /* as dinov2_hip_kmeans: 1 with LAST_PATCHES = one segment per image of the last un-split forward
+                                 (rows.n = last_b * P, n_seg = last_b) */
+    const int32_t *offsets;   /* GIVEN only, HOST, [n_seg + 1], strictly ascending, offsets[0] = 0, offsets[n_seg] = rows.n: segment i is
+                                 rows [offsets[i], offsets[i + 1]).  NULL = one segment (n_seg must be 1).  Must be NULL for a resident source. */
+    int32_t n_seg;            /* 1 .. 4096; LAST_PATCHES: 1, or last_b with all_images.  n_seg * K * H <= 2^28 */
+    int32_t K;                /* 1 .. 1024 */
+    const float *centers;     /* [K, H] f32 HOST: vectors of any length, e.g. what dinov2_hip_kmeans_tokens returned */
+    uint32_t flags;           /* DINOV2_HIP_VLAD_INTRA_NORM | DINOV2_HIP_VLAD_L2_NORM; 0 = the raw residual sums */
+    float   *vlad;            /* [n_seg, K, H] HOST; any output may be NULL, not all */
+    int32_t *counts;          /* [n_seg, K] */
+    int32_t *labels;          /* [rows.n] */
+    float   *sim;             /* [rows.n] */
+    int32_t reserved[4];
+} dinov2_hip_vlad;
+/* Synchronous: returns after the copy-out, like dinov2_hip_kmeans_tokens.  Argument errors (NULL session, request or centers; all outputs
+ * NULL; rows, H, K, n_seg or n_seg * K * H out of range; offsets that do not ascend strictly from 0 to rows.n, or NULL with n_seg != 1;
+ * offsets or all_images with a source they do not go with; LAST_CLS; n_seg or rows.n that are not the resident source's; the
+ * resident-source errors of dinov2_hip_bank_add; a misaligned device pointer; unknown flag bits) return DINOV2_HIP_ERR_INVALID before
+ * anything is launched, allocated or copied, with the outputs untouched.  The scratch (host rows' staging copy, X^ and X^T in f16 in the
+ * padded layout, the centres, the tables, at most 32 MiB of partial sums -- the segments are walked in passes --, the results) is a
+ * session-owned buffer grown on demand; an allocation the device refuses returns DINOV2_HIP_ERR_HIP.  The session's last forward stays
+ * what it was. */
+int dinov2_hip_vlad_tokens(dinov2_hip_session *s, const dinov2_hip_vlad *v, char *err, size_t errlen);
+
 /* -- linear dense-prediction heads (no reference counterpart: semantic segmentation and depth estimation with a linear head on frozen
  *    patch features, two of the evaluation protocols of the DINOv2 paper; upstream: BNHead of
  *    dinov2/eval/segmentation/models/decode_heads/linear_head.py and of dinov2/eval/depth/models/decode_heads/linear_head.py).  A resident head

@@ -6,7 +6,7 @@
  * kernel against the oracle in isolation -- the per-op granularity the reference gets from ggml's own op tests and
  * that /root/reference itself never had (it holds no tests at all).  All return 0 on success, -1 on a HIP error
  * (the entry points with guard bands -- attention_ex, layer_tap, attn_rows, pca_prepare / pca_cov / pca_power / pca_project, dense_reduce,
- * dense_pack, slide_reduce, slide_gather, kmeans_assign / _update / kmeans -- also DINOV2_HIP_OP_GUARD_CHANGED).  Each family has its cases in tests/*_cases.py, CPU probes of those cases and a GPU file; for the
+ * dense_pack, slide_reduce, slide_gather, kmeans_assign / _update / kmeans, vlad -- also DINOV2_HIP_OP_GUARD_CHANGED).  Each family has its cases in tests/*_cases.py, CPU probes of those cases and a GPU file; for the
  * pca_* entry points: tests/pca_cases.py, tests/test_pca_probes.py, tests/test_gpu_pca_kernels.py.
  */
 #ifndef DINOV2_HIP_OPS_H
@@ -266,6 +266,28 @@ int dinov2_hip_op_kmeans(const float *rows, int32_t n, int32_t K, int32_t H, int
                          int32_t *converged);
 int dinov2_hip_op_kmeans_bench(const float *rows_dev, int32_t n, int32_t K, int32_t H, int32_t nsplit, int32_t max_iter, int32_t warmup,
                                int32_t iters, float *ms);
+
+/* the kernels behind dinov2_hip_vlad_tokens (csrc/vlad.hip) with the shared normaliser and k-means' transpose, without a model or session;
+ * cases, the numpy restatement and the bounds: tests/vlad_cases.py.  offsets [n_seg + 1] strictly ascending from 0 to at most 2^20,
+ * 1 <= n_seg <= 4096, 1 <= K <= 1024, 8 <= H <= 4096, n_seg K H <= 2^28, flags within DINOV2_HIP_VLAD_INTRA_NORM | _L2_NORM, else
+ * DINOV2_HIP_ERR_INVALID.  Every device buffer starts as 0xff bytes; labels (padded and the caller's order), sim, counts, the rows' sums
+ * of squares and the descriptors sit between guard bands: a changed one returns DINOV2_HIP_OP_GUARD_CHANGED.
+ * vlad_plan (no device): out[0 .. 11] = kpad, hpad, hpad128, chunk rows, chunks per pass, rows of the padded layout, its tiles, chunks,
+ *             passes, bytes of the partials, bytes of the workspace, 0; segs [n_seg, 4] (may be NULL) = first padded row, length, first
+ *             chunk, chunks of every segment; chunks [max_chunks, 3] (may be NULL; max_chunks below the plan's count is refused) =
+ *             segment, first padded row, K-tiles of every chunk.
+ * vlad:       host rows [offsets[n_seg], H] and centers [K, H] through the whole of the call's device work; any output may be NULL:
+ *             labels, sim [n], counts [n_seg, K], vlad [n_seg, K, H], and the f32 values of the f16 operands xhat_f16_as_f32 [n, H],
+ *             chat_f16_as_f32 [K, H].
+ * vlad_bench (tools/vlad_bench.py): DEVICE rows_dev [n, H] and centers_dev [K, H]: ms[0] = the assignment, ms[1] = sums, finish and L2 step,
+ *             ms[2] = the whole device work (normalise, assign, transpose, sums), each the mean of `iters` timed runs after `warmup`, by HIP
+ *             events on the null stream. */
+int dinov2_hip_op_vlad_plan(const int32_t *offsets, int32_t n_seg, int32_t K, int32_t H, int64_t *out, int32_t *segs, int32_t *chunks,
+                            int32_t max_chunks);
+int dinov2_hip_op_vlad(const float *rows, const int32_t *offsets, int32_t n_seg, const float *centers, int32_t K, int32_t H, uint32_t flags,
+                       int32_t *labels, float *sim, int32_t *counts, float *vlad, float *xhat_f16_as_f32, float *chat_f16_as_f32);
+int dinov2_hip_op_vlad_bench(const float *rows_dev, const int32_t *offsets, int32_t n_seg, const float *centers_dev, int32_t K, int32_t H,
+                             uint32_t flags, int32_t warmup, int32_t iters, float *ms);
 
 /* the two kernels of csrc/dense.hip (behind dinov2_hip_predict_dense) without a model or session; cases and the numpy restatement:
  * tests/dense_cases.py.
