@@ -103,6 +103,13 @@ class TopK(C.Structure):
     _fields_ = [("queries", Rows), ("k", C.c_int32), ("idx", C.c_void_p), ("sim", C.c_void_p), ("reserved", C.c_int32 * 4)]
 
 
+class PropagateReq(C.Structure):
+    """dinov2_hip_propagate_req (include/dinov2_hip.h)."""
+    _fields_ = [("queries", Rows), ("slots", C.c_uint64), ("radius", C.c_int32), ("k", C.c_int32), ("temperature", C.c_float),
+                ("keep", C.c_int32), ("labels", C.c_void_p), ("argmax", C.c_void_p), ("idx", C.c_void_p), ("sim", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
 class KMeans(C.Structure):
     """dinov2_hip_kmeans (include/dinov2_hip.h)."""
     _fields_ = [("rows", Rows), ("all_images", C.c_int32), ("K", C.c_int32), ("max_iter", C.c_int32), ("init", C.c_int32),
@@ -388,6 +395,53 @@ def op_bank_topk(q, b, k, chunk_tiles=0):
     _op_rc(lib().dinov2_hip_op_bank_topk(_ptr(q), nq, _ptr(b), nb, q.shape[1], int(k), int(chunk_tiles), _ptr(out["idx"]), _ptr(out["sim"])),
            "bank_topk")
     return out
+
+
+def _slot_mask(slots):
+    """A slots argument -- a mask, or an iterable of slot numbers -- as the 64-bit mask."""
+    if isinstance(slots, (int, np.integer)):
+        return int(slots)
+    m = 0
+    for f in slots:
+        if not 0 <= int(f) < 64:
+            raise ValueError(f"slot {f} outside 0 .. 63")
+        m |= 1 << int(f)
+    return m
+
+
+def op_propagate(q, rows, labels, grid, slots, radius, k, temperature, chunk_tiles=0):
+    """The kernels behind dinov2_hip_propagate alone (dinov2_hip_op_propagate): q [P, H] against a memory built from rows [frames, P, H] and
+    labels [frames, P, C], grid = (h0, w0), `slots` a mask or a list of slot numbers -> dict of labels [P, C], argmax [P], idx / sim [P, k]
+    and kept [P, C] (what a call with keep leaves in the memory).  chunk_tiles: items per workgroup, 0 = the planner's choice.  No model,
+    no session."""
+    q, rows, labels = _f32(q), _f32(rows), _f32(labels)
+    h0, w0 = int(grid[0]), int(grid[1])
+    P = h0 * w0
+    assert q.ndim == 2 and rows.ndim == 3 and labels.ndim == 3 and q.shape[0] == P and rows.shape[1:] == q.shape, (q.shape, rows.shape)
+    assert labels.shape[:2] == rows.shape[:2], (labels.shape, rows.shape)
+    frames, Cn, k = rows.shape[0], labels.shape[2], int(k)
+    out = {"labels": np.full((P, Cn), np.nan, np.float32), "argmax": np.full(P, -7, np.int32), "idx": np.full((P, k), -7, np.int32),
+           "sim": np.full((P, k), np.nan, np.float32), "kept": np.full((P, Cn), np.nan, np.float32)}
+    _op_rc(lib().dinov2_hip_op_propagate(_ptr(q), _ptr(rows), _ptr(labels), h0, w0, q.shape[1], frames, Cn, _slot_mask(slots), int(radius), k,
+                                         float(temperature), int(chunk_tiles), _ptr(out["labels"]), _ptr(out["argmax"]), _ptr(out["idx"]),
+                                         _ptr(out["sim"]), _ptr(out["kept"])), "propagate")
+    return out
+
+
+PROPAGATE_PLAN_FIELDS = ("chunk_tiles", "nchunks", "qtiles", "max_items", "kept_items", "partial_bytes", "bytes", "memory_bytes")
+
+
+def op_propagate_plan(grid, H, nactive, radius, k, C_=1, chunk_tiles=0):
+    """propagate_plan (csrc/kernels.h) as a dict, with "ranges" [query tiles, 2] = the kept column tiles [t0, t1) of every query tile; no
+    device needed."""
+    h0, w0 = int(grid[0]), int(grid[1])
+    buf = (C.c_int64 * len(PROPAGATE_PLAN_FIELDS))()
+    ranges = np.full((max(-(-h0 * w0 // 128), 1), 2), -1, np.int32)
+    if lib().dinov2_hip_op_propagate_plan(h0, w0, int(H), int(nactive), int(radius), int(k), int(C_), int(chunk_tiles), buf, _ptr(ranges)) != 0:
+        raise ValueError(f"propagate refuses grid={grid} H={H} nactive={nactive} radius={radius} k={k} C={C_}")
+    p = dict(zip(PROPAGATE_PLAN_FIELDS, [int(v) for v in buf]))
+    p["ranges"] = ranges
+    return p
 
 
 KMEANS_PLAN_FIELDS = ("npad", "kpad", "hpad", "hpad128", "chunk", "nsplit", "partial_bytes", "bytes")
@@ -758,6 +812,12 @@ def lib():
     L.dinov2_hip_bank_clear.argtypes = [vp]
     L.dinov2_hip_bank_add.argtypes = [vp, vp, C.POINTER(Rows), C.POINTER(i32), cp, sz]
     L.dinov2_hip_bank_topk.argtypes = [vp, vp, C.POINTER(TopK), cp, sz]
+    L.dinov2_hip_propmem_create.argtypes = [vp, i32, i32, i32, i32, i32, C.POINTER(vp), cp, sz]
+    L.dinov2_hip_propmem_free.argtypes = [vp]
+    L.dinov2_hip_propmem_free.restype = None
+    L.dinov2_hip_propmem_set.argtypes = [vp, vp, i32, C.POINTER(Rows), vp, i32, cp, sz]
+    L.dinov2_hip_propmem_drop.argtypes = [vp, i32]
+    L.dinov2_hip_propagate.argtypes = [vp, vp, C.POINTER(PropagateReq), cp, sz]
     L.dinov2_hip_dense_head_create.argtypes = [vp, C.POINTER(DenseDesc), C.POINTER(vp), cp, sz]
     L.dinov2_hip_dense_head_free.argtypes = [vp]
     L.dinov2_hip_dense_head_free.restype = None
@@ -804,6 +864,9 @@ def lib():
     L.dinov2_hip_op_vlad_plan.argtypes = [ip, i32, i32, i32, C.POINTER(C.c_int64), ip, ip, i32]
     L.dinov2_hip_op_vlad.argtypes = [fp, ip, i32, fp, i32, i32, u32, ip, fp, ip, fp, fp, fp]
     L.dinov2_hip_op_vlad_bench.argtypes = [vp, ip, i32, vp, i32, i32, u32, i32, i32, fp]
+    L.dinov2_hip_op_propagate.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, C.c_uint64, i32, i32, C.c_float, i32, fp, ip, ip, fp, fp]
+    L.dinov2_hip_op_propagate_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int64), ip]
+    L.dinov2_hip_op_propagate_bench.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_uint64, i32, i32, C.c_float, i32, i32, i32, fp]
     L.dinov2_hip_op_bank_plan.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64)]
     L.dinov2_hip_op_dense_reduce.argtypes = [fp, i32, i32, i32, i32, i32, i32, fp, C.c_float, C.POINTER(C.c_uint8), fp]
     L.dinov2_hip_op_dense_pack.argtypes = [fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32, fp]
@@ -1255,6 +1318,76 @@ class Bank(_Handle):
 
     def clear(self):
         lib().dinov2_hip_bank_clear(self._h)
+
+
+class PropMemory(_Handle):
+    """dinov2_hip_propmem: a device-resident memory of `frames` slots of one patch grid (unit-length f16 rows and f32 label vectors of
+    `channels` channels per patch) and label propagation from it (include/dinov2_hip.h, dinov2_hip_propagate).  Rows come from host arrays,
+    DeviceArrays, or -- source="last_patches" -- from the session's last un-split predict without leaving the device."""
+    _free = "dinov2_hip_propmem_free"
+    OUTPUTS = ("labels", "argmax", "idx", "sim")
+
+    def __init__(self, model: "Model", H: int, grid, frames: int, channels: int):
+        h = C.c_void_p()
+        h0, w0 = int(grid[0]), int(grid[1])
+        _call(lib().dinov2_hip_propmem_create, model._h, int(H), h0, w0, int(frames), int(channels), C.byref(h))
+        self._h = h
+        self.H, self.grid, self.P, self.frames, self.channels = int(H), (h0, w0), h0 * w0, int(frames), int(channels)
+
+    def _rows(self, rows, source, image):
+        """(Rows struct, the array it points into: kept alive by the caller)."""
+        if source is None:
+            source = "given" if rows is not None else None
+        if source not in _ROWS_SOURCE or (source == "given") != (rows is not None):
+            raise ValueError("propagate: give rows, or source = 'last_patches' without rows")
+        if source != "given":
+            return Rows(_ROWS_SOURCE[source], None, self.P, self.H, int(image), 0), None
+        if isinstance(rows, DeviceArray):
+            if len(rows.shape) != 2:
+                raise ValueError("propagate: rows must be [P, H]")
+            return Rows(ROWS_GIVEN, rows.ptr, rows.shape[0], rows.shape[1], 0, 1), rows
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        if x.ndim != 2:
+            raise ValueError("propagate: rows must be [P, H]")
+        return Rows(ROWS_GIVEN, x.ctypes.data, x.shape[0], x.shape[1], 0, 0), x
+
+    def set(self, sess: "Session", slot: int, rows=None, labels=None, *, source=None, image: int = 0):
+        """Fills slot `slot`: rows [P, H] (host array or DeviceArray), or rows=None with source="last_patches" (the patch rows of image
+        `image` of the session's last predict); labels [P, channels] (host array or DeviceArray), or None: the result the last
+        propagate(keep=True) left in this memory."""
+        r, keep = self._rows(rows, source, image)
+        lab, on_dev = None, 0
+        if isinstance(labels, DeviceArray):
+            lab, on_dev = labels.ptr, 1
+        elif labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.float32)
+            if labels.shape != (self.P, self.channels):
+                raise ValueError(f"propagate: labels must be [{self.P}, {self.channels}]")
+            lab = labels.ctypes.data
+        _call(lib().dinov2_hip_propmem_set, sess._h, self._h, int(slot), C.byref(r), lab, on_dev)
+
+    def drop(self, slot: int):
+        if lib().dinov2_hip_propmem_drop(self._h, int(slot)) != 0:
+            raise ValueError(f"propagate: slot {slot} outside 0 .. {self.frames - 1}")
+
+    def propagate(self, sess: "Session", queries=None, *, slots, radius: int = -1, k: int = 5, temperature: float = 0.1, keep: bool = False,
+                  want=OUTPUTS, source=None, image: int = 0) -> dict:
+        """Propagates the labels of the slots `slots` (a mask or a list of slot numbers) to the P queries (as the rows of set()): dict of
+        the outputs named in `want` -- labels [P, channels] f32, argmax [P] int32, idx / sim [P, k] (index = slot * P + patch; -1 / -inf past
+        a short window).  keep: the result also stays in the memory for the next set(labels=None)."""
+        bad = [w for w in want if w not in self.OUTPUTS]
+        if bad:
+            raise ValueError(f"propagate: unknown outputs {bad}")
+        r, alive = self._rows(queries, source, image)
+        k = int(k)
+        shapes = {"labels": ((self.P, self.channels), np.float32), "argmax": ((self.P,), np.int32), "idx": ((self.P, k), np.int32),
+                  "sim": ((self.P, k), np.float32)}
+        out = {w: np.empty(tuple(max(d, 0) for d in shapes[w][0]), shapes[w][1]) for w in want}
+        ptr = {w: (out[w].ctypes.data if w in out else None) for w in self.OUTPUTS}
+        req = PropagateReq(r, _slot_mask(slots), int(radius), k, float(temperature), int(bool(keep)), ptr["labels"], ptr["argmax"], ptr["idx"],
+                           ptr["sim"])
+        _call(lib().dinov2_hip_propagate, sess._h, self._h, C.byref(req))
+        return out
 
 
 class DenseHead(_Handle):

@@ -458,6 +458,124 @@ inline BankTopkPlan bank_topk_plan(int nq, int count, int H, int k, int chunk_ti
 // `floor_only`: the sweep without its selection epilogue (a measuring aid: the results are meaningless).
 hipError_t launch_bank_topk(const float* q, size_t ldq, int nq, const _Float16* bank, int count, int H, int k, char* ws, const BankTopkPlan& plan,
                             bool floor_only, hipStream_t stream);
+// bank_merge_kernel on its own, for propagate.hip: row r < nrows: the sorted lists part[(c * pass_rows + r) * k ..] of chunks c < nchunks
+// merged into idx / sim [r * k ..], empty slots as (-1, -inf)
+hipError_t launch_bank_merge(const BankEntry* part, int pass_rows, int nchunks, int k, int nrows, int* idx, float* sim, hipStream_t stream);
+
+// Label propagation over a frame memory (csrc/propagate.hip; contract in include/dinov2_hip.h, dinov2_hip_propagate).  The memory holds
+// `frames` slots of one h0 x w0 patch grid, each P = h0 w0 rows padded to ppad (whole 128-row tiles), so a slot owns whole column tiles.
+// propagate_topk_kernel is bank_topk_kernel with two changes: its columns are the ITEMS (active slot a, kept column tile t), a-major, and
+// a candidate must lie within `radius` cells (Chebyshev) of its query.  Column tiles none of whose grid rows can reach a grid row of the
+// query tile are not walked: for query tile y the kept tiles are the range propagate_tile_range gives, the same for every slot.  The items
+// of a query tile are cut into chunks of chunk_tiles items, one workgroup each; a workgroup past a query tile's last item leaves empty
+// lists.  All P queries are one pass, and the chunk count is capped so that the partials (chunks x ppad x k x 8 bytes) stay within
+// BANK_PARTIAL_MAX.  bank_merge_kernel merges the chunks; propagate_combine_kernel forms the weights and the weighted label mean.
+constexpr int PROP_FRAMES_MAX = 64, PROP_GRID_MAX = 256, PROP_C_MAX = 256, PROP_RADIUS_MAX = 255;
+constexpr int PROP_ROWS_MAX = 1 << 24;  // frames * ppad
+// The cell of patch p of the grid: y << 16 | x (the memory's cell table; entries P .. ppad - 1 are never read as cells of candidates)
+inline uint32_t propagate_cell(int p, int w0) { return (uint32_t)(p / w0) << 16 | (uint32_t)(p % w0); }
+// Column tiles [*t0, *t1) of a slot that can hold a candidate of query tile qt (queries [128 qt, 128 qt + 128) n [0, P)): those with a patch in
+// grid rows [first query row - radius, last query row + radius].  radius < 0: all of them.
+__host__ __device__ inline void propagate_tile_range(int qt, int P, int w0, int radius, int* t0, int* t1) {
+    const int ntiles = (P + MATCH_TN - 1) / MATCH_TN;
+    if (radius < 0) {
+        *t0 = 0;
+        *t1 = ntiles;
+        return;
+    }
+    const int q0 = qt * MATCH_TM, q1 = q0 + MATCH_TM - 1 < P - 1 ? q0 + MATCH_TM - 1 : P - 1;
+    const int h0 = P / w0;
+    int y0 = q0 / w0 - radius, y1 = q1 / w0 + radius;
+    if (y0 < 0) y0 = 0;
+    if (y1 > h0 - 1) y1 = h0 - 1;
+    *t0 = y0 * w0 / MATCH_TN;
+    *t1 = ((y1 + 1) * w0 - 1) / MATCH_TN + 1;
+}
+// The a-th set bit of `slots` (a < popcount)
+__host__ __device__ inline int propagate_slot_of(uint64_t slots, int a) {
+    for (int f = 0; f < 64; ++f)
+        if (slots >> f & 1) {
+            if (a == 0) return f;
+            --a;
+        }
+    return -1;
+}
+struct PropagatePlan {
+    int P, ppad, hpad, qtiles;   // patches of the grid, padded to whole tiles; H to a multiple of 64; query (and per-slot column) tiles
+    int nactive;                 // set bits of `slots`
+    int max_items, kept_items;   // items (active slot x kept column tile) of the query tile that has most; of all query tiles together
+    int chunk_tiles, nchunks;    // items per workgroup, workgroups per query tile
+    size_t q16;                  // normalised queries [ppad, hpad] f16
+    size_t part;                 // BankEntry [nchunks][ppad][k]
+    size_t idx, sim;             // the merged lists [P, k]
+    size_t out, argmax;          // f32 [P, C], int32 [P]
+    size_t bytes;
+};
+// chunk_tiles = 0: as many chunks as fill BANK_TARGET_WGS workgroups; a given value is raised where the partials would pass BANK_PARTIAL_MAX
+inline PropagatePlan propagate_plan(int h0, int w0, int H, int nactive, int radius, int k, int C, int chunk_tiles) {
+    PropagatePlan p{};
+    p.P = h0 * w0;
+    p.ppad = (p.P + MATCH_TN - 1) / MATCH_TN * MATCH_TN;
+    p.hpad = (H + 63) / 64 * 64;
+    p.qtiles = p.ppad / MATCH_TM;
+    p.nactive = nactive;
+    for (int qt = 0; qt < p.qtiles; ++qt) {
+        int t0, t1;
+        propagate_tile_range(qt, p.P, w0, radius, &t0, &t1);
+        const int items = nactive * (t1 - t0);
+        p.kept_items += items;
+        if (items > p.max_items) p.max_items = items;
+    }
+    const int want = (BANK_TARGET_WGS + p.qtiles - 1) / p.qtiles;
+    if (chunk_tiles <= 0) chunk_tiles = (p.max_items + want - 1) / want;
+    const size_t per_chunk = (size_t)p.ppad * k * sizeof(BankEntry);  // partials of one chunk of every query tile
+    const int max_chunks = (int)(BANK_PARTIAL_MAX / per_chunk);      // >= 1: ppad <= 2^16, k <= 64
+    const int floor_tiles = (p.max_items + max_chunks - 1) / max_chunks;
+    if (chunk_tiles < floor_tiles) chunk_tiles = floor_tiles;
+    if (chunk_tiles > p.max_items) chunk_tiles = p.max_items;
+    p.chunk_tiles = chunk_tiles;
+    p.nchunks = (p.max_items + chunk_tiles - 1) / chunk_tiles;
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t off = need; need += (bytes + 255) / 256 * 256; return off; };
+    p.q16 = take((size_t)p.ppad * p.hpad * 2);
+    p.part = take(per_chunk * p.nchunks);
+    p.idx = take((size_t)p.P * k * 4);
+    p.sim = take((size_t)p.P * k * 4);
+    p.out = take((size_t)p.P * C * 4);
+    p.argmax = take((size_t)p.P * 4);
+    p.bytes = need;
+    return p;
+}
+// Where everything sits in the memory's one allocation (256-byte aligned offsets; 64-bit throughout)
+struct PropMemLayout {
+    size_t rows;    // f16 [frames][ppad][hpad]
+    size_t labels;  // f32 [frames][P][C]
+    size_t kept;    // f32 [P][C]: `out` of the last propagate with keep
+    size_t cells;   // uint32 [ppad]: propagate_cell
+    size_t bytes;
+};
+inline PropMemLayout propmem_layout(int frames, int P, int ppad, int hpad, int C) {
+    PropMemLayout l{};
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t off = need; need += (bytes + 255) / 256 * 256; return off; };
+    l.rows = take((size_t)frames * ppad * hpad * 2);
+    l.labels = take((size_t)frames * P * C * 4);
+    l.kept = take((size_t)P * C * 4);
+    l.cells = take((size_t)ppad * 4);
+    l.bytes = need;
+    return l;
+}
+struct PropMemView {  // the device arrays of a memory
+    const _Float16* rows;
+    const float* labels;
+    float* kept;
+    const uint32_t* cells;
+    int h0, w0, C;
+};
+// q [P, H]: DEVICE f32 rows with row stride ldq (floats); ws: DEVICE workspace of plan.bytes, where idx, sim, out and argmax are left.
+// keep: `out` is also written to m.kept.  Every set bit of `slots` must be a slot below the memory's frames.  No wait.
+hipError_t launch_propagate(const float* q, size_t ldq, int H, const PropMemView& m, uint64_t slots, int radius, int k, float temperature,
+                            bool keep, char* ws, const PropagatePlan& plan, hipStream_t stream);
 
 // Spherical k-means of token rows (csrc/kmeans.hip; contract in include/dinov2_hip.h, dinov2_hip_kmeans).  The assignment has match_kernel's
 // tile; the update is a GEMM X^T [hpad128, npad] x one-hot [npad, kpad] with the same tile, its rows split into `nsplit` chunks (a multiple of

@@ -139,6 +139,7 @@ enum Scratch : int {
     SCRATCH_KMEANS,      // dinov2_hip_kmeans_tokens (staged host rows, the f16 operands, the update's partials, the results)
     SCRATCH_SLIDE,       // dinov2_hip_predict_dense_slide (a host input's images, the window table, the window batch, every window's logits, host outputs' staging)
     SCRATCH_VLAD,        // dinov2_hip_vlad_tokens (staged host rows, the f16 operands, the tables, one pass's partials, the results)
+    SCRATCH_PROPAGATE,   // dinov2_hip_propmem_set / dinov2_hip_propagate (staged host rows and labels, the f16 queries, the partial lists, the results)
     SCRATCH_COUNT
 };
 
@@ -223,6 +224,19 @@ struct dinov2_hip_bank {
     int device = 0;
     int H = 0, hpad = 0, capacity = 0, cap_pad = 0, count = 0;
     _Float16* rows = nullptr;
+};
+
+// A resident memory of frames for label propagation (dinov2_hip_propmem_*, dinov2_hip_propagate): one device allocation laid out by
+// dinov2::propmem_layout, made at create and never moved -- the f16 rows of `frames` slots of one h0 x w0 grid, each padded to whole tiles,
+// their f32 labels, the kept result of the last propagate and the cell table.  `filled`: bit f = slot f holds a frame; has_kept: `kept` holds
+// the result of a propagate with keep.  It keeps the device ordinal only, so it may outlive the model it was created with.
+struct dinov2_hip_propmem {
+    int device = 0;
+    int H = 0, hpad = 0, h0 = 0, w0 = 0, P = 0, ppad = 0, frames = 0, C = 0;
+    uint64_t filled = 0;
+    bool has_kept = false;
+    dinov2::PropMemLayout lay{};
+    char* dev = nullptr;
 };
 
 // A resident linear dense-prediction head (dinov2_hip_dense_head_*): one device allocation made at create -- the f16 weight [cpad, K] with zero

@@ -971,6 +971,117 @@ extern "C" int dinov2_hip_op_bank_bench(const float* q_dev, int32_t nq, const fl
     return rc;
 }
 
+// ---- dinov2_hip_propagate's kernels (csrc/propagate.hip) on host data: a memory of `frames` slots is built by the shared normaliser, then
+// ---- swept, merged and combined ----
+namespace {
+bool propagate_shape_ok(int h0, int w0, int H, int frames, int C, uint64_t slots, int radius, int k, float T) {
+    if (h0 < 1 || h0 > PROP_GRID_MAX || w0 < 1 || w0 > PROP_GRID_MAX || H < 8 || H > 4096 || frames < 1 || frames > PROP_FRAMES_MAX || C < 1 ||
+        C > PROP_C_MAX || k < 1 || k > BANK_K_MAX || radius < -1 || radius > PROP_RADIUS_MAX)
+        return false;
+    const int ppad = (h0 * w0 + MATCH_TN - 1) / MATCH_TN * MATCH_TN;
+    if ((int64_t)frames * ppad > PROP_ROWS_MAX) return false;
+    if (slots == 0 || (frames < 64 && (slots >> frames) != 0)) return false;
+    return T >= 1e-3f && T <= 1e3f;
+}
+// The memory of one diagnostic call: `fill` bytes everywhere, then the cell table and the rows of every slot normalised into their places
+// (the padding rows of a slot keep the fill)
+struct PropOpMem {
+    OpBuf dev;
+    PropMemLayout lay{};
+    PropMemView view{};
+    hipError_t build(const float* rows_dev, const float* labels_host, int h0, int w0, int H, int frames, int C, const PropagatePlan& plan,
+                     OpBuf::Fill fill) {
+        const int P = plan.P;
+        lay = propmem_layout(frames, P, plan.ppad, plan.hpad, C);
+        hipError_t e = dev.alloc(lay.bytes, 1, fill);
+        if (e != hipSuccess) return e;
+        char* const d = dev.as<char>();
+        std::vector<uint32_t> cells((size_t)plan.ppad, 0u);
+        for (int p = 0; p < P; ++p) cells[p] = propagate_cell(p, w0);
+        e = hipMemcpy(d + lay.cells, cells.data(), cells.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && labels_host) e = hipMemcpy(d + lay.labels, labels_host, (size_t)frames * P * C * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !labels_host) e = hipMemset(d + lay.labels, 0, (size_t)frames * P * C * 4);
+        for (int f = 0; f < frames && e == hipSuccess; ++f)
+            e = launch_match_normalise(rows_dev + (size_t)f * P * H, (size_t)H, (_Float16*)(d + lay.rows) + (size_t)f * plan.ppad * plan.hpad, P, P, H,
+                                       plan.hpad, nullptr);
+        view = PropMemView{(const _Float16*)(d + lay.rows), (const float*)(d + lay.labels), (float*)(d + lay.kept), (const uint32_t*)(d + lay.cells),
+                           h0, w0, C};
+        return e;
+    }
+};
+}  // namespace
+extern "C" int dinov2_hip_op_propagate_plan(int32_t h0, int32_t w0, int32_t H, int32_t nactive, int32_t radius, int32_t k, int32_t C,
+                                            int32_t chunk_tiles, int64_t* out, int32_t* ranges) {
+    if (!out || nactive < 1 || nactive > PROP_FRAMES_MAX || chunk_tiles < 0 ||
+        !propagate_shape_ok(h0, w0, H, nactive, C, 1, radius, k, 1.0f))
+        return DINOV2_HIP_ERR_INVALID;
+    const PropagatePlan p = propagate_plan(h0, w0, H, nactive, radius, k, C, chunk_tiles);
+    out[0] = p.chunk_tiles;
+    out[1] = p.nchunks;
+    out[2] = p.qtiles;
+    out[3] = p.max_items;
+    out[4] = p.kept_items;
+    out[5] = (int64_t)((size_t)p.nchunks * p.ppad * k * sizeof(BankEntry));
+    out[6] = (int64_t)p.bytes;
+    out[7] = (int64_t)propmem_layout(nactive, p.P, p.ppad, p.hpad, C).bytes;
+    for (int qt = 0; ranges && qt < p.qtiles; ++qt) {
+        int t0, t1;
+        propagate_tile_range(qt, p.P, w0, radius, &t0, &t1);
+        ranges[2 * qt] = t0;
+        ranges[2 * qt + 1] = t1;
+    }
+    return 0;
+}
+extern "C" int dinov2_hip_op_propagate(const float* q, const float* rows, const float* labels, int32_t h0, int32_t w0, int32_t H, int32_t frames,
+                                       int32_t C, uint64_t slots, int32_t radius, int32_t k, float temperature, int32_t chunk_tiles, float* out,
+                                       int32_t* argmax, int32_t* idx, float* sim, float* kept) {
+    if (!q || !rows || !labels || !out || !argmax || !idx || !sim || chunk_tiles < 0 ||
+        !propagate_shape_ok(h0, w0, H, frames, C, slots, radius, k, temperature))
+        return DINOV2_HIP_ERR_INVALID;
+    const PropagatePlan plan = propagate_plan(h0, w0, H, __builtin_popcountll(slots), radius, k, C, chunk_tiles);
+    const int P = plan.P;
+    OpBuf dQ, dR, dW;
+    PropOpMem mem;
+    OP_TRY(dQ.upload(q, (size_t)P * H * 4));
+    OP_TRY(dR.upload(rows, (size_t)frames * P * H * 4));
+    OP_TRY(mem.build(dR.as<float>(), labels, h0, w0, H, frames, C, plan, OpBuf::nans()));  // padding rows stay NaN: the sweep must mask them
+    OP_TRY(dW.alloc(plan.bytes, 1, OpBuf::nans()));
+    OP_TRY(launch_propagate(dQ.as<float>(), (size_t)H, H, mem.view, slots, radius, k, temperature, kept != nullptr, dW.as<char>(), plan, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    OP_TRY(dW.read(out, plan.out, (size_t)P * C * 4));
+    OP_TRY(dW.read(argmax, plan.argmax, (size_t)P * 4));
+    OP_TRY(dW.read(idx, plan.idx, (size_t)P * k * 4));
+    OP_TRY(dW.read(sim, plan.sim, (size_t)P * k * 4));
+    if (kept) OP_TRY(mem.dev.read(kept, mem.lay.kept, (size_t)P * C * 4));
+    return 0;
+}
+extern "C" int dinov2_hip_op_propagate_bench(const float* q_dev, const float* rows_dev, int32_t h0, int32_t w0, int32_t H, int32_t frames, int32_t C,
+                                             uint64_t slots, int32_t radius, int32_t k, float temperature, int32_t chunk_tiles, int32_t warmup,
+                                             int32_t iters, float* ms) {
+    if (!q_dev || !rows_dev || !ms || chunk_tiles < 0 || warmup < 0 || iters < 1 ||
+        !propagate_shape_ok(h0, w0, H, frames, C, slots, radius, k, temperature))
+        return DINOV2_HIP_ERR_INVALID;
+    const PropagatePlan plan = propagate_plan(h0, w0, H, __builtin_popcountll(slots), radius, k, C, chunk_tiles);
+    OpBuf dW;
+    PropOpMem mem;
+    EventPair ev;
+    OP_TRY(mem.build(rows_dev, nullptr, h0, w0, H, frames, C, plan, OpBuf::zeros()));
+    OP_TRY(dW.alloc(plan.bytes, 1, OpBuf::none()));
+    OP_TRY(ev.create());
+    int rc = 0;
+    for (int i = 0; i < warmup + iters && rc == 0; ++i) {
+        if (i == warmup && hipEventRecord(ev.e0, nullptr) != hipSuccess) rc = -1;
+        if (launch_propagate(q_dev, (size_t)H, H, mem.view, slots, radius, k, temperature, true, dW.as<char>(), plan, nullptr) != hipSuccess) rc = -1;
+    }
+    float t = 0.0f;
+    if (rc == 0 && (hipEventRecord(ev.e1, nullptr) != hipSuccess || hipEventSynchronize(ev.e1) != hipSuccess ||
+                    hipEventElapsedTime(&t, ev.e0, ev.e1) != hipSuccess))
+        rc = -1;
+    (void)hipDeviceSynchronize();
+    *ms = t / (float)iters;
+    return rc;
+}
+
 // ---- dinov2_hip_kmeans_tokens' kernels (csrc/kmeans.hip) on host data ----
 namespace {
 bool kmeans_shape_ok(int n, int K, int H) { return n >= 1 && n <= KMEANS_N_MAX && K >= 1 && K <= KMEANS_K_MAX && H >= 8 && H <= 4096; }

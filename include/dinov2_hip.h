@@ -627,6 +627,81 @@ typedef struct dinov2_hip_vlad {
  * what it was. */
 int dinov2_hip_vlad_tokens(dinov2_hip_session *s, const dinov2_hip_vlad *v, char *err, size_t errlen);
 
+/* -- video label propagation over a frame memory (no reference counterpart: the label-propagation protocol of DINO's video-segmentation
+ *    evaluation on DAVIS -- every patch of a new frame looks at the patches of a few remembered frames (the first one and the last few)
+ *    inside a spatial window around its own cell, keeps its k most similar ones and takes the softmax-weighted mean of their label vectors.
+ *    Masks, part labels, clicked points or a dense head's output on a key frame then follow a video at one forward per frame: forward,
+ *    propagate with keep, set -- no token and no label crosses PCIe).  The memory is one device allocation on the model's device, made at
+ *    create and never moved: f16 rows [frames][P rounded up to the 128-row tile][H rounded up to 64], zeroed at create, so that every slot
+ *    owns whole tiles; f32 labels [frames][P][C]; the kept result [P][C]; a cell table.  All offsets are 64-bit.  It keeps only the device
+ *    ordinal, so it may outlive the model; a session of another device is refused.  One host thread at a time uses a memory.  On the device
+ *    (csrc/propagate.hip): dinov2_hip_match's normalisation kernel, a selection kernel with the tile of dinov2_hip_match and the per-row
+ *    list of dinov2_hip_bank_topk (one source each: csrc/sim_tile.h, csrc/topk_list.h), the bank's merge kernel, and a combine kernel.  The
+ *    affinity matrix is never written.
+ *    Contract:
+ *    1. Operands.  Contract 1 of dinov2_hip_match, the same row code (csrc/normalise_row.h): f16 unit rows, a zero row stays zero.  Inputs
+ *       must be finite.
+ *    2. Similarity.  Contract 2 of dinov2_hip_match: the same tile and K loop, so a pair has the bits it has in dinov2_hip_match_tokens and
+ *       dinov2_hip_bank_topk.
+ *    3. Candidates.  Query i sits at cell (i / w0, i % w0).  Column (f, p) -- patch p of slot f -- is a candidate iff bit f of `slots` is
+ *       set and (radius < 0 or max(|qy - py|, |qx - px|) <= radius).  Rows P .. Ppad - 1 of a slot and unset slots never enter a list, and
+ *       nothing is assumed about their memory (dinov2_hip_propmem_drop does not touch it).
+ *    4. Selection.  The first k candidates in the strict total order of dinov2_hip_bank_topk: the larger f32 value first (-0 is read as
+ *       +0), among equal values the LOWEST index, where index = f * P + p.  Slots beyond the number of candidates hold idx = -1 and
+ *       sim = -INFINITY.  Hence with radius = -1 and slots 0 .. n - 1 set, idx and sim equal those of dinov2_hip_bank_topk on a bank that
+ *       holds the same frames in slot order, bit for bit.  A query's result does not depend on the chunking, nor on which other queries
+ *       travel with it.
+ *    5. Weights.  w_j = expf((sim_j - sim_0) / T): an f32 subtraction, a correctly rounded f32 division, the device library's expf (not
+ *       the fast intrinsic).  w_0 = 1 exactly; an empty slot weighs 0.
+ *    6. Output.  out[c] = (sum_j w_j L[idx_j][c]) / (sum_j w_j): every product rounded to f32, both sums in f32 with j ascending, the
+ *       division correctly rounded.  No atomics: the result is bit-reproducible run to run.  argmax[i] is the LOWEST c among the largest
+ *       out[i][c].  With keep, out also stays in the memory for the next dinov2_hip_propmem_set with labels == NULL.  This is DINO's
+ *       procedure (exp(sim / T) masked to the window, the top k per query, normalised, labels x affinity) wherever no tie sits on the
+ *       k-th value; there the published code keeps ALL the tied entries, and this keeps those with the lowest indices.
+ *    Out of scope: device-side outputs, the device group, the rows of a list forward, bf16 operands, k > 64, non-rectangular windows,
+ *    upsampling of the result to pixels, dinov2_compat.hpp and the example programs.
+ *    Times: profiles/propagate.md. */
+typedef struct dinov2_hip_propmem dinov2_hip_propmem;   /* resident: F slots of one h0 x w0 patch grid */
+
+/* 8 <= H <= 4096, 1 <= h0, w0 <= 256, 1 <= frames <= 64, frames * Ppad <= 2^24 (Ppad = h0 w0 rounded up to 128), 1 <= C <= 256, else
+ * DINOV2_HIP_ERR_INVALID.  Every slot starts empty.  An allocation the device refuses returns DINOV2_HIP_ERR_HIP and leaves nothing
+ * behind for the next launch to report. */
+int  dinov2_hip_propmem_create(dinov2_hip_model *model, int32_t H, int32_t h0, int32_t w0, int32_t frames, int32_t C,
+                               dinov2_hip_propmem **out, char *err, size_t errlen);
+/* waits for the device first, like dinov2_hip_bank_free */
+void dinov2_hip_propmem_free(dinov2_hip_propmem *mem);
+/* Fills slot `slot` (0 .. frames - 1; a filled slot is overwritten): `rows` -- GIVEN (host or device, [P, H]) or LAST_PATCHES of one image
+ * of the last un-split forward; LAST_CLS is refused; n must be P = h0 w0 -- are normalised into the slot, and `labels` [P, C] f32 (host,
+ * or device with labels_on_device = 1) become its labels.  labels == NULL: the soft labels that the last dinov2_hip_propagate with
+ * keep = 1 left in this memory (refused when there are none).  Returns after the stream has finished, like dinov2_hip_bank_add.
+ * Argument errors (NULLs; a slot out of range; those of dinov2_hip_bank_add for `rows`, the resident-source errors included; H unequal
+ * to the memory's; a misaligned device pointer; a session of another device) return DINOV2_HIP_ERR_INVALID
+ * before anything is launched, allocated or copied, with the memory untouched. */
+int  dinov2_hip_propmem_set(dinov2_hip_session *s, dinov2_hip_propmem *mem, int32_t slot, const dinov2_hip_rows *rows,
+                            const float *labels, int32_t labels_on_device, char *err, size_t errlen);
+/* the slot becomes empty; the memory is not touched.  DINOV2_HIP_ERR_INVALID for NULL or a slot out of range. */
+int  dinov2_hip_propmem_drop(dinov2_hip_propmem *mem, int32_t slot);
+
+typedef struct dinov2_hip_propagate_req {
+    dinov2_hip_rows queries; /* GIVEN or LAST_PATCHES; n must be P */
+    uint64_t slots;          /* bit f set: slot f is context.  Every set bit must be a filled slot; at least one must be set */
+    int32_t radius;          /* Chebyshev radius in patch cells, 0 .. 255; -1: no window */
+    int32_t k;               /* 1 .. 64 */
+    float   temperature;     /* finite, 1e-3 .. 1e3 */
+    int32_t keep;            /* 1: out also stays in the memory for the next dinov2_hip_propmem_set(labels = NULL); else 0 */
+    float   *labels;         /* [P, C] HOST: out of contract 6.  Any output may be NULL, but not all of them with keep == 0 */
+    int32_t *argmax;         /* [P] */
+    int32_t *idx;            /* [P, k] */
+    float   *sim;            /* [P, k] */
+    int32_t reserved[4];
+} dinov2_hip_propagate_req;
+/* Synchronous: returns after the copy-out.  Argument errors (NULLs; those of dinov2_hip_propmem_set for `queries`; LAST_CLS; a set bit
+ * that is no filled slot; no bit set; radius, k, temperature or keep out of range; nothing asked for) return DINOV2_HIP_ERR_INVALID
+ * before anything is launched, allocated or copied, with the outputs and the memory untouched.  The scratch (the f16 queries, host queries'
+ * staging copy, at most 32 MiB of partial lists, the results) is a session-owned buffer grown on demand; an allocation the device refuses
+ * returns DINOV2_HIP_ERR_HIP. */
+int  dinov2_hip_propagate(dinov2_hip_session *s, dinov2_hip_propmem *mem, const dinov2_hip_propagate_req *req, char *err, size_t errlen);
+
 /* -- linear dense-prediction heads (no reference counterpart: semantic segmentation and depth estimation with a linear head on frozen
  *    patch features, two of the evaluation protocols of the DINOv2 paper; upstream: BNHead of
  *    dinov2/eval/segmentation/models/decode_heads/linear_head.py and of dinov2/eval/depth/models/decode_heads/linear_head.py).  A resident head

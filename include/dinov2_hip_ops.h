@@ -242,6 +242,27 @@ int dinov2_hip_op_bank_plan(int32_t nq, int32_t nb, int32_t H, int32_t k, int32_
 int dinov2_hip_op_bank_bench(const float *q_dev, int32_t nq, const float *b_dev, int32_t nb, int32_t H, int32_t k, int32_t chunk_tiles,
                              int32_t warmup, int32_t iters, int32_t floor_only, float *ms);
 
+/* the kernels behind dinov2_hip_propagate (csrc/propagate.hip) with the shared normaliser and the bank's merge, without a model or session:
+ * host q [P, H] (P = h0 w0) against a memory built here from host rows [frames, P, H] and labels [frames, P, C] -- every slot is written,
+ * `slots` says which ones are context (bits below `frames` only, at least one) -> out [P, C], argmax [P], idx / sim [P, k] (all required)
+ * and, unless NULL, kept [P, C]: what a call with keep leaves in the memory.  Limits as dinov2_hip_propmem_create / dinov2_hip_propagate,
+ * else DINOV2_HIP_ERR_INVALID.  chunk_tiles: items (active slot x kept column tile) per workgroup, 0 = the planner's choice (raised where
+ * the partials would pass their bound).  The memory and the workspace are filled with 0xff bytes first, so the padding rows of a slot and
+ * anything the kernels read without having written it are NaN.
+ * propagate_plan (no device): propagate_plan of csrc/kernels.h for `nactive` set slots: out[0 .. 7] = chunk_tiles, nchunks, query tiles,
+ *   the most items of a query tile, the items of all query tiles together, bytes of the partials, bytes of the workspace, bytes of a memory
+ *   of nactive frames; ranges (may be NULL) [query tiles][2] = the kept column tiles [t0, t1) of every query tile.
+ * propagate_bench (tools/propagate_bench.py): DEVICE q_dev [P, H] and rows_dev [frames, P, H], labels zero: *ms = one call's device work
+ *   (normalise, select, merge, combine with keep), the mean of `iters` after `warmup`. */
+int dinov2_hip_op_propagate(const float *q, const float *rows, const float *labels, int32_t h0, int32_t w0, int32_t H, int32_t frames, int32_t C,
+                            uint64_t slots, int32_t radius, int32_t k, float temperature, int32_t chunk_tiles, float *out, int32_t *argmax,
+                            int32_t *idx, float *sim, float *kept);
+int dinov2_hip_op_propagate_plan(int32_t h0, int32_t w0, int32_t H, int32_t nactive, int32_t radius, int32_t k, int32_t C, int32_t chunk_tiles,
+                                 int64_t *out, int32_t *ranges);
+int dinov2_hip_op_propagate_bench(const float *q_dev, const float *rows_dev, int32_t h0, int32_t w0, int32_t H, int32_t frames, int32_t C,
+                                  uint64_t slots, int32_t radius, int32_t k, float temperature, int32_t chunk_tiles, int32_t warmup, int32_t iters,
+                                  float *ms);
+
 /* the kernels behind dinov2_hip_kmeans_tokens (csrc/kmeans.hip) and the shared normaliser, without a model or session; cases, the numpy
  * restatement and the bounds: tests/kmeans_cases.py.  1 <= n <= 2^20, 1 <= K <= 1024, 8 <= H <= 4096, else DINOV2_HIP_ERR_INVALID.  Every
  * device buffer starts as 0xff bytes, so anything the kernels read without having written it shows up as NaN / -1; labels, sim, centres and
