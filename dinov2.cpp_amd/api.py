@@ -130,6 +130,27 @@ class Vlad(C.Structure):
 VLAD_INTRA_NORM, VLAD_L2_NORM = 1, 2
 
 
+class NCut(C.Structure):
+    """dinov2_hip_ncut (include/dinov2_hip.h)."""
+    _fields_ = [("rows", Rows), ("all_images", C.c_int32), ("affinity", C.c_int32), ("tau", C.c_float), ("floor", C.c_float),
+                ("n_eig", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_float), ("values", C.c_void_p), ("vectors", C.c_void_p),
+                ("degree", C.c_void_p), ("residual", C.c_void_p), ("iterations", C.c_void_p), ("converged", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
+NCUT_THRESHOLD, NCUT_RELU, NCUT_EXP = 0, 1, 2
+NCUT_NB = 8  # the block width (csrc/kernels.h NCUT_NB)
+_NCUT_AFFINITY = {"threshold": NCUT_THRESHOLD, "relu": NCUT_RELU, "exp": NCUT_EXP}
+
+
+def _ncut_affinity(affinity):
+    if affinity in _NCUT_AFFINITY:
+        return _NCUT_AFFINITY[affinity]
+    if isinstance(affinity, (int, np.integer)):
+        return int(affinity)  # (an unknown id reaches the library, which refuses it)
+    raise ValueError(f"ncut: affinity must be one of {sorted(_NCUT_AFFINITY)}")
+
+
 class DenseDesc(C.Structure):
     """dinov2_hip_dense_desc (include/dinov2_hip.h)."""
     _fields_ = [("layers", C.POINTER(C.c_int32)), ("n_layers", C.c_int32), ("norm", C.c_int32), ("concat_cls", C.c_int32),
@@ -516,6 +537,80 @@ def op_kmeans(rows, K, max_iter=20, init=None, seed=0):
 VLAD_PLAN_FIELDS = ("kpad", "hpad", "hpad128", "chunk", "cap", "npad", "ntiles", "nchunks", "npass", "partial_bytes", "bytes")
 
 
+def op_ncut_plan(n, H, nchunk=0):
+    """ncut_plan (csrc/kernels.h) as a dict; no device needed."""
+    buf = (C.c_int64 * 8)()
+    if lib().dinov2_hip_op_ncut_plan(int(n), int(H), int(nchunk), buf) != 0:
+        raise ValueError(f"ncut refuses n={n} H={H} nchunk={nchunk}")
+    return dict(zip(("npad", "hpad", "ntiles", "chunk_tiles", "nchunks", "part_bytes", "bytes"), (int(v) for v in buf)))
+
+
+def _f64(a):
+    return None if a is None else np.ascontiguousarray(a, np.float64)
+
+
+def op_ncut_apply(rows, affinity, tau=0.2, floor=1e-5, scale=None, q=None, nchunk=0, want=("t", "degree", "xhat")):
+    """ncut_apply_kernel and the degree pass on host rows [n, H] (dinov2_hip_op_ncut_apply): dict of t [n, 8] f64 = W (scale * q) (q [n, 8],
+    scale [n] or None = ones), degree [n] f64, xhat [n, H] = the f32 values of the device's f16 rows."""
+    x, s, qq = _f32(rows), _f64(scale), _f64(q)
+    n, H = x.shape
+    if qq is not None and qq.shape != (n, NCUT_NB) or s is not None and s.shape != (n,):
+        raise ValueError("ncut_apply: q must be [n, 8] and scale [n]")
+    out = {}
+    if "t" in want and qq is not None:
+        out["t"] = np.full((n, NCUT_NB), np.nan, np.float64)
+    if "degree" in want:
+        out["degree"] = np.full(n, np.nan, np.float64)
+    if "xhat" in want:
+        out["xhat"] = np.full((n, H), np.nan, np.float32)
+    _op_rc(lib().dinov2_hip_op_ncut_apply(_ptr(x), n, H, _ncut_affinity(affinity), float(tau), float(floor), _ptr(s), _ptr(qq), int(nchunk),
+                                          _ptr(out.get("t")), _ptr(out.get("degree")), _ptr(out.get("xhat"))), "ncut_apply")
+    return out
+
+
+def op_ncut_step(rows, affinity, tau, floor, yprev, gprev_parts, nchunk=0):
+    """One full step of dinov2_hip_ncut's iteration on host rows (dinov2_hip_op_ncut_step): yprev [n, 8] f64 and the partials of its Gram
+    matrix gprev_parts [<= row tiles, 64] (missing partials are zeros) -> dict of ynext [n, 8], gnext_parts, ritz_parts [row tiles, 64]."""
+    x, y = _f32(rows), _f64(yprev)
+    n, H = x.shape
+    nt = op_ncut_plan(n, H, nchunk)["ntiles"]
+    g = np.zeros((nt, 64), np.float64)
+    gp = _f64(gprev_parts).reshape(-1, 64)
+    if y.shape != (n, NCUT_NB) or gp.shape[0] > nt:
+        raise ValueError("ncut_step: yprev must be [n, 8] and gprev_parts at most [row tiles, 64]")
+    g[:gp.shape[0]] = gp
+    out = {"ynext": np.full((n, NCUT_NB), np.nan), "gnext_parts": np.full((nt, 64), np.nan), "ritz_parts": np.full((nt, 64), np.nan)}
+    _op_rc(lib().dinov2_hip_op_ncut_step(_ptr(x), n, H, _ncut_affinity(affinity), float(tau), float(floor), int(nchunk), _ptr(y), _ptr(g),
+                                         _ptr(out["ynext"]), _ptr(out["gnext_parts"]), _ptr(out["ritz_parts"])), "ncut_step")
+    return out
+
+
+def _ncut_out(n, n_eig):
+    n, n_eig = max(int(n), 0), max(int(n_eig), 0)
+    return {"values": np.full(n_eig, np.nan, np.float32), "vectors": np.full((n_eig, n), np.nan, np.float32),
+            "degree": np.full(n, np.nan, np.float32), "residual": np.full(n_eig, np.nan, np.float32)}
+
+
+def op_ncut(rows, n_eig=4, affinity="threshold", tau=0.2, floor=1e-5, max_iter=1000, tol=1e-4):
+    """The whole of dinov2_hip_ncut_tokens on host rows without a model or session (dinov2_hip_op_ncut); the dict of Session.ncut."""
+    x = _f32(rows)
+    n, H = x.shape
+    out = _ncut_out(n, n_eig)
+    it, conv = C.c_int32(-1), C.c_int32(-1)
+    _op_rc(lib().dinov2_hip_op_ncut(_ptr(x), n, H, _ncut_affinity(affinity), float(tau), float(floor), int(n_eig), int(max_iter), float(tol),
+                                    _ptr(out["values"]), _ptr(out["vectors"]), _ptr(out["degree"]), _ptr(out["residual"]), C.byref(it),
+                                    C.byref(conv)), "ncut")
+    out.update(iterations=int(it.value), converged=bool(conv.value))
+    return out
+
+
+def tokencut_mask(v):
+    """TokenCut's bipartition of a second eigenvector: v > mean(v), with the side that holds the entry of largest magnitude as foreground."""
+    v = np.asarray(v)
+    mask = v > v.mean()
+    return mask if mask[int(np.argmax(np.abs(v)))] else ~mask
+
+
 def _vlad_offsets(offsets, n):
     """[n_seg + 1] int32 offsets; None = one segment of n rows."""
     return np.asarray([0, n], np.int32) if offsets is None else np.ascontiguousarray(offsets, np.int32)
@@ -861,6 +956,13 @@ def lib():
     L.dinov2_hip_op_kmeans_plan.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int64)]
     L.dinov2_hip_op_kmeans.argtypes = [fp, i32, i32, i32, i32, fp, ip, ip, fp, fp, ip, ip, ip]
     L.dinov2_hip_op_kmeans_bench.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, fp]
+    dp, f32 = C.POINTER(C.c_double), C.c_float
+    L.dinov2_hip_ncut_tokens.argtypes = [vp, C.POINTER(NCut), cp, sz]
+    L.dinov2_hip_op_ncut_plan.argtypes = [i32, i32, i32, C.POINTER(C.c_int64)]
+    L.dinov2_hip_op_ncut_apply.argtypes = [fp, i32, i32, i32, f32, f32, dp, dp, i32, dp, dp, fp]
+    L.dinov2_hip_op_ncut_step.argtypes = [fp, i32, i32, i32, f32, f32, i32, dp, dp, dp, dp, dp]
+    L.dinov2_hip_op_ncut.argtypes = [fp, i32, i32, i32, f32, f32, i32, i32, f32, fp, fp, fp, fp, ip, ip]
+    L.dinov2_hip_op_ncut_bench.argtypes = [vp, i32, i32, i32, f32, f32, i32, i32, i32, f32, i32, i32, fp, ip]
     L.dinov2_hip_op_vlad_plan.argtypes = [ip, i32, i32, i32, C.POINTER(C.c_int64), ip, ip, i32]
     L.dinov2_hip_op_vlad.argtypes = [fp, ip, i32, fp, i32, i32, u32, ip, fp, ip, fp, fp, fp]
     L.dinov2_hip_op_vlad_bench.argtypes = [vp, ip, i32, vp, i32, i32, u32, i32, i32, fp]
@@ -1491,7 +1593,9 @@ class Session(_Handle):
         i = Input(img.ctypes.data, B, hh, ww, layout, 0)
         _call(lib().dinov2_hip_predict, self._h, C.byref(i), C.byref(o), CLASSIFY if classify else 0)
         # the resident rows a Bank may name: one CLS row per image, P patch rows per image
-        self._last_rows = {"last_cls": B, "last_patches": _grid(self.model.hparams, hh, ww, layout, classify)[2]}
+        nh, nw, P = _grid(self.model.hparams, hh, ww, layout, classify)
+        self._last_rows = {"last_cls": B, "last_patches": P}
+        self._last_grid = _grid_dims(self.model.hparams, nh, nw)  # (Session.tokencut's reshape)
         return out
 
     def predict_device(self, img_ptr: int, B: int, hh: int, ww: int, *, classify: bool, layout: int = RGB_CHW,
@@ -1808,6 +1912,54 @@ class Session(_Handle):
         _call(lib().dinov2_hip_kmeans_tokens, self._h, C.byref(km))
         out.update(iterations=int(it.value), converged=bool(conv.value))
         return out
+
+    def ncut(self, rows=None, n_eig: int = 4, affinity="threshold", tau: float = 0.2, floor: float = 1e-5, max_iter: int = 1000,
+             tol: float = 1e-4, *, source=None, image: int = 0, all_images: bool = False, n: int | None = None, H: int | None = None):
+        """Spectral embedding on the device (dinov2_hip_ncut_tokens): the n_eig smallest eigen-pairs of (D - W) z = lambda D z over the
+        rows' affinity graph.  rows: [n, H] host array or DeviceArray; or rows=None with source="last_patches" (the patch rows of image
+        `image` of the last un-split predict, or of every image with all_images=True) or "last_cls"; `n` and `H` as in Session.kmeans.
+        affinity: "threshold" (w = s > tau ? 1 : floor), "relu" or "exp" (w = exp((s - 1) / tau)).
+        Returns a dict: values [n_eig] ascending, vectors [n_eig, n] (unit length, largest entry positive), degree [n], residual [n_eig],
+        iterations, converged."""
+        if source is None:
+            source = "given" if rows is not None else None
+        if source not in _ROWS_SOURCE or (source == "given") != (rows is not None):
+            raise ValueError("ncut: give rows, or source = 'last_cls' / 'last_patches' without rows")
+        if source != "given":
+            last = getattr(self, "_last_rows", {})
+            if n is None:
+                n = last.get(source, 0) * (last.get("last_cls", 0) if all_images else 1)
+            r = Rows(_ROWS_SOURCE[source], None, int(n), int(H if H is not None else self.model.hparams.hidden_size), int(image), 0)
+            keep = None
+        elif isinstance(rows, DeviceArray):
+            if len(rows.shape) != 2:
+                raise ValueError("ncut: rows must be [n, H]")
+            r, keep = Rows(ROWS_GIVEN, rows.ptr, rows.shape[0], rows.shape[1], 0, 1), rows
+        else:
+            keep = np.ascontiguousarray(rows, dtype=np.float32)
+            if keep.ndim != 2:
+                raise ValueError("ncut: rows must be [n, H]")
+            r = Rows(ROWS_GIVEN, keep.ctypes.data, keep.shape[0], keep.shape[1], 0, 0)
+        out = _ncut_out(r.n, n_eig)
+        it, conv = C.c_int32(-1), C.c_int32(-1)
+        nc = NCut(r, int(bool(all_images)), _ncut_affinity(affinity), float(tau), float(floor), int(n_eig), int(max_iter), float(tol),
+                  out["values"].ctypes.data, out["vectors"].ctypes.data, out["degree"].ctypes.data, out["residual"].ctypes.data,
+                  C.addressof(it), C.addressof(conv))
+        _call(lib().dinov2_hip_ncut_tokens, self._h, C.byref(nc))
+        del keep
+        out.update(iterations=int(it.value), converged=bool(conv.value))
+        return out
+
+    def tokencut(self, image: int = 0, tau: float = 0.2, *, grid=None):
+        """TokenCut on the patch tokens of image `image` of the last un-split predict: the second eigenvector of Session.ncut(affinity=
+        "threshold", tau, floor=1e-5) reshaped to the patch grid (`grid`: (h0, w0), by default that of the last Session.predict), and the
+        boolean mask v > mean(v) -- flipped where needed so that the foreground is the side that holds the entry of largest magnitude."""
+        res = self.ncut(n_eig=2, affinity="threshold", tau=tau, floor=1e-5, source="last_patches", image=image)
+        h0, w0 = grid if grid is not None else getattr(self, "_last_grid", (0, 0))
+        v = res["vectors"][1]
+        if h0 * w0 != v.size:
+            raise ValueError(f"tokencut: the patch grid {h0} x {w0} does not hold {v.size} patches")
+        return v.reshape(h0, w0), tokencut_mask(v).reshape(h0, w0)
 
     def vlad(self, rows=None, centers=None, *, source=None, image: int = 0, all_images: bool = False, offsets=None, intra_norm: bool = True,
              l2_norm: bool = True, want=("vlad", "counts"), n: int | None = None, H: int | None = None):

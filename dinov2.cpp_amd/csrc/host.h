@@ -1,4 +1,4 @@
-// Internal helpers of the host files behind the C-ABI (load.cpp, model.cpp, extras.cpp, pca.cpp, resident.cpp, vlad.cpp, propagate.cpp): error text, HIP_TRY, sizes, the session's
+// Internal helpers of the host files behind the C-ABI (load.cpp, model.cpp, extras.cpp, pca.cpp, resident.cpp, vlad.cpp, propagate.cpp, ncut.cpp): error text, HIP_TRY, sizes, the session's
 // scratch buffers.  Not for group.cpp, which talks to the sessions through the C-ABI and has an error macro of its own.
 #pragma once
 #include <cstdarg>
@@ -95,13 +95,26 @@ inline LayerListFault check_layer_list(const int32_t* layers, int n, int lo, int
     return LAYER_LIST_OK;
 }
 
-// resident.cpp, for vlad.cpp and propagate.cpp: its check of a dinov2_hip_rows of row width H against the session.  On success *src / *ld are the device view
+// resident.cpp, for vlad.cpp, propagate.cpp and ncut.cpp: its check of a dinov2_hip_rows of row width H against the session.  On success *src / *ld are the device view
 // of a resident source (nullptr for DINOV2_HIP_ROWS_GIVEN).  Touches nothing.
 int check_session_rows(const char* who, const dinov2_hip_session* s, int H, const dinov2_hip_rows* r, const float** src, size_t* ld, char* err,
                        size_t errlen);
 
 // pca.cpp, for ops_testing.cpp: the Rayleigh-Ritz step of dinov2_hip_pca3 on the host
 void pca_ritz(const double* yprev, const double* ynext, const double* g_parts, int nparts, int H, double* evals, double* comp);
+
+// ncut.cpp, for ops_testing.cpp: the ranges of dinov2_hip_ncut, the start block, the host's Rayleigh-Ritz step and the loop of
+// dinov2_hip_ncut_tokens from the normalised rows on (it waits for the stream; the results stay f64 until the caller narrows them)
+struct NcutResult {
+    std::vector<double> values, vectors, degree, residual;  // [n_eig], [n_eig][n], [n], [n_eig]; values and vectors empty unless finite
+    int iterations = 0, converged = 0;
+    bool finite = true;
+};
+bool ncut_args_ok(int n, int H, int affinity, float tau, float floor, int n_eig, int max_iter, float tol);
+void ncut_start_block(const double* deg, int n, int npad, int nparts, double* y0, double* g0);
+void ncut_ritz(const double* b_parts, const double* g_parts, int nparts, double* theta, double* V, double* resid);
+hipError_t ncut_run(const NcutBufs& b, int n, int affinity, float tau, float floor, int n_eig, int max_iter, float tol, const NcutPlan& plan,
+                    hipStream_t stream, NcutResult* out);
 
 // interpolate_pos_embed of the reference (load.cpp).  pos: [1 + M*M, H]; out: [1 + h_new*w_new, H].
 void interpolate_pos_embed(const float* pos, int M, int H, int h_new, int w_new, float* out);

@@ -972,6 +972,71 @@ hipError_t launch_slide_reduce(const float* logits, int ldl, int B, int h0, int 
                                const int* tab, int reduce, const float* centers, float eps, uint8_t* labels, float* value, const SlideReducePlan& plan,
                                hipStream_t stream);
 
+// Spectral embedding of token rows (csrc/ncut.hip, csrc/ncut.cpp; contract in include/dinov2_hip.h, dinov2_hip_ncut).  ncut_apply_kernel has
+// match_kernel's tile: workgroup (x, y) owns row tile x and the `chunk_tiles` column tiles of chunk y, forms the affinities of each tile on
+// the accumulators and sums w_ij (scale_j q_j) over its columns in f64 for the NCUT_NB columns of the block; ncut_finish_kernel folds the
+// chunks in ascending order.  The chunk count is capped so that the partials [nchunks][npad][NCUT_NB] f64 never exceed NCUT_PARTIAL_MAX.
+constexpr int NCUT_NB = PCA_NB, NCUT_N_MIN = 16, NCUT_N_MAX = 1 << 17, NCUT_EIG_MAX = 6, NCUT_ITER_MAX = 10000, NCUT_TARGET_WGS = 256;
+constexpr size_t NCUT_PARTIAL_MAX = (size_t)32 << 20;
+enum NcutAffinity : int { NCUT_THRESHOLD = 0, NCUT_RELU = 1, NCUT_EXP = 2 };
+// the steps between two Rayleigh-Ritz checks on the host, by the steps already taken
+inline int ncut_check_interval(int steps_done) { return steps_done < 32 ? 8 : 16; }
+struct NcutPlan {
+    int npad, hpad;            // rows to whole tiles, H to a multiple of 64
+    int ntiles;                // row tiles = column tiles = workgroups of ncut_finish_kernel
+    int chunk_tiles, nchunks;  // column tiles per workgroup of ncut_apply_kernel, workgroups per row tile
+    size_t x16;                // normalised rows [npad, hpad] f16
+    size_t y[2];               // the block, f64 [npad][NCUT_NB], two slots (rows >= n zero)
+    size_t gram[2];            // f64 [ntiles][64]: per-workgroup partials of Y^T Y of the block in the same slot
+    size_t ritz;               // f64 [ntiles][64]: per-workgroup partials of Q^T Y_next of the last step
+    size_t deg, cs;            // f64 [npad]: d_i, c_i (rows >= n zero)
+    size_t part;               // f64 [nchunks][npad][NCUT_NB]
+    size_t part_bytes, bytes;
+};
+// nchunks = 0: as many chunks as bring the grid to about NCUT_TARGET_WGS workgroups (never more than there are column tiles); a given value
+// is lowered where the partials would pass NCUT_PARTIAL_MAX.  Pure: (n, H, nchunks) alone decide every summation order.
+inline NcutPlan ncut_plan(int n, int H, int nchunks) {
+    NcutPlan p{};
+    p.npad = (n + MATCH_TM - 1) / MATCH_TM * MATCH_TM;
+    p.hpad = (H + 63) / 64 * 64;
+    p.ntiles = p.npad / MATCH_TM;
+    const size_t per_chunk = (size_t)p.npad * NCUT_NB * 8;  // <= 8 MiB
+    if (nchunks <= 0) nchunks = (NCUT_TARGET_WGS + p.ntiles - 1) / p.ntiles;
+    const int cap = (int)(NCUT_PARTIAL_MAX / per_chunk);
+    if (nchunks > cap) nchunks = cap;
+    if (nchunks > p.ntiles) nchunks = p.ntiles;
+    p.chunk_tiles = (p.ntiles + nchunks - 1) / nchunks;
+    p.nchunks = (p.ntiles + p.chunk_tiles - 1) / p.chunk_tiles;  // no empty chunk
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t off = need; need += (bytes + 255) / 256 * 256; return off; };
+    p.x16 = take((size_t)p.npad * p.hpad * 2);
+    for (int k = 0; k < 2; ++k) p.y[k] = take((size_t)p.npad * NCUT_NB * 8);
+    for (int k = 0; k < 2; ++k) p.gram[k] = take((size_t)p.ntiles * 64 * 8);
+    p.ritz = take((size_t)p.ntiles * 64 * 8);
+    p.deg = take((size_t)p.npad * 8);
+    p.cs = take((size_t)p.npad * 8);
+    p.part_bytes = per_chunk * p.nchunks;
+    p.part = take(p.part_bytes);
+    p.bytes = need;
+    return p;
+}
+struct NcutBufs {  // the device arrays of one call: views of a workspace (ncut_bufs) or buffers of their own
+    _Float16* x16;
+    double *y[2], *gram[2], *ritz, *deg, *cs, *part;
+};
+NcutBufs ncut_bufs(char* ws, const NcutPlan& plan);
+// part [nchunks][npad][NCUT_NB] = the chunk sums of sum_j w_ij (scale_j q_j): x16 normalised (launch_match_normalise with nout = npad), scale
+// [npad] or nullptr = ones, q [npad][NCUT_NB] or nullptr = a ones column 0 beside seven zero columns (the degree pass).  Columns >= n weigh 0.
+hipError_t launch_ncut_apply(const _Float16* x16, int n, int affinity, float tau, float floor, const double* scale, const double* q, double* part,
+                             const NcutPlan& plan, hipStream_t stream);
+// deg [npad] = the chunk partials' column 0 folded in ascending order, cs = deg > 0 ? 1 / sqrt(deg) : 0; rows >= n get 0 in both
+hipError_t launch_ncut_degree(const double* part, int n, double* deg, double* cs, const NcutPlan& plan, hipStream_t stream);
+// One step's second half: t = the chunk partials folded in ascending order, ynext = (1/2 (yprev + cs t)) R^-1 with R^-1 = pca_chol_rinv of the
+// sum of gprev's ntiles partials; gnext [ntiles][64] and ritz [ntiles][64] = the per-workgroup partials of ynext^T ynext and (yprev R^-1)^T ynext.
+// Rows >= n of ynext are written as zeros and contribute nothing.
+hipError_t launch_ncut_finish(const double* part, const double* cs, const double* yprev, const double* gprev, int n, double* ynext, double* gnext,
+                              double* ritz, const NcutPlan& plan, hipStream_t stream);
+
 // clock probe (device_types.h): per translation unit, [CLK_SLOTS][4] = running sums of shader cycles and 100 MHz ticks of workgroup 0 over
 // all launches of each kernel kind on the current device, the 100 MHz end stamp of the last one, the launch count
 hipError_t gemm_clock_probe_read(unsigned long long* out);

@@ -140,6 +140,7 @@ enum Scratch : int {
     SCRATCH_SLIDE,       // dinov2_hip_predict_dense_slide (a host input's images, the window table, the window batch, every window's logits, host outputs' staging)
     SCRATCH_VLAD,        // dinov2_hip_vlad_tokens (staged host rows, the f16 operands, the tables, one pass's partials, the results)
     SCRATCH_PROPAGATE,   // dinov2_hip_propmem_set / dinov2_hip_propagate (staged host rows and labels, the f16 queries, the partial lists, the results)
+    SCRATCH_NCUT,        // dinov2_hip_ncut_tokens (staged host rows, the f16 operand, the block and its partials, degrees)
     SCRATCH_COUNT
 };
 

@@ -1238,6 +1238,181 @@ extern "C" int dinov2_hip_op_kmeans_bench(const float* rows_dev, int32_t n, int3
     return rc;
 }
 
+// ---- dinov2_hip_ncut_tokens' kernels (csrc/ncut.hip) and its loop (csrc/ncut.cpp) on host data ----
+namespace {
+bool ncut_shape_ok(int n, int H) { return n >= NCUT_N_MIN && n <= NCUT_N_MAX && H >= 8 && H <= 4096; }
+bool ncut_affinity_ok(int n, int H, int affinity, float tau, float floor) { return ncut_args_ok(n, H, affinity, tau, floor, 1, 1, 1e-3f); }
+// The buffers of one run, each an allocation of its own that starts as 0xff bytes; the partials, the blocks, the degrees and the 8 x 8
+// partials between guard bands.
+struct NcutOpBufs {
+    OpBuf x16, y[2], gram[2], ritz, deg, cs, part;
+    NcutBufs b{};
+    hipError_t alloc(const NcutPlan& p) {
+        const struct { OpBuf* buf; size_t n, esz, guard; } all[] = {
+            {&x16, (size_t)p.npad * p.hpad, 2, 0}, {&y[0], (size_t)p.npad * NCUT_NB, 8, NCUT_NB}, {&y[1], (size_t)p.npad * NCUT_NB, 8, NCUT_NB},
+            {&gram[0], (size_t)p.ntiles * 64, 8, 64}, {&gram[1], (size_t)p.ntiles * 64, 8, 64}, {&ritz, (size_t)p.ntiles * 64, 8, 64},
+            {&deg, (size_t)p.npad, 8, 1}, {&cs, (size_t)p.npad, 8, 1}, {&part, p.part_bytes / 8, 8, NCUT_NB}};
+        for (const auto& a : all) {
+            const hipError_t e = a.buf->alloc(a.n, a.esz, OpBuf::nans(), a.guard);
+            if (e != hipSuccess) return e;
+        }
+        b.x16 = x16.as<_Float16>(); b.ritz = ritz.as<double>(); b.deg = deg.as<double>(); b.cs = cs.as<double>(); b.part = part.as<double>();
+        for (int k = 0; k < 2; ++k) { b.y[k] = y[k].as<double>(); b.gram[k] = gram[k].as<double>(); }
+        return hipSuccess;
+    }
+    // every guarded buffer's bands
+    int guards() const {
+        for (const OpBuf* g : {&y[0], &y[1], &gram[0], &gram[1], &ritz, &deg, &cs, &part}) {
+            std::vector<double> all(g->n);
+            OP_FETCH(g->fetch(all.data()));
+        }
+        return 0;
+    }
+};
+}  // namespace
+
+extern "C" int dinov2_hip_op_ncut_plan(int32_t n, int32_t H, int32_t nchunk, int64_t* out) {
+    if (!out || !ncut_shape_ok(n, H) || nchunk < 0) return DINOV2_HIP_ERR_INVALID;
+    const NcutPlan p = ncut_plan(n, H, nchunk);
+    const int64_t v[8] = {p.npad, p.hpad, p.ntiles, p.chunk_tiles, p.nchunks, (int64_t)p.part_bytes, (int64_t)p.bytes, 0};
+    std::copy(v, v + 8, out);
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_ncut_apply(const float* rows, int32_t n, int32_t H, int32_t affinity, float tau, float floor, const double* scale,
+                                        const double* q, int32_t nchunk, double* t_out, double* degree_out, float* xhat_f16_as_f32) {
+    if (!rows || !ncut_shape_ok(n, H) || !ncut_affinity_ok(n, H, affinity, tau, floor) || nchunk < 0 || (t_out && !q) ||
+        (!t_out && !degree_out && !xhat_f16_as_f32))
+        return DINOV2_HIP_ERR_INVALID;
+    const NcutPlan plan = ncut_plan(n, H, nchunk);
+    OpBuf dX, dS, dQ;
+    NcutOpBufs w;
+    OP_TRY(dX.upload(rows, (size_t)n * H * 4));
+    OP_TRY(w.alloc(plan));
+    OP_TRY(launch_match_normalise(dX.as<float>(), (size_t)H, w.b.x16, n, plan.npad, H, plan.hpad, nullptr));
+    std::vector<double> part(plan.part_bytes / 8);
+    auto fold = [&](int cols, double* out) {  // the chunks in ascending order, as ncut_degree_kernel and ncut_finish_kernel fold them
+        for (int i = 0; i < n; ++i)
+            for (int c = 0; c < cols; ++c) {
+                double s = part[(size_t)i * NCUT_NB + c];
+                for (int k = 1; k < plan.nchunks; ++k) s += part[((size_t)k * plan.npad + i) * NCUT_NB + c];
+                out[(size_t)i * cols + c] = s;
+            }
+    };
+    if (degree_out) {
+        OP_TRY(launch_ncut_apply(w.b.x16, n, affinity, tau, floor, nullptr, nullptr, w.b.part, plan, nullptr));
+        OP_TRY(launch_ncut_degree(w.b.part, n, w.b.deg, w.b.cs, plan, nullptr));
+        OP_TRY(hipDeviceSynchronize());
+        std::vector<double> d((size_t)plan.npad);
+        OP_FETCH(w.deg.fetch(d.data()));
+        std::copy(d.begin(), d.begin() + n, degree_out);
+        OP_FETCH(w.part.fetch(part.data()));  // (its guards)
+    }
+    if (t_out) {
+        if (scale) OP_TRY(dS.upload(scale, (size_t)n * 8));
+        OP_TRY(dQ.upload(q, (size_t)n * NCUT_NB * 8));
+        OP_TRY(launch_ncut_apply(w.b.x16, n, affinity, tau, floor, scale ? dS.as<double>() : nullptr, dQ.as<double>(), w.b.part, plan, nullptr));
+        OP_TRY(hipDeviceSynchronize());
+        OP_FETCH(w.part.fetch(part.data()));
+        fold(NCUT_NB, t_out);
+    }
+    if (xhat_f16_as_f32) {
+        std::vector<uint16_t> x16((size_t)plan.npad * plan.hpad);
+        OP_TRY(w.x16.read(x16.data(), 0, x16.size() * 2));
+        for (int i = 0; i < n; ++i) widen_to_f32(false, (const unsigned char*)(x16.data() + (size_t)i * plan.hpad), (size_t)H, xhat_f16_as_f32 + (size_t)i * H);
+    }
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_ncut_step(const float* rows, int32_t n, int32_t H, int32_t affinity, float tau, float floor, int32_t nchunk,
+                                       const double* yprev, const double* gprev_parts, double* ynext, double* gnext_parts, double* ritz_parts) {
+    if (!rows || !yprev || !gprev_parts || !ynext || !gnext_parts || !ritz_parts || !ncut_shape_ok(n, H) ||
+        !ncut_affinity_ok(n, H, affinity, tau, floor) || nchunk < 0)
+        return DINOV2_HIP_ERR_INVALID;
+    const NcutPlan plan = ncut_plan(n, H, nchunk);
+    OpBuf dX;
+    NcutOpBufs w;
+    OP_TRY(dX.upload(rows, (size_t)n * H * 4));
+    OP_TRY(w.alloc(plan));
+    OP_TRY(launch_match_normalise(dX.as<float>(), (size_t)H, w.b.x16, n, plan.npad, H, plan.hpad, nullptr));
+    OP_TRY(launch_ncut_apply(w.b.x16, n, affinity, tau, floor, nullptr, nullptr, w.b.part, plan, nullptr));
+    OP_TRY(launch_ncut_degree(w.b.part, n, w.b.deg, w.b.cs, plan, nullptr));
+    OP_TRY(hipMemcpy(w.b.y[0], yprev, (size_t)n * NCUT_NB * 8, hipMemcpyHostToDevice));  // (rows >= n stay NaN: the kernels do not read them)
+    OP_TRY(hipMemcpy(w.b.gram[0], gprev_parts, (size_t)plan.ntiles * 64 * 8, hipMemcpyHostToDevice));
+    OP_TRY(launch_ncut_apply(w.b.x16, n, affinity, tau, floor, w.b.cs, w.b.y[0], w.b.part, plan, nullptr));
+    OP_TRY(launch_ncut_finish(w.b.part, w.b.cs, w.b.y[0], w.b.gram[0], n, w.b.y[1], w.b.gram[1], w.b.ritz, plan, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    std::vector<double> y((size_t)plan.npad * NCUT_NB);
+    OP_FETCH(w.y[1].fetch(y.data()));
+    for (size_t i = (size_t)n * NCUT_NB; i < y.size(); ++i)
+        if (y[i] != 0.0) return -1;  // the rows >= n are written as zeros
+    std::copy(y.begin(), y.begin() + (size_t)n * NCUT_NB, ynext);
+    OP_FETCH(w.gram[1].fetch(gnext_parts));
+    OP_FETCH(w.ritz.fetch(ritz_parts));
+    return w.guards();
+}
+
+extern "C" int dinov2_hip_op_ncut(const float* rows, int32_t n, int32_t H, int32_t affinity, float tau, float floor, int32_t n_eig, int32_t max_iter,
+                                  float tol, float* values, float* vectors, float* degree, float* residual, int32_t* iterations,
+                                  int32_t* converged) {
+    if (!rows || !ncut_args_ok(n, H, affinity, tau, floor, n_eig, max_iter, tol)) return DINOV2_HIP_ERR_INVALID;
+    const NcutPlan plan = ncut_plan(n, H, 0);
+    OpBuf dX;
+    NcutOpBufs w;
+    OP_TRY(dX.upload(rows, (size_t)n * H * 4));
+    OP_TRY(w.alloc(plan));
+    OP_TRY(launch_match_normalise(dX.as<float>(), (size_t)H, w.b.x16, n, plan.npad, H, plan.hpad, nullptr));
+    NcutResult res;
+    OP_TRY(ncut_run(w.b, n, affinity, tau, floor, n_eig, max_iter, tol, plan, nullptr, &res));
+    OP_TRY(hipDeviceSynchronize());
+    OP_FETCH(w.guards());
+    if (!res.finite) return -1;
+    if (values) std::copy(res.values.begin(), res.values.end(), values);
+    if (vectors) std::copy(res.vectors.begin(), res.vectors.end(), vectors);
+    if (degree) std::copy(res.degree.begin(), res.degree.end(), degree);
+    if (residual) std::copy(res.residual.begin(), res.residual.end(), residual);
+    if (iterations) *iterations = res.iterations;
+    if (converged) *converged = res.converged;
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_ncut_bench(const float* rows_dev, int32_t n, int32_t H, int32_t affinity, float tau, float floor, int32_t nchunk,
+                                        int32_t n_eig, int32_t max_iter, float tol, int32_t warmup, int32_t iters, float* ms, int32_t* steps) {
+    if (!rows_dev || !ms || !steps || !ncut_args_ok(n, H, affinity, tau, floor, n_eig, max_iter, tol) || nchunk < 0 || warmup < 0 || iters < 1)
+        return DINOV2_HIP_ERR_INVALID;
+    const NcutPlan plan = ncut_plan(n, H, nchunk);
+    OpBuf dW;
+    EventPair ev;
+    OP_TRY(dW.alloc(plan.bytes, 1, OpBuf::none()));
+    OP_TRY(ev.create());
+    const NcutBufs b = ncut_bufs(dW.as<char>(), plan);
+    NcutResult res;
+    auto whole = [&] {
+        const hipError_t e = launch_match_normalise(rows_dev, (size_t)H, b.x16, n, plan.npad, H, plan.hpad, nullptr);
+        return e != hipSuccess ? e : ncut_run(b, n, affinity, tau, floor, n_eig, max_iter, tol, plan, nullptr, &res);
+    };
+    OP_TRY(whole());  // leaves every buffer of the single steps in a real state
+    *steps = res.iterations;
+    auto timed = [&](auto step, float* out) {
+        int rc = 0;
+        for (int i = 0; i < warmup + iters && rc == 0; ++i) {
+            if (i == warmup && hipEventRecord(ev.e0, nullptr) != hipSuccess) rc = -1;
+            if (step() != hipSuccess) rc = -1;
+        }
+        float t = 0.0f;
+        if (rc == 0 && (hipEventRecord(ev.e1, nullptr) != hipSuccess || hipEventSynchronize(ev.e1) != hipSuccess ||
+                        hipEventElapsedTime(&t, ev.e0, ev.e1) != hipSuccess))
+            rc = -1;
+        *out = t / (float)iters;
+        return rc;
+    };
+    int rc = timed([&] { return launch_ncut_apply(b.x16, n, affinity, tau, floor, b.cs, b.y[0], b.part, plan, nullptr); }, ms + 0);
+    if (rc == 0) rc = timed([&] { return launch_ncut_finish(b.part, b.cs, b.y[0], b.gram[0], n, b.y[1], b.gram[1], b.ritz, plan, nullptr); }, ms + 1);
+    if (rc == 0) rc = timed(whole, ms + 2);
+    (void)hipDeviceSynchronize();
+    return rc;
+}
+
 // ---- dinov2_hip_vlad_tokens' kernels (csrc/vlad.hip) on host data ----
 namespace {
 bool vlad_shape_ok(const int32_t* offsets, int n_seg, int K, int H) {

@@ -627,6 +627,65 @@ typedef struct dinov2_hip_vlad {
  * what it was. */
 int dinov2_hip_vlad_tokens(dinov2_hip_session *s, const dinov2_hip_vlad *v, char *err, size_t errlen);
 
+/* -- spectral embedding of token rows (no reference counterpart: the leading eigenvectors of the normalised patch-affinity graph,
+ *    (D - W) z = lambda D z.  TokenCut cuts the second one of one image's patches at its mean: unsupervised object discovery; Deep Spectral
+ *    Methods and the NCut visualisations feed the first few to k-means -- dinov2_hip_kmeans_tokens -- or show them as colours).  The rows
+ *    are a caller's matrix or resident tokens of the session's last un-split forward; only [n_eig, n] vectors cross PCIe, and the n x n
+ *    matrix W never exists: every step forms it tile by tile on the matrix cores (dinov2_hip_match's tile and K loop), maps the f32
+ *    accumulators to affinities and multiplies them into an 8-column f64 block at once (csrc/ncut.hip; the loop: csrc/ncut.cpp).
+ *    Contract:
+ *    1. Operands.  Contract 1 of dinov2_hip_match, the same row code: f16 unit rows x^, a zero row stays zero.  Inputs must be finite.
+ *    2. Similarity.  s_ij is contract 2 of dinov2_hip_match through the same tile code (csrc/sim_tile.h): the bits dinov2_hip_match_tokens,
+ *       the bank and k-means give that pair.  The diagonal is a pair like any other.  Columns j >= n carry weight 0 whatever f(0) is.
+ *    3. Affinity.  w_ij = f(s_ij) in f32 on the f32 similarity, -0 read as +0.  THRESHOLD: s > tau ? 1 : floor (strictly greater).  RELU:
+ *       max(s, 0).  EXP: expf((s - 1) / tau), the difference and the correctly rounded quotient in f32, expf the device library's (at most
+ *       1 ulp from the exact exponential of its argument).
+ *    4. Degrees and operator.  d_i = sum_j w_ij; c_i = d_i > 0 ? 1 / sqrt(d_i) : 0 in f64, so a vertex of degree 0 has zero entries in every
+ *       vector.  The iteration runs on A = 1/2 (I + C W C), C = diag(c): the shift keeps the spectrum in [0, 1], so an affinity that is not
+ *       positive semi-definite (THRESHOLD) cannot make the iteration converge to the negative end.  Every sum over j is f64 (w_ij exact in
+ *       f64, one fused multiply-add per term) in an order a pure planner fixes from (n, H) alone: within a chunk of column tiles every one
+ *       of 8 accumulators per row (column j of the tile belongs to accumulator (j / 64) * 4 + (j % 16) / 4) adds its columns in ascending
+ *       order, the accumulators fold as ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)), then the chunks fold in ascending order.  No atomics
+ *       anywhere: a call is bit-reproducible run to run.
+ *    5. Iteration.  Block width 8, Y in f64 [n, 8].  Every step: Q = Y_prev R^-1 (CholeskyQR: R from the Gram matrix Y_prev^T Y_prev, the
+ *       sum of per-workgroup partials -- 128 rows each, ascending -- in ascending order), then Y_next = A Q.  The start block is a fixed
+ *       function of (n, d): column 0 is sqrt(d_i), the known top eigenvector of A; column c = 1 .. 7 is
+ *       sin(0.37 (i + 1) (c + 1)) + (c == i % 8 ? 0.5 : 0); a row of degree 0 is zero.  Every 8 steps for the first 32, then every 16, the
+ *       host does Rayleigh-Ritz from two 8 x 8 matrices, B = Q^T Y_next (symmetrised) and G = Y_next^T Y_next, both from per-workgroup
+ *       partials: B v_k = theta_k v_k (theta descending), residual r_k^2 = v_k^T G v_k - theta_k^2 = ||A u_k - theta_k u_k||^2 for
+ *       u_k = Q v_k.  The loop ends when r_k <= tol for every k < n_eig (converged = 1) or when at least max_iter steps are done;
+ *       iterations = the steps done, max_iter rounded up to the check interval.  lambda_k = 2 (1 - theta_k).
+ *    6. Vectors.  Formed once at the end on the host in f64 from the last Y_next: z_k = C (Y_next v_k), scaled to unit Euclidean length,
+ *       the entry of largest magnitude positive (the lowest index at a tie), then rounded to f32.
+ *    Out of scope: Nystrom and other sub-sampling; Lanczos or LOBPCG; exploiting the symmetry of W; a materialised W; n_eig > 6;
+ *    device-side outputs; bf16 operands; the device group; the rows of a list forward; KNN-sparsified graphs; dinov2_compat.hpp and the
+ *    example programs.
+ *    Times: profiles/ncut.md. */
+enum dinov2_hip_ncut_affinity { DINOV2_HIP_NCUT_THRESHOLD = 0, DINOV2_HIP_NCUT_RELU = 1, DINOV2_HIP_NCUT_EXP = 2 };
+typedef struct dinov2_hip_ncut {
+    dinov2_hip_rows rows;   /* GIVEN (host / device), LAST_CLS, LAST_PATCHES of rows.image; 16 <= n <= 131 072, 8 <= H <= 4096 */
+    int32_t all_images;     /* as dinov2_hip_kmeans: 1 with LAST_PATCHES = the patch rows of every image of the last un-split forward */
+    int32_t affinity;       /* THRESHOLD: w = s > tau ? 1 : floor (TokenCut: tau 0.2, floor 1e-5); RELU: w = max(s, 0); EXP: w = exp((s - 1) / tau) */
+    float   tau, floor;     /* THRESHOLD: -1 <= tau < 1, 0 <= floor <= 1; EXP: 2^-6 <= tau <= 16; otherwise ignored */
+    int32_t n_eig;          /* 1 .. 6 */
+    int32_t max_iter;       /* 1 .. 10 000 steps (rounded up to the check interval) */
+    float   tol;            /* 1e-6 .. 1e-1: stop when every residual ||A u_k - theta_k u_k|| <= tol, k < n_eig */
+    float   *values;        /* [n_eig] HOST: lambda_k of (D - W) z = lambda D z, ascending (lambda_0 ~ 0); any output may be NULL, not all */
+    float   *vectors;       /* [n_eig, n]: z_k = D^-1/2 u_k, unit Euclidean length, entry of largest magnitude positive (lowest index at a tie) */
+    float   *degree;        /* [n] d_i = sum_j w_ij */
+    float   *residual;      /* [n_eig] */
+    int32_t *iterations, *converged;
+    int32_t reserved[4];
+} dinov2_hip_ncut;
+/* Synchronous: returns after the copy-out, like dinov2_hip_kmeans_tokens; the host waits for the stream at the degrees and at every check.
+ * Argument errors (NULL session or request; n, H, n_eig, max_iter, tol, tau or floor out of range; an unknown affinity; all outputs NULL;
+ * all_images with a source other than LAST_PATCHES or an n that is not last_b * P; the resident-source errors of dinov2_hip_bank_add; a
+ * misaligned device pointer) return DINOV2_HIP_ERR_INVALID before anything is launched, allocated or copied, with the outputs untouched.
+ * Rows that are not finite are found at the first check and return DINOV2_HIP_ERR_INVALID too, outputs untouched.  The scratch (host
+ * rows' staging copy, x^ in f16, two blocks, their 8 x 8 partials, d and c, at most 32 MiB of partial sums) is a session-owned buffer grown
+ * on demand; an allocation the device refuses returns DINOV2_HIP_ERR_HIP.  The session's last forward stays what it was. */
+int dinov2_hip_ncut_tokens(dinov2_hip_session *s, const dinov2_hip_ncut *nc, char *err, size_t errlen);
+
 /* -- video label propagation over a frame memory (no reference counterpart: the label-propagation protocol of DINO's video-segmentation
  *    evaluation on DAVIS -- every patch of a new frame looks at the patches of a few remembered frames (the first one and the last few)
  *    inside a spatial window around its own cell, keeps its k most similar ones and takes the softmax-weighted mean of their label vectors.

@@ -6,7 +6,7 @@
  * kernel against the oracle in isolation -- the per-op granularity the reference gets from ggml's own op tests and
  * that /root/reference itself never had (it holds no tests at all).  All return 0 on success, -1 on a HIP error
  * (the entry points with guard bands -- attention_ex, layer_tap, attn_rows, pca_prepare / pca_cov / pca_power / pca_project, dense_reduce,
- * dense_pack, slide_reduce, slide_gather, kmeans_assign / _update / kmeans, vlad -- also DINOV2_HIP_OP_GUARD_CHANGED).  Each family has its cases in tests/*_cases.py, CPU probes of those cases and a GPU file; for the
+ * dense_pack, slide_reduce, slide_gather, kmeans_assign / _update / kmeans, vlad, ncut_apply / _step / ncut -- also DINOV2_HIP_OP_GUARD_CHANGED).  Each family has its cases in tests/*_cases.py, CPU probes of those cases and a GPU file; for the
  * pca_* entry points: tests/pca_cases.py, tests/test_pca_probes.py, tests/test_gpu_pca_kernels.py.
  */
 #ifndef DINOV2_HIP_OPS_H
@@ -287,6 +287,32 @@ int dinov2_hip_op_kmeans(const float *rows, int32_t n, int32_t K, int32_t H, int
                          int32_t *converged);
 int dinov2_hip_op_kmeans_bench(const float *rows_dev, int32_t n, int32_t K, int32_t H, int32_t nsplit, int32_t max_iter, int32_t warmup,
                                int32_t iters, float *ms);
+
+/* the kernels behind dinov2_hip_ncut_tokens (csrc/ncut.hip), its loop (csrc/ncut.cpp) and the shared normaliser, without a model or session;
+ * cases, the numpy restatement and the bounds: tests/ncut_cases.py.  16 <= n <= 131 072, 8 <= H <= 4096, affinity, tau and floor as in
+ * dinov2_hip_ncut, else DINOV2_HIP_ERR_INVALID.  Every device buffer starts as 0xff bytes; the partials, both blocks, the 8 x 8 partials,
+ * the degrees and c sit between guard bands: a changed one returns DINOV2_HIP_OP_GUARD_CHANGED.  The block width is 8 throughout.
+ * ncut_plan (no device): out[0 .. 7] = npad, hpad, row tiles, column tiles per chunk, chunks, bytes of the partials, bytes of the workspace, 0.
+ *             nchunk: chunks of column tiles, 0 = the planner's choice.
+ * ncut_apply: host rows [n, H]; t_out [n, 8] f64 = the raw sums sum_j w_ij scale_j q_jc (scale [n] f64 or NULL = ones, q [n, 8] f64; the
+ *             chunk partials of one ncut_apply_kernel launch folded in ascending order), degree_out [n] f64 = d_i (the degree pass and
+ *             ncut_degree_kernel), xhat_f16_as_f32 [n, H] = the f32 values of the f16 rows.  Any output may be NULL, not all; t_out needs q.
+ * ncut_step:  one full step of contract 5 from yprev [n, 8] f64 and the partials gprev_parts [row tiles, 64] f64 of its Gram matrix (their
+ *             sum in ascending order is the matrix): the degree pass, ncut_apply_kernel on c and yprev, ncut_finish_kernel -> ynext [n, 8],
+ *             gnext_parts and ritz_parts [row tiles, 64]: the per-workgroup partials of ynext^T ynext and (yprev R^-1)^T ynext.  All required.
+ * ncut:       the whole of dinov2_hip_ncut_tokens on host rows; any output may be NULL.
+ * ncut_bench (tools/ncut_bench.py): DEVICE f32 rows_dev [n, H]: ms[0] = one ncut_apply_kernel launch, ms[1] = one ncut_finish_kernel launch,
+ *             ms[2] = the whole call (normalise, degrees, the loop with its checks, the vectors), each the mean of `iters` timed runs after
+ *             `warmup`, by HIP events on the null stream; steps[0] = the steps the whole call took. */
+int dinov2_hip_op_ncut_plan(int32_t n, int32_t H, int32_t nchunk, int64_t *out);
+int dinov2_hip_op_ncut_apply(const float *rows, int32_t n, int32_t H, int32_t affinity, float tau, float floor, const double *scale,
+                             const double *q, int32_t nchunk, double *t_out, double *degree_out, float *xhat_f16_as_f32);
+int dinov2_hip_op_ncut_step(const float *rows, int32_t n, int32_t H, int32_t affinity, float tau, float floor, int32_t nchunk,
+                            const double *yprev, const double *gprev_parts, double *ynext, double *gnext_parts, double *ritz_parts);
+int dinov2_hip_op_ncut(const float *rows, int32_t n, int32_t H, int32_t affinity, float tau, float floor, int32_t n_eig, int32_t max_iter,
+                       float tol, float *values, float *vectors, float *degree, float *residual, int32_t *iterations, int32_t *converged);
+int dinov2_hip_op_ncut_bench(const float *rows_dev, int32_t n, int32_t H, int32_t affinity, float tau, float floor, int32_t nchunk,
+                             int32_t n_eig, int32_t max_iter, float tol, int32_t warmup, int32_t iters, float *ms, int32_t *steps);
 
 /* the kernels behind dinov2_hip_vlad_tokens (csrc/vlad.hip) with the shared normaliser and k-means' transpose, without a model or session;
  * cases, the numpy restatement and the bounds: tests/vlad_cases.py.  offsets [n_seg + 1] strictly ascending from 0 to at most 2^20,
