@@ -120,6 +120,13 @@ class KMeans(C.Structure):
 KMEANS_INIT_GIVEN, KMEANS_INIT_ROWS = 0, 1
 
 
+class Coreset(C.Structure):
+    """dinov2_hip_coreset (include/dinov2_hip.h)."""
+    _fields_ = [("rows", Rows), ("all_images", C.c_int32), ("bank", C.c_void_p), ("m", C.c_int32), ("first", C.c_int32),
+                ("stop_sim", C.c_float), ("idx", C.c_void_p), ("cover", C.c_void_p), ("selected", C.c_void_p), ("nearest", C.c_void_p),
+                ("near_sim", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
 class Vlad(C.Structure):
     """dinov2_hip_vlad (include/dinov2_hip.h)."""
     _fields_ = [("rows", Rows), ("all_images", C.c_int32), ("offsets", C.c_void_p), ("n_seg", C.c_int32), ("K", C.c_int32),
@@ -531,6 +538,38 @@ def op_kmeans(rows, K, max_iter=20, init=None, seed=0):
     _op_rc(lib().dinov2_hip_op_kmeans(_ptr(x), n, int(K), H, int(max_iter), _ptr(cen), _ptr(idx), _ptr(out["labels"]), _ptr(out["sim"]),
                                       _ptr(out["centers"]), _ptr(out["counts"]), C.byref(it), C.byref(conv)), "kmeans")
     out.update(iterations=int(it.value), converged=bool(conv.value))
+    return out
+
+
+CORESET_PLAN_FIELDS = ("npad", "hpad", "rows_per_wg", "nparts", "bytes")
+
+
+def op_coreset_plan(n, H, m=1, rows_per_wg=0):
+    """coreset_plan (csrc/kernels.h) as a dict; no device needed."""
+    buf = (C.c_int64 * len(CORESET_PLAN_FIELDS))()
+    if lib().dinov2_hip_op_coreset_plan(int(n), int(H), int(m), int(rows_per_wg), buf) != 0:
+        raise ValueError(f"coreset refuses n={n} H={H} m={m} rows_per_wg={rows_per_wg}")
+    return dict(zip(CORESET_PLAN_FIELDS, [int(v) for v in buf]))
+
+
+def _coreset_out(n, m):
+    return {"idx": np.full(m, -7, np.int32), "cover": np.full(m, np.nan, np.float32), "nearest": np.full(n, -7, np.int32),
+            "near_sim": np.full(n, np.nan, np.float32)}
+
+
+def op_coreset(rows, m, first=0, stop_sim=None, rows_per_wg=0):
+    """The kernels of csrc/coreset.hip on host rows without a model or session (dinov2_hip_op_coreset); the dict of Session.coreset.
+    rows_per_wg: rows per workgroup, 0 = the planner's choice."""
+    x = _f32(rows)
+    n, H = x.shape
+    out = _coreset_out(n, int(m))
+    sel = C.c_int32(-1)
+    rc = lib().dinov2_hip_op_coreset(_ptr(x), n, H, int(m), int(first), float(np.inf if stop_sim is None else stop_sim), int(rows_per_wg),
+                                     _ptr(out["idx"]), _ptr(out["cover"]), C.byref(sel), _ptr(out["nearest"]), _ptr(out["near_sim"]))
+    if rc == 4:
+        raise ValueError(f"coreset refuses n={n} H={H} m={m} first={first} stop_sim={stop_sim} rows_per_wg={rows_per_wg}")
+    _op_rc(rc, "coreset")
+    out["selected"] = int(sel.value)
     return out
 
 
@@ -956,6 +995,11 @@ def lib():
     L.dinov2_hip_op_kmeans_plan.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int64)]
     L.dinov2_hip_op_kmeans.argtypes = [fp, i32, i32, i32, i32, fp, ip, ip, fp, fp, ip, ip, ip]
     L.dinov2_hip_op_kmeans_bench.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, fp]
+    L.dinov2_hip_coreset_tokens.argtypes = [vp, C.POINTER(Coreset), cp, sz]
+    L.dinov2_hip_bank_keep.argtypes = [vp, vp, ip, i32, cp, sz]
+    L.dinov2_hip_op_coreset.argtypes = [fp, i32, i32, i32, i32, C.c_float, i32, ip, fp, ip, ip, fp]
+    L.dinov2_hip_op_coreset_plan.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int64)]
+    L.dinov2_hip_op_coreset_bench.argtypes = [vp, i32, i32, i32, i32, i32, i32, fp]
     dp, f32 = C.POINTER(C.c_double), C.c_float
     L.dinov2_hip_ncut_tokens.argtypes = [vp, C.POINTER(NCut), cp, sz]
     L.dinov2_hip_op_ncut_plan.argtypes = [i32, i32, i32, C.POINTER(C.c_int64)]
@@ -1413,6 +1457,19 @@ class Bank(_Handle):
         t = TopK(r, int(k), out["idx"].ctypes.data, out["sim"].ctypes.data)
         _call(lib().dinov2_hip_bank_topk, sess._h, self._h, C.byref(t))
         return out
+
+    def keep(self, sess: "Session", idx) -> np.ndarray:
+        """Compacts the bank to the rows `idx` (dinov2_hip_bank_keep): distinct indices in [0, count), in any order.  They are sorted; the
+        sorted array is returned, so that new row j is old row result[j] (e.g. the picks of Session.coreset(bank=...))."""
+        a = np.asarray(idx)
+        if a.ndim != 1 or a.size < 1 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("bank.keep: idx must be a non-empty 1-D integer array")
+        a = np.sort(a.astype(np.int64))
+        if a[0] < 0 or a[-1] >= self.count or (np.diff(a) == 0).any():
+            raise ValueError(f"bank.keep: indices must be distinct and inside [0, {self.count})")
+        a = np.ascontiguousarray(a, np.int32)
+        _call(lib().dinov2_hip_bank_keep, sess._h, self._h, _ptr(a), len(a))
+        return a
 
     @property
     def count(self) -> int:
@@ -1875,34 +1932,66 @@ class Session(_Handle):
         out["mutual"] = out["idx_ba"][out["idx_ab"]] == np.arange(na, dtype=np.int32)
         return out
 
+    def _rows_request(self, who, rows, source, image, all_images, n, H):
+        """(Rows struct, the array it points into: kept alive by the caller) of the rows arguments of kmeans and coreset."""
+        if source is None:
+            source = "given" if rows is not None else None
+        if source not in _ROWS_SOURCE or (source == "given") != (rows is not None):
+            raise ValueError(f"{who}: give rows, or source = 'last_cls' / 'last_patches' without rows")
+        if source != "given":
+            last = getattr(self, "_last_rows", {})
+            if n is None:
+                n = last.get(source, 0) * (last.get("last_cls", 0) if all_images else 1)
+            return Rows(_ROWS_SOURCE[source], None, int(n), int(H if H is not None else self.model.hparams.hidden_size), int(image), 0), None
+        if isinstance(rows, DeviceArray):
+            if len(rows.shape) != 2:
+                raise ValueError(f"{who}: rows must be [n, H]")
+            return Rows(ROWS_GIVEN, rows.ptr, rows.shape[0], rows.shape[1], 0, 1), rows
+        keep = np.ascontiguousarray(rows, dtype=np.float32)
+        if keep.ndim != 2:
+            raise ValueError(f"{who}: rows must be [n, H]")
+        return Rows(ROWS_GIVEN, keep.ctypes.data, keep.shape[0], keep.shape[1], 0, 0), keep
+
+    def coreset(self, rows=None, m: int | None = None, first: int = 0, stop_sim: float | None = None, *, source=None, image: int = 0,
+                all_images: bool = False, bank: "Bank | None" = None, n: int | None = None, H: int | None = None) -> dict:
+        """Greedy k-center (farthest-point) selection of m rows by cosine similarity on the device (dinov2_hip_coreset_tokens).  The rows
+        as in kmeans(); or bank=: the rows of a Bank where they lie (Bank.keep(sess, result["idx"][:result["selected"]]) then thins it).
+        first: the first pick.  stop_sim: stop once every unselected row has a pick at least this similar (None: never).
+        Returns a dict: idx [m] int32 picks in selection order (-1 past `selected`), cover [m] f32 (the similarity of each pick to the picks
+        before it when it was chosen; -inf for the first, +inf past `selected`), selected, nearest [n] int32 (position of each row's most
+        similar pick) and near_sim [n] f32."""
+        if m is None:
+            raise ValueError("coreset: m, the number of rows to select, is required")
+        if bank is not None:
+            if rows is not None or source is not None:
+                raise ValueError("coreset: give bank=, or rows / source, not both")
+            r, keep, nn = Rows(), None, bank.count
+        else:
+            r, keep = self._rows_request("coreset", rows, source, image, all_images, n, H)
+            nn = max(int(r.n), 0)
+        out = _coreset_out(nn, max(int(m), 0))
+        sel = C.c_int32(-1)
+        c = Coreset(r, int(bool(all_images)), None if bank is None else bank._h.value, int(m), int(first), float(np.inf if stop_sim is None else stop_sim),
+                    out["idx"].ctypes.data, out["cover"].ctypes.data, C.addressof(sel), out["nearest"].ctypes.data, out["near_sim"].ctypes.data)
+        _call(lib().dinov2_hip_coreset_tokens, self._h, C.byref(c))
+        out["selected"] = int(sel.value)
+        return out
+
     def kmeans(self, rows=None, K: int = 8, max_iter: int = 20, init=None, seed: int = 0, *, source=None, image: int = 0,
                all_images: bool = False, n: int | None = None, H: int | None = None):
         """Spherical k-means on the device (dinov2_hip_kmeans_tokens).  rows: [n, H] host array or DeviceArray; or rows=None with
         source="last_patches" (the patch rows of image `image` of the last un-split predict, or of every image with all_images=True) or
         "last_cls"; `n` and `H` are taken from the session's last predict() unless given.  init: None (K distinct rows drawn by
-        numpy.random.default_rng(seed), sorted), [K] row indices or [K, H] centre vectors.  max_iter=0 only assigns.
+        numpy.random.default_rng(seed), sorted), "maximin" (the K picks of Session.coreset from row seed % n on: with a resident source only
+        K indices cross PCIe), [K] row indices or [K, H] centre vectors.  max_iter=0 only assigns.
         Returns a dict: labels [n] int32, sim [n] f32, centers [K, H] f32 (cluster sums: right direction, not unit length), counts [K],
         iterations, converged."""
-        if source is None:
-            source = "given" if rows is not None else None
-        if source not in _ROWS_SOURCE or (source == "given") != (rows is not None):
-            raise ValueError("kmeans: give rows, or source = 'last_cls' / 'last_patches' without rows")
-        if source != "given":
-            last = getattr(self, "_last_rows", {})
-            if n is None:
-                n = last.get(source, 0) * (last.get("last_cls", 0) if all_images else 1)
-            r = Rows(_ROWS_SOURCE[source], None, int(n), int(H if H is not None else self.model.hparams.hidden_size), int(image), 0)
-            keep = None
-        elif isinstance(rows, DeviceArray):
-            if len(rows.shape) != 2:
-                raise ValueError("kmeans: rows must be [n, H]")
-            r, keep = Rows(ROWS_GIVEN, rows.ptr, rows.shape[0], rows.shape[1], 0, 1), rows
-        else:
-            keep = np.ascontiguousarray(rows, dtype=np.float32)
-            if keep.ndim != 2:
-                raise ValueError("kmeans: rows must be [n, H]")
-            r = Rows(ROWS_GIVEN, keep.ctypes.data, keep.shape[0], keep.shape[1], 0, 0)
+        r, keep = self._rows_request("kmeans", rows, source, image, all_images, n, H)
         nn, HH, K = max(int(r.n), 0), int(r.H), int(K)
+        if isinstance(init, str):
+            if init != "maximin":
+                raise ValueError("kmeans: init must be None, 'maximin', [K] row indices or [K, H] centre vectors")
+            init = self.coreset(rows, m=K, first=int(seed) % max(nn, 1), source=source, image=image, all_images=all_images, n=n, H=H)["idx"]
         kind, cen, idx = _kmeans_init(init, nn, K, HH, seed)
         out = _kmeans_out(nn, max(K, 0), HH)
         it, conv = C.c_int32(-1), C.c_int32(-1)

@@ -1,4 +1,4 @@
-// Internal helpers of the host files behind the C-ABI (load.cpp, model.cpp, extras.cpp, pca.cpp, resident.cpp, vlad.cpp, propagate.cpp, ncut.cpp): error text, HIP_TRY, sizes, the session's
+// Internal helpers of the host files behind the C-ABI (load.cpp, model.cpp, extras.cpp, pca.cpp, resident.cpp, vlad.cpp, propagate.cpp, ncut.cpp, coreset.cpp): error text, HIP_TRY, sizes, the session's
 // scratch buffers.  Not for group.cpp, which talks to the sessions through the C-ABI and has an error macro of its own.
 #pragma once
 #include <cstdarg>
@@ -95,7 +95,7 @@ inline LayerListFault check_layer_list(const int32_t* layers, int n, int lo, int
     return LAYER_LIST_OK;
 }
 
-// resident.cpp, for vlad.cpp, propagate.cpp and ncut.cpp: its check of a dinov2_hip_rows of row width H against the session.  On success *src / *ld are the device view
+// resident.cpp, for vlad.cpp, propagate.cpp, ncut.cpp and coreset.cpp: its check of a dinov2_hip_rows of row width H against the session.  On success *src / *ld are the device view
 // of a resident source (nullptr for DINOV2_HIP_ROWS_GIVEN).  Touches nothing.
 int check_session_rows(const char* who, const dinov2_hip_session* s, int H, const dinov2_hip_rows* r, const float** src, size_t* ld, char* err,
                        size_t errlen);

@@ -461,6 +461,10 @@ hipError_t launch_bank_topk(const float* q, size_t ldq, int nq, const _Float16* 
 // bank_merge_kernel on its own, for propagate.hip: row r < nrows: the sorted lists part[(c * pass_rows + r) * k ..] of chunks c < nchunks
 // merged into idx / sim [r * k ..], empty slots as (-1, -inf)
 hipError_t launch_bank_merge(const BankEntry* part, int pass_rows, int nchunks, int k, int nrows, int* idx, float* sim, hipStream_t stream);
+// dinov2_hip_bank_keep: out[j, :] = rows[idx[j], :] for j < count (DEVICE indices, f16 rows of hpad elements; 64-bit offsets); `out` must
+// not overlap the rows read
+constexpr size_t BANK_KEEP_STAGE = (size_t)32 << 20;  // bytes of session scratch one chunk of the compaction is staged through
+hipError_t launch_bank_gather(const _Float16* rows, const int* idx, int count, int hpad, _Float16* out, hipStream_t stream);
 
 // Label propagation over a frame memory (csrc/propagate.hip; contract in include/dinov2_hip.h, dinov2_hip_propagate).  The memory holds
 // `frames` slots of one h0 x w0 patch grid, each P = h0 w0 rows padded to ppad (whole 128-row tiles), so a slot owns whole column tiles.
@@ -651,6 +655,73 @@ hipError_t launch_kmeans_gather(const float* src, int per, size_t outer, size_t 
 // The loop (contract 5): b.x16 = the normalised rows, b.cvec = the init vectors on entry; synchronises the stream once per assignment.
 hipError_t kmeans_run(const KmeansBufs& b, int n, int K, int H, int max_iter, const KmeansPlan& plan, hipStream_t stream, int* iterations,
                       int* converged);
+
+// Greedy k-center selection of rows (csrc/coreset.hip; contract in include/dinov2_hip.h, dinov2_hip_coreset).  One launch of
+// coreset_sweep_kernel per pick: workgroup x owns rows [x rows_per_wg, +rows_per_wg) -- whole 128-row tiles -- and leaves one (smallest
+// similarity, lowest row) partial over its unselected rows; the next launch's workgroups each fold the nparts partials themselves.  The
+// partials are double-buffered ([2][CORESET_PARTS_MAX]), so a launch never reads what it writes.
+constexpr int CORESET_N_MAX = 1 << 20, CORESET_BANK_N_MAX = 1 << 24, CORESET_PARTS_MAX = 1024;
+constexpr int CORESET_POLL = 256;                    // picks between two reads of the stop flag by the host
+constexpr size_t CORESET_WG_BYTES = (size_t)64 << 10;  // a workgroup's share of the f16 rows is at least this where that still leaves 512 workgroups
+struct CoresetPlan {
+    int npad, hpad;            // rows to whole tiles, H to a multiple of 64
+    int rows_per_wg, nparts;   // rows per workgroup (a multiple of 128), workgroups = partials (<= CORESET_PARTS_MAX)
+    size_t x16;                // normalised rows [npad, hpad] f16 (not used when the rows are a bank's)
+    size_t sim, nearest, mark; // f32 [npad], int32 [npad], uint8 [npad]: s, the position of the most similar pick, 1 = selected
+    size_t part;               // BankEntry [2][CORESET_PARTS_MAX]
+    size_t head;               // int32 [4]: [0] the stop flag, [1] `selected`
+    size_t idx, cover;         // int32 [m], f32 [m]
+    size_t bytes;
+};
+// rows_per_wg = 0: one tile a workgroup; more where n needs it to stay within CORESET_PARTS_MAX partials, and where a tile is shorter than
+// CORESET_WG_BYTES and 512 workgroups remain.  A given value is rounded up to whole tiles and raised to the first of these bounds.  Pure:
+// (n, H) alone fix the geometry (m only sizes the two result arrays), and no result depends on it.
+inline CoresetPlan coreset_plan(int n, int H, int m, int rows_per_wg, bool own_rows = true) {
+    CoresetPlan p{};
+    p.npad = (n + 127) / 128 * 128;
+    p.hpad = (H + 63) / 64 * 64;
+    const int tiles = p.npad / 128;
+    const int floor_tiles = (tiles + CORESET_PARTS_MAX - 1) / CORESET_PARTS_MAX;
+    int tpw = (rows_per_wg + 127) / 128;
+    if (rows_per_wg <= 0) {
+        const int want = (int)((CORESET_WG_BYTES + (size_t)128 * p.hpad * 2 - 1) / ((size_t)128 * p.hpad * 2));
+        const int spare = tiles / 512;
+        tpw = want < spare ? want : spare;
+    }
+    if (tpw < floor_tiles) tpw = floor_tiles;
+    if (tpw < 1) tpw = 1;
+    if (tpw > tiles) tpw = tiles;
+    p.rows_per_wg = tpw * 128;
+    p.nparts = (tiles + tpw - 1) / tpw;
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t off = need; need += (bytes + 255) / 256 * 256; return off; };
+    p.x16 = take(own_rows ? (size_t)p.npad * p.hpad * 2 : 0);
+    p.sim = take((size_t)p.npad * 4);
+    p.nearest = take((size_t)p.npad * 4);
+    p.mark = take((size_t)p.npad);
+    p.part = take((size_t)2 * CORESET_PARTS_MAX * sizeof(BankEntry));
+    p.head = take(16);
+    p.idx = take((size_t)m * 4);
+    p.cover = take((size_t)m * 4);
+    p.bytes = need;
+    return p;
+}
+struct CoresetBufs {  // the device arrays of one run: views of a workspace (coreset_bufs) or buffers of their own
+    const _Float16* x16;
+    float* sim;
+    int* nearest;
+    unsigned char* mark;
+    BankEntry* part;
+    int* head;
+    int* idx;
+    float* cover;
+};
+CoresetBufs coreset_bufs(char* ws, const CoresetPlan& plan, const _Float16* bank_rows);
+// Contracts 3 - 5 of dinov2_hip_coreset on the normalised rows b.x16 [>= n rounded up to 16 rows, hpad] (rows >= n are never looked at):
+// once the stream has run what this enqueues, idx / cover [m], head[1] = selected, nearest / sim [n] hold the results on the device.
+// Enqueues one init launch and one sweep per pick, and waits for the stream only every CORESET_POLL picks, to read the 4-byte stop flag
+// (never when stop_sim is +inf); the picked rows' indices stay on the device.
+hipError_t coreset_run(const CoresetBufs& b, int n, int m, int first, float stop_sim, const CoresetPlan& plan, hipStream_t stream);
 
 // VLAD descriptors of row segments (csrc/vlad.hip; contract in include/dinov2_hip.h, dinov2_hip_vlad).  Every segment has a block of its own
 // in the f16 operand, padded to whole 128-row tiles, so that an assignment tile belongs to one segment and the K-tiles of the cluster sums

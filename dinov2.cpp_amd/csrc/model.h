@@ -129,7 +129,7 @@ enum Scratch : int {
     SCRATCH_RAW,     // raw 8-bit images of DINOV2_HIP_U8_BGR_HWC host inputs
     SCRATCH_PCA,     // dinov2_hip_pca3
     SCRATCH_MATCH,   // dinov2_hip_match_tokens
-    SCRATCH_BANK,    // dinov2_hip_bank_add / dinov2_hip_bank_topk (staged host rows, f16 queries, partials, results)
+    SCRATCH_BANK,    // dinov2_hip_bank_add / _topk / _keep (staged host rows, f16 queries, partials, results; the compaction's stage and indices)
     SCRATCH_DENSE,   // dinov2_hip_predict_dense (the f16 operand and the logits of one pass, host outputs' staging)
     SCRATCH_TAP,     // dinov2_hip_predict_layers with host outputs: where the tap kernel writes before the copy-out
     SCRATCH_ATTN,    // dinov2_hip_predict_attention with a host output: where attn_rows_kernel writes before the copy-out
@@ -141,6 +141,7 @@ enum Scratch : int {
     SCRATCH_VLAD,        // dinov2_hip_vlad_tokens (staged host rows, the f16 operands, the tables, one pass's partials, the results)
     SCRATCH_PROPAGATE,   // dinov2_hip_propmem_set / dinov2_hip_propagate (staged host rows and labels, the f16 queries, the partial lists, the results)
     SCRATCH_NCUT,        // dinov2_hip_ncut_tokens (staged host rows, the f16 operand, the block and its partials, degrees)
+    SCRATCH_CORESET,     // dinov2_hip_coreset_tokens (staged host rows, the f16 operand, s / nearest / marks, the partials, the results)
     SCRATCH_COUNT
 };
 

@@ -1238,6 +1238,65 @@ extern "C" int dinov2_hip_op_kmeans_bench(const float* rows_dev, int32_t n, int3
     return rc;
 }
 
+// ---- dinov2_hip_coreset_tokens' kernels (csrc/coreset.hip) on host data ----
+namespace {
+bool coreset_args_ok(int n, int H, int m, int first, float stop_sim, int rows_per_wg) {
+    return n >= 1 && n <= CORESET_N_MAX && H >= 8 && H <= 4096 && m >= 1 && m <= n && first >= 0 && first < n && stop_sim == stop_sim &&
+           rows_per_wg >= 0;
+}
+}  // namespace
+
+extern "C" int dinov2_hip_op_coreset_plan(int32_t n, int32_t H, int32_t m, int32_t rows_per_wg, int64_t* out) {
+    if (!out || !coreset_args_ok(n, H, m, 0, 0.0f, rows_per_wg)) return DINOV2_HIP_ERR_INVALID;
+    const CoresetPlan p = coreset_plan(n, H, m, rows_per_wg);
+    const int64_t v[5] = {p.npad, p.hpad, p.rows_per_wg, p.nparts, (int64_t)p.bytes};
+    std::copy(v, v + 5, out);
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_coreset(const float* rows, int32_t n, int32_t H, int32_t m, int32_t first, float stop_sim, int32_t rows_per_wg,
+                                     int32_t* idx, float* cover, int32_t* selected, int32_t* nearest, float* near_sim) {
+    if (!rows || !coreset_args_ok(n, H, m, first, stop_sim, rows_per_wg)) return DINOV2_HIP_ERR_INVALID;
+    const CoresetPlan plan = coreset_plan(n, H, m, rows_per_wg);
+    OpBuf dX, dW;
+    OP_TRY(dX.upload(rows, (size_t)n * H * 4));
+    OP_TRY(dW.alloc(plan.bytes, 1, OpBuf::nans()));
+    const CoresetBufs b = coreset_bufs(dW.as<char>(), plan, nullptr);
+    OP_TRY(launch_match_normalise(dX.as<float>(), (size_t)H, dW.as<_Float16>() + plan.x16 / 2, n, plan.npad, H, plan.hpad, nullptr));
+    OP_TRY(coreset_run(b, n, m, first, stop_sim, plan, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    if (idx) OP_TRY(dW.read(idx, plan.idx, (size_t)m * 4));
+    if (cover) OP_TRY(dW.read(cover, plan.cover, (size_t)m * 4));
+    if (selected) OP_TRY(dW.read(selected, plan.head + 4, 4));
+    if (nearest) OP_TRY(dW.read(nearest, plan.nearest, (size_t)n * 4));
+    if (near_sim) OP_TRY(dW.read(near_sim, plan.sim, (size_t)n * 4));
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_coreset_bench(const float* rows_dev, int32_t n, int32_t H, int32_t m, int32_t rows_per_wg, int32_t warmup,
+                                           int32_t iters, float* us_per_pick) {
+    if (!rows_dev || !us_per_pick || !coreset_args_ok(n, H, m, 0, INFINITY, rows_per_wg) || warmup < 0 || iters < 1) return DINOV2_HIP_ERR_INVALID;
+    const CoresetPlan plan = coreset_plan(n, H, m, rows_per_wg);
+    OpBuf dW;
+    EventPair ev;
+    OP_TRY(dW.alloc(plan.bytes, 1, OpBuf::none()));
+    OP_TRY(ev.create());
+    const CoresetBufs b = coreset_bufs(dW.as<char>(), plan, nullptr);
+    OP_TRY(launch_match_normalise(rows_dev, (size_t)H, dW.as<_Float16>() + plan.x16 / 2, n, plan.npad, H, plan.hpad, nullptr));
+    float total = 0.0f;
+    for (int i = 0; i < warmup + iters; ++i) {
+        float t = 0.0f;
+        OP_TRY(hipEventRecord(ev.e0, nullptr));
+        OP_TRY(coreset_run(b, n, m, 0, INFINITY, plan, nullptr));
+        OP_TRY(hipEventRecord(ev.e1, nullptr));
+        OP_TRY(hipEventSynchronize(ev.e1));
+        OP_TRY(hipEventElapsedTime(&t, ev.e0, ev.e1));
+        if (i >= warmup) total += t;
+    }
+    *us_per_pick = total * 1000.0f / ((float)iters * (float)m);
+    return 0;
+}
+
 // ---- dinov2_hip_ncut_tokens' kernels (csrc/ncut.hip) and its loop (csrc/ncut.cpp) on host data ----
 namespace {
 bool ncut_shape_ok(int n, int H) { return n >= NCUT_N_MIN && n <= NCUT_N_MAX && H >= 8 && H <= 4096; }

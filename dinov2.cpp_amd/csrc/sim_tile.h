@@ -1,12 +1,16 @@
 // sim_tile.h -- the 128 x 128 tile of A . B^T on the matrix cores that match_kernel (match.hip), bank_topk_kernel (bank.hip),
-// kmeans_assign_kernel and kmeans_update_kernel (kmeans.hip) share, and the total order of "best" that their results are chosen by.
+// kmeans_assign_kernel and kmeans_update_kernel (kmeans.hip) share, its one-column form for coreset_sweep_kernel (coreset.hip), and the
+// total order of "best" that their results are chosen by.
 //
 // The contract: the similarity of a pair is one chain of hpad / 32 v_mfma_f32_16x16x32_f16 k steps in ascending order from a zero
 // accumulator.  It depends on hpad alone -- not on the tile the pair falls in, nor on the kernel or the pass that computes it -- so a pair
-// has the same bits in match, bank top-k and k-means (tests/test_gpu_bank.py::test_top1_is_match, tests/test_gpu_kmeans.py::
-// test_assign_is_match_bit_for_bit_and_inside_its_tolerance).  It holds because the staging, the LDS image and the K loop exist here only.
+// has the same bits in match, bank top-k, k-means and the coreset sweep (tests/test_gpu_bank.py::test_top1_is_match,
+// tests/test_gpu_kmeans.py::test_assign_is_match_bit_for_bit_and_inside_its_tolerance, tests/test_gpu_coreset.py::test_one_pick_is_match).
+// It holds because the staging, the LDS image and the K loops exist here only: the tile's (sim_tile) and the one column's (sim_column),
+// which issues the same instruction with the same operand roles over the same k steps.
 // "Best" is one strict total order -- the larger f32 value first (-0 == +0), among equal values the lower index -- so a result does not
-// depend on which lane, wave, tile, chunk or pass met a candidate first.
+// depend on which lane, wave, tile, chunk or pass met a candidate first.  "Farthest" (the coreset's next pick) is the same order with the
+// values reversed: the smaller value first, among equal values still the lower index.
 #pragma once
 #include <climits>
 
@@ -32,8 +36,18 @@ __device__ __forceinline__ void fold_lane(Best& b) {
     const int i = __shfl_xor(b.i, OFF);
     fold(b, v, i);
 }
+// "farthest": (v, i) comes before b when its value is smaller, among equal values when its index is lower; an empty slot is (+inf, INT_MAX)
+__device__ __forceinline__ void fold_far(Best& b, float v, int i) {
+    if (v < b.v || (v == b.v && i < b.i)) b = Best{v, i};
+}
+template <int OFF>
+__device__ __forceinline__ void fold_far_lane(Best& b) {
+    const float v = __shfl_xor(b.v, OFF);
+    const int i = __shfl_xor(b.i, OFF);
+    fold_far(b, v, i);
+}
 
-// ---- the tile --------------------------------------------------------------------------------------------------------------------------
+// ---- the tile--------------------------------------------------------------------------------------------------------------------------
 // 256 threads = four waves, 2 x 2, each 64 x 64 = 4 x 4 accumulator blocks of 16 x 16.  LDS image of an operand as in gemm.hip: [row][64 k]
 // f16, 128-byte rows, 16-byte chunk c of row r at chunk c ^ ((r >> 1) & 7), which spreads every 16-lane ds_read_b128 group over 16 bank
 // slots.  The caller declares the two images (bank_topk_kernel reuses them as its queue); nothing here owns shared memory.
@@ -177,6 +191,37 @@ __device__ __forceinline__ Best sim_best_of_rows(const SimPlace& p, char* sA, ch
     for (int i = 0; i < 4; ++i) sim_row_share(p, i, best[i], red_v, red_i);
     __syncthreads();
     return p.tid < SIM_TILE ? sim_fold_waves(red_v, red_i, p.tid) : Best{-INFINITY, INT_MAX};
+}
+
+// ---- one column: 16 rows of A against ONE row of B (coreset_sweep_kernel) ----------------------------------------------------------------
+// The chain of sim_tile for a single column: per k step the same MFMA with the same operand roles (the B fragment first), from a zero
+// accumulator, k steps ascending -- so the value has the bits the tile gives the pair.  The B row is the only real row of its 16-row
+// fragment: lanes fr != 0 hand in zeros, lane fr == 0 reads it from sCol, a plain hpad f16 image of the row in LDS.  The A rows are
+// streamed from global memory (each element is used once: no LDS image): `a` = this lane's row (row0 + fr of a row-major [.., hpad]
+// operand) at column 8 fh.  One wave, all 64 lanes; nks = hpad / 32 (even).  Afterwards lane fr of the lanes fh == 0 holds sim(row0 + fr,
+// the column); the other lanes' values mean nothing.
+// U k steps from step ks on: the U loads of A are requested together, then the MFMAs follow in ascending order
+template <int U>
+__device__ __forceinline__ void sim_column_k(const _Float16* a, const char* sCol, int fr, int fh, int ks, f32x4& acc) {
+    using E = Elem<_Float16>;
+    const f16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    f16x8 af[U], bf[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) af[u] = *(const f16x8*)(a + (size_t)(ks + u) * 32);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const f16x8 c = *(const f16x8*)(sCol + (((ks + u) * 4 + fh) << 4));
+        bf[u] = fr == 0 ? c : zero;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc = E::mfma16(bf[u], af[u], acc);
+}
+__device__ __forceinline__ float sim_column(const _Float16* a, const char* sCol, int fr, int fh, int nks) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    int ks = 0;
+    for (; ks + 8 <= nks; ks += 8) sim_column_k<8>(a, sCol, fr, fh, ks, acc);  // eight 16-byte loads a lane in flight
+    for (; ks < nks; ks += 2) sim_column_k<2>(a, sCol, fr, fh, ks, acc);        // a K-tile of 64, as sim_tile_k
+    return acc[0];
 }
 
 }  // namespace dinov2

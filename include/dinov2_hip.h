@@ -472,7 +472,8 @@ int dinov2_hip_match_tokens(dinov2_hip_session *session, const dinov2_hip_match 
  *        for (j = 0; j < k && idx[i * k + j] >= 0; ++j)
  *            votes[label[idx[i * k + j]]] += expf(sim[i * k + j] / 0.07f);
  *        predicted[i] = argmax(votes);
- *    -- removal of single rows, bf16 operands, the device group, device-side outputs, k > 64.
+ *    -- removal of rows other than by keeping an ascending subset (dinov2_hip_bank_keep below; dinov2_hip_coreset_tokens chooses one), bf16
+ *    operands, the device group, device-side outputs, k > 64.
  *    Times: profiles/bank_topk.md. */
 typedef struct dinov2_hip_bank dinov2_hip_bank;
 
@@ -516,6 +517,13 @@ typedef struct dinov2_hip_topk {
  * in passes of at most 4 096 and the bank in at most as many chunks that the partial lists of one pass stay within 32 MiB whatever nq,
  * count and k.  An allocation the device refuses returns DINOV2_HIP_ERR_HIP. */
 int  dinov2_hip_bank_topk(dinov2_hip_session *s, const dinov2_hip_bank *bank, const dinov2_hip_topk *q, char *err, size_t errlen);
+/* Compacts the bank to rows idx[0 .. m) in that order: idx (HOST) strictly ascending, each in [0, count), 1 <= m <= count.  New row j is old
+ * row idx[j], bit for bit; count = m; the memory past row m is left as it is (it is masked).  In place on the device, in ascending chunks of
+ * destination rows staged through at most 32 MiB of the session's bank scratch (idx[j] >= j, so no chunk overwrites a later chunk's
+ * sources); returns after the stream has finished.  Hence dinov2_hip_bank_topk afterwards equals, bit for bit, the search of a fresh bank
+ * to which the kept rows were added in that order.  Argument errors (NULLs; m out of range; an index out of range or not above the one
+ * before it; a session of another device) return DINOV2_HIP_ERR_INVALID and change nothing. */
+int  dinov2_hip_bank_keep(dinov2_hip_session *s, dinov2_hip_bank *bank, const int32_t *idx, int32_t m, char *err, size_t errlen);
 
 /* -- spherical k-means of token rows (no reference counterpart: k-means over the patch tokens of one image for unsupervised part or object
  *    segments, over the patches of a whole batch for co-segmentation, and a fixed vocabulary of centres applied to new frames -- visual
@@ -543,7 +551,8 @@ int  dinov2_hip_bank_topk(dinov2_hip_session *s, const dinov2_hip_bank *bank, co
  *       t = 1).  changed == 0: stop, converged, iterations = t - 1.  Otherwise update, giving c^t.  After max_iter updates one more
  *       assignment runs against c^max_iter (converged if it changes nothing).  The returned labels, sim and counts are always the assignment
  *       against the returned centers.  The host reads one 4-byte `changed` per iteration.
- *    Out of scope: Euclidean k-means; k-means++ or maximin seeding (the Python Session.kmeans offers a seeded sample of rows through
+ *    Out of scope: Euclidean k-means; k-means++ seeding (the Python Session.kmeans offers a seeded sample of rows through
+ *    DINOV2_HIP_KMEANS_INIT_ROWS, and maximin seeding as init="maximin": the K picks of dinov2_hip_coreset_tokens below, handed over as
  *    DINOV2_HIP_KMEANS_INIT_ROWS); re-seeding empty clusters; K > 1024; bf16 operands; the device group; device-side outputs; the rows of a
  *    list forward; dinov2_compat.hpp and the example programs.
  *    Times: profiles/kmeans.md. */
@@ -572,6 +581,60 @@ typedef struct dinov2_hip_kmeans {
  * most 32 MiB of partial sums, the results) is a session-owned buffer grown on demand; an allocation the device refuses returns
  * DINOV2_HIP_ERR_HIP.  The session's last forward stays what it was. */
 int dinov2_hip_kmeans_tokens(dinov2_hip_session *s, const dinov2_hip_kmeans *km, char *err, size_t errlen);
+
+/* -- greedy k-center selection of rows (no reference counterpart: thinning a memory bank of nominal patch tokens to the 1 - 10 % that cover
+ *    the rest -- the coreset step of memory-bank anomaly detection, PatchCore and AnomalyDINO, whose other steps are dinov2_hip_predict,
+ *    dinov2_hip_bank_add from resident patches and dinov2_hip_bank_topk with k = 1 --, and maximin seeding of dinov2_hip_kmeans_tokens).
+ *    Farthest-point selection by cosine similarity: the next pick is the row least similar to everything picked so far.  The rows are a
+ *    caller's matrix, resident tokens of the session's last un-split forward, or the rows of a bank where they lie; only [m] picks and, if
+ *    asked for, [n] assignments cross PCIe.  On the device (csrc/coreset.hip): one launch per pick sweeps the n x hpad f16 rows once --
+ *    every row's similarity to the picked row against its best so far, and each workgroup's unselected rows folded to one (smallest value,
+ *    lowest index) partial; every workgroup of the next launch folds the partials to the next pick itself, so the picked row's index never
+ *    travels to the host between picks.  Stream order between the launches is the only synchronisation: no grid-wide barrier, no
+ *    cooperative launch, no workgroup waits for another.
+ *    Contract:
+ *    1. Operands.  Contract 1 of dinov2_hip_match, the same kernel: f16 unit rows, a zero row stays zero.  A bank's rows are used as they
+ *       are (they went through that kernel when they were added).  Inputs must be finite.
+ *    2. Similarity.  sim(i, c) is contract 2 of dinov2_hip_match: one chain of hpad / 32 16x16x32 f16 MFMA k-steps, ascending, from a zero
+ *       accumulator, the same operand roles (csrc/sim_tile.h) -- the bits it has in match, bank top-k and k-means.  A row's values do not
+ *       depend on the rows that travel with it, and selecting from a bank equals selecting from the rows that were added to it.
+ *    3. Greedy rule.  idx[0] = first, cover[0] = -INFINITY.  After picks 0 .. t - 1, s(i) is the largest sim(i, idx[u]) over u < t and
+ *       nearest(i) the LOWEST such u among equal values; -0 is read as +0.  A row's own pick takes part like any other pick.  Pick t is the
+ *       not-yet-selected row with the SMALLEST s, among equal values the LOWEST row index, and cover[t] is that s (before pick t changes
+ *       it).  cover[1 ..] is therefore non-decreasing: s never falls and the rows to choose from only get fewer.  A selected row is never
+ *       selected again, whatever its s (a zero row has s = 0 to itself).  Rows >= n never take part.
+ *    4. Stop.  If before pick t >= 1 the smallest s is >= stop_sim, selection ends with selected = t; slots t .. m - 1 then hold idx = -1
+ *       and cover = +INFINITY.  nearest / near_sim are always against exactly the `selected` picks, the last one included.
+ *    5. Determinism.  The result depends on the rows, first, m and stop_sim alone -- not on launch geometry, on how the rows are split over
+ *       workgroups (a pure planner fixes that from (n, H)), or on how often the host looks at the stop flag (a 4-byte read every 256 picks,
+ *       none with stop_sim = +INFINITY; a launch that finds the flag set returns at once).  No atomics.
+ *    Out of scope: Euclidean distance; the random-projection speed-up of PatchCore (a caller passes projected rows: H >= 8 is accepted); a
+ *    choice of `first` by the library; warm starts from an existing selection; bf16 operands; the device group; device-side outputs; the
+ *    rows of a list forward; dinov2_compat.hpp and the example programs.
+ *    Times: profiles/coreset.md. */
+typedef struct dinov2_hip_coreset {
+    dinov2_hip_rows rows;         /* GIVEN (host / device), LAST_CLS, LAST_PATCHES of `rows.image`; 1 <= n <= 1 048 576, 8 <= H <= 4096 */
+    int32_t all_images;           /* as in dinov2_hip_kmeans */
+    const dinov2_hip_bank *bank;  /* non-NULL: the rows are rows [0, count) of this bank, already normalised; `rows` and `all_images` are not
+                                     read; n = count (up to 2^24), H = the bank's */
+    int32_t m;                    /* rows to select, 1 .. n */
+    int32_t first;                /* the first pick, in [0, n) */
+    float   stop_sim;             /* stop once every unselected row has a selected row at least this similar; +INFINITY = never; NaN refused */
+    int32_t *idx;                 /* [m] HOST: picks in selection order; -1 past `selected`.  Any output may be NULL, not all */
+    float   *cover;               /* [m] see contract 3 */
+    int32_t *selected;            /* picks made, 1 .. m */
+    int32_t *nearest;             /* [n] position in 0 .. selected - 1 of the most similar pick */
+    float   *near_sim;            /* [n] that similarity */
+    int32_t reserved[4];
+} dinov2_hip_coreset;
+/* Synchronous: returns after the copy-out, like dinov2_hip_kmeans_tokens.  Argument errors (NULL session or request; n or H out of range;
+ * m > n or m < 1; first outside [0, n); a NaN stop_sim; all outputs NULL; all_images with a source other than LAST_PATCHES or an n that is
+ * not last_b * P; the resident-source errors of dinov2_hip_bank_add; an empty bank; a bank or session of another device; a misaligned
+ * device pointer) return DINOV2_HIP_ERR_INVALID before anything is launched, allocated or copied, with the outputs untouched.  The scratch
+ * (host rows' staging copy, the f16 rows unless they are a bank's, 9 bytes of state per row, 16 KiB of partials, the results) is a
+ * session-owned buffer grown on demand; an allocation the device refuses returns DINOV2_HIP_ERR_HIP.  The session's last forward stays
+ * what it was, and a bank is only read. */
+int dinov2_hip_coreset_tokens(dinov2_hip_session *s, const dinov2_hip_coreset *c, char *err, size_t errlen);
 
 /* -- VLAD descriptors of row segments (no reference counterpart: one vector per image for place recognition and image retrieval from
  *    frozen patch tokens -- every token is assigned to the nearest centre of a k-means vocabulary, the residuals are summed per centre,

@@ -288,6 +288,21 @@ int dinov2_hip_op_kmeans(const float *rows, int32_t n, int32_t K, int32_t H, int
 int dinov2_hip_op_kmeans_bench(const float *rows_dev, int32_t n, int32_t K, int32_t H, int32_t nsplit, int32_t max_iter, int32_t warmup,
                                int32_t iters, float *ms);
 
+/* the kernels behind dinov2_hip_coreset_tokens (csrc/coreset.hip) and the shared normaliser, without a model or session; cases and the numpy
+ * restatement of the greedy rule: tests/coreset_cases.py.  1 <= n <= 2^20, 8 <= H <= 4096, 1 <= m <= n, 0 <= first < n, stop_sim not NaN,
+ * rows_per_wg >= 0, else DINOV2_HIP_ERR_INVALID.
+ * coreset:       host rows [n, H] -> idx [m], cover [m], *selected, nearest [n], near_sim [n] (any may be NULL).  rows_per_wg: rows per
+ *                workgroup, 0 = the planner's choice (a value is rounded up to whole 128-row tiles and raised where n needs it).  The
+ *                workspace is filled with 0xff bytes first, so anything the kernels read without having written it shows up as NaN / -1.
+ * coreset_plan (no device): out[0 .. 4] = npad, hpad, rows per workgroup, partials (= workgroups), bytes of the workspace for m picks.
+ * coreset_bench (tools/coreset_bench.py): DEVICE f32 rows_dev [n, H], first = 0, never stops: *us_per_pick = the time of `m` sweep
+ *                launches in a row divided by m, the mean of `iters` timed chains after `warmup`, by HIP events on the null stream. */
+int dinov2_hip_op_coreset(const float *rows, int32_t n, int32_t H, int32_t m, int32_t first, float stop_sim, int32_t rows_per_wg, int32_t *idx,
+                          float *cover, int32_t *selected, int32_t *nearest, float *near_sim);
+int dinov2_hip_op_coreset_plan(int32_t n, int32_t H, int32_t m, int32_t rows_per_wg, int64_t *out);
+int dinov2_hip_op_coreset_bench(const float *rows_dev, int32_t n, int32_t H, int32_t m, int32_t rows_per_wg, int32_t warmup, int32_t iters,
+                                float *us_per_pick);
+
 /* the kernels behind dinov2_hip_ncut_tokens (csrc/ncut.hip), its loop (csrc/ncut.cpp) and the shared normaliser, without a model or session;
  * cases, the numpy restatement and the bounds: tests/ncut_cases.py.  16 <= n <= 131 072, 8 <= H <= 4096, affinity, tau and floor as in
  * dinov2_hip_ncut, else DINOV2_HIP_ERR_INVALID.  Every device buffer starts as 0xff bytes; the partials, both blocks, the 8 x 8 partials,
