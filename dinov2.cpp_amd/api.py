@@ -127,6 +127,13 @@ class Coreset(C.Structure):
                 ("near_sim", C.c_void_p), ("reserved", C.c_int32 * 4)]
 
 
+class Rerank(C.Structure):
+    """dinov2_hip_rerank (include/dinov2_hip.h)."""
+    _fields_ = [("queries", Rows), ("n_seg", C.c_int32), ("first", C.c_void_p), ("len", C.c_void_p), ("min_sim", C.c_float),
+                ("score_q", C.c_void_p), ("score_b", C.c_void_p), ("mutual", C.c_void_p), ("mutual_sim", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
 class Vlad(C.Structure):
     """dinov2_hip_vlad (include/dinov2_hip.h)."""
     _fields_ = [("rows", Rows), ("all_images", C.c_int32), ("offsets", C.c_void_p), ("n_seg", C.c_int32), ("K", C.c_int32),
@@ -573,6 +580,45 @@ def op_coreset(rows, m, first=0, stop_sim=None, rows_per_wg=0):
     return out
 
 
+RERANK_PLAN_FIELDS = ("nq_pad", "hpad", "qtiles", "npass", "max_segs", "partial_bytes", "bytes")
+
+
+def _segments(segments):
+    """A sequence of (first, len) as the two int32 arrays of dinov2_hip_rerank."""
+    seg = np.asarray(segments, np.int64).reshape(-1, 2)
+    return np.ascontiguousarray(seg[:, 0], np.int32), np.ascontiguousarray(seg[:, 1], np.int32)
+
+
+def _rerank_out(n_seg):
+    return {"score_q": np.full(n_seg, np.nan, np.float32), "score_b": np.full(n_seg, np.nan, np.float32),
+            "mutual": np.full(n_seg, -7, np.int32), "mutual_sim": np.full(n_seg, np.nan, np.float32)}
+
+
+def op_rerank_plan(nq, H, lens, pass_bytes=0):
+    """rerank_plan (csrc/kernels.h) as a dict, with pass_of [n_seg] = the pass of every segment; no device needed."""
+    ln = np.ascontiguousarray(lens, np.int32)
+    buf, pass_of = (C.c_int64 * len(RERANK_PLAN_FIELDS))(), np.full(len(ln), -1, np.int32)
+    if lib().dinov2_hip_op_rerank_plan(int(nq), int(H), _ptr(ln), len(ln), int(pass_bytes), buf, _ptr(pass_of)) != 0:
+        raise ValueError(f"rerank refuses nq={nq} H={H} n_seg={len(ln)} pass_bytes={pass_bytes}")
+    return dict(zip(RERANK_PLAN_FIELDS, [int(v) for v in buf]), pass_of=pass_of)
+
+
+def op_bank_rerank(q, b, segments, min_sim=None, pass_bytes=0):
+    """The kernels of csrc/rerank.hip alone (dinov2_hip_op_bank_rerank): q [nq, H] against the segments (first, len) of the bank built from
+    b [nb, H] -> the dict of Bank.rerank.  pass_bytes: the bound of one pass's column partials, 0 = the planner's.  No model, no session."""
+    q, b = _f32(q), _f32(b)
+    assert q.ndim == 2 and b.ndim == 2 and q.shape[1] == b.shape[1], (q.shape, b.shape)
+    first, ln = _segments(segments)
+    out = _rerank_out(len(ln))
+    rc = lib().dinov2_hip_op_bank_rerank(_ptr(q), q.shape[0], _ptr(b), b.shape[0], q.shape[1], _ptr(first), _ptr(ln), len(ln),
+                                         float(-np.inf if min_sim is None else min_sim), int(pass_bytes), _ptr(out["score_q"]),
+                                         _ptr(out["score_b"]), _ptr(out["mutual"]), _ptr(out["mutual_sim"]))
+    if rc == 4:
+        raise ValueError(f"rerank refuses nq={q.shape[0]} nb={b.shape[0]} H={q.shape[1]} n_seg={len(ln)} min_sim={min_sim} pass_bytes={pass_bytes}")
+    _op_rc(rc, "bank_rerank")
+    return out
+
+
 VLAD_PLAN_FIELDS = ("kpad", "hpad", "hpad128", "chunk", "cap", "npad", "ntiles", "nchunks", "npass", "partial_bytes", "bytes")
 
 
@@ -1000,6 +1046,10 @@ def lib():
     L.dinov2_hip_op_coreset.argtypes = [fp, i32, i32, i32, i32, C.c_float, i32, ip, fp, ip, ip, fp]
     L.dinov2_hip_op_coreset_plan.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int64)]
     L.dinov2_hip_op_coreset_bench.argtypes = [vp, i32, i32, i32, i32, i32, i32, fp]
+    L.dinov2_hip_bank_rerank.argtypes = [vp, vp, C.POINTER(Rerank), cp, sz]
+    L.dinov2_hip_op_bank_rerank.argtypes = [fp, i32, fp, i32, i32, ip, ip, i32, C.c_float, C.c_int64, fp, fp, ip, fp]
+    L.dinov2_hip_op_rerank_plan.argtypes = [i32, i32, ip, i32, C.c_int64, C.POINTER(C.c_int64), ip]
+    L.dinov2_hip_op_rerank_bench.argtypes = [vp, i32, vp, i32, i32, ip, ip, i32, i32, i32, fp]
     dp, f32 = C.POINTER(C.c_double), C.c_float
     L.dinov2_hip_ncut_tokens.argtypes = [vp, C.POINTER(NCut), cp, sz]
     L.dinov2_hip_op_ncut_plan.argtypes = [i32, i32, i32, C.POINTER(C.c_int64)]
@@ -1456,6 +1506,20 @@ class Bank(_Handle):
         out = {"idx": np.empty((nq, int(k)), np.int32), "sim": np.empty((nq, int(k)), np.float32)}
         t = TopK(r, int(k), out["idx"].ctypes.data, out["sim"].ctypes.data)
         _call(lib().dinov2_hip_bank_topk, sess._h, self._h, C.byref(t))
+        return out
+
+    def rerank(self, sess: "Session", queries=None, segments=(), min_sim: float | None = None, *, source=None, image: int = 0,
+               n: int | None = None) -> dict:
+        """Scores row ranges of the bank against one query set (dinov2_hip_bank_rerank).  segments: a sequence of (first, len) -- what add()
+        returned and the rows it was given.  Dict of score_q, score_b (the sums of the per-row maxima in either direction), mutual (the number
+        of mutual nearest-neighbour pairs with similarity >= min_sim; None = all) and mutual_sim (their summed similarity), [n_seg] each.
+        queries as the rows of add()."""
+        r, keep = self._rows(sess, queries, source, image, n)
+        first, ln = _segments(segments)
+        out = _rerank_out(len(ln))
+        t = Rerank(r, len(ln), first.ctypes.data, ln.ctypes.data, float(-np.inf if min_sim is None else min_sim), out["score_q"].ctypes.data,
+                   out["score_b"].ctypes.data, out["mutual"].ctypes.data, out["mutual_sim"].ctypes.data)
+        _call(lib().dinov2_hip_bank_rerank, sess._h, self._h, C.byref(t))
         return out
 
     def keep(self, sess: "Session", idx) -> np.ndarray:

@@ -723,6 +723,101 @@ CoresetBufs coreset_bufs(char* ws, const CoresetPlan& plan, const _Float16* bank
 // (never when stop_sim is +inf); the picked rows' indices stay on the device.
 hipError_t coreset_run(const CoresetBufs& b, int n, int m, int first, float stop_sim, const CoresetPlan& plan, hipStream_t stream);
 
+// Re-ranking of row ranges of a bank against one query set (csrc/rerank.hip; contract in include/dinov2_hip.h, dinov2_hip_rerank).
+// Segment s is rows [first, first + len) of the bank.  rerank_tile_kernel runs one workgroup per ITEM (segment, 128-row query tile): it walks
+// the segment's 128-column tiles in ascending order, keeps the best column of each of its query rows in registers over the walk and leaves
+// one (best value, lowest query row) partial per (item, column); rerank_fold_kernel, one workgroup per segment, folds those over the query
+// tiles and forms the four scalars.  The list is cut into passes of whole segments whose column partials (query tiles x len rounded up to
+// 128 x 8 bytes per segment; one segment takes at most 16 MiB) stay within RERANK_PARTIAL_MAX; a pass's row partials are never larger.
+constexpr int RERANK_N_MAX = 1 << 14, RERANK_LEN_MAX = 1 << 14, RERANK_SEG_MAX = 1 << 16;
+constexpr size_t RERANK_PARTIAL_MAX = (size_t)32 << 20;
+static_assert(RERANK_N_MAX <= 1 << 16, "rerank_fold_kernel keeps a query row's index in 16 bits");
+struct RerankItem {  // one workgroup of rerank_tile_kernel: query rows [128 qt, 128 qt + 128) against segment `seg` of the list
+    int32_t seg, qt;
+};
+struct RerankSeg {  // one segment: its rows of the bank, and where its column partials [query tiles][lpad] start in the pass's arrays
+    int32_t first, len;
+    int64_t pcol;
+};
+struct RerankPass {  // segments [seg0, seg0 + nseg) of the list = items [item0, item0 + nseg * query tiles) of the table
+    int32_t seg0, nseg;
+    int64_t item0;
+    int64_t partials;  // (value, index) column partials of the pass
+};
+struct RerankTables {  // what the host uploads: all segments once, the items pass by pass
+    std::vector<RerankPass> passes;
+    std::vector<RerankSeg> segs;
+    std::vector<RerankItem> items;
+};
+struct RerankPlan {
+    int nq_pad, hpad, qtiles;      // queries to whole tiles, H to a multiple of 64, query tiles
+    int npass, max_segs;           // passes; the most segments of one pass
+    int64_t max_partials;          // the most column partials of one pass
+    size_t q16;                    // normalised queries [nq_pad, hpad] f16
+    size_t pcol_v, pcol_i;         // f32 / int32 [max_partials]
+    size_t prow_v, prow_i;         // f32 / int32 [max_segs][nq_pad]: the best column of every query row within each segment of the pass
+    size_t segs, items;            // RerankSeg [n_seg], RerankItem [max_segs * qtiles]
+    size_t score_q, score_b, mutual, mutual_sim;  // the results [n_seg]
+    size_t bytes;
+};
+inline int rerank_lpad(int len) { return (len + MATCH_TN - 1) / MATCH_TN * MATCH_TN; }
+// Pure: (n, H, the lengths, pass_bytes) alone.  A pass takes segments in list order while its column partials stay within pass_bytes
+// (0, or more than RERANK_PARTIAL_MAX: RERANK_PARTIAL_MAX); a segment that alone is larger than a small pass_bytes is a pass of its own.
+// No result depends on the cut.  `first` is only copied into the tables; tables = NULL (then first may be NULL too): sizes only.
+inline RerankPlan rerank_plan(int n, int H, int n_seg, const int32_t* first, const int32_t* len, size_t pass_bytes, RerankTables* tables) {
+    RerankPlan p{};
+    p.nq_pad = (n + MATCH_TM - 1) / MATCH_TM * MATCH_TM;
+    p.hpad = (H + 63) / 64 * 64;
+    p.qtiles = p.nq_pad / MATCH_TM;
+    const int64_t bound = (int64_t)(pass_bytes == 0 || pass_bytes > RERANK_PARTIAL_MAX ? RERANK_PARTIAL_MAX : pass_bytes) / 8;
+    if (tables) {
+        tables->passes.clear();
+        tables->segs.resize((size_t)n_seg);
+        tables->items.resize((size_t)n_seg * p.qtiles);
+    }
+    RerankPass cur{0, 0, 0, 0};
+    auto close = [&]() {
+        if (tables) tables->passes.push_back(cur);
+        ++p.npass;
+        if (cur.nseg > p.max_segs) p.max_segs = cur.nseg;
+        if (cur.partials > p.max_partials) p.max_partials = cur.partials;
+    };
+    for (int s = 0; s < n_seg; ++s) {
+        const int64_t mine = (int64_t)p.qtiles * rerank_lpad(len[s]);
+        if (cur.nseg > 0 && cur.partials + mine > bound) {
+            close();
+            cur = RerankPass{s, 0, (int64_t)s * p.qtiles, 0};
+        }
+        if (tables) {
+            tables->segs[(size_t)s] = RerankSeg{first[s], len[s], cur.partials};
+            for (int qt = 0; qt < p.qtiles; ++qt) tables->items[(size_t)s * p.qtiles + qt] = RerankItem{s, qt};
+        }
+        ++cur.nseg;
+        cur.partials += mine;
+    }
+    close();
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t off = need; need += (bytes + 255) / 256 * 256; return off; };
+    p.q16 = take((size_t)p.nq_pad * p.hpad * 2);
+    p.pcol_v = take((size_t)p.max_partials * 4);
+    p.pcol_i = take((size_t)p.max_partials * 4);
+    p.prow_v = take((size_t)p.max_segs * p.nq_pad * 4);
+    p.prow_i = take((size_t)p.max_segs * p.nq_pad * 4);
+    p.segs = take((size_t)n_seg * sizeof(RerankSeg));
+    p.items = take((size_t)p.max_segs * p.qtiles * sizeof(RerankItem));
+    p.score_q = take((size_t)n_seg * 4);
+    p.score_b = take((size_t)n_seg * 4);
+    p.mutual = take((size_t)n_seg * 4);
+    p.mutual_sim = take((size_t)n_seg * 4);
+    p.bytes = need;
+    return p;
+}
+// q [n, H]: DEVICE f32 rows with row stride ldq (floats); bank: normalised f16 rows of hpad elements, of which rows 0 .. last_row are
+// allocated (no row past last_row is read); tables: rerank_plan's for this list, unchanged until the stream has run what this enqueues
+// (the uploads read them); ws: DEVICE workspace of plan.bytes.  Afterwards ws + plan.score_q etc. hold [n_seg].  No wait.
+hipError_t launch_rerank(const float* q, size_t ldq, int n, int H, const _Float16* bank, int last_row, int n_seg, float min_sim, char* ws,
+                         const RerankPlan& plan, const RerankTables& tables, hipStream_t stream);
+
 // VLAD descriptors of row segments (csrc/vlad.hip; contract in include/dinov2_hip.h, dinov2_hip_vlad).  Every segment has a block of its own
 // in the f16 operand, padded to whole 128-row tiles, so that an assignment tile belongs to one segment and the K-tiles of the cluster sums
 // start at the segment's first row: what a segment's sums are made of, and in which order, never depends on its neighbours or its offset.

@@ -1297,6 +1297,86 @@ extern "C" int dinov2_hip_op_coreset_bench(const float* rows_dev, int32_t n, int
     return 0;
 }
 
+// ---- dinov2_hip_bank_rerank's kernels (csrc/rerank.hip) on host data: the bank is built by the shared normaliser and is exactly nb rows
+// ---- long, so a tile that reaches past a segment's end at the bank's end has nothing behind it to read ----
+namespace {
+bool rerank_args_ok(int nq, int H, const int32_t* len, int n_seg, int64_t pass_bytes) {
+    if (nq < 1 || nq > RERANK_N_MAX || H < 8 || H > 4096 || !len || n_seg < 1 || n_seg > RERANK_SEG_MAX || pass_bytes < 0) return false;
+    for (int s = 0; s < n_seg; ++s)
+        if (len[s] < 1 || len[s] > RERANK_LEN_MAX) return false;
+    return true;
+}
+bool rerank_ranges_ok(const int32_t* first, const int32_t* len, int n_seg, int nb) {
+    if (!first || nb < 1 || nb > (1 << 24)) return false;
+    for (int s = 0; s < n_seg; ++s)
+        if (first[s] < 0 || first[s] > nb - len[s]) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" int dinov2_hip_op_rerank_plan(int32_t nq, int32_t H, const int32_t* len, int32_t n_seg, int64_t pass_bytes, int64_t* out,
+                                         int32_t* pass_of) {
+    if (!out || !rerank_args_ok(nq, H, len, n_seg, pass_bytes)) return DINOV2_HIP_ERR_INVALID;
+    RerankTables t;
+    const std::vector<int32_t> first((size_t)n_seg, 0);
+    const RerankPlan p = rerank_plan(nq, H, n_seg, first.data(), len, (size_t)pass_bytes, &t);
+    const int64_t v[7] = {p.nq_pad, p.hpad, p.qtiles, p.npass, p.max_segs, p.max_partials * 8, (int64_t)p.bytes};
+    std::copy(v, v + 7, out);
+    for (size_t i = 0; pass_of && i < t.passes.size(); ++i)
+        for (int s = 0; s < t.passes[i].nseg; ++s) pass_of[t.passes[i].seg0 + s] = (int32_t)i;
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_bank_rerank(const float* q, int32_t nq, const float* b, int32_t nb, int32_t H, const int32_t* first,
+                                         const int32_t* len, int32_t n_seg, float min_sim, int64_t pass_bytes, float* score_q, float* score_b,
+                                         int32_t* mutual, float* mutual_sim) {
+    if (!q || !b || !rerank_args_ok(nq, H, len, n_seg, pass_bytes) || !rerank_ranges_ok(first, len, n_seg, nb) || min_sim != min_sim)
+        return DINOV2_HIP_ERR_INVALID;
+    RerankTables t;
+    const RerankPlan plan = rerank_plan(nq, H, n_seg, first, len, (size_t)pass_bytes, &t);
+    OpBuf dQ, dB, dBank, dW;
+    OP_TRY(dQ.upload(q, (size_t)nq * H * 4));
+    OP_TRY(dB.upload(b, (size_t)nb * H * 4));
+    OP_TRY(dBank.alloc((size_t)nb * plan.hpad, 2, OpBuf::nans()));
+    OP_TRY(dW.alloc(plan.bytes, 1, OpBuf::nans()));
+    OP_TRY(launch_match_normalise(dB.as<float>(), (size_t)H, dBank.as<_Float16>(), nb, nb, H, plan.hpad, nullptr));
+    OP_TRY(launch_rerank(dQ.as<float>(), (size_t)H, nq, H, dBank.as<_Float16>(), nb - 1, n_seg, min_sim, dW.as<char>(), plan, t, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    if (score_q) OP_TRY(dW.read(score_q, plan.score_q, (size_t)n_seg * 4));
+    if (score_b) OP_TRY(dW.read(score_b, plan.score_b, (size_t)n_seg * 4));
+    if (mutual) OP_TRY(dW.read(mutual, plan.mutual, (size_t)n_seg * 4));
+    if (mutual_sim) OP_TRY(dW.read(mutual_sim, plan.mutual_sim, (size_t)n_seg * 4));
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_rerank_bench(const float* q_dev, int32_t nq, const float* b_dev, int32_t nb, int32_t H, const int32_t* first,
+                                          const int32_t* len, int32_t n_seg, int32_t warmup, int32_t iters, float* ms) {
+    if (!q_dev || !b_dev || !ms || !rerank_args_ok(nq, H, len, n_seg, 0) || !rerank_ranges_ok(first, len, n_seg, nb) || warmup < 0 || iters < 1)
+        return DINOV2_HIP_ERR_INVALID;
+    RerankTables t;
+    const RerankPlan plan = rerank_plan(nq, H, n_seg, first, len, 0, &t);
+    OpBuf dBank, dW;
+    EventPair ev;
+    std::vector<float> host((size_t)n_seg * 4);
+    OP_TRY(dBank.alloc((size_t)nb * plan.hpad, 2, OpBuf::none()));
+    OP_TRY(dW.alloc(plan.bytes, 1, OpBuf::none()));
+    OP_TRY(ev.create());
+    OP_TRY(launch_match_normalise(b_dev, (size_t)H, dBank.as<_Float16>(), nb, nb, H, plan.hpad, nullptr));
+    for (int i = 0; i < warmup + iters; ++i) {  // one call as dinov2_hip_bank_rerank makes it: the launches, the four copies out, the wait
+        OP_TRY(hipEventRecord(ev.e0, nullptr));
+        OP_TRY(launch_rerank(q_dev, (size_t)H, nq, H, dBank.as<_Float16>(), nb - 1, n_seg, -INFINITY, dW.as<char>(), plan, t, nullptr));
+        const size_t outs[4] = {plan.score_q, plan.score_b, plan.mutual, plan.mutual_sim};
+        for (int k = 0; k < 4; ++k)
+            OP_TRY(hipMemcpyAsync(host.data() + (size_t)k * n_seg, dW.as<char>() + outs[k], (size_t)n_seg * 4, hipMemcpyDeviceToHost, nullptr));
+        OP_TRY(hipEventRecord(ev.e1, nullptr));
+        OP_TRY(hipEventSynchronize(ev.e1));
+        float tms = 0.0f;
+        OP_TRY(hipEventElapsedTime(&tms, ev.e0, ev.e1));
+        if (i >= warmup) ms[i - warmup] = tms;
+    }
+    return 0;
+}
+
 // ---- dinov2_hip_ncut_tokens' kernels (csrc/ncut.hip) and its loop (csrc/ncut.cpp) on host data ----
 namespace {
 bool ncut_shape_ok(int n, int H) { return n >= NCUT_N_MIN && n <= NCUT_N_MAX && H >= 8 && H <= 4096; }

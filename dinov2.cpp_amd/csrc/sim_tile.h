@@ -1,6 +1,7 @@
 // sim_tile.h -- the 128 x 128 tile of A . B^T on the matrix cores that match_kernel (match.hip), bank_topk_kernel (bank.hip),
 // kmeans_assign_kernel and kmeans_update_kernel (kmeans.hip) share, its one-column form for coreset_sweep_kernel (coreset.hip), and the
-// total order of "best" that their results are chosen by.
+// total order of "best" that their results are chosen by.  rerank_tile_kernel (rerank.hip) walks the tile over row ranges of a bank that
+// start at any row: its B operand is SimRowsClamped, its column direction sim_col_fold / sim_col_share.
 //
 // The contract: the similarity of a pair is one chain of hpad / 32 v_mfma_f32_16x16x32_f16 k steps in ascending order from a zero
 // accumulator.  It depends on hpad alone -- not on the tile the pair falls in, nor on the kernel or the pass that computes it -- so a pair
@@ -98,6 +99,18 @@ struct SimRows {
     }
 };
 
+// SimRows for a tile that starts at ANY row of a matrix whose last allocated row is `last_row`: the row index is clamped to it, so a tile
+// that reaches past the allocation reads the last row again instead.  The caller masks those rows (rerank_tile_kernel: columns >= len).
+struct SimRowsClamped : SimRows {
+    __device__ __forceinline__ SimRowsClamped(const SimPlace& p, const _Float16* base, int row0, int last_row, size_t ld) : SimRows(p, base, 0, ld) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int row = row0 + p.srow[j] < last_row ? row0 + p.srow[j] : last_row;
+            src[j] = (const char*)base + (size_t)row * ld * 2 + p.sc * 16;
+        }
+    }
+};
+
 // One K-tile of arithmetic from the images: two k steps of 32 in ascending order, sixteen MFMAs each.
 __device__ __forceinline__ void sim_tile_k(const SimPlace& p, const char* sA, const char* sB, f32x4 (&acc)[4][4]) {
     using E = Elem<_Float16>;
@@ -165,6 +178,28 @@ __device__ __forceinline__ Best sim_fold_waves(const float (&red_v)[2][SIM_TILE]
     Best b{red_v[0][e], red_i[0][e]};
     fold(b, red_v[1][e], red_i[1][e]);
     return b;
+}
+
+// ---- the best row of a column (rerank_tile_kernel; match_kernel's epilogue has the same steps) ------------------------------------------------
+// A lane's 4 rows of accumulator column (j, r) in ascending order into b; rowb = the tile's first row + 64 wm + fr.  Rows >= nrows are masked.
+__device__ __forceinline__ void sim_col_fold(const f32x4 (&acc)[4][4], int j, int r, int rowb, int nrows, Best& b) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = rowb + i * 16;
+        if (row < nrows) fold(b, acc[i][j][r] + 0.0f, row);
+    }
+}
+// b of accumulator column (j, r) over the sixteen lanes that share the column, left in red[wm]; after a barrier sim_fold_waves folds the two
+// waves above each other
+__device__ __forceinline__ void sim_col_share(const SimPlace& p, int j, int r, Best b, float (&red_v)[2][SIM_TILE], int (&red_i)[2][SIM_TILE]) {
+    fold_lane<1>(b);
+    fold_lane<2>(b);
+    fold_lane<4>(b);
+    fold_lane<8>(b);
+    if (p.fr == 0) {
+        red_v[p.wm][p.wn * 64 + j * 16 + 4 * p.fh + r] = b.v;
+        red_i[p.wm][p.wn * 64 + j * 16 + 4 * p.fh + r] = b.i;
+    }
 }
 
 // ---- the best column of every row of one 128-row tile of A over all of B's tiles (kmeans_assign_kernel, vlad_assign_kernel) ----------------

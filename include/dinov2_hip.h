@@ -636,6 +636,60 @@ typedef struct dinov2_hip_coreset {
  * what it was, and a bank is only read. */
 int dinov2_hip_coreset_tokens(dinov2_hip_session *s, const dinov2_hip_coreset *c, char *err, size_t errlen);
 
+/* -- re-ranking a shortlist by local features (no reference counterpart: the last step of place recognition and instance retrieval on frozen
+ *    patch tokens -- a global descriptor or a top-k search gives 20 - 200 candidate images, and each candidate is then scored by comparing
+ *    every patch token of the query image with every patch token of the candidate: the sum of the per-token maxima (ColBERT's MaxSim, the
+ *    Chamfer similarity) or the number and summed similarity of mutual nearest neighbours, as in Patch-NetVLAD, SelaVPR and R2Former).  The
+ *    candidates are row ranges ("segments") of a bank, where their tokens already lie normalised: what dinov2_hip_bank_add reported as
+ *    `first`, and the n it was given.  One call scores the whole list; only [n_seg] scalars per output cross PCIe.  On the device
+ *    (csrc/rerank.hip): one launch over a work table with one workgroup per (segment, 128-row query tile), which walks the segment's 128-row
+ *    tiles on the matrix cores -- the best column of a query row stays in registers over the walk, the best query row of a column leaves one
+ *    partial per query tile --, then one workgroup per segment that folds the partials and forms the scalars.  A segment may start at any
+ *    row, so its tiles are not the bank's: loads are clamped to the allocation and what a tile holds outside the segment is masked.
+ *    Contract:
+ *    1. Operands.  The queries go through contract 1 of dinov2_hip_match, the same kernel: f16 unit rows, a zero row stays zero.  The
+ *       bank's rows are used as they lie (they went through that kernel when they were added).
+ *    2. Similarity.  sim(i, j) is contract 2 of dinov2_hip_match: one chain of hpad / 32 16x16x32 f16 MFMA k-steps, ascending, from a zero
+ *       accumulator, the same operand roles (csrc/sim_tile.h) -- the bits the pair has in match, bank top-k, k-means and the coreset sweep.
+ *    3. Best.  Within segment s, idx_q[i] / sim_q[i] is the best column of query row i among the segment's len rows ONLY (0 .. len - 1,
+ *       counted from `first`), idx_b[j] / sim_b[j] the best query row of segment row j among the n real queries; one strict total order:
+ *       the larger f32 value first (-0 is read as +0), among equal values the LOWEST index.  Hence these four arrays equal idx_ab, sim_ab,
+ *       idx_ba, sim_ba of dinov2_hip_match_tokens(queries, the rows that were added at [first, first + len)) bit for bit.
+ *    4. Scores.  score_q = sum_i sim_q[i]; score_b = sum_j sim_b[j]; pair i is mutual iff idx_b[idx_q[i]] == i and sim_q[i] >= min_sim;
+ *       mutual = the number of mutual pairs, mutual_sim = the sum of their sim_q.  The sums are f32 in a fixed order: term e (query row i
+ *       for score_q and mutual_sim, where a pair that is not mutual is left out; segment row j for score_b) belongs to slot e mod 256; every
+ *       slot adds its terms in ascending order from 0; slots x and x ^ 1 are added, then pairs of those results (x ^ 2), and so on through
+ *       x ^ 32, which leaves four sums of 64 slots, w0 .. w3, and the result is (w0 + w1) + (w2 + w3).  The order of score_q depends on n
+ *       alone, of score_b on len alone, of mutual_sim on n and on which pairs are mutual.  No atomics: bit-reproducible run to run.
+ *    5. Independence.  A segment's four outputs have the same bits wherever it stands in the list, whatever segments travel with it
+ *       (ranges may overlap or repeat), however the list is cut into passes, and whatever lies in the bank outside the range -- other
+ *       segments, rows past count, the padding of the allocation; memory past the last allocated row is never read.
+ *    6. Passes.  A pure planner from (n, H, the lengths) cuts the list into passes of whole segments so that the column partials of a
+ *       pass (query tiles x len rounded up to 128 x 8 bytes per segment, at most 16 MiB for one) stay within 32 MiB.
+ *    Out of scope: the correspondences themselves (a caller runs dinov2_hip_match_tokens on the winner); geometric verification (RANSAC);
+ *    several query sets per call; bf16 or int8 rows; the device group; device-side outputs; the rows of a list forward;
+ *    dinov2_compat.hpp and the example programs.
+ *    Times against the loop of dinov2_hip_match_tokens calls it replaces: profiles/bank_rerank.md. */
+typedef struct dinov2_hip_rerank {
+    dinov2_hip_rows queries;  /* GIVEN (host / device), LAST_CLS, LAST_PATCHES of queries.image; 1 <= n <= 16 384; H = the bank's */
+    int32_t n_seg;            /* 1 .. 65 536 candidates */
+    const int32_t *first;     /* [n_seg] HOST: candidate s is rows [first[s], first[s] + len[s]) of the bank */
+    const int32_t *len;       /* [n_seg] HOST: 1 .. 16 384; first >= 0, first + len <= count.  Ranges may overlap or repeat */
+    float   min_sim;          /* a mutual pair counts only if its similarity is >= min_sim; -INFINITY = all; NaN refused */
+    float   *score_q;         /* [n_seg] HOST: sum over query rows i of max_j sim(i, j)   (any output may be NULL, not all) */
+    float   *score_b;         /* [n_seg] sum over the segment's rows j of max_i sim(i, j) */
+    int32_t *mutual;          /* [n_seg] number of mutual nearest-neighbour pairs */
+    float   *mutual_sim;      /* [n_seg] sum of their similarities */
+    int32_t reserved[4];
+} dinov2_hip_rerank;
+/* Synchronous: returns after the copy-out, like dinov2_hip_bank_topk.  Argument errors (NULL session, bank or request; those of
+ * dinov2_hip_bank_add for `queries`; more than 16 384 queries; an empty bank; n_seg out of range; NULL first or len; a len out of range or a
+ * range outside [0, count); a NaN min_sim; all outputs NULL; a session of another device) return DINOV2_HIP_ERR_INVALID before anything is
+ * launched, allocated or copied, with the outputs untouched.  The scratch (host queries' staging copy, the f16 queries, at most 32 MiB each of
+ * column and row partials, the two tables, the results) is a session-owned buffer grown on demand; an allocation the device refuses returns
+ * DINOV2_HIP_ERR_HIP.  The session's last forward stays what it was, and the bank is only read. */
+int dinov2_hip_bank_rerank(dinov2_hip_session *s, const dinov2_hip_bank *bank, const dinov2_hip_rerank *r, char *err, size_t errlen);
+
 /* -- VLAD descriptors of row segments (no reference counterpart: one vector per image for place recognition and image retrieval from
  *    frozen patch tokens -- every token is assigned to the nearest centre of a k-means vocabulary, the residuals are summed per centre,
  *    each centre's sum is normalised, then the whole; the recipe of AnyLoc).  The last step of forward -> vocabulary

@@ -303,6 +303,26 @@ int dinov2_hip_op_coreset_plan(int32_t n, int32_t H, int32_t m, int32_t rows_per
 int dinov2_hip_op_coreset_bench(const float *rows_dev, int32_t n, int32_t H, int32_t m, int32_t rows_per_wg, int32_t warmup, int32_t iters,
                                 float *us_per_pick);
 
+/* the kernels behind dinov2_hip_bank_rerank (csrc/rerank.hip) and the shared normaliser, without a model or session.  1 <= nq <= 16 384,
+ * 8 <= H <= 4096, 1 <= n_seg <= 65 536, 1 <= len[s] <= 16 384, pass_bytes >= 0, else DINOV2_HIP_ERR_INVALID.
+ * bank_rerank: host q [nq, H] against the bank built here from host b [nb, H] (1 <= nb <= 2^24), segments first / len [n_seg] with
+ *              0 <= first, first + len <= nb, min_sim not NaN -> score_q, score_b, mutual, mutual_sim [n_seg] (any may be NULL).  The bank is
+ *              allocated exactly nb rows long -- nothing lies behind its last row -- and, like the workspace, starts as 0xff bytes, so
+ *              anything the kernels read without having written it shows up as NaN.  pass_bytes: the bound of one pass's column
+ *              partials, 0 = the planner's 32 MiB (a smaller value forces the multi-pass path at small sizes; a segment larger than it is a
+ *              pass of its own).
+ * rerank_plan (no device): rerank_plan of csrc/kernels.h: out[0 .. 6] = nq_pad, hpad, query tiles, passes, the most segments of a pass, the
+ *              most bytes of column partials of a pass, bytes of the workspace; pass_of [n_seg] (may be NULL) = the pass of every segment.
+ * rerank_bench (tools/rerank_bench.py): DEVICE q_dev [nq, H] and b_dev [nb, H], min_sim = -INFINITY: ms [iters] = each timed call's work
+ *              after `warmup` (normalise the queries, the table uploads, both kernels pass by pass, the four copies out), by HIP events on
+ *              the null stream. */
+int dinov2_hip_op_bank_rerank(const float *q, int32_t nq, const float *b, int32_t nb, int32_t H, const int32_t *first, const int32_t *len,
+                              int32_t n_seg, float min_sim, int64_t pass_bytes, float *score_q, float *score_b, int32_t *mutual,
+                              float *mutual_sim);
+int dinov2_hip_op_rerank_plan(int32_t nq, int32_t H, const int32_t *len, int32_t n_seg, int64_t pass_bytes, int64_t *out, int32_t *pass_of);
+int dinov2_hip_op_rerank_bench(const float *q_dev, int32_t nq, const float *b_dev, int32_t nb, int32_t H, const int32_t *first,
+                               const int32_t *len, int32_t n_seg, int32_t warmup, int32_t iters, float *ms);
+
 /* the kernels behind dinov2_hip_ncut_tokens (csrc/ncut.hip), its loop (csrc/ncut.cpp) and the shared normaliser, without a model or session;
  * cases, the numpy restatement and the bounds: tests/ncut_cases.py.  16 <= n <= 131 072, 8 <= H <= 4096, affinity, tau and floor as in
  * dinov2_hip_ncut, else DINOV2_HIP_ERR_INVALID.  Every device buffer starts as 0xff bytes; the partials, both blocks, the 8 x 8 partials,
