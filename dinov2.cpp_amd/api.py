@@ -134,6 +134,12 @@ class Rerank(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class TopkProbe(C.Structure):
+    """dinov2_hip_topk_probe (include/dinov2_hip.h)."""
+    _fields_ = [("queries", Rows), ("n_seg", C.c_int32), ("first", C.c_void_p), ("len", C.c_void_p), ("n_probe", C.c_int32),
+                ("probe", C.c_void_p), ("k", C.c_int32), ("idx", C.c_void_p), ("sim", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
 class Vlad(C.Structure):
     """dinov2_hip_vlad (include/dinov2_hip.h)."""
     _fields_ = [("rows", Rows), ("all_images", C.c_int32), ("offsets", C.c_void_p), ("n_seg", C.c_int32), ("K", C.c_int32),
@@ -619,6 +625,67 @@ def op_bank_rerank(q, b, segments, min_sim=None, pass_bytes=0):
     return out
 
 
+PROBE_PLAN_FIELDS = ("nq_pad", "hpad", "piece_tiles", "npass", "n_wide", "n_narrow", "n_rows", "partial_bytes", "bytes", "narrow_lds")
+PROBE_FORMS = {"auto": 0, "wide": 1, "narrow": 2}
+
+
+def ivf_order(labels, n_lists):
+    """The inverted-file layout of rows with list labels in [0, n_lists): (perm, first, len) -- perm a stable sort by label, so that
+    rows[perm] holds list 0, then list 1, ... and bank row j is the caller's row perm[j]; list i is bank rows [first[i], first[i] + len[i])
+    (an empty list has len 0: leave it out of the segments, or never probe it)."""
+    lab = np.asarray(labels)
+    if lab.ndim != 1 or (lab.size and (lab.min() < 0 or lab.max() >= int(n_lists))):
+        raise ValueError(f"ivf_order: labels must be 1-D and inside [0, {n_lists})")
+    perm = np.argsort(lab, kind="stable").astype(np.int32)
+    ln = np.bincount(lab, minlength=int(n_lists)).astype(np.int32)
+    first = (np.cumsum(ln) - ln).astype(np.int32)
+    return perm, first, ln
+
+
+def _probes(probes, nq):
+    p = np.ascontiguousarray(probes, np.int32)
+    if p.ndim != 2 or p.shape[0] != nq or p.shape[1] < 1:
+        raise ValueError(f"probes must be [{nq}, n_probe] segment ids (-1 = unused)")
+    return p
+
+
+def op_bank_probe_plan(nq, nb, H, segments, probes, k, piece_tiles=0, pass_bytes=0, force_form="auto"):
+    """probe_plan (csrc/kernels.h) as a dict, with passes [npass, 3] = (first query, queries, slots), items [n_items, 6] = (pass, first bank
+    row, rows, queries, form, first row-table entry) and rows [n_rows, 2] = (query, list number within the pass); no device needed.
+    ValueError with the library's wording where the request is refused."""
+    first, ln = _segments(segments)
+    pr = _probes(probes, int(nq))
+    buf, err = (C.c_int64 * len(PROBE_PLAN_FIELDS))(), C.create_string_buffer(256)
+    head = (int(nq), int(nb), int(H), _ptr(first), _ptr(ln), len(ln), _ptr(pr), pr.shape[1], int(k), int(piece_tiles), int(pass_bytes),
+            PROBE_FORMS[force_form], buf)
+    if lib().dinov2_hip_op_bank_probe_plan(*head, None, 0, None, 0, None, 0, err, len(err)) != 0:
+        raise ValueError("bank_probe refuses: " + err.value.decode())
+    p = dict(zip(PROBE_PLAN_FIELDS, [int(v) for v in buf]))
+    n_items = p["n_wide"] + p["n_narrow"]
+    passes, items, rows = np.zeros((p["npass"], 3), np.int32), np.zeros((n_items, 6), np.int32), np.zeros((p["n_rows"], 2), np.int32)
+    rc = lib().dinov2_hip_op_bank_probe_plan(*head, _ptr(passes), len(passes), _ptr(items), n_items, _ptr(rows), len(rows), err, len(err))
+    assert rc == 0, rc
+    return dict(p, passes=passes, items=items, rows=rows)
+
+
+def op_bank_probe(q, b, segments, probes, k, piece_tiles=0, pass_bytes=0, force_form="auto"):
+    """The kernels of csrc/probe.hip alone (dinov2_hip_op_bank_probe): q [nq, H] against the segments (first, len) of the bank built from
+    b [nb, H] that probes [nq, n_probe] names per query -> the dict of Bank.topk_probe.  piece_tiles / pass_bytes / force_form override the
+    planner (0 / 0 / "auto" = its own choice).  No model, no session."""
+    q, b = _f32(q), _f32(b)
+    assert q.ndim == 2 and b.ndim == 2 and q.shape[1] == b.shape[1], (q.shape, b.shape)
+    first, ln = _segments(segments)
+    pr = _probes(probes, q.shape[0])
+    out = {"idx": np.full((q.shape[0], int(k)), -7, np.int32), "sim": np.full((q.shape[0], int(k)), np.nan, np.float32)}
+    rc = lib().dinov2_hip_op_bank_probe(_ptr(q), q.shape[0], _ptr(b), b.shape[0], q.shape[1], _ptr(first), _ptr(ln), len(ln), _ptr(pr),
+                                        pr.shape[1], int(k), int(piece_tiles), int(pass_bytes), PROBE_FORMS[force_form], _ptr(out["idx"]),
+                                        _ptr(out["sim"]))
+    if rc == 4:
+        raise ValueError(f"bank_probe refuses nq={q.shape[0]} nb={b.shape[0]} H={q.shape[1]} n_seg={len(ln)} n_probe={pr.shape[1]} k={k}")
+    _op_rc(rc, "bank_probe")
+    return out
+
+
 VLAD_PLAN_FIELDS = ("kpad", "hpad", "hpad128", "chunk", "cap", "npad", "ntiles", "nchunks", "npass", "partial_bytes", "bytes")
 
 
@@ -1050,6 +1117,10 @@ def lib():
     L.dinov2_hip_op_bank_rerank.argtypes = [fp, i32, fp, i32, i32, ip, ip, i32, C.c_float, C.c_int64, fp, fp, ip, fp]
     L.dinov2_hip_op_rerank_plan.argtypes = [i32, i32, ip, i32, C.c_int64, C.POINTER(C.c_int64), ip]
     L.dinov2_hip_op_rerank_bench.argtypes = [vp, i32, vp, i32, i32, ip, ip, i32, i32, i32, fp]
+    L.dinov2_hip_bank_topk_probe.argtypes = [vp, vp, C.POINTER(TopkProbe), cp, sz]
+    L.dinov2_hip_op_bank_probe.argtypes = [fp, i32, fp, i32, i32, ip, ip, i32, ip, i32, i32, i32, C.c_int64, i32, ip, fp]
+    L.dinov2_hip_op_bank_probe_plan.argtypes = [i32, i32, i32, ip, ip, i32, ip, i32, i32, i32, C.c_int64, i32, C.POINTER(C.c_int64), ip, C.c_int64,
+                                                ip, C.c_int64, ip, C.c_int64, cp, sz]
     dp, f32 = C.POINTER(C.c_double), C.c_float
     L.dinov2_hip_ncut_tokens.argtypes = [vp, C.POINTER(NCut), cp, sz]
     L.dinov2_hip_op_ncut_plan.argtypes = [i32, i32, i32, C.POINTER(C.c_int64)]
@@ -1520,6 +1591,23 @@ class Bank(_Handle):
         t = Rerank(r, len(ln), first.ctypes.data, ln.ctypes.data, float(-np.inf if min_sim is None else min_sim), out["score_q"].ctypes.data,
                    out["score_b"].ctypes.data, out["mutual"].ctypes.data, out["mutual_sim"].ctypes.data)
         _call(lib().dinov2_hip_bank_rerank, sess._h, self._h, C.byref(t))
+        return out
+
+    def topk_probe(self, sess: "Session", queries=None, segments=(), probes=(), k: int = 1, *, source=None, image: int = 0,
+                   n: int | None = None) -> dict:
+        """The k most similar rows of every query among the segments it probes (dinov2_hip_bank_topk_probe): the search step of an inverted
+        file.  segments: a sequence of disjoint (first, len) row ranges of the bank (ivf_order lays rows out list by list); probes:
+        [nq, n_probe] segment ids per query, -1 = unused -- e.g. the idx of topk() on a bank of the list centres.  Dict of idx [nq, k] int32
+        (bank rows, best first; -1 where a query's segments hold fewer than k rows) and sim [nq, k] f32 (-inf there).  queries as the rows
+        of add()."""
+        r, keep = self._rows(sess, queries, source, image, n)
+        nq = max(int(r.n), 0)
+        first, ln = _segments(segments)
+        pr = _probes(probes, nq)
+        out = {"idx": np.empty((nq, int(k)), np.int32), "sim": np.empty((nq, int(k)), np.float32)}
+        t = TopkProbe(r, len(ln), first.ctypes.data, ln.ctypes.data, pr.shape[1], pr.ctypes.data, int(k), out["idx"].ctypes.data,
+                      out["sim"].ctypes.data)
+        _call(lib().dinov2_hip_bank_topk_probe, sess._h, self._h, C.byref(t))
         return out
 
     def keep(self, sess: "Session", idx) -> np.ndarray:

@@ -1,4 +1,4 @@
-// Internal helpers of the host files behind the C-ABI (load.cpp, model.cpp, extras.cpp, pca.cpp, resident.cpp, vlad.cpp, propagate.cpp, ncut.cpp, coreset.cpp, rerank.cpp): error text, HIP_TRY, sizes, the session's
+// Internal helpers of the host files behind the C-ABI (load.cpp, model.cpp, extras.cpp, pca.cpp, resident.cpp, vlad.cpp, propagate.cpp, ncut.cpp, coreset.cpp, rerank.cpp, probe.cpp): error text, HIP_TRY, sizes, the session's
 // scratch buffers.  Not for group.cpp, which talks to the sessions through the C-ABI and has an error macro of its own.
 #pragma once
 #include <cstdarg>

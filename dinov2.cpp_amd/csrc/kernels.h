@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <utility>
 #include <vector>
 
@@ -817,6 +818,193 @@ inline RerankPlan rerank_plan(int n, int H, int n_seg, const int32_t* first, con
 // (the uploads read them); ws: DEVICE workspace of plan.bytes.  Afterwards ws + plan.score_q etc. hold [n_seg].  No wait.
 hipError_t launch_rerank(const float* q, size_t ldq, int n, int H, const _Float16* bank, int last_row, int n_seg, float min_sim, char* ws,
                          const RerankPlan& plan, const RerankTables& tables, hipStream_t stream);
+
+// Top-k over probed row ranges of a bank -- the inverted-file search (csrc/probe.hip; contract in include/dinov2_hip.h,
+// dinov2_hip_topk_probe).  Segment s is rows [first, first + len) of the bank; query q looks into the segments probe[q][0 .. n_probe) only.
+// The probe table is inverted: an ITEM is one piece of a segment (at most piece_tiles 128-row tiles) with up to 128 of the queries that
+// probe the segment (wide form, probe_tile_kernel) or up to 16 of them (narrow form, probe_narrow_kernel), one workgroup each.  An item
+// leaves one sorted list of k entries per query; the lists of a query -- one per (probe, piece) -- take the slots 0, 1, .. of that query in
+// the layout of bank_merge_kernel, part[(slot * pass_rows + q) * k], which folds them.  The queries are cut into passes of consecutive
+// queries whose lists (slots of the pass x its queries x k x 8 bytes) stay within PROBE_PARTIAL_MAX.
+constexpr int PROBE_N_MAX = 1 << 16, PROBE_SEG_MAX = 1 << 16, PROBE_SLOTS_MAX = 64;
+constexpr int PROBE_PIECE_TILES = 8, PROBE_TARGET_WGS = 512, PROBE_NARROW_ROWS = 16, PROBE_NARROW_WAVES = 4;
+constexpr size_t PROBE_PARTIAL_MAX = (size_t)32 << 20, PROBE_NARROW_LDS_MAX = (size_t)96 << 10;
+enum ProbeForm : int { PROBE_FORM_AUTO = 0, PROBE_FORM_WIDE = 1, PROBE_FORM_NARROW = 2 };
+struct ProbeItem {  // one workgroup: bank rows [row0, row0 + nrows) against the queries rows_q[rows .. rows + nq) of the pass's row table
+    int32_t row0, nrows, nq, form;
+    int64_t rows;
+};
+struct ProbePass {  // queries [q0, q0 + nq); items [item0, +n_wide) are wide, the next n_narrow narrow; row table entries [row0, +nrows)
+    int32_t q0, nq, slots, n_wide, n_narrow;
+    int64_t item0, row0, nrows;
+};
+struct ProbeTables {  // what the host uploads pass by pass
+    std::vector<ProbePass> passes;
+    std::vector<ProbeItem> items;
+    std::vector<int32_t> rows_q, rows_dst;  // per item row: the query (a row of the normalised query matrix) and its list slot * pass_rows + (q - q0)
+};
+struct ProbePlan {
+    int nq_pad, hpad, piece_tiles;  // queries to whole tiles, H to a multiple of 64, column tiles of a piece
+    int npass, n_wide, n_narrow;    // passes; items of either form over the whole call
+    int64_t max_items, max_rows, max_lists;  // the most items, row table entries and lists (slots x queries) of one pass
+    size_t narrow_lds;              // dynamic LDS of probe_narrow_kernel (0: the narrow form does not fit, every item is wide)
+    size_t q16, part, items, rows_q, rows_dst, idx, sim;
+    size_t bytes;
+};
+// The refusals of a probe request that need no device, worded into msg; true when there is nothing to refuse.
+inline bool probe_check(int count, int n, int n_seg, const int32_t* first, const int32_t* len, int n_probe, const int32_t* probe, int k, char* msg,
+                        size_t msglen) {
+    auto say = [&](const char* fmt, auto... a) { if (msg && msglen) snprintf(msg, msglen, fmt, a...); return false; };
+    if (n < 1 || n > PROBE_N_MAX) return say("need 1 <= n <= %d queries", PROBE_N_MAX);
+    if (k < 1 || k > BANK_K_MAX || n_probe < 1 || n_probe > PROBE_SLOTS_MAX)
+        return say("need 1 <= k <= %d and 1 <= n_probe <= %d", BANK_K_MAX, PROBE_SLOTS_MAX);
+    if (n_seg < 1 || n_seg > PROBE_SEG_MAX || !first || !len || !probe) return say("need 1 <= n_seg <= %d, first, len and probe", PROBE_SEG_MAX);
+    if (count < 1) return say("%s", "the bank is empty");
+    std::vector<int32_t> order((size_t)n_seg);
+    for (int s = 0; s < n_seg; ++s) {
+        if (len[s] < 1 || first[s] < 0 || first[s] > count - len[s])
+            return say("segment %d is rows [%d, %d + %d): need len >= 1 inside the bank's %d rows", s, (int)first[s], (int)first[s], (int)len[s], count);
+        order[(size_t)s] = s;
+    }
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return first[a] != first[b] ? first[a] < first[b] : a < b; });
+    for (int i = 1; i < n_seg; ++i) {
+        const int a = order[(size_t)i - 1], b = order[(size_t)i];
+        if (first[b] < first[a] + len[a])
+            return say("segments %d and %d overlap: rows [%d, %d) and [%d, %d)", std::min(a, b), std::max(a, b), (int)first[a], (int)(first[a] + len[a]),
+                       (int)first[b], (int)(first[b] + len[b]));
+    }
+    std::vector<int32_t> seen((size_t)n_seg, -1);
+    for (int q = 0; q < n; ++q)
+        for (int j = 0; j < n_probe; ++j) {
+            const int s = probe[(size_t)q * n_probe + j];
+            if (s < -1 || s >= n_seg) return say("query %d probes segment %d: ids lie in [-1, %d)", q, s, n_seg);
+            if (s < 0) continue;
+            if (seen[(size_t)s] == q) return say("query %d probes segment %d twice", q, s);
+            seen[(size_t)s] = q;
+        }
+    return true;
+}
+// Pure: the arguments alone (a request that passed probe_check).  piece_tiles = 0: as many tiles a piece, 1 .. PROBE_PIECE_TILES, as leave
+// about PROBE_TARGET_WGS items; any value is doubled until one query's lists fit PROBE_PARTIAL_MAX.  A pass takes queries in order while
+// its lists stay within pass_bytes (0, or more than PROBE_PARTIAL_MAX: PROBE_PARTIAL_MAX); a query that alone is larger than a small
+// pass_bytes is a pass of its own.  The form of an item: wide for every full 128 queries of a segment and for a rest of more than 16, narrow
+// for a rest of at most 16 (force_form: PROBE_FORM_WIDE all wide, PROBE_FORM_NARROW 16 a piece); where the narrow form's LDS image does not
+// fit (PROBE_NARROW_LDS_MAX) every item is wide.  No result depends on any of this.
+inline ProbePlan probe_plan(int n, int H, int k, int n_seg, const int32_t* first, const int32_t* len, int n_probe, const int32_t* probe,
+                            int piece_tiles, size_t pass_bytes, int force_form, ProbeTables* t) {
+    ProbePlan p{};
+    p.nq_pad = (n + MATCH_TM - 1) / MATCH_TM * MATCH_TM;
+    p.hpad = (H + 63) / 64 * 64;
+    const size_t lds = (size_t)PROBE_NARROW_ROWS * p.hpad * 2 + (size_t)PROBE_NARROW_WAVES * PROBE_NARROW_ROWS * k * sizeof(BankEntry);
+    p.narrow_lds = lds <= PROBE_NARROW_LDS_MAX ? lds : 0;
+    if (!p.narrow_lds) force_form = PROBE_FORM_WIDE;
+    auto tiles_of = [&](int s) { return (int64_t)(len[s] + MATCH_TN - 1) / MATCH_TN; };
+    // the piece: from the work of the whole call
+    std::vector<int32_t> users((size_t)n_seg, 0);
+    const size_t npairs = (size_t)n * n_probe;
+    for (size_t e = 0; e < npairs; ++e)
+        if (probe[e] >= 0) ++users[(size_t)probe[e]];
+    if (piece_tiles <= 0) {
+        int64_t total = 0;
+        for (int s = 0; s < n_seg; ++s) total += tiles_of(s) * ((users[(size_t)s] + MATCH_TM - 1) / MATCH_TM);
+        const int64_t want = total / PROBE_TARGET_WGS;
+        piece_tiles = (int)(want < 1 ? 1 : want > PROBE_PIECE_TILES ? PROBE_PIECE_TILES : want);
+    }
+    std::vector<int64_t> slots((size_t)n);
+    const int64_t hard = (int64_t)(PROBE_PARTIAL_MAX / ((size_t)k * sizeof(BankEntry)));
+    for (;; piece_tiles *= 2) {
+        int64_t most = 0;
+        for (int q = 0; q < n; ++q) {
+            int64_t c = 0;
+            for (int j = 0; j < n_probe; ++j) {
+                const int s = probe[(size_t)q * n_probe + j];
+                if (s >= 0) c += (tiles_of(s) + piece_tiles - 1) / piece_tiles;
+            }
+            slots[(size_t)q] = c;
+            most = std::max(most, c);
+        }
+        if (most <= hard) break;
+    }
+    p.piece_tiles = piece_tiles;
+    const int64_t bound = (int64_t)((pass_bytes == 0 || pass_bytes > PROBE_PARTIAL_MAX ? PROBE_PARTIAL_MAX : pass_bytes) / ((size_t)k * sizeof(BankEntry)));
+    t->passes.clear();
+    t->items.clear();
+    t->rows_q.clear();
+    t->rows_dst.clear();
+    std::vector<uint64_t> pairs;
+    std::vector<int32_t> next;
+    std::vector<ProbeItem> narrow;
+    const int piece_rows = piece_tiles * MATCH_TN;
+    for (int q0 = 0; q0 < n;) {
+        int q1 = q0;
+        int64_t most = 0;
+        while (q1 < n) {  // queries in order while slots x queries stays within the bound
+            const int64_t m = std::max(most, slots[(size_t)q1]);
+            if (q1 > q0 && m * (q1 + 1 - q0) > bound) break;
+            most = m;
+            ++q1;
+        }
+        ProbePass ps{q0, q1 - q0, (int32_t)most, 0, 0, (int64_t)t->items.size(), (int64_t)t->rows_q.size(), 0};
+        pairs.clear();
+        for (int q = q0; q < q1; ++q)
+            for (int j = 0; j < n_probe; ++j) {
+                const int s = probe[(size_t)q * n_probe + j];
+                if (s >= 0) pairs.push_back((uint64_t)s << 32 | (uint32_t)q);
+            }
+        std::sort(pairs.begin(), pairs.end());  // by segment, then by query: the inverted table of the pass
+        next.assign((size_t)ps.nq, 0);
+        narrow.clear();
+        for (size_t a = 0; a < pairs.size();) {
+            const int s = (int)(pairs[a] >> 32);
+            size_t b = a;
+            while (b < pairs.size() && (int)(pairs[b] >> 32) == s) ++b;
+            while (a < b) {  // the queries of segment s, a group at a time
+                const size_t left = b - a;
+                const bool is_narrow = force_form == PROBE_FORM_NARROW || (force_form == PROBE_FORM_AUTO && left <= (size_t)PROBE_NARROW_ROWS);
+                const int g = (int)std::min(left, (size_t)(is_narrow ? PROBE_NARROW_ROWS : MATCH_TM));
+                for (int r0 = 0; r0 < len[s]; r0 += piece_rows) {  // one item per piece, each with lists of its own
+                    const ProbeItem it{first[s] + r0, std::min(piece_rows, len[s] - r0), g, is_narrow ? PROBE_FORM_NARROW : PROBE_FORM_WIDE,
+                                       (int64_t)t->rows_q.size() - ps.row0};
+                    for (int i = 0; i < g; ++i) {
+                        const int q = (int)(uint32_t)pairs[a + i];
+                        t->rows_q.push_back(q);
+                        t->rows_dst.push_back((int32_t)((int64_t)next[(size_t)(q - q0)]++ * ps.nq + (q - q0)));
+                    }
+                    if (is_narrow) narrow.push_back(it); else t->items.push_back(it);
+                }
+                a += (size_t)g;
+            }
+        }
+        ps.n_wide = (int32_t)((int64_t)t->items.size() - ps.item0);
+        ps.n_narrow = (int32_t)narrow.size();
+        t->items.insert(t->items.end(), narrow.begin(), narrow.end());
+        ps.nrows = (int64_t)t->rows_q.size() - ps.row0;
+        t->passes.push_back(ps);
+        ++p.npass;
+        p.n_wide += ps.n_wide;
+        p.n_narrow += ps.n_narrow;
+        p.max_items = std::max(p.max_items, (int64_t)ps.n_wide + ps.n_narrow);
+        p.max_rows = std::max(p.max_rows, ps.nrows);
+        p.max_lists = std::max(p.max_lists, (int64_t)ps.slots * ps.nq);
+        q0 = q1;
+    }
+    size_t need = 0;
+    auto take = [&](size_t bytes) { const size_t off = need; need += (bytes + 255) / 256 * 256; return off; };
+    p.q16 = take((size_t)p.nq_pad * p.hpad * 2);
+    p.part = take((size_t)p.max_lists * k * sizeof(BankEntry));
+    p.items = take((size_t)p.max_items * sizeof(ProbeItem));
+    p.rows_q = take((size_t)p.max_rows * 4);
+    p.rows_dst = take((size_t)p.max_rows * 4);
+    p.idx = take((size_t)n * k * 4);
+    p.sim = take((size_t)n * k * 4);
+    p.bytes = need;
+    return p;
+}
+// q [n, H]: DEVICE f32 rows with row stride ldq (floats); bank: normalised f16 rows of hpad elements, of which rows 0 .. last_row are
+// allocated (no row past last_row is read); tables: probe_plan's for this request, unchanged until the stream has run what this enqueues
+// (the uploads read them); ws: DEVICE workspace of plan.bytes.  Afterwards ws + plan.idx / plan.sim hold [n, k].  No wait.
+hipError_t launch_probe(const float* q, size_t ldq, int n, int H, const _Float16* bank, int last_row, int k, char* ws, const ProbePlan& plan,
+                        const ProbeTables& tables, hipStream_t stream);
 
 // VLAD descriptors of row segments (csrc/vlad.hip; contract in include/dinov2_hip.h, dinov2_hip_vlad).  Every segment has a block of its own
 // in the f16 operand, padded to whole 128-row tiles, so that an assignment tile belongs to one segment and the K-tiles of the cluster sums

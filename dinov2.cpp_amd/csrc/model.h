@@ -143,6 +143,7 @@ enum Scratch : int {
     SCRATCH_NCUT,        // dinov2_hip_ncut_tokens (staged host rows, the f16 operand, the block and its partials, degrees)
     SCRATCH_CORESET,     // dinov2_hip_coreset_tokens (staged host rows, the f16 operand, s / nearest / marks, the partials, the results)
     SCRATCH_RERANK,      // dinov2_hip_bank_rerank (staged host queries, the f16 queries, one pass's partials, the tables, the results)
+    SCRATCH_PROBE,       // dinov2_hip_bank_topk_probe (staged host queries, the f16 queries, one pass's lists and tables, the results)
     SCRATCH_COUNT
 };
 

@@ -1377,6 +1377,67 @@ extern "C" int dinov2_hip_op_rerank_bench(const float* q_dev, int32_t nq, const 
     return 0;
 }
 
+// ---- dinov2_hip_bank_topk_probe's kernels (csrc/probe.hip) on host data: the bank is built by the shared normaliser and is exactly nb rows
+// ---- long; the planner on its own ----
+namespace {
+bool probe_args_ok(int nq, int nb, int H, const int32_t* first, const int32_t* len, int n_seg, const int32_t* probe, int n_probe, int k,
+                   int piece_tiles, int64_t pass_bytes, int force_form, char* err, size_t errlen) {
+    if (nb < 1 || nb > (1 << 24) || H < 8 || H > 4096 || piece_tiles < 0 || pass_bytes < 0 || force_form < 0 || force_form > 2) {
+        if (err && errlen) snprintf(err, errlen, "need 1 <= nb <= 2^24, 8 <= H <= 4096, piece_tiles >= 0, pass_bytes >= 0, force_form in 0 .. 2");
+        return false;
+    }
+    return probe_check(nb, nq, n_seg, first, len, n_probe, probe, k, err, errlen);
+}
+}  // namespace
+
+extern "C" int dinov2_hip_op_bank_probe_plan(int32_t nq, int32_t nb, int32_t H, const int32_t* first, const int32_t* len, int32_t n_seg,
+                                             const int32_t* probe, int32_t n_probe, int32_t k, int32_t piece_tiles, int64_t pass_bytes,
+                                             int32_t force_form, int64_t* out, int32_t* passes, int64_t passes_cap, int32_t* items,
+                                             int64_t items_cap, int32_t* rows, int64_t rows_cap, char* err, size_t errlen) {
+    if (!out || !probe_args_ok(nq, nb, H, first, len, n_seg, probe, n_probe, k, piece_tiles, pass_bytes, force_form, err, errlen))
+        return DINOV2_HIP_ERR_INVALID;
+    ProbeTables t;
+    const ProbePlan p = probe_plan(nq, H, k, n_seg, first, len, n_probe, probe, piece_tiles, (size_t)pass_bytes, force_form, &t);
+    const int64_t v[10] = {p.nq_pad, p.hpad, p.piece_tiles, p.npass, p.n_wide, p.n_narrow, (int64_t)t.rows_q.size(),
+                           p.max_lists * k * (int64_t)sizeof(BankEntry), (int64_t)p.bytes, (int64_t)p.narrow_lds};
+    std::copy(v, v + 10, out);
+    if ((passes && passes_cap < (int64_t)t.passes.size()) || (items && items_cap < (int64_t)t.items.size()) ||
+        (rows && rows_cap < (int64_t)t.rows_q.size()))
+        return DINOV2_HIP_ERR_INVALID;
+    for (size_t i = 0; i < t.passes.size(); ++i) {
+        const ProbePass& ps = t.passes[i];
+        if (passes) { passes[3 * i] = ps.q0; passes[3 * i + 1] = ps.nq; passes[3 * i + 2] = ps.slots; }
+        for (int64_t j = ps.item0; items && j < ps.item0 + ps.n_wide + ps.n_narrow; ++j) {
+            const ProbeItem& it = t.items[(size_t)j];
+            const int32_t w[6] = {(int32_t)i, it.row0, it.nrows, it.nq, it.form, (int32_t)(ps.row0 + it.rows)};
+            std::copy(w, w + 6, items + 6 * j);
+        }
+    }
+    for (size_t i = 0; rows && i < t.rows_q.size(); ++i) { rows[2 * i] = t.rows_q[i]; rows[2 * i + 1] = t.rows_dst[i]; }
+    return 0;
+}
+
+extern "C" int dinov2_hip_op_bank_probe(const float* q, int32_t nq, const float* b, int32_t nb, int32_t H, const int32_t* first,
+                                        const int32_t* len, int32_t n_seg, const int32_t* probe, int32_t n_probe, int32_t k, int32_t piece_tiles,
+                                        int64_t pass_bytes, int32_t force_form, int32_t* idx, float* sim) {
+    if (!q || !b || !idx || !sim ||
+        !probe_args_ok(nq, nb, H, first, len, n_seg, probe, n_probe, k, piece_tiles, pass_bytes, force_form, nullptr, 0))
+        return DINOV2_HIP_ERR_INVALID;
+    ProbeTables t;
+    const ProbePlan plan = probe_plan(nq, H, k, n_seg, first, len, n_probe, probe, piece_tiles, (size_t)pass_bytes, force_form, &t);
+    OpBuf dQ, dB, dBank, dW;
+    OP_TRY(dQ.upload(q, (size_t)nq * H * 4));
+    OP_TRY(dB.upload(b, (size_t)nb * H * 4));
+    OP_TRY(dBank.alloc((size_t)nb * plan.hpad, 2, OpBuf::nans()));
+    OP_TRY(dW.alloc(plan.bytes, 1, OpBuf::nans()));
+    OP_TRY(launch_match_normalise(dB.as<float>(), (size_t)H, dBank.as<_Float16>(), nb, nb, H, plan.hpad, nullptr));
+    OP_TRY(launch_probe(dQ.as<float>(), (size_t)H, nq, H, dBank.as<_Float16>(), nb - 1, k, dW.as<char>(), plan, t, nullptr));
+    OP_TRY(hipDeviceSynchronize());
+    OP_TRY(dW.read(idx, plan.idx, (size_t)nq * k * 4));
+    OP_TRY(dW.read(sim, plan.sim, (size_t)nq * k * 4));
+    return 0;
+}
+
 // ---- dinov2_hip_ncut_tokens' kernels (csrc/ncut.hip) and its loop (csrc/ncut.cpp) on host data ----
 namespace {
 bool ncut_shape_ok(int n, int H) { return n >= NCUT_N_MIN && n <= NCUT_N_MAX && H >= 8 && H <= 4096; }

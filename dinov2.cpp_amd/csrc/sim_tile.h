@@ -1,7 +1,8 @@
 // sim_tile.h -- the 128 x 128 tile of A . B^T on the matrix cores that match_kernel (match.hip), bank_topk_kernel (bank.hip),
 // kmeans_assign_kernel and kmeans_update_kernel (kmeans.hip) share, its one-column form for coreset_sweep_kernel (coreset.hip), and the
 // total order of "best" that their results are chosen by.  rerank_tile_kernel (rerank.hip) walks the tile over row ranges of a bank that
-// start at any row: its B operand is SimRowsClamped, its column direction sim_col_fold / sim_col_share.
+// start at any row: its B operand is SimRowsClamped, its column direction sim_col_fold / sim_col_share.  probe_tile_kernel (probe.hip)
+// gathers its A rows by a list (SimRowsGathered).
 //
 // The contract: the similarity of a pair is one chain of hpad / 32 v_mfma_f32_16x16x32_f16 k steps in ascending order from a zero
 // accumulator.  It depends on hpad alone -- not on the tile the pair falls in, nor on the kernel or the pass that computes it -- so a pair
@@ -107,6 +108,19 @@ struct SimRowsClamped : SimRows {
         for (int j = 0; j < 4; ++j) {
             const int row = row0 + p.srow[j] < last_row ? row0 + p.srow[j] : last_row;
             src[j] = (const char*)base + (size_t)row * ld * 2 + p.sc * 16;
+        }
+    }
+};
+
+// SimRows for a tile whose rows are picked by a list: tile row r is row index[r] of `base` for r < count (count >= 1); the tile rows past
+// the list read row index[count - 1] again.  The caller masks those rows (probe_tile_kernel: rows >= the item's queries).
+struct SimRowsGathered : SimRows {
+    __device__ __forceinline__ SimRowsGathered(const SimPlace& p, const _Float16* base, const int* __restrict__ index, int count, size_t ld)
+        : SimRows(p, base, 0, ld) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = p.srow[j] < count ? p.srow[j] : count - 1;
+            src[j] = (const char*)base + (size_t)index[r] * ld * 2 + p.sc * 16;
         }
     }
 };

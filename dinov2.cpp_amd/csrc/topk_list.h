@@ -1,7 +1,8 @@
 // topk_list.h -- the per-row sorted list of k (value, index) pairs that bank_topk_kernel (bank.hip) and propagate_topk_kernel
 // (propagate.hip) keep in LDS while they walk column tiles of sim_tile.h, and the merge step of a list held one entry per lane
 // (bank_merge_kernel).  Written once, so that the two selections cannot drift apart: dinov2_hip_propagate with no window equals
-// dinov2_hip_bank_topk bit for bit (tests/test_gpu_propagate.py).
+// dinov2_hip_bank_topk bit for bit (tests/test_gpu_propagate.py).  probe_tile_kernel (probe.hip) keeps the same lists and writes them out
+// through the scatter form, topk_list_scatter; probe_narrow_kernel shares wave_insert.
 //
 // A workgroup of sim_tile.h's 256 threads owns 128 rows.  list [128][k] lives in LDS, sorted by sim_tile.h's order; an empty slot is
 // (-inf, INT_MAX).  After a column tile the accumulators that beat their row's k-th entry go through a queue in LDS (the operand image,
@@ -87,6 +88,16 @@ __device__ __forceinline__ void topk_list_write(const SimPlace& p, const BankEnt
     for (int rr = 0; rr < 32; ++rr) {
         const int rl = p.wid * 32 + rr;
         if (rl < nrows && p.lane < k) out[(size_t)rl * k + p.lane] = list[rl * k + p.lane];
+    }
+}
+
+// The scatter form (probe_tile_kernel): the list of row r < nrows goes to list number dst_of(r) of out, k entries each.
+template <class DstOf>
+__device__ __forceinline__ void topk_list_scatter(const SimPlace& p, const BankEntry* list, int k, int nrows, BankEntry* __restrict__ out,
+                                                  DstOf dst_of) {
+    for (int rr = 0; rr < 32; ++rr) {
+        const int rl = p.wid * 32 + rr;
+        if (rl < nrows && p.lane < k) out[(size_t)dst_of(rl) * k + p.lane] = list[rl * k + p.lane];
     }
 }
 

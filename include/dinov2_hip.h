@@ -690,6 +690,47 @@ typedef struct dinov2_hip_rerank {
  * DINOV2_HIP_ERR_HIP.  The session's last forward stays what it was, and the bank is only read. */
 int dinov2_hip_bank_rerank(dinov2_hip_session *s, const dinov2_hip_bank *bank, const dinov2_hip_rerank *r, char *err, size_t errlen);
 
+/* -- top-k over probed row ranges of a bank (no reference counterpart: the search step of an inverted file, IVF -- the rows of a large
+ *    gallery are grouped into lists by a coarse quantiser (dinov2_hip_kmeans_tokens trains and assigns it; the rows are added list by
+ *    list), and a query looks only into the few lists whose centres are nearest to it (dinov2_hip_bank_topk on a small bank of the
+ *    centres names them: k there is n_probe here) instead of sweeping the whole bank as dinov2_hip_bank_topk does).  A list is a
+ *    "segment", a row range of the bank as in dinov2_hip_bank_rerank; every query has a probe table of its own.  On the device
+ *    (csrc/probe.hip): the probe table is inverted on the host into items, one piece of a segment with the queries that probe it; one
+ *    workgroup per item walks the piece on the matrix cores -- bank_topk's tile and lists for up to 128 queries, a 16-query form that
+ *    streams the bank rows once for a handful of queries -- and leaves one sorted list per query, which bank_topk's merge folds.
+ *    Contract:
+ *    1. Operands and similarity: contracts 1 and 2 of dinov2_hip_bank_rerank -- the bits a pair has in match, bank_topk and rerank.
+ *    2. Best.  Per query, the first k rows of the union of its probed segments in bank_topk's strict total order: the larger f32 value
+ *       first (-0 is read as +0), among equal values the LOWEST bank row.  idx holds bank rows (insertion indices), best first; where the
+ *       union has fewer than k rows the tail is (-1, -inf); a query whose slots are all -1 gets nothing but the tail.  Probing every
+ *       segment of a partition of [0, count) gives dinov2_hip_bank_topk's result bit for bit.
+ *    3. Independence.  With the same (first, len, its probe row, k) a query's result has the same bits whatever queries travel with it,
+ *       whatever the order of its probe slots, and however the work was cut into pieces, items, forms and passes; rows of the bank outside
+ *       its probed segments never matter, and memory past the last allocated row is never read.
+ *    4. Passes.  A pure planner cuts the queries into passes whose partial lists stay within 32 MiB.
+ *    Out of scope: training or holding the quantiser (the caller keeps first / len; api.ivf_order sorts rows by list); residual or product
+ *    quantisation; overlapping segments; device-side outputs; the device group; dinov2_compat.hpp and the example programs.
+ *    Times against dinov2_hip_bank_topk on the same bank and queries, and recall: profiles/bank_probe.md. */
+typedef struct dinov2_hip_topk_probe {
+    dinov2_hip_rows queries;  /* GIVEN (host / device), LAST_CLS, LAST_PATCHES of queries.image; 1 <= n <= 65 536; H = the bank's */
+    int32_t n_seg;            /* 1 .. 65 536 segments */
+    const int32_t *first;     /* [n_seg] HOST: segment i is rows [first[i], first[i] + len[i]) of the bank */
+    const int32_t *len;       /* [n_seg] HOST: >= 1; first >= 0, first + len <= count; pairwise disjoint */
+    int32_t n_probe;          /* 1 .. 64 probe slots per query */
+    const int32_t *probe;     /* [n, n_probe] HOST: segment ids; -1 = unused slot; the ids of one query are distinct */
+    int32_t k;                /* 1 .. 64 */
+    int32_t *idx;             /* [n, k] HOST: bank rows, best first; -1 where the union has fewer than k rows (either may be NULL, not both) */
+    float   *sim;             /* [n, k] HOST: their similarities; -inf there */
+    int32_t reserved[4];
+} dinov2_hip_topk_probe;
+/* Synchronous: returns after the copy-out, like dinov2_hip_bank_topk.  Argument errors (NULL session, bank or request; those of
+ * dinov2_hip_bank_add for `queries`; more than 65 536 queries; an empty bank; n_seg, n_probe or k out of range; NULL first, len or probe; a
+ * segment outside [0, count); two segments that overlap; a probe id outside [-1, n_seg); an id twice among one query's probes; both outputs
+ * NULL; a session of another device) return DINOV2_HIP_ERR_INVALID with a message that names the offending query or segment, before
+ * anything is launched, allocated or copied, with the outputs untouched.  The scratch is a session-owned buffer grown on demand; an
+ * allocation the device refuses returns DINOV2_HIP_ERR_HIP.  The session's last forward stays what it was, and the bank is only read. */
+int dinov2_hip_bank_topk_probe(dinov2_hip_session *s, const dinov2_hip_bank *bank, const dinov2_hip_topk_probe *p, char *err, size_t errlen);
+
 /* -- VLAD descriptors of row segments (no reference counterpart: one vector per image for place recognition and image retrieval from
  *    frozen patch tokens -- every token is assigned to the nearest centre of a k-means vocabulary, the residuals are summed per centre,
  *    each centre's sum is normalised, then the whole; the recipe of AnyLoc).  The last step of forward -> vocabulary

@@ -323,6 +323,28 @@ int dinov2_hip_op_rerank_plan(int32_t nq, int32_t H, const int32_t *len, int32_t
 int dinov2_hip_op_rerank_bench(const float *q_dev, int32_t nq, const float *b_dev, int32_t nb, int32_t H, const int32_t *first,
                                const int32_t *len, int32_t n_seg, int32_t warmup, int32_t iters, float *ms);
 
+/* the kernels behind dinov2_hip_bank_topk_probe (csrc/probe.hip), bank.hip's merge and the shared normaliser, without a model or session.
+ * 1 <= nq <= 65 536, 1 <= nb <= 2^24, 8 <= H <= 4096, piece_tiles >= 0, pass_bytes >= 0, force_form in 0 .. 2, and what probe_check of
+ * csrc/kernels.h asks of (nb, first, len, probe, k) -- the refusals of dinov2_hip_bank_topk_probe -- else DINOV2_HIP_ERR_INVALID.
+ * bank_probe:      host q [nq, H] against the bank built here from host b [nb, H]: segments first / len [n_seg], probe [nq, n_probe] ->
+ *                  idx, sim [nq, k].  The bank is allocated exactly nb rows long and, like the workspace, starts as 0xff bytes, so anything
+ *                  the kernels read without having written it shows up as NaN / -1.  piece_tiles: 128-row tiles of a piece, 0 = the planner's;
+ *                  pass_bytes: the bound of one pass's lists, 0 = the planner's 32 MiB (a query larger than it is a pass of its own);
+ *                  force_form: 0 = the planner picks per item, 1 = every item wide (128 queries), 2 = every item narrow (16 queries).
+ * bank_probe_plan (no device): probe_plan of csrc/kernels.h.  out[0 .. 9] = nq_pad, hpad, tiles of a piece, passes, wide items, narrow
+ *                  items, row table entries, the most bytes of lists of a pass, bytes of the workspace, dynamic LDS of the narrow kernel.
+ *                  passes [passes_cap][3] = (first query, queries, slots) per pass; items [items_cap][6] = (pass, first bank row, rows,
+ *                  queries, form, first row table entry) per item; rows [rows_cap][2] = (query, list number within the pass = slot *
+ *                  the pass's queries + query - the pass's first) per row table entry.  Each may be NULL; a cap that is too small returns
+ *                  DINOV2_HIP_ERR_INVALID.  err (may be NULL) receives the wording of a refusal. */
+int dinov2_hip_op_bank_probe(const float *q, int32_t nq, const float *b, int32_t nb, int32_t H, const int32_t *first, const int32_t *len,
+                             int32_t n_seg, const int32_t *probe, int32_t n_probe, int32_t k, int32_t piece_tiles, int64_t pass_bytes,
+                             int32_t force_form, int32_t *idx, float *sim);
+int dinov2_hip_op_bank_probe_plan(int32_t nq, int32_t nb, int32_t H, const int32_t *first, const int32_t *len, int32_t n_seg,
+                                  const int32_t *probe, int32_t n_probe, int32_t k, int32_t piece_tiles, int64_t pass_bytes, int32_t force_form,
+                                  int64_t *out, int32_t *passes, int64_t passes_cap, int32_t *items, int64_t items_cap, int32_t *rows,
+                                  int64_t rows_cap, char *err, size_t errlen);
+
 /* the kernels behind dinov2_hip_ncut_tokens (csrc/ncut.hip), its loop (csrc/ncut.cpp) and the shared normaliser, without a model or session;
  * cases, the numpy restatement and the bounds: tests/ncut_cases.py.  16 <= n <= 131 072, 8 <= H <= 4096, affinity, tau and floor as in
  * dinov2_hip_ncut, else DINOV2_HIP_ERR_INVALID.  Every device buffer starts as 0xff bytes; the partials, both blocks, the 8 x 8 partials,
